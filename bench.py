@@ -3,6 +3,8 @@
 224x224 graphs (BASELINE.json metric), one process per GPU.
 
     python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3 --full                 # + every secondary measurement below
+    python bench.py --gpus 1 --steps 10 --warmup 3 --dump-outputs DIR     # + the last timed step's outputs as DIR/*.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \\
         bench.py --gpus N --steps K --warmup W
 
@@ -14,12 +16,15 @@ and the predicted relative poses are all-gathered over RCCL every step.  Rank 0 
 `python bench.py --gpus N` with N > 1 and no torchrun environment starts the N ranks itself (a child
 `python -m torch.distributed.run`, spawned before this process touches the GPU) and relays their JSON line.
 
-The line also carries
+A plain run sets up, warms up, times the --steps steps and prints the line (value, ms_per_step, ...).  With --full the
+line also carries
   roofline     for the dominant kernel (the Winograd F(4,3) f32-MFMA convolution): the FLOP its launches EXECUTE on the
                matrix pipe / their summed HIP-event durations, against the 157.3 TFLOP/s f32 matrix peak (frac <= 1); the
                algorithmic (direct-convolution) rate and the algorithmic / executed ratio are separate fields;
-  cpu_baseline the CPU oracle (validated against the reference in this repo's build container) timed on this box's
-               host cores on a bounded sample of the same workload (N=1 only).
+  cpu_baseline the CPU oracle (validated against the reference model when the golden vectors were written) timed on the
+               host's cores on a bounded sample of the same workload (N=1 only);
+and the per-kernel rates, the single-graph latency, the secondary BASELINE.json configs, the reference's default flags
+and what the collectives observed (per-rank times, all-gather latency).
 """
 from __future__ import annotations
 
@@ -55,7 +60,7 @@ def parse():
     ap.add_argument("--graphs", type=int, default=32, help="graphs per step per GPU (configs[1]: 32)")
     ap.add_argument("--no-other-configs", action="store_true",
                     help="skip the secondary BASELINE.json configs (configs[2] bf16 at 64 graphs, configs[3]/[4] evaluation streams at "
-                         "256x341) that the default N=1 run measures after the headline and reports under `other_configs`")
+                         "256x341) that the --full N=1 run measures after the headline and reports under `other_configs`")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=120.0,
                     help="budget of the whole CPU baseline leg (three thread counts x B = 1/8/32); 0 disables it")
     ap.add_argument("--no-kernel-timing", action="store_true", help="do not bracket kernels with HIP events")
@@ -72,7 +77,29 @@ def parse():
     ap.add_argument("--schedule", default="", help="explicit stream schedule g0:g1:slot,... (experiments; default: --streams equal groups)")
     ap.add_argument("--encoder-dtype", choices=("f32", "bf16"), default="f32",
                     help="f32 = the headline configuration (configs[1]); bf16 = configs[2] (bf16 activations + MFMA conv)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement (CPU baseline, roofline / per-kernel pass, latency, other configs, "
+                         "reference default flags, per-rank report); the --no-* / --cpu-baseline-seconds options trim it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (abs / rel poses, edge index) as DIR/<name>.npy")
     return ap.parse_args()
+
+
+DUMP_BYTES_MAX = 64 << 20
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """Each array as ``out_dir/<name>.npy`` (float32 stays float32, anything else becomes float64).  An array larger than its
+    share of DUMP_BYTES_MAX is cut to a fixed, seeded sample of its rows (sorted), so that two runs stay comparable."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BYTES_MAX // max(1, len(arrays))
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        a = a if a.dtype == np.float32 else a.astype(np.float64)
+        if a.nbytes > share:
+            keep = max(1, share // max(1, a.nbytes // a.shape[0]))
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], size=keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 CPU_THREADS_BEST = 32      # measured optimum of torch-CPU for this model on the 2 x EPYC 9575F host (tests/probes/cpu_threads_probe.py)
@@ -444,7 +471,7 @@ def main():
     if (args.gpus > 1 or args.launcher) and "WORLD_SIZE" not in os.environ:
         raise SystemExit(spawn_ranks(args.gpus, argv=[a for a in sys.argv[1:] if a != "--launcher"]))
     cpu_line = None
-    if int(os.environ.get("WORLD_SIZE", "1")) == 1 and args.cpu_baseline_seconds > 0:
+    if args.full and int(os.environ.get("WORLD_SIZE", "1")) == 1 and args.cpu_baseline_seconds > 0:
         cpu_line = cpu_baseline(args.cpu_baseline_seconds)      # child processes, before any GPU initialisation here
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -505,23 +532,25 @@ def main():
     counts = [B] * world
 
     def step():
-        _, rel, _ = model(data)
+        # (abs poses, rel poses, edge index): what a caller of the model receives; under a launcher the rel poses of
+        # every rank, all-gathered
+        a, rel, ei = model(data)
         if under_launcher:
-            return gather_rows(rel.view(B, NODES * (NODES - 1), 6), counts, always=True)
-        return rel
+            rel = gather_rows(rel.view(B, NODES * (NODES - 1), 6), counts, always=True)
+        return a, rel, ei
 
     for _ in range(max(args.warmup, 1)):
-        out = step()
+        outs = step()
     torch.cuda.synchronize()
 
     def timed(n_steps):
-        nonlocal out
+        nonlocal outs
         if under_launcher:
             dist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(n_steps):
-            out = step()
+            outs = step()
         torch.cuda.synchronize()
         if under_launcher:
             dist.barrier()
@@ -529,11 +558,14 @@ def main():
 
     # pass 1: the K timed steps that define `value` (no instrumentation inside the region)
     elapsed = timed(args.steps)
+    out = outs[1]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"abs_poses": outs[0], "rel_poses": outs[1], "edge_index": outs[2]})
     # pass 2 (roofline): the same K steps again on ONE stream, every launch of the hot kernels bracketed by HIP events
     # on its launch stream.  One stream, because with two the kernels of the two batch halves overlap and a launch's
     # duration would include sharing the GPU; and outside pass 1, because hipEventRecord costs a few % of the step.
     kt, elapsed_ev = None, None
-    if not args.no_kernel_timing:
+    if args.full and not args.no_kernel_timing:
         model.hip_streams = 1
         step()                         # workspaces for the unsplit batch
         ops.timing_read()              # drop anything recorded so far
@@ -571,7 +603,7 @@ def main():
     # call, host-synchronised after every call (median of 40) and streamed (40 calls, one synchronisation).  Reported next
     # to `value`, never as `value`.
     lat1 = None
-    if rank == 0 and args.encoder_dtype == "f32" and not args.no_kernel_timing and not args.no_latency:
+    if args.full and rank == 0 and args.encoder_dtype == "f32" and not args.no_kernel_timing and not args.no_latency:
         d1 = fc_batch(x[:NODES], NODES)
         for _ in range(5):
             model(d1)
@@ -590,24 +622,27 @@ def main():
                 "streamed_1graph_ms": round(1e3 * (time.perf_counter() - t0) / 40, 4),
                 "image_streams": int(getattr(model, "small_batch_streams", 1))}
     others = None
-    if rank == 0 and world == 1 and args.encoder_dtype == "f32" and args.graphs == 32 and not args.no_other_configs:
+    if args.full and rank == 0 and world == 1 and args.encoder_dtype == "f32" and args.graphs == 32 and not args.no_other_configs:
         try:
             others = other_configs(model, args, dev)
         except Exception as exc:                                         # a secondary leg must not take the headline down
             others = {"error": f"{type(exc).__name__}: {exc}"}
     ref_flags = None
-    if rank == 0 and world == 1 and args.encoder_dtype == "f32" and args.graphs == 32 and not args.no_other_configs:
+    if args.full and rank == 0 and world == 1 and args.encoder_dtype == "f32" and args.graphs == 32 and not args.no_other_configs:
         try:
             ref_flags = reference_default_flags(model_factory, args, dev, x, 1e3 * elapsed / args.steps)
         except Exception as exc:
             ref_flags = {"error": f"{type(exc).__name__}: {exc}"}
-    from relpose_gnn_amd.shard import rank_report
-    report = rank_report(dev, elapsed, args.steps, None if host_cpus is None else len(host_cpus))     # collective: every rank
+    report = None
+    if args.full:
+        from relpose_gnn_amd.shard import rank_report
+        report = rank_report(dev, elapsed, args.steps, None if host_cpus is None else len(host_cpus))     # collective: every rank
     allgather_ms = None
     if under_launcher:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if under_launcher and args.full:
         # the step's one collective on its own: 20 all-gathers of the rel poses back to back (latency-bound: 43 KB per rank)
         rel0 = out[:B].contiguous() if out.shape[0] >= B else out
         dist.barrier()
@@ -777,9 +812,10 @@ def main():
         # what the collectives themselves observed (shard.rank_report): flat scalars, so a < 7x result at 8 GPUs can be attributed
         # to a rank (slowest_rank, rank_ms_spread), a socket (numa_nodes_seen, host_cpus_*), a launcher mistake (distinct_gpus <
         # ranks) or the collective (allgather_ms against ms_per_step)
-        line["rccl_ranks_seen"] = report["rccl_ranks_seen"]
-        for kk, v in report.items():
-            line["config"][kk] = v
+        if report is not None:
+            line["rccl_ranks_seen"] = report["rccl_ranks_seen"]
+            for kk, v in report.items():
+                line["config"][kk] = v
         if allgather_ms is not None:
             line["config"]["allgather_ms"] = allgather_ms
         if cpu_line is not None:

@@ -66,7 +66,7 @@ def test_bench_through_its_own_launcher_world1():
     """`python bench.py --gpus 1 --launcher`: spawn_ranks' torch.distributed.run command line -> rank 0 initialises RCCL,
     runs the per-step all-gather of the relative poses, the barriers and the all_reduce(MAX) of the elapsed time."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--launcher", "--steps", "2", "--warmup", "1",
-           "--graphs", "4", "--cpu-baseline-seconds", "0", "--no-kernel-timing"]
+           "--graphs", "4", "--cpu-baseline-seconds", "0", "--no-kernel-timing", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=_env(), cwd=ROOT)
     lines = [ln for ln in r.stdout.splitlines() if ln.lstrip().startswith("{") and '"metric"' in ln]
     assert r.returncode == 0 and len(lines) == 1, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])

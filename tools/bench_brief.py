@@ -1,12 +1,12 @@
 #!/usr/bin/env python3
-"""Run bench.py (no CPU baseline) and print the few numbers that matter for A/B work: graphs/s, ms/step, per-class launch time."""
+"""Run bench.py --full (no CPU baseline) and print the few numbers that matter for A/B work: graphs/s, ms/step, per-class launch time."""
 import json
 import os
 import subprocess
 import sys
 
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "20", "--warmup", "5", "--cpu-baseline-seconds", "0"] + sys.argv[1:],
+out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "20", "--warmup", "5", "--full", "--cpu-baseline-seconds", "0"] + sys.argv[1:],
                      capture_output=True, text=True)
 line = [l for l in out.stdout.splitlines() if l.startswith("{")]
 if not line:

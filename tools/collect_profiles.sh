@@ -9,7 +9,7 @@ OUT=$R/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd /tmp
-B="$R/bench.py --steps 5 --warmup 2 --cpu-baseline-seconds 0 --no-latency --no-other-configs"
+B="$R/bench.py --steps 5 --warmup 2 --full --cpu-baseline-seconds 0 --no-latency --no-other-configs"
 timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace_default" -o t -- python3 $B > "$OUT/trace_default.log" 2>&1
 timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace_1stream" -o t -- python3 $B --streams 1 > "$OUT/trace_1stream.log" 2>&1
 P="$R/bench.py --steps 3 --warmup 1 --cpu-baseline-seconds 0 --no-other-configs --streams 1 --no-kernel-timing"
@@ -17,7 +17,7 @@ timeout 400 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d "$O
 timeout 400 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d "$OUT/pmc_write" -o p -- python3 $P > "$OUT/pmc_write.log" 2>&1
 timeout 400 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES GRBM_GUI_ACTIVE SQ_INSTS_VALU_MFMA_F32 --output-format csv -d "$OUT/pmc_mfma" -o p -- python3 $P > "$OUT/pmc_mfma.log" 2>&1
 # bf16 path (configs[2]: 64 graphs, bf16 encoder + bf16 GNN Linears): kernel trace + matrix-pipe / LDS / traffic counters
-BB="$R/bench.py --steps 5 --warmup 2 --cpu-baseline-seconds 0 --graphs 64 --encoder-dtype bf16 --gnn-dtype bf16"
+BB="$R/bench.py --steps 5 --warmup 2 --full --cpu-baseline-seconds 0 --graphs 64 --encoder-dtype bf16 --gnn-dtype bf16"
 timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace_bf16_1stream" -o t -- python3 $BB --streams 1 > "$OUT/trace_bf16_1stream.log" 2>&1
 PB="$BB --steps 3 --warmup 1 --streams 1 --no-kernel-timing"
 timeout 400 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES GRBM_GUI_ACTIVE SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT SQ_WAIT_INST_LDS SQ_WAVE_CYCLES SQ_WAIT_ANY --output-format csv -d "$OUT/pmc_bf16_sq" -o p -- python3 $PB > "$OUT/pmc_bf16_sq.log" 2>&1

@@ -15,6 +15,6 @@ fi
 echo "pytest rc=$?" >> "$OUT/pytest.log"
 tail -5 "$OUT/pytest.log"
 cp gpurun_out/parity_report.jsonl "$OUT/" 2>/dev/null
-timeout 600 python bench.py --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout 600 python bench.py --steps 20 --warmup 5 --full > "$OUT/bench.json" 2> "$OUT/bench.err"
 echo "bench rc=$?"
 cut -c1-1500 "$OUT/bench.json"

@@ -5,7 +5,7 @@ OUT=$R/gpurun_out/per_layer_${1:-x}
 mkdir -p $OUT
 export TMPDIR=/tmp
 cd /tmp
-B="$R/bench.py --steps 5 --warmup 2 --cpu-baseline-seconds 0 --no-kernel-timing"
+B="$R/bench.py --steps 5 --warmup 2 --full --cpu-baseline-seconds 0 --no-kernel-timing"
 timeout 400 rocprofv3 --kernel-trace --output-format csv -d $OUT/t1 -o t -- python3 $B --streams 1 > $OUT/t1.log 2>&1
 timeout 400 rocprofv3 --kernel-trace --output-format csv -d $OUT/t2 -o t -- python3 $B > $OUT/t2.log 2>&1
 timeout 400 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES GRBM_GUI_ACTIVE SQ_INSTS_VALU_MFMA_F32 --output-format csv -d $OUT/p1 -o p -- python3 $B --streams 1 > $OUT/p1.log 2>&1
