@@ -10,7 +10,7 @@
  *
  * Conventions
  *   - every pointer is a DEVICE pointer to caller-owned, 16-byte aligned memory (except where
- *     marked HOST); no call synchronises the device (except rpg_timing_read* and
+ *     marked HOST, and the uint8 frames of rpg_frames_u8_to_*, which may start at any byte); no call synchronises the device (except rpg_timing_read* and
  *     rpg_release_scratch);
  *   - the composite forwards (rpg_resnet_forward_*, rpg_gnn_forward_*) allocate nothing: all their
  *     memory, including the partial-tile scratch of the split-K / stream-K launches, is the
@@ -423,6 +423,41 @@ int rpg_host_f32_to_bf16_isa(const float* src, void* dst_bf16, size_t count, int
 #define RPG_TUNE_BF16_PAIR 31        /* bf16 encoder: 1 (default) = the 3x3 / stride-2 convolution and the 1x1 / stride-2 shortcut of a down-sampling BasicBlock
                                      run as ONE launch of the LDS-DMA kernel (their tiles side by side in the grid; same arithmetic) | 0 = two launches */
 int rpg_set_tuning(int key, int value);
+
+/* ------------------------------------------------------------------------------------------- */
+/* Input transform (replaces the reference's CPU transform of every node image,                 */
+/* dataset_7Scenes_multi.py:290-298: torchvision-0.9.1 Resize(256) on a PIL RGB image, ToTensor, */
+/* Normalize(mean = stats[0], std = sqrt(stats[1])); images from torchvision's default_loader)   */
+/* ------------------------------------------------------------------------------------------- */
+
+/* HOST: Pillow's 8-bit bilinear resampling table of one axis, in -> out samples (Image.resize(..., BILINEAR), the resampler
+ * behind Resize(256)): scale = in / out, support = max(scale, 1), ksize = 2 * ceil(support) + 1; for output index o
+ * bounds[2 o] = first source index, bounds[2 o + 1] = tap count, weights[o * ksize + j] = the normalised bilinear weight of tap j
+ * as int32 with 22 fraction bits (zero beyond the tap count).  Returns ksize (rpg_resize_table_ksize) or RPG_ERR_BAD_ARG
+ * (non-positive size, downscale beyond 31x).  bounds [2 * out], weights [out * ksize].                                    */
+int rpg_resize_table_ksize(int in, int out);
+int rpg_resize_table_bilinear(int in, int out, int32_t* bounds, int32_t* weights);
+
+/* uint8 RGB frames [n][in_h][in_w][3] (HWC, what PIL's convert("RGB") holds) -> the encoder's input [n][3][out_h][out_w]:
+ * the resize of rpg_resize_table_bilinear bit for bit (horizontal pass first, over the source rows the vertical pass reads; an
+ * axis whose size does not change is not resampled: its tables may be NULL), then ((float)u / 255 - mean_c) / std_c in fp32
+ * with correctly rounded divisions (torch's ToTensor + Normalize on the CPU); the bf16 form rounds that value to nearest even
+ * (the rounding the bf16 encoder applies to fp32 input, so both give the same poses).
+ *   frames    DEVICE, any byte alignment (a frame tensor may start anywhere); 64-bit offsets throughout
+ *   h_*, v_*  DEVICE copies of the tables of (in_w -> out_w) and (in_h -> out_h), built once per geometry by the caller
+ *   mean*, std*  per channel, by value (std = sqrt(var) rounded to fp32)
+ *   out       fp32 (4-byte aligned) or bf16 (2-byte aligned)
+ * One launch, no allocation, no synchronisation (graph-capturable).  rpg_frames_workspace_bytes: workspace of the launch;
+ * the fused kernel keeps its intermediate in LDS, so it is 0 for every geometry taken today.                              */
+size_t rpg_frames_workspace_bytes(int n, int in_h, int in_w, int out_h, int out_w);
+int rpg_frames_u8_to_f32(const uint8_t* frames, int n, int in_h, int in_w, int out_h, int out_w, const int32_t* h_bounds,
+                         const int32_t* h_weights, const int32_t* v_bounds, const int32_t* v_weights, float mean0, float mean1,
+                         float mean2, float std0, float std1, float std2, float* out, void* workspace, size_t workspace_bytes,
+                         void* stream);
+int rpg_frames_u8_to_bf16(const uint8_t* frames, int n, int in_h, int in_w, int out_h, int out_w, const int32_t* h_bounds,
+                          const int32_t* h_weights, const int32_t* v_bounds, const int32_t* v_weights, float mean0, float mean1,
+                          float mean2, float std0, float std1, float std2, void* out_bf16, void* workspace, size_t workspace_bytes,
+                          void* stream);
 
 #ifdef __cplusplus
 }

@@ -28,6 +28,8 @@ SYMBOLS = (
     "rpg_release_scratch", "rpg_timing_read_ex", "rpg_stem_conv7x7s2_bn_relu_maxpool_f32", "rpg_stem_pair_table",
     "rpg_attention_aggregate_f32", "rpg_stem_conv7x7s2_bn_relu_maxpool_bf16", "rpg_stem_conv7x7s2_bn_relu_maxpool_bf16_xbf16",
     "rpg_resnet_forward_bf16_xbf16", "rpg_host_f32_to_bf16", "rpg_basicblock64_bf16", "rpg_linear_gather_ex_f32", "rpg_probe_mfma_bf16", "rpg_host_f32_to_bf16_isa",
+    "rpg_resize_table_ksize", "rpg_resize_table_bilinear", "rpg_frames_workspace_bytes", "rpg_frames_u8_to_f32",
+    "rpg_frames_u8_to_bf16",
 )
 
 
@@ -97,6 +99,12 @@ def _declare(lib: C.CDLL) -> None:
     lib.rpg_host_f32_to_bf16.argtypes = [_vp, _vp, _sz]
     lib.rpg_host_f32_to_bf16_isa.argtypes = [_vp, _vp, _sz, _i]
     lib.rpg_probe_mfma_bf16.argtypes = [_vp, C.c_long, _i, _vp, _vp]
+    lib.rpg_resize_table_ksize.argtypes = [_i, _i]
+    lib.rpg_resize_table_bilinear.argtypes = [_i, _i, _vp, _vp]
+    lib.rpg_frames_workspace_bytes.argtypes = [_i] * 5
+    lib.rpg_frames_workspace_bytes.restype = _sz
+    lib.rpg_frames_u8_to_f32.argtypes = [_vp] + [_i] * 5 + [_vp] * 4 + [C.c_float] * 6 + [_vp, _vp, _sz, _vp]
+    lib.rpg_frames_u8_to_bf16.argtypes = lib.rpg_frames_u8_to_f32.argtypes
     for name in SYMBOLS:
         getattr(lib, name)          # AttributeError here = the library does not export a declared symbol
 

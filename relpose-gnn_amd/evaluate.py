@@ -116,10 +116,11 @@ class _InputPipeline:
         self.dtype = dtype
         self.copy_stream = torch.cuda.Stream(device=device)
         self.host = [torch.empty((rows, row_floats), dtype=dtype, pin_memory=True) for _ in range(2)]
-        self.host_np = [t.numpy() for t in self.host] if dtype == torch.float32 else None
+        # dtype = torch.uint8: camera frames (the model's frame_transform runs the image transform on the device), copied as they are
+        self.host_np = [t.numpy() for t in self.host] if dtype != torch.bfloat16 else None
         import os
         from concurrent.futures import ThreadPoolExecutor
-        self.workers = staging_workers(dtype == torch.float32, local_world)
+        self.workers = staging_workers(dtype != torch.bfloat16, local_world)
         self.pool = ThreadPoolExecutor(max_workers=self.workers) if self.workers > 1 else None
         self.dev = [torch.empty((rows, row_floats), dtype=dtype, device=device) for _ in range(2)]
         self.sent = [torch.cuda.Event() for _ in range(2)]
@@ -146,8 +147,8 @@ class _InputPipeline:
         jobs = []
         for g in chunk:
             n = g.x.shape[0]
-            if g.x.is_pinned() and g.x.dtype == self.dtype:
-                direct.append((off, n, g.x))
+            if g.x.is_pinned() and g.x.dtype == self.dtype and (g.x.dim() == 2 or g.x.is_contiguous()):
+                direct.append((off, n, g.x if g.x.dim() == 2 else g.x.view(n, -1)))
                 self.direct_bytes += g.x.numel() * g.x.element_size()
             else:
                 jobs.append((off, n, g.x))
@@ -162,7 +163,7 @@ class _InputPipeline:
             def copy_some(part):
                 for o, n, src in part:
                     if host_np is not None:
-                        np.copyto(host_np[o:o + n], src.detach().numpy())
+                        np.copyto(host_np[o:o + n], src.detach().reshape(n, -1).numpy())
                     else:
                         # fp32 -> bf16 (round to nearest even) on the way, in the library's host helper (ctypes releases the GIL)
                         t = src.detach()
@@ -208,6 +209,17 @@ class _InputPipeline:
 
     def release(self, k: int) -> None:
         self.used[k].record(torch.cuda.current_stream())
+
+
+def _frame_shape(chunk: Sequence[Data]):
+    """(H, W, 3) if the chunk's node images are uint8 frames [n, H, W, 3] (all of one size), None for processed images."""
+    if not any(g.x.dtype == torch.uint8 for g in chunk):
+        return None
+    shapes = {tuple(g.x.shape[1:]) if g.x.dtype == torch.uint8 and g.x.dim() == 4 else None for g in chunk}
+    if len(shapes) != 1 or None in shapes or next(iter(shapes))[-1] != 3:
+        raise ValueError("a micro-batch with uint8 frames must hold frames [n, H, W, 3] of one size only, got "
+                         f"{sorted(str(s) for s in shapes)}")
+    return next(iter(shapes))
 
 
 def _collate_on_device(chunk: Sequence[Data], x_dev: torch.Tensor, device) -> Batch:
@@ -264,7 +276,10 @@ class _MicroBatchRunner:
         device = self.device
         rows, width = sum(g.x.shape[0] for g in chunk), int(chunk[0].x.shape[1])
         dtype = self.h2d_dtype
-        if self.pinned_direct and dtype != torch.float32 and all(g.x.dtype == torch.float32 and g.x.is_pinned() for g in chunk):
+        fshape = _frame_shape(chunk)
+        if fshape is not None:                                  # uint8 frames: sent as they are, whatever the staging dtype
+            dtype, width = torch.uint8, int(np.prod(fshape))
+        elif self.pinned_direct and dtype != torch.float32 and all(g.x.dtype == torch.float32 and g.x.is_pinned() for g in chunk):
             dtype = torch.float32                               # the loader's own pinned fp32 tensors: no rounding pass, no staging copy
         pipe = self.pipes.get(dtype)
         if pipe is None or not pipe.fits(rows, width, dtype):
@@ -297,6 +312,9 @@ class _MicroBatchRunner:
             pipe, handle = (pre[1], pre[2]) if pre is not None else self._begin_staging(k, chunk)
             x_dev = pipe.stage_end(handle)
             self.h2d_bytes += x_dev.numel() * x_dev.element_size()
+            fshape = _frame_shape(chunk)
+            if fshape is not None:
+                x_dev = x_dev.view(-1, *fshape)
             batch = _collate_on_device(chunk, x_dev, device)
             pipe.acquire(k)
         else:
@@ -357,7 +375,11 @@ def evaluate_stream(model, graphs: Sequence[Data], device, micro_batch: int = 64
     accepts, i.e. True for the bf16 encoder with its fused stem): host-resident images are rounded to bf16 while they are staged --
     except, by default, micro-batches whose fp32 images all sit in PINNED memory (the reference's loader, test.py:193): those are sent
     as they are, with no host pass at all (``bf16_input=True`` forces the rounding pass for them too).  Same poses either way:
-    the bf16 encoder rounds fp32 input first thing."""
+    the bf16 encoder rounds fp32 input first thing.
+    Graphs whose ``x`` is uint8 camera frames ``[n, H, W, 3]`` (one size per micro-batch) are sent as uint8 -- pinned sources
+    straight from where they are, pageable ones through the staging threads as a plain copy -- and the model's
+    ``frame_transform`` (frames.FrameTransform) runs the reference's image transform on the device; the byte counts in ``stats``
+    are then uint8 bytes."""
     from .shard import rank_host_slice
     if world > 1 and torch.device(device).type == "cuda":
         import os

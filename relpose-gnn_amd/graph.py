@@ -63,6 +63,9 @@ class Batch(Data):
     def from_data_list(cls, graphs: Sequence[Data]) -> "Batch":
         xs, eis, ys, eas, bs = [], [], [], [], []
         off = 0
+        frames = [tuple(d.x.shape[1:]) for d in graphs if torch.is_tensor(d.x) and d.x.dtype == torch.uint8 and d.x.dim() == 4]
+        if frames and len(set(frames)) > 1:
+            raise ValueError(f"uint8 frames of different sizes in one batch: {sorted(set(frames))} (one transform launch takes one size)")
         for g, d in enumerate(graphs):
             n = d.num_nodes
             xs.append(d.x)

@@ -21,6 +21,9 @@ class GraphedForward:
     def __init__(self, model, example, warmup: int = 2):
         if not example.x.is_cuda:
             raise RuntimeError("GraphedForward needs a batch on the GPU")
+        if example.x.dtype == torch.uint8:
+            raise TypeError("GraphedForward does not take uint8 frames: capture the model on its fp32 / bf16 input "
+                            "(frame_transform.apply(frames) outside the graph)")
         if getattr(model, "droprate", 0) > 0 or getattr(model, "knn", -1) > 0:
             raise NotImplementedError("graph capture covers the deterministic fully-connected path (droprate=0, knn<=0)")
         self.model = model

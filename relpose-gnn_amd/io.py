@@ -142,3 +142,36 @@ def load_checkpoint_state_dict(path: str, map_location="cpu") -> Dict[str, torch
     if isinstance(ck, dict) and "model_state_dict" in ck:
         return ck["model_state_dict"]
     return ck
+
+
+def frames_from_normalized(x: torch.Tensor, mean, std, height: int = 256) -> torch.Tensor:
+    """The exact inverse of ToTensor + Normalize(mean, std) for processed samples: fp32 node images ``x`` [n, 3*H*W] (or
+    [n, 3, H, W]) that the reference's transform made out of uint8 pixels -> uint8 frames [n, H, W, 3] (RGB, HWC) that
+    ``frames.FrameTransform(resize=None, mean, std)`` -- or the model's frame_transform when the frames are already at the
+    target size -- turns back into the same bits.  Per channel the 256 images ((float)u / 255 - mean) / std are built with the
+    same CPU fp32 operations and looked up with ``searchsorted``; the map is strictly increasing for the 7-Scenes statistics,
+    so the inverse is unique.  Raises ValueError if any value is not one of the 256 images (not a processed uint8 sample)."""
+    x = torch.as_tensor(x).detach().cpu()
+    if x.dtype != torch.float32:
+        raise ValueError(f"expected fp32 processed images, got {x.dtype}")
+    if x.dim() == 2:
+        if x.shape[1] % (3 * int(height)):
+            raise ValueError(f"rows of {x.shape[1]} values are not 3 x {height} x W images")
+        x = x.view(x.shape[0], 3, int(height), -1)
+    if x.dim() != 4 or x.shape[1] != 3:
+        raise ValueError("expected [n, 3*H*W] or [n, 3, H, W] images")
+    import numpy as np
+    m32 = np.asarray([float(v) for v in mean], dtype=np.float64).astype(np.float32)
+    s32 = np.asarray([float(v) for v in std], dtype=np.float64).astype(np.float32)
+    u = np.arange(256, dtype=np.float32) / np.float32(255)                   # ToTensor: img.float().div(255), correctly rounded
+    lut = torch.from_numpy((u[None, :] - m32[:, None]) / s32[:, None])        # Normalize: sub_(mean).div_(std)
+    if bool((lut[:, 1:] <= lut[:, :-1]).any()):
+        raise ValueError("normalisation is not strictly increasing for these statistics: no unique inverse")
+    out = torch.empty((x.shape[0], x.shape[2], x.shape[3], 3), dtype=torch.uint8)
+    for c in range(3):
+        v = x[:, c].contiguous()
+        idx = torch.searchsorted(lut[c].contiguous(), v.reshape(-1)).clamp_(max=255).view_as(v)
+        if not torch.equal(lut[c][idx], v):
+            raise ValueError(f"channel {c}: values that are not a normalised uint8 pixel (not a processed sample of these statistics)")
+        out[..., c] = idx.to(torch.uint8)
+    return out

@@ -145,6 +145,9 @@ class Lookahead:
     @staticmethod
     def _as_graph(item) -> Data:
         x = item.x
+        if x.dtype == torch.uint8:
+            raise TypeError("lookahead() does not take uint8 frames: use evaluate_stream (model.frame_transform) or transform "
+                            "them first (FrameTransform.apply)")
         if x.dim() != 2:
             x = x.reshape(x.shape[0], -1)
         b = getattr(item, "batch", None)

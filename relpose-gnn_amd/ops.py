@@ -181,6 +181,58 @@ def f32_to_bf16(x: torch.Tensor, out: Optional[torch.Tensor] = None, col_off: in
     return out
 
 
+def _frames(frames: torch.Tensor, out_hw: Tuple[int, int], tables, mean: Sequence[float], std: Sequence[float],
+            dtype, out: Optional[torch.Tensor]) -> torch.Tensor:
+    if not torch.is_tensor(frames):
+        raise TypeError("frames: expected a tensor")
+    if not frames.is_cuda:
+        raise RuntimeError(f"frames: expected a tensor on the GPU (the HIP kernels are the only compute path), got {frames.device}")
+    if frames.dtype != torch.uint8:
+        raise TypeError(f"frames: expected uint8, got {frames.dtype}")
+    if frames.dim() != 4 or frames.shape[3] != 3:
+        raise ValueError(f"frames: expected uint8 [n, H, W, 3] (RGB, HWC), got {tuple(frames.shape)}")
+    frames = frames if frames.is_contiguous() else frames.contiguous()
+    n, h, w, _ = frames.shape
+    oh, ow = int(out_hw[0]), int(out_hw[1])
+    hb, hw, vb, vw = tables
+    if out is None:
+        out = torch.empty((n, 3, oh, ow), dtype=dtype, device=frames.device)
+    if out.shape != (n, 3, oh, ow) or out.dtype != dtype or not out.is_contiguous() or out.device != frames.device:
+        raise ValueError(f"out must be a contiguous {dtype} [{n}, 3, {oh}, {ow}] tensor on the frames' device")
+    fn = L.lib().rpg_frames_u8_to_bf16 if dtype == torch.bfloat16 else L.lib().rpg_frames_u8_to_f32
+    L.check(fn(_p(frames), n, h, w, oh, ow, _p(hb), _p(hw), _p(vb), _p(vw), *[float(v) for v in mean], *[float(v) for v in std],
+               _p(out), None, 0, _stream()), "frames_u8")
+    return out
+
+
+def frames_u8_to_f32(frames: torch.Tensor, out_hw: Tuple[int, int], tables, mean: Sequence[float], std: Sequence[float],
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 RGB frames [n, H, W, 3] -> fp32 [n, 3, out_h, out_w]: Pillow's bilinear resize + ToTensor + Normalize, bit for bit.
+    ``tables`` = (h_bounds, h_weights, v_bounds, v_weights) int32 device tensors of ``resize_table`` (None for an axis whose size
+    does not change); ``mean`` / ``std`` three floats each (frames.FrameTransform builds and caches all of it)."""
+    return _frames(frames, out_hw, tables, mean, std, torch.float32, out)
+
+
+def frames_u8_to_bf16(frames: torch.Tensor, out_hw: Tuple[int, int], tables, mean: Sequence[float], std: Sequence[float],
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """As ``frames_u8_to_f32``, rounded to bf16 (nearest even): the bf16 encoder's rounding of the fp32 result."""
+    return _frames(frames, out_hw, tables, mean, std, torch.bfloat16, out)
+
+
+def resize_table(n_in: int, n_out: int):
+    """HOST: Pillow's 8-bit bilinear table of one axis -> (bounds int32 [n_out, 2], weights int32 [n_out, ksize])."""
+    lib = L.lib()
+    ks = lib.rpg_resize_table_ksize(int(n_in), int(n_out))
+    if ks <= 0:
+        raise ValueError(f"resize_table: unsupported sizes {n_in} -> {n_out}")
+    bounds = torch.empty((n_out, 2), dtype=torch.int32)
+    weights = torch.empty((n_out, ks), dtype=torch.int32)
+    rc = lib.rpg_resize_table_bilinear(int(n_in), int(n_out), bounds.data_ptr(), weights.data_ptr())
+    if rc != ks:
+        raise ValueError(f"resize_table: unsupported sizes {n_in} -> {n_out}")
+    return bounds, weights
+
+
 def linear_bf16(a: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None,
                 residual: Optional[torch.Tensor] = None, res_idx: Optional[torch.Tensor] = None,
                 residual2: Optional[torch.Tensor] = None, res2_idx: Optional[torch.Tensor] = None, relu: bool = False) -> torch.Tensor:

@@ -141,6 +141,9 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
         self._status_host: Optional[torch.Tensor] = None     # pinned mirror
         self._status_event: Optional[torch.cuda.Event] = None
         self._status_pending = False
+        # optional frames.FrameTransform: with it forward() also takes uint8 frames data.x [n, H, W, 3] (RGB, HWC) on the GPU and
+        # runs the reference's image transform there (a plain attribute: not a module, parameter or buffer -- state_dict unchanged)
+        self.frame_transform = None
 
     @property
     def encoder_dtype(self) -> str:
@@ -391,6 +394,8 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
                                "(there is no CPU fallback)")
         if not torch.is_tensor(edge_index) or edge_index.device != x.device:
             raise RuntimeError("data.edge_index must be a tensor on the same GPU as data.x")
+        if x.dtype == torch.uint8 and self.frame_transform is not None:
+            x = self._transform_frames(x)
         if x.dtype != torch.float32 and not (x.dtype == torch.bfloat16 and self.accepts_bf16_input):
             raise TypeError(f"data.x must be float32 (the reference's input dtype; bf16 images are taken by the bf16 encoder "
                             f"only), got {x.dtype}")
@@ -459,6 +464,24 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
             abs_pose = ops.linear_gather([(node_f, lo), (node_f, hi)], self._extra["heads_pair_w"],
                                          self._extra["heads_pair_b"], e)
         return abs_pose, rel_pose, (edge_index_knn if k is not None else edge_index)
+
+    def _transform_frames(self, frames: torch.Tensor) -> torch.Tensor:
+        """uint8 frames [n, H, W, 3] -> the encoder's input [n, 3, input_img_height, W'] through ``frame_transform``, in bf16 for
+        the bf16 encoder (it rounds fp32 input to bf16 first thing: same poses) and fp32 otherwise.  Written into a pooled buffer
+        on the caller's stream, before any side stream is forked off it; the buffer is reused by the next call, which the
+        stream order of this call's readers (all joined back to the caller's stream) makes safe."""
+        if frames.dim() != 4 or frames.shape[3] != 3:
+            raise ValueError(f"uint8 data.x must be frames [n, H, W, 3] (RGB, HWC), got {tuple(frames.shape)}")
+        ft = self.frame_transform
+        oh, ow = ft.output_size(frames.shape[1], frames.shape[2])
+        if oh != self.input_img_height:
+            raise ValueError(f"frame_transform turns {frames.shape[1]}x{frames.shape[2]} frames into {oh}x{ow} images, but the "
+                             f"model's input_img_height is {self.input_img_height}")
+        dtype = torch.bfloat16 if self.accepts_bf16_input else torch.float32
+        n = frames.shape[0]
+        nbytes = n * 3 * oh * ow * (2 if dtype == torch.bfloat16 else 4)
+        buf = self._ws_pool.get((200, 0), max(nbytes, 16), frames.device)[:nbytes].view(dtype).view(n, 3, oh, ow)
+        return ft.apply(frames, dtype, out=buf)
 
     def _encode_small(self, x: torch.Tensor) -> torch.Tensor:
         """The encoder for a batch that cannot be cut at graph boundaries (one graph: the reference's batch_size=1 loop,
