@@ -116,8 +116,8 @@ __device__ __forceinline__ void block64_strip_epilogue(f32x16 (&acc)[FM][1], uns
             y.x = v.x * sc.x + sh.x; y.y = v.y * sc.y + sh.y; y.z = v.z * sc.z + sh.z; y.w = v.w * sc.w + sh.w;
             const bf16x4 rs = __builtin_bit_cast(bf16x4, rs_cur[t]);
             y.x += (float)rs[0]; y.y += (float)rs[1]; y.z += (float)rs[2]; y.w += (float)rs[3];
-            const bf16x4 ob = {(__bf16)(relu ? fmaxf(y.x, 0.f) : y.x), (__bf16)(relu ? fmaxf(y.y, 0.f) : y.y), (__bf16)(relu ? fmaxf(y.z, 0.f) : y.z),
-                               (__bf16)(relu ? fmaxf(y.w, 0.f) : y.w)};
+            const float4 yr = rpg::relu4_if(relu, y);
+            const bf16x4 ob = {(__bf16)yr.x, (__bf16)yr.y, (__bf16)yr.z, (__bf16)yr.w};
             __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2e, ob), ro, offs[i][t], 0, 0);
         }
         __builtin_amdgcn_wave_barrier();
@@ -422,7 +422,8 @@ __global__ __launch_bounds__(512) void block64_bf16_fused_kernel(BlockArgs a, co
                         float4 y;
                         y.x = acc1[i][0][4 * q + 0] * sc[q].x + sh[q].x; y.y = acc1[i][0][4 * q + 1] * sc[q].y + sh[q].y;
                         y.z = acc1[i][0][4 * q + 2] * sc[q].z + sh[q].z; y.w = acc1[i][0][4 * q + 3] * sc[q].w + sh[q].w;
-                        const bf16x4 ob = {(__bf16)fmaxf(y.x, 0.f), (__bf16)fmaxf(y.y, 0.f), (__bf16)fmaxf(y.z, 0.f), (__bf16)fmaxf(y.w, 0.f)};
+                        const float4 yr = rpg::relu4(y);
+                        const bf16x4 ob = {(__bf16)yr.x, (__bf16)yr.y, (__bf16)yr.z, (__bf16)yr.w};
                         *reinterpret_cast<u32x2e*>(tbuf + slot * 64 + 16 * (q ^ sw) + 8 * half) = __builtin_bit_cast(u32x2e, ob);
                     }
                 }
@@ -506,7 +507,8 @@ __global__ __launch_bounds__(512) void block64_bf16_fused_kernel(BlockArgs a, co
                     float4 y;
                     y.x = acc1[i][0][4 * q + 0] * sc[q].x + sh[q].x; y.y = acc1[i][0][4 * q + 1] * sc[q].y + sh[q].y;
                     y.z = acc1[i][0][4 * q + 2] * sc[q].z + sh[q].z; y.w = acc1[i][0][4 * q + 3] * sc[q].w + sh[q].w;
-                    const bf16x4 ob = {(__bf16)fmaxf(y.x, 0.f), (__bf16)fmaxf(y.y, 0.f), (__bf16)fmaxf(y.z, 0.f), (__bf16)fmaxf(y.w, 0.f)};
+                    const float4 yr = rpg::relu4(y);
+                    const bf16x4 ob = {(__bf16)yr.x, (__bf16)yr.y, (__bf16)yr.z, (__bf16)yr.w};
                     *reinterpret_cast<u32x2e*>(tbuf + slot * 64 + 16 * (q ^ sw) + 8 * half) = __builtin_bit_cast(u32x2e, ob);
                 }
             }

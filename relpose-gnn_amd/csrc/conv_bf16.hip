@@ -126,11 +126,11 @@ __device__ __forceinline__ void bf16_tile_epilogue(f32x16 (&acc)[FM][FN], unsign
                     }
                 }
                 if (ep.out2) {
-                    const float f2 = ep.relu2 ? 0.f : -INFINITY;
-                    const bf16x4 o2 = {(__bf16)fmaxf(y.x, f2), (__bf16)fmaxf(y.y, f2), (__bf16)fmaxf(y.z, f2), (__bf16)fmaxf(y.w, f2)};
+                    const float4 y2 = rpg::relu4_if(ep.relu2, y);
+                    const bf16x4 o2 = {(__bf16)y2.x, (__bf16)y2.y, (__bf16)y2.z, (__bf16)y2.w};
                     *reinterpret_cast<bf16x4*>(ep.out2 + (size_t)m * ep.ld2 + nb) = o2;
                 }
-                if (ep.relu) { y.x = fmaxf(y.x, 0.f); y.y = fmaxf(y.y, 0.f); y.z = fmaxf(y.z, 0.f); y.w = fmaxf(y.w, 0.f); }
+                if (ep.relu) y = rpg::relu4(y);
                 if (!ep.out) {
                 } else if (ep.out_f32) {
                     *reinterpret_cast<float4*>(reinterpret_cast<float*>(ep.out) + o) = y;
@@ -174,7 +174,7 @@ __device__ __forceinline__ void bf16_tile_epilogue_lean_body(f32x16 (&acc)[FM][F
     const unsigned row_b = 2u * (unsigned)ep.ldc;             // bytes per output row
     const unsigned base = n_ok ? (unsigned)r_in * row_b + 2u * (unsigned)nb : OOB;      // row r_in of fragment 0
     const int rows_left = M - mw;                             // rows of this wave's range that exist (may be <= 0)
-    const bool relu = ep.relu != 0;          // (a select, not a max with -inf: a NaN accumulator of a non-ReLU convolution stays NaN, as in the general epilogue)
+    const bool relu = ep.relu != 0;          // (rpg::relu4_if: a NaN accumulator of a non-ReLU convolution stays NaN, as in the general epilogue)
     auto off = [&](int i, int t) -> unsigned {
         const int r = i * 32 + r_in + RPI * t;
         return (n_ok && r < rows_left) ? base + (unsigned)(i * 32 + RPI * t) * row_b : OOB;
@@ -204,8 +204,8 @@ __device__ __forceinline__ void bf16_tile_epilogue_lean_body(f32x16 (&acc)[FM][F
                 const bf16x4 rs = __builtin_bit_cast(bf16x4, rs_cur[t]);
                 y.x += (float)rs[0]; y.y += (float)rs[1]; y.z += (float)rs[2]; y.w += (float)rs[3];
             }
-            const bf16x4 ob = {(__bf16)(relu ? fmaxf(y.x, 0.f) : y.x), (__bf16)(relu ? fmaxf(y.y, 0.f) : y.y), (__bf16)(relu ? fmaxf(y.z, 0.f) : y.z),
-                               (__bf16)(relu ? fmaxf(y.w, 0.f) : y.w)};
+            const float4 yr = rpg::relu4_if(relu, y);
+            const bf16x4 ob = {(__bf16)yr.x, (__bf16)yr.y, (__bf16)yr.z, (__bf16)yr.w};
 #if defined(RPG_PATCH_ABL) && (RPG_PATCH_ABL & 4)      // diagnostic: all stores of the wave land in one 64-KB window (L2-resident): the
             __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2e, ob), ro, off(i, t) & 0xffffu, 0, 0);      // epilogue without its HBM writes
 #else
@@ -1400,7 +1400,7 @@ __global__ __launch_bounds__(NT) void maxpool3x3s2_bf16_kernel(const uint4* __re
                 if ((unsigned)ix >= (unsigned)w) continue;
                 const bf16x8 v = __builtin_bit_cast(bf16x8, img[((long)iy * w + ix) * c8 + c]);
 #pragma unroll
-                for (int k = 0; k < 8; ++k) m[k] = fmaxf(m[k], (float)v[k]);
+                for (int k = 0; k < 8; ++k) m[k] = rpg::nan_max(m[k], (float)v[k]);
             }
         }
         bf16x8 o;

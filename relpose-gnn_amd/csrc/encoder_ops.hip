@@ -45,7 +45,7 @@ __global__ __launch_bounds__(NT) void maxpool3x3s2_kernel(const float4* __restri
                 const int ix = ox * 2 - 1 + dx;
                 if ((unsigned)ix >= (unsigned)w) continue;
                 const float4 v = img[((long)iy * w + ix) * c4 + c];
-                m.x = fmaxf(m.x, v.x); m.y = fmaxf(m.y, v.y); m.z = fmaxf(m.z, v.z); m.w = fmaxf(m.w, v.w);
+                m = rpg::nan_max4(m, v);
             }
         }
         y[i] = m;

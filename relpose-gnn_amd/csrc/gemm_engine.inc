@@ -585,14 +585,14 @@ __device__ __forceinline__ void tile_epilogue(float* lds, const Epilogue& ep, in
                 o.y = v[t].y * sc.y + sh.y + rs[t].y;
                 o.z = v[t].z * sc.z + sh.z + rs[t].z;
                 o.w = v[t].w * sc.w + sh.w + rs[t].w;
-                if (ep.relu) { o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f); }
+                if (ep.relu) o = rpg::relu4(o);
                 if (COH) {
                     if (n_ok && m < M) rpg::agent_store_f4(rpg::agent_rsrc(ep.out), 4u * (unsigned)(m * ep.ldc + nb), 0, o);
                 } else if (n_ok && m < M) {
                     *reinterpret_cast<float4*>(ep.out + (size_t)m * ep.ldc + nb) = o;
                     if (ep.out_relu)
                         *reinterpret_cast<float4*>(ep.out_relu + (size_t)m * ep.ldc + nb) =
-                            make_float4(fmaxf(o.x, 0.f), fmaxf(o.y, 0.f), fmaxf(o.z, 0.f), fmaxf(o.w, 0.f));
+                            rpg::relu4(o);
                 }
             }
             __builtin_amdgcn_wave_barrier();
@@ -618,9 +618,9 @@ __device__ __forceinline__ void tile_epilogue(float* lds, const Epilogue& ep, in
                             v += ep.residual[res_off(ep, m) + n];
                             if (ep.residual2) v += ep.residual2[(size_t)ep.res2_idx[m] * ep.ldr + n];
                         }
-                        if (ep.relu) v = fmaxf(v, 0.f);
+                        if (ep.relu) v = rpg::relu(v);
                         ep.out[o] = v;
-                        if (ep.out_relu) ep.out_relu[o] = fmaxf(v, 0.f);
+                        if (ep.out_relu) ep.out_relu[o] = rpg::relu(v);
                     }
                 }
             }
@@ -687,10 +687,10 @@ __device__ __forceinline__ void streamk_finish_quad(const float4& s, const Epilo
         float4 v;
         v.x = s.x * sc.x + sh.x + rs.x; v.y = s.y * sc.y + sh.y + rs.y;
         v.z = s.z * sc.z + sh.z + rs.z; v.w = s.w * sc.w + sh.w + rs.w;
-        if (ep.relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+        if (ep.relu) v = rpg::relu4(v);
         *reinterpret_cast<float4*>(ep.out + o) = v;
         if (ep.out_relu)
-            *reinterpret_cast<float4*>(ep.out_relu + o) = make_float4(fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f));
+            *reinterpret_cast<float4*>(ep.out_relu + o) = rpg::relu4(v);
     } else {
         const float sv[4] = {s.x, s.y, s.z, s.w};
         for (int c = 0; c < 4 && n + c < N; ++c) {
@@ -699,9 +699,9 @@ __device__ __forceinline__ void streamk_finish_quad(const float4& s, const Epilo
                 v += ep.residual[res_off(ep, m) + n + c];
                 if (ep.residual2) v += ep.residual2[(size_t)ep.res2_idx[m] * ep.ldr + n + c];
             }
-            if (ep.relu) v = fmaxf(v, 0.f);
+            if (ep.relu) v = rpg::relu(v);
             ep.out[o + c] = v;
-            if (ep.out_relu) ep.out_relu[o + c] = fmaxf(v, 0.f);
+            if (ep.out_relu) ep.out_relu[o + c] = rpg::relu(v);
         }
     }
 }

@@ -117,8 +117,8 @@ __global__ __launch_bounds__(NT) void gather_add2_relu_kernel(const float4* __re
         const float4 b = pq[(size_t)hi[e] * (2 * d4) + d4 + c];
         const float4 bb = bias[c];
         float4 v;
-        v.x = fmaxf(a.x + b.x + bb.x, 0.f); v.y = fmaxf(a.y + b.y + bb.y, 0.f);
-        v.z = fmaxf(a.z + b.z + bb.z, 0.f); v.w = fmaxf(a.w + b.w + bb.w, 0.f);
+        v.x = rpg::relu(a.x + b.x + bb.x); v.y = rpg::relu(a.y + b.y + bb.y);
+        v.z = rpg::relu(a.z + b.z + bb.z); v.w = rpg::relu(a.w + b.w + bb.w);
         out[i] = v;
     }
 }
@@ -126,7 +126,7 @@ __global__ __launch_bounds__(NT) void gather_add2_relu_kernel(const float4* __re
 __global__ __launch_bounds__(NT) void relu_inplace_kernel(float4* __restrict__ x, long total) {
     for (long i = (long)blockIdx.x * NT + threadIdx.x; i < total; i += (long)gridDim.x * NT) {
         float4 v = x[i];
-        v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
+        v = rpg::relu4(v);
         x[i] = v;
     }
 }

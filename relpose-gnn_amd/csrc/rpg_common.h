@@ -32,6 +32,23 @@ void timing_end(int slot, double work, hipStream_t s, double executed = 0.0);
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// ---- NaN-propagating activation and pooling (the reference's torch semantics: relu(NaN) = NaN, max_pool2d propagates NaN) ----
+// fmaxf is IEEE maxNum: fmaxf(NaN, 0) = 0 swallows a NaN, and fmaxf(NaN, -inf) = -inf.  __builtin_elementwise_maximum is IEEE
+// 754-2019 maximum (NaN in -> NaN out, -0 < +0), one v_maximum3_f32 on gfx950.  Every ReLU and max-pool of the library goes
+// through these.  relu4_if, an optional ReLU, is ONE maximum per element, with 0 or -inf: under IEEE maximum -inf is the identity
+// for every input, NaN included (a select after the ReLU would add a v_cndmask per element to the convolution epilogues).
+__device__ __forceinline__ float nan_max(float a, float b) { return __builtin_elementwise_maximum(a, b); }
+__device__ __forceinline__ float nan_max3(float a, float b, float c) { return nan_max(nan_max(a, b), c); }
+__device__ __forceinline__ float relu(float y) { return nan_max(y, 0.f); }
+__device__ __forceinline__ float4 relu4(float4 v) { return make_float4(relu(v.x), relu(v.y), relu(v.z), relu(v.w)); }
+__device__ __forceinline__ float4 nan_max4(float4 a, float4 b) {
+    return make_float4(nan_max(a.x, b.x), nan_max(a.y, b.y), nan_max(a.z, b.z), nan_max(a.w, b.w));
+}
+__device__ __forceinline__ float4 relu4_if(bool on, float4 v) {
+    const float f = on ? 0.f : -__builtin_inff();
+    return nan_max4(v, make_float4(f, f, f, f));
+}
+
 
 // ---- internal launchers shared between the fine-grained C ABI and the composite forwards ----
 struct GatherSrc {

@@ -242,18 +242,18 @@ __global__ __launch_bounds__(ST_NT) void stem_pool_kernel(StemArgs a) {
                         float v[4];
 #pragma unroll
                         for (int xx = 0; xx < 4; ++xx) {
-                            const float t = fmaxf(acc[nf][4 * y + xx] + sh[nf], 0.f);
+                            const float t = rpg::relu(acc[nf][4 * y + xx] + sh[nf]);
                             v[xx] = rok[y] && cok[xx] ? t : 0.f;  // outside the image: 0, the identity of max over values >= 0
                         }
                         c[y][0] = v[0];
-                        c[y][1] = fmaxf(fmaxf(v[0], v[1]), v[2]);
-                        c[y][2] = fmaxf(v[2], v[3]);
+                        c[y][1] = rpg::nan_max3(v[0], v[1], v[2]);
+                        c[y][2] = rpg::nan_max(v[2], v[3]);
                     }
 #pragma unroll
                     for (int qi = 0; qi < 3; ++qi) {
                         const float m0 = c[0][qi];                                           // pooled row r - 1: block row 0
-                        const float m1 = fmaxf(fmaxf(c[0][qi], c[1][qi]), c[2][qi]);         // pooled row r: rows 0-2
-                        const float m2 = fmaxf(c[2][qi], c[3][qi]);                          // pooled row r + 1: rows 2-3
+                        const float m1 = rpg::nan_max3(c[0][qi], c[1][qi], c[2][qi]);        // pooled row r: rows 0-2
+                        const float m2 = rpg::nan_max(c[2][qi], c[3][qi]);                      // pooled row r + 1: rows 2-3
                         const float m[3] = {m0, m1, m2};
 #pragma unroll
                         for (int ri = 0; ri < 3; ++ri) {
@@ -274,8 +274,8 @@ __global__ __launch_bounds__(ST_NT) void stem_pool_kernel(StemArgs a) {
 #pragma unroll
                 for (int e = 0; e < 16; ++e) {
                     const uint4 cells = tab[l0 + (e & 3) + 8 * (e >> 2)];      // uniform over a half-wave: broadcast read
-                    const unsigned v0 = __float_as_uint(fmaxf(acc[0][e] + sh[0], 0.f));
-                    const unsigned v1 = __float_as_uint(fmaxf(acc[1][e] + sh[1], 0.f));
+                    const unsigned v0 = __float_as_uint(rpg::relu(acc[0][e] + sh[0]));
+                    const unsigned v1 = __float_as_uint(rpg::relu(acc[1][e] + sh[1]));
                     const unsigned co[4] = {cells.x, cells.y, cells.z, cells.w};
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
@@ -402,7 +402,7 @@ __global__ __launch_bounds__(SF_NT) __attribute__((amdgpu_waves_per_eu(2, 2))) v
                 const int mi = __builtin_bit_cast(int, mx[f][e]);
                 const float right = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(mi, mi, 0x101, 0xf, 0xf, false));   // lane i <- lane i + 1 (row of 16)
                 const float odd = __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(mi, 0x401f));                        // lane i <- lane i ^ 16
-                r[e] = fmaxf(fmaxf(mx[f][e], right), odd);
+                r[e] = rpg::nan_max3(mx[f][e], right, odd);
             }
             if (l < nq) {
                 float* o = out_n + ((size_t)py * a.Wp + Q0 + l) * 64 + 32 * f;
@@ -410,8 +410,8 @@ __global__ __launch_bounds__(SF_NT) __attribute__((amdgpu_waves_per_eu(2, 2))) v
                 for (int g = 0; g < 4; ++g) {
                     const float4 sh = *reinterpret_cast<const float4*>(shl + 32 * (nf + f) + 8 * g + 4 * h);
                     float4 v;
-                    v.x = fmaxf(r[4 * g + 0] + sh.x, 0.f); v.y = fmaxf(r[4 * g + 1] + sh.y, 0.f);
-                    v.z = fmaxf(r[4 * g + 2] + sh.z, 0.f); v.w = fmaxf(r[4 * g + 3] + sh.w, 0.f);
+                    v.x = rpg::relu(r[4 * g + 0] + sh.x); v.y = rpg::relu(r[4 * g + 1] + sh.y);
+                    v.z = rpg::relu(r[4 * g + 2] + sh.z); v.w = rpg::relu(r[4 * g + 3] + sh.w);
                     *reinterpret_cast<float4*>(o + 8 * g) = v;
                 }
             }
@@ -475,7 +475,7 @@ __global__ __launch_bounds__(SF_NT) __attribute__((amdgpu_waves_per_eu(2, 2))) v
                     _Pragma("unroll") for (int e = 0; e < 16; ++e) mx[f][e] = acc[f][e];                                    \
             } else {                                                                                                           \
                 _Pragma("unroll") for (int f = 0; f < NFH; ++f)                                                                \
-                    _Pragma("unroll") for (int e = 0; e < 16; ++e) mx[f][e] = fmaxf(mx[f][e], acc[f][e]);                   \
+                    _Pragma("unroll") for (int e = 0; e < 16; ++e) mx[f][e] = rpg::nan_max(mx[f][e], acc[f][e]);           \
             }                                                                                                                  \
             if ((R) & 1) {                                                                                                     \
                 emit((oy - 1) >> 1);                                                                                           \

@@ -185,7 +185,7 @@ __global__ __launch_bounds__(SB_NT) __attribute__((amdgpu_waves_per_eu(3, 3))) v
                         const f32x4 sh = *reinterpret_cast<const f32x4*>(aff + 64 + 32 * nf + 8 * g + 4 * h);
                         bf16x4 v;
 #pragma unroll
-                        for (int k = 0; k < 4; ++k) v[k] = (__bf16)fmaxf(fmaf(acc[nf][4 * g + k], sc[k], sh[k]), 0.f);
+                        for (int k = 0; k < 4; ++k) v[k] = (__bf16)rpg::relu(fmaf(acc[nf][4 * g + k], sc[k], sh[k]));
                         *reinterpret_cast<bf16x4*>(cp + (((4 * nf + g) ^ (pl & 7)) << 4)) = v;
                     }
             }
@@ -194,7 +194,8 @@ __global__ __launch_bounds__(SB_NT) __attribute__((amdgpu_waves_per_eu(3, 3))) v
         // ---- phase 3: max-pool 3x3 / 2 from the LDS tile straight to global memory, 8 channels (16 bytes) per thread and cell.
         // Pooled cell (r, q) of the tile covers convolution rows 2r .. 2r + 2, columns 2q .. 2q + 2 (tile-local); positions outside
         // the image are replaced by a valid neighbour of the same window (a duplicate does not change a maximum), so no masks.
-        // Post-ReLU values are >= 0: the unsigned 16-bit maximum of the bit patterns is the bf16 maximum.
+        // Post-ReLU values are +0, positive or NaN: the unsigned 16-bit maximum of the bit patterns is the bf16 maximum, and a NaN of
+        // either sign (0x7F81.. / 0xFF81..) lies above every other pattern, so it wins as torch's max_pool2d makes it.
         {
             // valid range of tile-local convolution rows / columns: the image's [0, Hc) x [0, Wc)
             const int ylo = cy0 < 0 ? -cy0 : 0, yhi = (a.Hc - 1 - cy0) < (CR - 1) ? (a.Hc - 1 - cy0) : (CR - 1);
@@ -247,9 +248,9 @@ __global__ __launch_bounds__(SB_NT) __attribute__((amdgpu_waves_per_eu(3, 3))) v
 //     channel (3 operands instead of 11), straight from global memory into the lanes that need it (raw buffer loads, 8 consecutive
 //     columns per lane; neighbouring lanes overlap and are served by the vector L1), one row ahead of its use;
 //   * the weights are the MFMA's A operand and stay in registers (12 x 4 VGPRs per 32 channels): accumulators come out
-//     pixel-major, BatchNorm in fp32, rounded to bf16, and the 3 x 3 / 2 max-pool happens IN REGISTERS: vertically a running
-//     maximum over the rows of a pooled row (v_pk_max_i16 on the bf16 bits against a maximum that starts at +0: that is the ReLU,
-//     and bf16 rounding is monotone, so the bits equal round(max)); horizontally the lanes are ordered even columns | odd columns,
+//     pixel-major, BatchNorm + ReLU in fp32, rounded to bf16, and the 3 x 3 / 2 max-pool happens IN REGISTERS: vertically a running
+//     maximum over the rows of a pooled row (v_pk_max_i16 on the bf16 bits of values that are +0, positive or a NaN with its sign
+//     cleared (ss_relu_pk), and bf16 rounding is monotone, so the bits equal round(max)); horizontally the lanes are ordered even columns | odd columns,
 //     so the three columns of a pooled cell are this lane, its right neighbour (DPP row_shl:1) and lane ^ 16 (ds_swizzle);
 //   * edges: image columns outside [0, W) are masked to zero after the conversion in the first / last strip only (lane-constant
 //     masks), rows outside [0, H) in a wave-uniform slow path; convolution columns outside [0, Wc) are clamped duplicates of a
@@ -263,6 +264,12 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ unsigned pk2_bf16(float lo, float hi) {
     const f32x2 v = {lo, hi};
     return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
+}
+// BatchNorm + ReLU of two accumulators, rounded to a bf16 pair, for the strip stem's signed 16-bit pooling maximum: the NaN-propagating
+// ReLU leaves +0, a positive value or a NaN of either sign; clearing the two sign bits makes every NaN positive (0xFFC0 is -64 as
+// int16 and would lose to +0; a positive NaN pattern is above +inf's) and changes nothing else.
+__device__ __forceinline__ unsigned ss_relu_pk(float a0, float s0, float h0, float a1, float s1, float h1) {
+    return pk2_bf16(rpg::relu(fmaf(a0, s0, h0)), rpg::relu(fmaf(a1, s1, h1))) & 0x7FFF7FFFu;
 }
 constexpr int SS_NT = 256;
 constexpr int SS_TP = 15;                  // pooled columns per strip: 2 * 15 + 1 = 31 of the 32 convolution columns
@@ -464,8 +471,8 @@ __global__ __launch_bounds__(SS_NT) __attribute__((amdgpu_waves_per_eu(NF == 1 ?
                 _Pragma("unroll") for (int g = 0; g < 4; ++g) {                                                                \
                     const f32x4 sc = *reinterpret_cast<const f32x4*>(aff + 32 * (nf + f) + 8 * g + 4 * h);                     \
                     const f32x4 sh = *reinterpret_cast<const f32x4*>(aff + 64 + 32 * (nf + f) + 8 * g + 4 * h);                \
-                    pv[f][2 * g] = pk2_bf16(fmaf(acc[f][4 * g + 0], sc[0], sh[0]), fmaf(acc[f][4 * g + 1], sc[1], sh[1]));     \
-                    pv[f][2 * g + 1] = pk2_bf16(fmaf(acc[f][4 * g + 2], sc[2], sh[2]), fmaf(acc[f][4 * g + 3], sc[3], sh[3])); \
+                    pv[f][2 * g] = ss_relu_pk(acc[f][4 * g + 0], sc[0], sh[0], acc[f][4 * g + 1], sc[1], sh[1]);                 \
+                    pv[f][2 * g + 1] = ss_relu_pk(acc[f][4 * g + 2], sc[2], sh[2], acc[f][4 * g + 3], sc[3], sh[3]);             \
                 }                                                                                                              \
                 _Pragma("unroll") for (int i = 0; i < 8; ++i) mx[f][i] = pk_max(mx[f][i], pv[f][i]);                           \
             }                                                                                                                  \

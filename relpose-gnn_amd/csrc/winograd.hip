@@ -122,7 +122,7 @@ __device__ __forceinline__ void wino43_epilogue(const f32x16 (&acc)[P], float* s
 #pragma unroll
             for (int it = 0; it < 8; ++it) rs[half][it] = f4zero();
     }
-    const float floor_v = ep.relu ? 0.f : -INFINITY;        // ReLU without a branch per store
+    const bool relu_on = ep.relu;                          // uniform: ReLU or identity, NaN kept either way
     // output transform y = AT m (AT of F(4,3), points 0, +-1, +-2, inf) on pairs of elements
     f32x2 y[4][8];
 #pragma unroll
@@ -157,7 +157,7 @@ __device__ __forceinline__ void wino43_epilogue(const f32x16 (&acc)[P], float* s
             const f32x2 r0 = {rs[half][it].x, rs[half][it].y}, r1 = {rs[half][it].z, rs[half][it].w};
             f32x2 o0 = f32x2{v.x, v.y} * f32x2{sc.x, sc.y} + f32x2{sh.x, sh.y} + r0;
             f32x2 o1 = f32x2{v.z, v.w} * f32x2{sc.z, sc.w} + f32x2{sh.z, sh.w} + r1;
-            const float4 yv = make_float4(fmaxf(o0.x, floor_v), fmaxf(o0.y, floor_v), fmaxf(o1.x, floor_v), fmaxf(o1.y, floor_v));
+            const float4 yv = rpg::relu4_if(relu_on, make_float4(o0.x, o0.y, o1.x, o1.y));
             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, yv), ro, voff[half][it], 0, 0);
         }
         __builtin_amdgcn_wave_barrier();
@@ -207,7 +207,7 @@ __device__ __forceinline__ void wino43_epilogue_lean_body(const f32x16 (&acc)[P]
     };
     int relu_i = ep.relu;                               // opaque: hoisted out of the caller's tile loop, the select below
     asm volatile("" : "+s"(relu_i));                     // became a VGPR that was spilled around the K loop
-    const float floor_v = relu_i ? 0.f : -INFINITY;
+    const bool relu_on = relu_i != 0;
     float4 rs[2][8];
     auto load_res = [&](int half) {
         if (RES) {
@@ -253,7 +253,7 @@ __device__ __forceinline__ void wino43_epilogue_lean_body(const f32x16 (&acc)[P]
                 o0 += f32x2{rs[half][it].x, rs[half][it].y};       // the compiler wait for ALL outstanding stores and loads
                 o1 += f32x2{rs[half][it].z, rs[half][it].w};       // before overwriting registers they might still target)
             }
-            const float4 yv = make_float4(fmaxf(o0.x, floor_v), fmaxf(o0.y, floor_v), fmaxf(o1.x, floor_v), fmaxf(o1.y, floor_v));
+            const float4 yv = rpg::relu4_if(relu_on, make_float4(o0.x, o0.y, o1.x, o1.y));
 #ifdef RPG_ABL_NOSTORE                     // ablation (tools/probes/wino_ablate.sh): only a value that never occurs is stored
             if (yv.x == 1234.5678f)
 #endif
@@ -574,7 +574,7 @@ __device__ __forceinline__ void wino43_finish_quad(const float4& s, const Epi& e
     float4 y;
     y.x = s.x * sc.x + sh.x + rs.x; y.y = s.y * sc.y + sh.y + rs.y;
     y.z = s.z * sc.z + sh.z + rs.z; y.w = s.w * sc.w + sh.w + rs.w;
-    if (ep.relu) { y.x = fmaxf(y.x, 0.f); y.y = fmaxf(y.y, 0.f); y.z = fmaxf(y.z, 0.f); y.w = fmaxf(y.w, 0.f); }
+    if (ep.relu) y = rpg::relu4(y);
     *reinterpret_cast<float4*>(ep.out + o) = y;
 }
 
