@@ -175,6 +175,18 @@ int rpg_resnet_forward_bf16_xbf16(const void* const* tensors, int n_tensors, con
 int rpg_graph_prepare(const int64_t* src, const int64_t* dst, int64_t node_offset, int e, int n, int64_t* ends,
                       int32_t* rowptr, int32_t* cursor, int32_t* perm, int32_t* status, void* stream);
 
+/* Node assembly from a pre-encoded map (the map path, PoseNetX_R2.forward_map): `x = torch.cat((query, db_batch))` of
+ * dataset_7Scenes_multi.py:340-345 on encoder OUTPUT -- graph g is its query followed by its K database images, in
+ * retrieval order:
+ *   out[g*(K+1)]       = query_feat[g]                       query_feat [g][d]
+ *   out[g*(K+1) + j]   = map_feat[neighbours[g][j-1]]        map_feat [m][d], neighbours [g][k] int64, j = 1..K
+ * Index contract of rpg_graph_prepare: status [1] += number of neighbours outside [0, m) (the caller zeroes it; the host
+ * mirror raises IndexError on a non-zero count); such rows are clamped into [0, m), so nothing reads out of bounds.
+ * d % 4 == 0, 16-byte aligned features (RPG_ERR_BAD_ARG otherwise); row offsets are 64-bit (maps past 2 GiB).
+ * One launch, no allocation, no synchronisation (graph-capturable).                                            */
+int rpg_gather_graph_nodes_f32(const float* query_feat, const float* map_feat, const int64_t* neighbours, int g, int k,
+                               int64_t m, int d, float* out, int32_t* status, void* stream);
+
 /* torch_cluster.knn_graph(x, k, batch, loop=False, flow='source_to_target') (posenet.py:1043-1050): for every node
  * the k nearest OTHER nodes of its graph by squared Euclidean distance (k+1 nearest including itself by
  * (distance, index), self match dropped).  x [n][d]; batch [n] int64 graph id per node, nodes of a graph contiguous,

@@ -503,3 +503,140 @@ def load_pose_stats(path):
     """Cambridge translation mean / std file, two rows of three numbers (test.py:126-130)."""
     m, s = np.loadtxt(path)
     return m, s
+
+
+@torch.no_grad()
+def relocalize(model, fmap, queries: torch.Tensor, neighbours, micro_batch: int = 64, pose_m=(0.0, 0.0, 0.0),
+               pose_s=(1.0, 1.0, 1.0), ref_node: int = 0, stats: Optional[dict] = None, targets=None,
+               bf16_input: Optional[bool] = None):
+    """The evaluation stream of the map path (``PoseNetX_R2.forward_map``): query g's graph is the query followed by the map
+    rows ``neighbours[g]`` (its retrieved database images, dataset_7Scenes_multi.py:340-345).  Single process.
+
+    ``queries``: [G, ...] images as ``forward_map`` takes them (processed fp32 / bf16, or uint8 frames), on the host or on the
+    map's GPU; ``neighbours``: int64 [G, K].  Only the queries cross the host link, through ``_InputPipeline`` as in
+    ``evaluate_stream`` (pinned sources go out directly, pageable ones are staged, bf16 rounding by the same rules), micro-batch
+    i + 1 staged while micro-batch i runs and micro-batch i - 1 is post-processed.
+
+    Returns, per query, the predicted pose [G, 7] by the rule of test.py:227-251 (``query_pose``), the "target" of the
+    reference edge's source node being ``fmap.poses[neighbours[g][src - 1]]``; with ``targets`` ([G, 6], the queries' own
+    ``[t, log q]``) an ``EvalResult`` instead (its ``pred_poses`` are those poses).  A map without poses gives the raw
+    ``(abs_pose [G*(K+1), 6], rel_pose [E, 6])`` host tensors.  ``stats`` as in ``evaluate_stream``."""
+    import time
+    from .graph import Data, fc_edge_index
+    device = fmap.device
+    if not torch.is_tensor(queries):
+        raise TypeError("relocalize: queries must be a tensor [G, ...]")
+    nb = torch.as_tensor(neighbours)
+    if nb.dtype != torch.int64 or nb.dim() != 2 or nb.shape[0] != queries.shape[0] or nb.shape[1] < 1:
+        raise ValueError(f"relocalize: neighbours must be int64 [G, K >= 1] with G = {queries.shape[0]} queries, got "
+                         f"{tuple(nb.shape)} {nb.dtype}")
+    if micro_batch < 1:
+        raise ValueError("relocalize: micro_batch must be >= 1")
+    g_all, kk = nb.shape
+    n_per = kk + 1
+    nb_dev = nb.to(device).contiguous()
+    nb_h = nb.cpu().numpy()
+    pose_m, pose_s = np.asarray(pose_m, dtype=np.float64), np.asarray(pose_s, dtype=np.float64)
+    poses_h = None if fmap.poses is None else fmap.poses.cpu().numpy().astype(np.float64)
+    targ_h = None if targets is None else np.asarray(torch.as_tensor(targets).cpu(), dtype=np.float64).reshape(g_all, 6)
+    fc_edges = fc_edge_index(n_per).numpy()
+
+    # the staging dtype: uint8 frames as they are; otherwise the rule of _MicroBatchRunner (bf16 for the bf16 encoder, except
+    # pinned fp32 sources sent as they are when this rank cannot spend >= 8 rounding threads)
+    on_host = not queries.is_cuda
+    want_bf16 = bf16_input if bf16_input is not None else getattr(model, "accepts_bf16_input", False)
+    dtype = torch.bfloat16 if want_bf16 else torch.float32
+    pinned_direct = bf16_input is None and not (dtype != torch.float32 and staging_workers(False, 1) >= 8)
+    if queries.dtype == torch.uint8:
+        dtype = torch.uint8
+    elif pinned_direct and dtype != torch.float32 and queries.dtype == torch.float32 and on_host and queries.is_pinned():
+        dtype = torch.float32
+    row_shape = tuple(queries.shape[1:])
+    width = int(np.prod(row_shape))
+    pipe = _InputPipeline(device, min(micro_batch, g_all), width, dtype) if on_host else None
+
+    def begin(i):
+        b0 = i * micro_batch
+        xq = queries[b0:b0 + micro_batch]
+        # the chunk cut in pieces, one per staging thread (a pinned source still goes out as one copy per piece)
+        w = max(1, min(pipe.workers, xq.shape[0]))
+        step = -(-xq.shape[0] // w)
+        return pipe.stage_begin(i & 1, [Data(x=xq[j:j + step]) for j in range(0, xq.shape[0], step)])
+
+    raw_abs, raw_rel, preds, targs = [], [], [], []
+    h2d = 0
+
+    def finish(item):
+        b0, host_abs, host_rel, host_ei, ev = item
+        ev.synchronize()
+        model.check_edge_index(wait=False)       # this micro-batch's counters were copied before `ev`
+        if poses_h is None:
+            raw_abs.append(host_abs)
+            raw_rel.append(host_rel)
+            return
+        rel = host_rel.numpy()
+        n_g = host_abs.shape[0] // n_per
+        if host_ei is not None:                  # a model-built (kNN) edge list
+            ei = host_ei.numpy()
+            first, per_graph = edges_per_graph(ei, [n_per] * n_g)
+            cut = [(per_graph[j], ei[:, per_graph[j]] - first[j]) for j in range(n_g)]
+        else:
+            e_g = fc_edges.shape[1]
+            cut = [(slice(j * e_g, (j + 1) * e_g), fc_edges) for j in range(n_g)]
+        for j, (cols, edges) in enumerate(cut):
+            g = b0 + j
+            target = np.zeros((n_per, 6))
+            target[1:] = poses_h[nb_h[g]]
+            if targ_h is not None:
+                target[0] = targ_h[g]
+            p, t = query_pose(rel[cols], target, edges, pose_m, pose_s, ref_node)
+            preds.append(p)
+            targs.append(t)
+
+    t0 = time.perf_counter()
+    n_mb = -(-g_all // micro_batch)
+    pending = None
+    handle = begin(0) if on_host and n_mb else None
+    for i in range(n_mb):
+        b0, b1 = i * micro_batch, min(g_all, (i + 1) * micro_batch)
+        if on_host:
+            x = pipe.stage_end(handle)
+            h2d += x.numel() * x.element_size()
+            x = x.view(b1 - b0, *row_shape) if dtype == torch.uint8 else x
+            pipe.acquire(i & 1)
+        else:
+            x = queries[b0:b1]
+        ab, rel, ei = model.forward_map(x, nb_dev[b0:b1], fmap)
+        if on_host:
+            pipe.release(i & 1)
+        host_abs = torch.empty(ab.shape, dtype=ab.dtype, pin_memory=True)
+        host_abs.copy_(ab, non_blocking=True)
+        host_rel = torch.empty(rel.shape, dtype=rel.dtype, pin_memory=True)
+        host_rel.copy_(rel, non_blocking=True)
+        host_ei = None
+        if model.knn > 0:
+            host_ei = torch.empty(ei.shape, dtype=ei.dtype, pin_memory=True)
+            host_ei.copy_(ei, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        if on_host and i + 1 < n_mb:
+            handle = begin(i + 1)
+        if pending is not None:
+            finish(pending)
+        pending = (b0, host_abs, host_rel, host_ei, ev)
+    if pending is not None:
+        finish(pending)
+    model.check_edge_index()
+    if stats is not None:
+        stats["local_seconds"] = time.perf_counter() - t0
+        stats["h2d_bytes"] = h2d
+        stats["micro_batches"] = n_mb
+        stats["staged_bytes"] = pipe.staged_bytes if pipe else 0
+        stats["direct_bytes"] = pipe.direct_bytes if pipe else 0
+        stats["staging_workers"] = pipe.workers if pipe else 0
+    if poses_h is None:
+        return torch.cat(raw_abs), torch.cat(raw_rel)
+    pred = np.stack(preds) if preds else np.zeros((0, 7))
+    if targ_h is None:
+        return pred
+    return errors(pred, np.stack(targs) if targs else np.zeros((0, 7)))

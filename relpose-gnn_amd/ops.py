@@ -354,6 +354,41 @@ def edge_concat_gather(x: torch.Tensor, edge_index: torch.Tensor) -> torch.Tenso
     return out
 
 
+def gather_graph_nodes(query_feat: torch.Tensor, map_feat: torch.Tensor, neighbours: torch.Tensor,
+                       out: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Node features of G graphs, each its query followed by K map rows (rpg_gather_graph_nodes_f32): query_feat [G, d],
+    map_feat [M, d], neighbours int64 [G, K] -> [G*(K+1), d].  A neighbour outside [0, M) is counted into ``status`` (int32
+    device tensor, accumulates; its row is clamped) -- with ``status=None`` the count is read back here (one synchronisation)
+    and a non-zero count raises IndexError."""
+    q, mp, nb = _req(query_feat, "query_feat"), _req(map_feat, "map_feat"), _req(neighbours, "neighbours", torch.int64)
+    if q.dim() != 2 or mp.dim() != 2 or nb.dim() != 2:
+        raise ValueError("gather_graph_nodes: query_feat [G, d], map_feat [M, d] and neighbours [G, K] must be 2-D")
+    (g, d), (m, dm), (gn, k) = q.shape, mp.shape, nb.shape
+    if dm != d or gn != g:
+        raise ValueError(f"gather_graph_nodes: shapes do not agree: query_feat {tuple(q.shape)}, map_feat {tuple(mp.shape)}, "
+                         f"neighbours {tuple(nb.shape)}")
+    if g == 0 or k == 0 or m == 0 or d % 4:
+        raise ValueError(f"gather_graph_nodes: needs G >= 1, K >= 1, M >= 1 and d % 4 == 0 (G={g}, K={k}, M={m}, d={d})")
+    if mp.device != q.device or nb.device != q.device:
+        raise RuntimeError("gather_graph_nodes: query_feat, map_feat and neighbours must be on the same GPU")
+    if out is None:
+        out = torch.empty((g * (k + 1), d), dtype=torch.float32, device=q.device)
+    elif out.shape != (g * (k + 1), d) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != q.device:
+        raise ValueError(f"gather_graph_nodes: out must be a contiguous fp32 [{g * (k + 1)}, {d}] tensor on the inputs' GPU")
+    sync = status is None
+    if sync:
+        status = torch.zeros(1, dtype=torch.int32, device=q.device)
+    elif status.dtype != torch.int32 or status.device != q.device or status.numel() < 1:
+        raise ValueError("gather_graph_nodes: status must be an int32 tensor on the inputs' GPU")
+    L.check(L.lib().rpg_gather_graph_nodes_f32(_p(q), _p(mp), _p(nb), g, k, m, d, _p(out), status.data_ptr(), _stream()),
+            "gather_graph_nodes")
+    if sync:
+        bad = int(status.item())
+        if bad:
+            raise IndexError(f"neighbours has {bad} index(es) outside the map's rows [0, {m})")
+    return out
+
+
 def linear_gather(sources: Sequence[Tuple[torch.Tensor, Optional[torch.Tensor]]], weight: torch.Tensor,
                   bias: Optional[torch.Tensor], m: int, residual: Optional[torch.Tensor] = None, relu: bool = False) -> torch.Tensor:
     """out[m] = act(cat_k(a_k[idx_k[m]]) @ weight.T + bias (+ residual)); sources = [(a_k, idx_k or None), ...]."""

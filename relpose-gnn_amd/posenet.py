@@ -137,13 +137,16 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
         self._gnn_dtype = "f32"
         self._extra: Dict[str, torch.Tensor] = {}
         self.index_check = "deferred"            # "deferred" | "sync" (see the module docstring)
-        self._status: Optional[torch.Tensor] = None          # device int32 [8]: bad-edge counters, one per stream slot
+        # device int32 [16]: bad-edge counters, one per stream slot, then the map path's bad-neighbour counters, one per slot
+        self._status: Optional[torch.Tensor] = None
         self._status_host: Optional[torch.Tensor] = None     # pinned mirror
         self._status_event: Optional[torch.cuda.Event] = None
         self._status_pending = False
         # optional frames.FrameTransform: with it forward() also takes uint8 frames data.x [n, H, W, 3] (RGB, HWC) on the GPU and
         # runs the reference's image transform there (a plain attribute: not a module, parameter or buffer -- state_dict unchanged)
         self.frame_transform = None
+        self._enc_digest: Optional[str] = None        # encoder_digest() cache (cleared wherever the packed weights are)
+        self._map_graphs: Dict[tuple, Tuple[torch.Tensor, torch.Tensor]] = {}   # forward_map: (G, K+1, device) -> (edges, batch)
 
     @property
     def encoder_dtype(self) -> str:
@@ -160,6 +163,7 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
     @encoder_dtype.setter
     def encoder_dtype(self, dtype: str) -> None:
         self._enc.set_dtype(dtype)
+        self._enc_digest = None
 
     @property
     def gnn_dtype(self) -> str:
@@ -183,6 +187,7 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
         self._gnn_bf16, self._gnn_bf16_ptrs = None, None
         self._extra = {}
         self._ws_pool.clear()
+        self._enc_digest = None
 
     def _apply(self, fn, *a, **k):
         if hasattr(self, "_enc"):
@@ -219,18 +224,25 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
     # ---- edge_index validation without a host synchronisation ----------------------------------------------------
     def _status_buffers(self, dev) -> torch.Tensor:
         if self._status is None or self._status.device != dev:
-            self._status = torch.zeros(8, dtype=torch.int32, device=dev)
-            self._status_host = torch.zeros(8, dtype=torch.int32).pin_memory()
+            self._status = torch.zeros(16, dtype=torch.int32, device=dev)
+            self._status_host = torch.zeros(16, dtype=torch.int32).pin_memory()
             self._status_event = torch.cuda.Event()
             self._status_pending = False
         return self._status
 
-    def _raise_bad_edges(self, bad: int):
+    def _raise_bad_edges(self, counts: torch.Tensor):
+        """``counts``: host int32 [16], the bad-edge counters (slots 0..7) and forward_map's bad-neighbour counters (8..15)."""
+        edges, nbrs = int(counts[:8].sum()), int(counts[8:].sum())
         self._status.zero_()                      # (stream-ordered: after every forward issued so far)
         self._status_host.zero_()                 # the mirror too, or a look without waiting would report it again
         self._status_pending = False
-        raise IndexError(f"edge_index has {bad} edge(s) with a node id outside its graph group / [0, N) "
-                         "(detected on the device; with index_check='deferred' this refers to an EARLIER forward call)")
+        what = []
+        if edges:
+            what.append(f"edge_index has {edges} edge(s) with a node id outside its graph group / [0, N)")
+        if nbrs:
+            what.append(f"neighbours has {nbrs} index(es) outside the feature map's rows [0, M)")
+        raise IndexError("; ".join(what) + " (detected on the device; with index_check='deferred' this refers to an EARLIER "
+                         "forward call)")
 
     def _poll_status(self, block: bool) -> None:
         """Look at the counters of the previous call(s) if their copy has landed (or wait for it when ``block``)."""
@@ -241,9 +253,8 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
         elif not self._status_event.query():
             return
         self._status_pending = False
-        bad = int(self._status_host.sum())
-        if bad:
-            self._raise_bad_edges(bad)
+        if int(self._status_host.sum()):
+            self._raise_bad_edges(self._status_host)
 
     def publish_status(self) -> None:
         """For callers that replay a captured forward (graphed.GraphedForward): the replayed kernels keep counting bad
@@ -256,9 +267,9 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
         if torch.cuda.is_current_stream_capturing():
             return                                # a captured forward is validated by its eager warm-up call
         if self.index_check == "sync":
-            bad = int(self._status.sum().item())
-            if bad:
-                self._raise_bad_edges(bad)
+            counts = self._status.cpu()
+            if int(counts.sum()):
+                self._raise_bad_edges(counts)
             return
         self._status_host.copy_(self._status, non_blocking=True)
         self._status_event.record()
@@ -275,10 +286,9 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
             self._poll_status(block=True)
             return
         if self._status_host is not None:
-            bad = int(self._status_host.sum())
-            if bad:
+            if int(self._status_host.sum()):
                 self._status_event.synchronize()
-                self._raise_bad_edges(bad)
+                self._raise_bad_edges(self._status_host)
 
     def _gnn_call(self, lib, feat, esrc_ptr, edst_ptr, node_off, n, e, abs_pose, rel_pose, node_f, edge_f, status, slot):
         d = feat.shape[1]
@@ -394,14 +404,9 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
                                "(there is no CPU fallback)")
         if not torch.is_tensor(edge_index) or edge_index.device != x.device:
             raise RuntimeError("data.edge_index must be a tensor on the same GPU as data.x")
-        if x.dtype == torch.uint8 and self.frame_transform is not None:
-            x = self._transform_frames(x)
-        if x.dtype != torch.float32 and not (x.dtype == torch.bfloat16 and self.accepts_bf16_input):
-            raise TypeError(f"data.x must be float32 (the reference's input dtype; bf16 images are taken by the bf16 encoder "
-                            f"only), got {x.dtype}")
+        x = self._encoder_input(x, "data.x")                                      # posenet.py:1035
         lib = _L.lib()
         self._poll_status(block=False)            # bad-edge report of the previous call, if it has landed
-        x = x.view(x.size(0), 3, self.input_img_height, -1)                       # posenet.py:1035
         # all weight packing happens here, on the caller's stream, BEFORE any side stream is forked off it
         self._pack_gnn()
         self._enc.ensure_packed(self.feature_extractor.state_dict, "", x.device)
@@ -414,9 +419,14 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
         fast = self.use_AP and not self.use_attention and k is None and knn_ok and not (self.knn > 0 and self._gnn_dtype == "bf16")
         parts = self._partition(data, x.size(0), edge_index.size(1) if self.knn <= 0 else None) if fast else None
         if parts is not None and edge_index.dtype == torch.int64 and edge_index.dim() == 2 and edge_index.is_contiguous():
-            return self._forward_streams(lib, x, edge_index, parts, batch_t)
+            enc_sd = self.feature_extractor.state_dict
+            return self._forward_streams(lib, lambda n0, n1, wkey: self._enc.run(enc_sd, "", x[n0:n1], slot=wkey), x.size(0),
+                                         x.device, edge_index, parts, batch_t)
         feat = self._encode_small(x)                                              # posenet.py:1037
+        return self._forward_tail(lib, feat, edge_index, getattr(data, "batch", None), k)
 
+    def _forward_tail(self, lib, feat, edge_index, batch, k):
+        """Everything after the encoder on one stream (posenet.py:1040-1091): feat [N, d] are the node features."""
         n, d = feat.shape
         if self.use_attention:                                                    # posenet.py:1040-1041
             ex = self._extra
@@ -424,7 +434,6 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
             feat = ops.linear_gather([(y, None)], ex["att_w"], ex["att_b"], n, residual=feat)
 
         edge_index_knn = None                                                     # posenet.py:1043-1050
-        batch = getattr(data, "batch", None)
         if k is not None:
             edge_index_knn = ops.knn_graph(feat, int(k), batch)
         if self.knn > 0:
@@ -464,6 +473,110 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
             abs_pose = ops.linear_gather([(node_f, lo), (node_f, hi)], self._extra["heads_pair_w"],
                                          self._extra["heads_pair_b"], e)
         return abs_pose, rel_pose, (edge_index_knn if k is not None else edge_index)
+
+    # ---- the map path: database images encoded once (featmap.FeatureMap), queries encoded per call ---------------------
+    def encoder_digest(self) -> str:
+        """SHA-256 of the encoder's state dict (names, dtypes, shapes, bytes): what a FeatureMap is bound to.  Computed once (one
+        copy of the weights to the host) and cached; cleared wherever the packed weights are (load_state_dict, refresh_packed,
+        _apply, the encoder_dtype setter)."""
+        if self._enc_digest is None:
+            import hashlib
+            h = hashlib.sha256()
+            for name, v in self.feature_extractor.state_dict().items():
+                t = v.detach().cpu().contiguous()
+                h.update(f"{name}|{t.dtype}|{tuple(t.shape)}|".encode())
+                h.update(t.reshape(-1).view(torch.uint8).numpy().tobytes())
+            self._enc_digest = h.hexdigest()
+        return self._enc_digest
+
+    @torch.no_grad()
+    def encode(self, x: torch.Tensor) -> torch.Tensor:
+        """Encoder features [n, feat_dim] fp32 of images ``x`` (what ``forward`` runs at posenet.py:1037, before the optional
+        model-level attention): fp32 processed images [n, 3*H*W] / [n, 3, H, W], bf16 ones for the bf16 encoder, or uint8 frames
+        [n, H, W, 3] through ``frame_transform``; on the GPU."""
+        if not torch.is_tensor(x) or not x.is_cuda:
+            raise RuntimeError("encode: the images must be a tensor on the GPU (there is no CPU fallback)")
+        if x.size(0) == 0:
+            raise ValueError("encode: no images")
+        x = self._encoder_input(x, "images")
+        self._enc.ensure_packed(self.feature_extractor.state_dict, "", x.device)
+        return self._encode_small(x)
+
+    def _map_graph(self, g: int, n_per: int, dev) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(edge_index [2, G * n(n-1)], batch [G * n]) of G fully-connected n-node graphs on ``dev``: fc_batch's order."""
+        key = (g, n_per, str(dev))
+        hit = self._map_graphs.get(key)
+        if hit is None:
+            from .graph import fc_batch
+            b = fc_batch(torch.empty((g * n_per, 0)), n_per)
+            hit = (b.edge_index.to(dev), b.batch.to(dev))
+            if len(self._map_graphs) >= 16:
+                self._map_graphs.clear()
+            self._map_graphs[key] = hit
+        return hit
+
+    @torch.no_grad()
+    def forward_map(self, queries: torch.Tensor, neighbours: torch.Tensor, fmap, k=None):
+        """The forward of G graphs, each query g followed by the K database images ``neighbours[g]`` of the feature map ``fmap``
+        (dataset_7Scenes_multi.py:340-345) -- with only the G queries through the encoder.  Returns what
+        ``forward(fc_batch(assembled, K + 1), k)`` returns for the assembled images: (abs_pose [G*(K+1), 6], rel_pose [E, 6],
+        edge_index [2, E]), fully-connected edges per graph in fc_edge_index order, or the kNN graph over the assembled node
+        features with ``knn > 0`` / ``k``.  ``queries``: images as ``encode`` takes them; ``neighbours``: int64 [G, K] on the
+        same GPU, K >= 1, rows of ``fmap`` (an index outside [0, M) raises IndexError under ``index_check``, as a bad edge does).
+        Every flag of ``forward`` applies; ``fmap.check(self)`` refuses a map of other encoder weights or precision."""
+        if not torch.is_tensor(queries) or not torch.is_tensor(neighbours):
+            raise TypeError("forward_map: queries and neighbours must be tensors")
+        if neighbours.dtype != torch.int64 or neighbours.dim() != 2:
+            raise TypeError(f"forward_map: neighbours must be an int64 tensor [G, K] (rows of the feature map per query), got "
+                            f"{neighbours.dtype} {tuple(neighbours.shape)}")
+        g, kk = neighbours.shape
+        if kk < 1:
+            raise ValueError("forward_map: neighbours needs K >= 1 database images per query")
+        if g < 1 or queries.size(0) != g:
+            raise ValueError(f"forward_map: {queries.size(0)} queries but neighbours has {g} rows")
+        if not queries.is_cuda:
+            raise RuntimeError("forward_map: queries must be on the GPU (there is no CPU fallback)")
+        if neighbours.device != queries.device or fmap.device != queries.device:
+            raise RuntimeError(f"forward_map: queries ({queries.device}), neighbours ({neighbours.device}) and the feature map "
+                               f"({fmap.device}) must be on the same GPU")
+        fmap.check(self)
+        x = self._encoder_input(queries, "queries")
+        lib = _L.lib()
+        self._poll_status(block=False)
+        dev = x.device
+        self._pack_gnn()
+        self._enc.ensure_packed(self.feature_extractor.state_dict, "", dev)
+        status = self._status_buffers(dev)
+        nb = neighbours.contiguous()
+        n_per = kk + 1
+        edge_index, batch = self._map_graph(g, n_per, dev)
+        edge_index = edge_index.clone()           # the caller's to keep (the cached copy serves the next call)
+        enc_sd = self.feature_extractor.state_dict
+
+        fast = self.use_AP and not self.use_attention and k is None and not (self.knn > 0 and self._gnn_dtype == "bf16")
+        parts = None
+        if fast:
+            from .graph import Data
+            spec = Data()
+            spec.graph_sizes = ([n_per] * g, [n_per * kk] * g)
+            parts = self._partition(spec, g * n_per, edge_index.size(1) if self.knn <= 0 else None)
+        if parts is not None:
+            def features(n0, n1, wkey):           # the slot's queries through the encoder, then its graphs' nodes
+                g0, g1 = n0 // n_per, n1 // n_per
+                qf = self._enc.run(enc_sd, "", x[g0:g1], slot=wkey)
+                return ops.gather_graph_nodes(qf, fmap.features, nb[g0:g1], status=status[8 + wkey[0]:9 + wkey[0]])
+            return self._forward_streams(lib, features, g * n_per, dev, edge_index, parts, batch)
+        feat = ops.gather_graph_nodes(self._encode_small(x), fmap.features, nb, status=status[8:9])
+        return self._forward_tail(lib, feat, edge_index, batch, k)
+
+    def _encoder_input(self, x: torch.Tensor, what: str) -> torch.Tensor:
+        """Images as the encoder takes them: uint8 frames through ``frame_transform``, dtype checked, viewed as [n, 3, H, W]."""
+        if x.dtype == torch.uint8 and self.frame_transform is not None:
+            x = self._transform_frames(x)
+        if x.dtype != torch.float32 and not (x.dtype == torch.bfloat16 and self.accepts_bf16_input):
+            raise TypeError(f"{what} must be float32 (the reference's input dtype; bf16 images are taken by the bf16 encoder "
+                            f"only), got {x.dtype}")
+        return x.view(x.size(0), 3, self.input_img_height, -1)                    # posenet.py:1035
 
     def _transform_frames(self, frames: torch.Tensor) -> torch.Tensor:
         """uint8 frames [n, H, W, 3] -> the encoder's input [n, 3, input_img_height, W'] through ``frame_transform``, in bf16 for
@@ -509,15 +622,15 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
             cur.wait_stream(st)
         return feat
 
-    def _forward_streams(self, lib, x, edge_index, parts, batch=None):
-        """use_AP / no extra attention / no explicit k, on ``len(parts)`` concurrent streams.  With ``knn > 0`` (the reference's
+    def _forward_streams(self, lib, features, n_total, dev, edge_index, parts, batch=None):
+        """use_AP / no extra attention / no explicit k, on ``len(parts)`` concurrent streams.  ``features(n0, n1, wkey)`` makes the
+        node features [n1 - n0, d] of nodes n0..n1 on the current (slot) stream: the encoder over those images for ``forward``,
+        the queries' encoder + node assembly from a feature map for ``forward_map``.  With ``knn > 0`` (the reference's
         default CLI, testing/test.py:308) every slot builds the kNN graph of ITS graphs from its own encoder output
         (posenet.py:1047-1048; graphs are independent, so the per-slot edge lists concatenate to the whole-batch list) and the
         host learns each slot's edge count behind an event on that slot's stream -- the other slots' encoders keep the GPU
         busy meanwhile -- before it enqueues the slot's GNN.  With ``droprate > 0`` the always-on dropout and the heads
         (posenet.py:1073-1086) run per slot on the slot's stream."""
-        dev = x.device
-        n_total = x.size(0)
         knn = int(self.knn) if self.knn > 0 else 0
         drop = self.droprate > 0
         n_slots = 1 + max(p[4] for p in parts)
@@ -554,7 +667,7 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
                     # workspaces are per (slot, position in the slot's queue): groups of a slot run in order, so they could share,
                     # but a different shape would re-allocate every call
                     wkey = (slot, gi)
-                    feat = self._enc.run(self.feature_extractor.state_dict, "", x[n0:n1], slot=wkey)
+                    feat = features(n0, n1, wkey)
                     heads(feat, n0, n1, (base + 8 * e0, base + 8 * (e_total + e0)), n0, e1 - e0, rel_pose[e0:e1], slot, wkey)
                     feat.record_stream(st)
             for st in self._streams[:n_slots]:
@@ -568,7 +681,7 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
             st = self._streams[slot]
             with torch.cuda.stream(st):
                 wkey = (slot, gi)
-                feat = self._enc.run(self.feature_extractor.state_dict, "", x[n0:n1], slot=wkey)
+                feat = features(n0, n1, wkey)
                 ei_buf, meta = ops.knn_graph_launch(feat, knn, batch[n0:n1])
                 meta_h = torch.empty(2, dtype=torch.int32).pin_memory()
                 meta_h.copy_(meta, non_blocking=True)
