@@ -300,6 +300,21 @@ int rpg_linear_bf16(const void* a, const void* weight, const float* bias, const 
                     const float* residual2, const int64_t* res2_idx, int ldr, float* out, int m, int k, int n_out,
                     int relu, void* stream);
 
+/* rpg_linear_bf16_ex: the general form rpg_gnn_forward_bf16 uses -- a rows with pitch lda >= k (lda % 8 == 0), primary output `out`
+ * fp32 (out_f32 = 1) or bf16 (0) or none (null, when out2 is given), and an optional second output out2 (bf16, row pitch ld2 >= n_out,
+ * ld2 % 4 == 0) = bf16(relu2 ? max(y, 0) : y) with y the sum BEFORE the primary's ReLU; both rounded once, to nearest even.
+ * rpg_conv_pair_bf16: the two convolutions that read the input of a down-sampling BasicBlock (torchvision BasicBlock.conv1 and
+ * .downsample, reference call site modules/posenet.py:1037) as one launch: ya = relu(bn_a(conv k x k / stride / pad (x))),
+ * yb = bn_b(conv 1 x 1 / stride / pad 0 (x)), both bf16 NHWC [n][ho][wo][cout]; the arithmetic of two rpg_conv2d_bn_act_nhwc_bf16
+ * calls.  RPG_ERR_BAD_ARG where the pair is not taken (fewer than 8192 output pixels, cin % 32 != 0, RPG_TUNE_BF16_PAIR = 0 or
+ * RPG_TUNE_BF16_DMA != 1): the caller launches the two convolutions one by one. */
+int rpg_linear_bf16_ex(const void* a, int lda, const void* weight, const float* bias, const float* residual, const int64_t* res_idx,
+                       const float* residual2, const int64_t* res2_idx, int ldr, void* out, int out_f32, void* out2, int ld2,
+                       int relu2, int m, int k, int n_out, int relu, void* stream);
+int rpg_conv_pair_bf16(const void* x, const void* wa_ohwi, const float* scale_a, const float* shift_a, void* ya, const void* wb_ohwi,
+                       const float* scale_b, const float* shift_b, void* yb, int n, int h, int w, int cin, int cout, int k,
+                       int stride, int pad, void* stream);
+
 /* ------------------------------------------------------------------------------------------- */
 /* Per-kernel timing with HIP events on the launch stream (used by bench.py for the roofline).  */
 /* ------------------------------------------------------------------------------------------- */

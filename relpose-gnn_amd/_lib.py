@@ -29,7 +29,7 @@ SYMBOLS = (
     "rpg_attention_aggregate_f32", "rpg_stem_conv7x7s2_bn_relu_maxpool_bf16", "rpg_stem_conv7x7s2_bn_relu_maxpool_bf16_xbf16",
     "rpg_resnet_forward_bf16_xbf16", "rpg_host_f32_to_bf16", "rpg_basicblock64_bf16", "rpg_linear_gather_ex_f32", "rpg_probe_mfma_bf16", "rpg_host_f32_to_bf16_isa",
     "rpg_resize_table_ksize", "rpg_resize_table_bilinear", "rpg_frames_workspace_bytes", "rpg_frames_u8_to_f32",
-    "rpg_frames_u8_to_bf16", "rpg_gather_graph_nodes_f32",
+    "rpg_frames_u8_to_bf16", "rpg_gather_graph_nodes_f32", "rpg_linear_bf16_ex", "rpg_conv_pair_bf16",
 )
 
 
@@ -74,6 +74,8 @@ def _declare(lib: C.CDLL) -> None:
                                          _vp, _vp, _vp, _vp, _vp, _sz, _vp]
     lib.rpg_f32_to_bf16.argtypes = [_vp, _i, _vp, _i, _i, C.c_long, _i, _vp]
     lib.rpg_linear_bf16.argtypes = [_vp] * 7 + [_i, _vp, _i, _i, _i, _i, _vp]
+    lib.rpg_linear_bf16_ex.argtypes = [_vp, _i] + [_vp] * 6 + [_i, _vp, _i, _vp] + [_i] * 6 + [_vp]
+    lib.rpg_conv_pair_bf16.argtypes = [_vp] * 9 + [_i] * 8 + [_vp]
     lib.rpg_timing_enable.argtypes = [_i]
     lib.rpg_set_tuning.argtypes = [_i, _i]
     lib.rpg_conv2d_bn_act_nhwc_bf16.argtypes = [_vp] * 6 + [_i] * 11 + [_vp]

@@ -1913,6 +1913,34 @@ extern "C" int rpg_linear_bf16(const void* a, const void* weight, const float* b
                                    rpg::as_stream(stream));
 }
 
+// The general form of the Linear as an entry point of its own (the bf16 GNN reaches it through forward.hip): A rows with pitch lda,
+// primary output fp32 / bf16 / none, optional second bf16 output out2 = bf16(relu2 ? max(y, 0) : y) with y taken before the primary's ReLU.
+extern "C" int rpg_linear_bf16_ex(const void* a, int lda, const void* weight, const float* bias, const float* residual,
+                                  const int64_t* res_idx, const float* residual2, const int64_t* res2_idx, int ldr, void* out,
+                                  int out_f32, void* out2, int ld2, int relu2, int m, int k, int n_out, int relu, void* stream) {
+    rpg::LinearBf16Out o{};
+    o.out = out; o.out_f32 = out_f32; o.out2 = out2; o.ld2 = ld2; o.relu2 = relu2;
+    return rpg::launch_linear_bf16_ex(a, lda, weight, bias, residual, res_idx, residual2, res2_idx, ldr, o, m, k, n_out, relu,
+                                      rpg::as_stream(stream));
+}
+
+// The paired launch of a down-sampling BasicBlock (RPG_TUNE_BF16_PAIR) as an entry point of its own: ya = relu(bn_a(conv k x k / stride
+// / pad (x))), yb = bn_b(conv 1 x 1 / stride (x)) in ONE launch.  RPG_ERR_BAD_ARG where the pair is not eligible (fewer than 8192 output
+// pixels, Cin % 32, pairing or the by-shape LDS-DMA dispatch switched off): the caller then uses two rpg_conv2d_bn_act_nhwc_bf16 calls.
+extern "C" int rpg_conv_pair_bf16(const void* x, const void* wa_ohwi, const float* scale_a, const float* shift_a, void* ya,
+                                  const void* wb_ohwi, const float* scale_b, const float* shift_b, void* yb, int n, int h, int w,
+                                  int cin, int cout, int k, int stride, int pad, void* stream) {
+    if (!scale_a || !shift_a || !scale_b || !shift_b || !rpg::aligned16(scale_a) || !rpg::aligned16(shift_a) ||
+        !rpg::aligned16(scale_b) || !rpg::aligned16(shift_b) || k <= 0 || stride <= 0 || pad < 0 || h <= 0 || w <= 0 || cin <= 0 ||
+        cout <= 0 || ya == yb)
+        return RPG_ERR_BAD_ARG;
+    if (!rpg::launch_conv_pair_bf16(x, wa_ohwi, scale_a, shift_a, ya, wb_ohwi, scale_b, shift_b, yb, n, h, w, cin, cout, k, stride, pad,
+                                    rpg::as_stream(stream)))
+        return RPG_ERR_BAD_ARG;
+    RPG_CHECK_LAUNCH("conv_pair_bf16");
+    return RPG_OK;
+}
+
 // ------------------------------------------------------------------------------------------------------------------------------
 // Measurement aid (no reference counterpart): what the bf16 matrix pipe of THIS device sustains chip-wide with
 // nothing else drawing power -- `iters` x 16 v_mfma_f32_32x32x16_bf16 per wave on 4 independent accumulators, operands from

@@ -257,6 +257,56 @@ def linear_bf16(a: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tens
     return out
 
 
+def linear_bf16_ex(a: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None,
+                   residual: Optional[torch.Tensor] = None, res_idx: Optional[torch.Tensor] = None,
+                   residual2: Optional[torch.Tensor] = None, res2_idx: Optional[torch.Tensor] = None, relu: bool = False,
+                   out_dtype: Optional[torch.dtype] = torch.float32, out2: bool = False, relu2: bool = False
+                   ) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """linear_bf16 in its general form (rpg_linear_bf16_ex): primary output fp32 / bf16 / none (``out_dtype``), and with ``out2`` a
+    second bf16 output = bf16(relu2 ? max(y, 0) : y), y taken before the primary's ReLU.  ``residual2`` may be a column-offset view
+    of ``residual``'s storage (common row pitch)."""
+    a, weight = _req(a, "a", torch.bfloat16), _req(weight, "weight", torch.bfloat16)
+    m, k = a.shape
+    n_out = weight.shape[0]
+    if weight.shape[1] != k:
+        raise ValueError("a.shape[1] != weight.shape[1]")
+    if out_dtype not in (torch.float32, torch.bfloat16, None) or (out_dtype is None and not out2):
+        raise ValueError("out_dtype: float32 | bfloat16 | None (then out2 must be set)")
+    for t, nm, dt in ((bias, "bias", torch.float32), (residual, "residual", torch.float32), (residual2, "residual2", torch.float32),
+                      (res_idx, "res_idx", torch.int64), (res2_idx, "res2_idx", torch.int64)):
+        if t is not None and (t.dtype != dt or not t.is_cuda):
+            raise TypeError(f"{nm}: expected {dt} on the GPU")
+    if residual2 is not None and (residual is None or residual2.stride(0) != residual.stride(0)):
+        raise ValueError("residual2 needs residual with the same row pitch")
+    ldr = 0 if residual is None else residual.stride(0)
+    y = None if out_dtype is None else torch.empty((m, n_out), dtype=out_dtype, device=a.device)
+    y2 = torch.empty((m, n_out), dtype=torch.bfloat16, device=a.device) if out2 else None
+    L.check(L.lib().rpg_linear_bf16_ex(_p(a), k, _p(weight), _p(bias), _p(residual), _p(res_idx), _p(residual2), _p(res2_idx), ldr,
+                                       _p(y), int(out_dtype == torch.float32), _p(y2), n_out if out2 else 0, int(relu2), m, k, n_out,
+                                       int(relu), _stream()), "linear_bf16_ex")
+    return y, y2
+
+
+def conv_pair_bf16(x: torch.Tensor, wa_ohwi: torch.Tensor, scale_a: torch.Tensor, shift_a: torch.Tensor, wb_ohwi: torch.Tensor,
+                   scale_b: torch.Tensor, shift_b: torch.Tensor, stride: int = 2, pad: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(relu(bn_a(conv k x k / stride / pad (x))), bn_b(conv 1 x 1 / stride (x))) of a down-sampling BasicBlock in one launch
+    (rpg_conv_pair_bf16); ValueError where the pair is not eligible."""
+    x, wa_ohwi, wb_ohwi = _req(x, "x", torch.bfloat16), _req(wa_ohwi, "wa_ohwi", torch.bfloat16), _req(wb_ohwi, "wb_ohwi", torch.bfloat16)
+    n, h, w, cin = x.shape
+    cout, k, kw, cin_a = wa_ohwi.shape
+    if k != kw or cin_a != cin or tuple(wb_ohwi.shape) != (cout, 1, 1, cin):
+        raise ValueError("conv_pair_bf16: wa [cout,k,k,cin], wb [cout,1,1,cin]")
+    ps = [_req(t, nm) for t, nm in ((scale_a, "scale_a"), (shift_a, "shift_a"), (scale_b, "scale_b"), (shift_b, "shift_b"))]
+    if any(t.numel() != cout for t in ps):
+        raise ValueError("conv_pair_bf16: scale / shift must have cout elements")
+    ho, wo = (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
+    ya = torch.empty((n, ho, wo, cout), dtype=torch.bfloat16, device=x.device)
+    yb = torch.empty_like(ya)
+    L.check(L.lib().rpg_conv_pair_bf16(_p(x), _p(wa_ohwi), _p(ps[0]), _p(ps[1]), _p(ya), _p(wb_ohwi), _p(ps[2]), _p(ps[3]), _p(yb),
+                                       n, h, w, cin, cout, k, stride, pad, _stream()), "conv_pair_bf16")
+    return ya, yb
+
+
 def stem_conv_bn_relu_maxpool(x_nchw: torch.Tensor, wpack: torch.Tensor, shift: torch.Tensor) -> torch.Tensor:
     """conv7x7/2 (3 -> 64) + BN + ReLU + maxpool3x3/2 in one kernel: [N,3,H,W] -> pooled NHWC [N,Hp,Wp,64]; wpack from
     params.pack_stem_pairs (BatchNorm scale folded in), shift [64]."""

@@ -2,7 +2,9 @@
 
 Tolerances (stated here, looser than the fp32 path's 1e-4 by design -- bf16 has an 8-bit mantissa):
   * one convolution vs F.conv2d evaluated on the SAME bf16-rounded inputs / weights in fp32: <= 1e-2 max-norm relative
-    (the kernel accumulates in fp32; the difference is the final bf16 rounding of the output, 2^-9 relative);
+    (the kernel accumulates in fp32; the difference is the final bf16 rounding of the output, 2^-9 relative -- this bar alone does
+    not prove that: tests/test_hip_bf16_rounding.py does, holding every kernel variant to the correctly rounded float64 answer
+    element by element);
   * whole forward (36 bf16 layers deep) vs the fp32 CPU oracle: <= 5e-2 max-norm relative on the poses.
 """
 import os
