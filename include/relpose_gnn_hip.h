@@ -187,6 +187,34 @@ int rpg_graph_prepare(const int64_t* src, const int64_t* dst, int64_t node_offse
 int rpg_gather_graph_nodes_f32(const float* query_feat, const float* map_feat, const int64_t* neighbours, int g, int k,
                                int64_t m, int d, float* out, int32_t* status, void* stream);
 
+/* Image retrieval against a map of descriptors: the selection step of the reference's obtain_KNNs
+ * (dataset_7Scenes_multi.py:238-264) with its random draws moved into `ranks` (made on the host, retrieval.py).
+ * For query g (descriptor q [g][d]) and database rows db [m][d]:
+ *   s[g][r]  = <q_g, db_r> / (|q_g| |db_r|); a zero-norm vector gives 0 (sklearn's normalize)
+ *   row r is allowed unless db_group[r] == q_group[g]; q_group[g] == -1, or both group arrays NULL, allows every row
+ *   the allowed rows are ordered by (s descending, r ascending), a non-finite s after every finite one
+ *   neighbours[g][j] = the row at position ranks[g][j] of that order; sims[g][j] (may be NULL) its similarity (NaN for a
+ *   non-finite one).  ranks int32 [g][k], strictly ascending per query.
+ * fp32 accumulation on the f32 matrix pipe in a fixed order that depends on d (and on the column slicing, a function of m and
+ * d) only: rows with equal bits get equal similarities wherever they sit in the map, a query's result does not depend on the
+ * other queries of the call, and two calls give the same bits.  The database is read once per 64 queries.
+ * db_inv_norm [m]: 1 / |db_r| from rpg_row_inv_norms_f32 (cached by the caller), or NULL to have it computed into the workspace.
+ * status [1] += the number of (g, j) whose rank is negative, not below query g's allowed-row count or not below
+ * rpg_retrieve_max_rank(), plus the number of queries whose ranks are not strictly ascending (the caller zeroes it; the host
+ * mirror raises IndexError on a non-zero count); such ranks are clamped, so nothing reads out of bounds and every written
+ * neighbour is in [0, m) (row 0 for a query with no allowed row).
+ * 1 <= g, 1 <= k <= 64, k <= m < 2^31, d % 4 == 0, q / db / workspace 16-byte aligned (RPG_ERR_BAD_ARG otherwise); row
+ * offsets are 64-bit (maps past 2 GiB).  workspace: rpg_retrieve_workspace_bytes(g, m, d) bytes, contents irrelevant on
+ * entry.  Three or four launches, no allocation, no synchronisation (graph-capturable).                               */
+size_t rpg_retrieve_workspace_bytes(int g, int64_t m, int d);
+int rpg_retrieve_max_rank(void);
+/* inv_norm[r] = 1 / |x_r| (0 for a zero row), x [m][d], d % 4 == 0, 16-byte aligned rows. */
+int rpg_row_inv_norms_f32(const float* x, int64_t m, int d, float* inv_norm, void* stream);
+int rpg_retrieve_cosine_f32(const float* q, const float* db, const float* db_inv_norm, const int64_t* q_group,
+                            const int64_t* db_group, const int32_t* ranks, int g, int k, int64_t m, int d,
+                            int64_t* neighbours, float* sims, void* workspace, size_t workspace_bytes, int32_t* status,
+                            void* stream);
+
 /* torch_cluster.knn_graph(x, k, batch, loop=False, flow='source_to_target') (posenet.py:1043-1050): for every node
  * the k nearest OTHER nodes of its graph by squared Euclidean distance (k+1 nearest including itself by
  * (distance, index), self match dropped).  x [n][d]; batch [n] int64 graph id per node, nodes of a graph contiguous,

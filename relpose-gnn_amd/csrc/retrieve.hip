@@ -1,0 +1,387 @@
+// Image retrieval against a feature map: for every query descriptor the database rows at given positions of the order
+// (cosine similarity descending, row index ascending) over the rows its exclusion group allows -- the selection step of the
+// reference's obtain_KNNs (dataset_7Scenes_multi.py:238-264) with everything random moved into `ranks` (retrieval.py).
+//
+// Three launches on the caller's stream, no allocation, no synchronisation:
+//   1. row_inv_norms_kernel     1 / |q_g| into the workspace (and 1 / |d_m| when the caller has not cached them)
+//   2. retrieve_dot_kernel<NQ>  <q_g, d_m> on the f32 matrix pipe (v_mfma_f32_16x16x4_f32).  A workgroup owns 16 database rows and
+//                               up to 64 queries, so the database is read from HBM once per 64 queries; its four waves take
+//                               every fourth 64-column block and are summed through LDS in wave order; the column range is cut
+//                               in `split` slices (grid.y) whose partial products go to the workspace and are summed in slice
+//                               order by the next kernel.  ONE code path for every g: a single query runs as a tile of 16 with 15
+//                               zero rows (still bandwidth-bound: 16 x the flop of a matrix-vector pass is a quarter of the time
+//                               the bytes take), and the slice count depends on (m, d) only -- so the bits of a similarity depend
+//                               on the two rows and on d, never on where the rows sit, on the tile, or on the batch.
+//   3. retrieve_select_kernel   one workgroup per query: similarity -> ordered 32-bit key (excluded rows and non-finite
+//                               similarities get the two largest keys), radix select of the R-th smallest (key, row) pair
+//                               (R = largest rank + 1 <= R_MAX), the R pairs collected and sorted in LDS, ranks read off.
+// The LDS atomics of (3) count integers (histogram bins, list slots whose order the sort erases): the result does not depend on
+// their arrival order.  No floating-point atomics anywhere.
+#include "rpg_common.h"
+
+#include <float.h>
+
+namespace {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int RT_NT = 256;            // dot kernel: 4 waves
+constexpr int RT_ROWS = 16;           // database rows per workgroup (one MFMA tile column block)
+constexpr int RT_BLK = 64;            // columns per wave step: 4 float4 per lane
+constexpr int RT_QCHUNK = 64;         // queries per workgroup (grid.z chunks beyond that re-read the database)
+constexpr int RS_NT = 1024;           // select kernel
+constexpr int R_MAX = 512;            // largest rank + 1 the select kernel serves
+constexpr int K_MAX = 64;
+constexpr int NORM_NT = 256;
+constexpr uint32_t KEY_NONFINITE = 0xFFFFFFFEu;
+constexpr uint32_t KEY_EXCLUDED = 0xFFFFFFFFu;
+
+// ---- 1 / |row| ------------------------------------------------------------------------------------------------------------
+// One workgroup per row (grid-strided).  Lane-strided float4 partial sums, then a shuffle tree per wave and the four wave sums
+// added in wave order: the same order for every row.  A zero row gives 0 (similarity 0, sklearn's normalize), NaN stays NaN.
+__global__ __launch_bounds__(NORM_NT) void row_inv_norms_kernel(const float4* __restrict__ x, int64_t rows, int d4,
+                                                                float* __restrict__ inv) {
+    __shared__ float wsum[NORM_NT / 64];
+    for (int64_t r = blockIdx.x; r < rows; r += gridDim.x) {
+        const float4* src = x + r * d4;
+        float s = 0.f;
+        for (int c = threadIdx.x; c < d4; c += NORM_NT) {
+            const float4 v = src[c];
+            s += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
+        }
+        for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
+        if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = s;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const float ss = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+            inv[r] = ss == 0.f ? 0.f : 1.f / sqrtf(ss);
+        }
+        __syncthreads();
+    }
+}
+
+// ---- <q, d> ---------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float4 ld4_or_zero(const float* p, bool ok) {
+    return ok ? *reinterpret_cast<const float4*>(p) : make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
+// A = queries (tile rows i), B = database rows (tile columns j).  Lane l holds A[i = l & 15][k = l >> 4] and B[k = l >> 4][j = l & 15];
+// a lane's float4 at column 16 u + 4 (l >> 4) feeds four MFMAs (.x .y .z .w), so one wave step of 64 columns is 16 MFMAs per
+// query tile, in a fixed column order.  D[i = 4 (l >> 4) + reg][j = l & 15].
+template <int NQ>
+__global__ __launch_bounds__(RT_NT) void retrieve_dot_kernel(const float* __restrict__ q, const float* __restrict__ db, int g,
+                                                             int64_t m, int d, int blocks_per_split,
+                                                             float* __restrict__ part) {
+    __shared__ float red[RT_NT / 64][NQ][4][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int r16 = lane & 15, c4 = lane >> 4;
+    const int64_t m0 = (int64_t)blockIdx.x * RT_ROWS;
+    const int split = blockIdx.y;
+    const int g0 = blockIdx.z * RT_QCHUNK;
+
+    int64_t row = m0 + r16;
+    if (row >= m) row = m - 1;                            // a tail tile reads a valid row again; its column is not stored
+    const float* brow = db + row * d;                     // 64-bit row offset
+    const float* arow[NQ];
+    bool aok[NQ];
+#pragma unroll
+    for (int t = 0; t < NQ; ++t) {
+        const int gi = g0 + 16 * t + r16;
+        aok[t] = gi < g;
+        arow[t] = q + (int64_t)(aok[t] ? gi : 0) * d;
+    }
+    const int nblk = (d + RT_BLK - 1) / RT_BLK;
+    const int b_begin = split * blocks_per_split;
+    const int b_end = b_begin + blocks_per_split < nblk ? b_begin + blocks_per_split : nblk;
+
+    f32x4 acc[NQ];
+#pragma unroll
+    for (int t = 0; t < NQ; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    for (int b = b_begin + wave; b < b_end; b += RT_NT / 64) {
+        const int col = b * RT_BLK + 4 * c4;
+        float4 bv[4], av[NQ][4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int c = col + 16 * u;
+            const bool in = c < d;                        // d % 4 == 0: a float4 is inside or outside as a whole
+            bv[u] = ld4_or_zero(brow + c, in);
+#pragma unroll
+            for (int t = 0; t < NQ; ++t) av[t][u] = ld4_or_zero(arow[t] + c, in && aok[t]);
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+#pragma unroll
+            for (int t = 0; t < NQ; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[t][u].x, bv[u].x, acc[t], 0, 0, 0);
+#pragma unroll
+            for (int t = 0; t < NQ; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[t][u].y, bv[u].y, acc[t], 0, 0, 0);
+#pragma unroll
+            for (int t = 0; t < NQ; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[t][u].z, bv[u].z, acc[t], 0, 0, 0);
+#pragma unroll
+            for (int t = 0; t < NQ; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[t][u].w, bv[u].w, acc[t], 0, 0, 0);
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < NQ; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) red[wave][t][r][lane] = acc[t][r];
+    __syncthreads();
+    const int reg = threadIdx.x >> 6;                     // this thread sums (tile t, reg, lane) over the waves, in wave order
+#pragma unroll
+    for (int t = 0; t < NQ; ++t) {
+        const float s = ((red[0][t][reg][lane] + red[1][t][reg][lane]) + red[2][t][reg][lane]) + red[3][t][reg][lane];
+        const int gi = g0 + 16 * t + 4 * c4 + reg;
+        const int64_t mm = m0 + r16;
+        if (gi < g && mm < m) part[((int64_t)split * g + gi) * m + mm] = s;
+    }
+}
+
+// ---- selection -------------------------------------------------------------------------------------------------------------
+// Larger similarity -> smaller key; -0 and +0 share a key; NaN / inf order after every finite value.
+__device__ __forceinline__ uint32_t sim_key(float s) {
+    if (!(fabsf(s) <= FLT_MAX)) return KEY_NONFINITE;
+    s += 0.0f;
+    const uint32_t u = __float_as_uint(s);
+    const uint32_t asc = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    return ~asc;
+}
+
+__device__ __forceinline__ float key_sim(uint32_t key) {
+    if (key >= KEY_NONFINITE) return __builtin_nanf("");
+    const uint32_t asc = ~key;
+    return __uint_as_float((asc & 0x80000000u) ? (asc & 0x7FFFFFFFu) : ~asc);
+}
+
+__global__ __launch_bounds__(RS_NT) void retrieve_select_kernel(float* __restrict__ part, int nsplit,
+                                                                const float* __restrict__ q_inv, const float* __restrict__ db_inv,
+                                                                const int64_t* __restrict__ q_group,
+                                                                const int64_t* __restrict__ db_group,
+                                                                const int32_t* __restrict__ ranks, int g, int k, int64_t m,
+                                                                int64_t* __restrict__ nbrs, float* __restrict__ sims,
+                                                                int32_t* __restrict__ status) {
+    __shared__ unsigned hist[256];
+    __shared__ unsigned long long list[R_MAX];
+    __shared__ int s_rank[K_MAX];
+    __shared__ unsigned s_allowed, s_cnt, s_bucket, s_need;
+    __shared__ int s_r;
+    const int tid = threadIdx.x;
+    const int gi = blockIdx.x;
+    // slice 0 of this query's row becomes its keys, in place: element mm is read and written by the same thread in every pass
+    uint32_t* keys = reinterpret_cast<uint32_t*>(part) + (int64_t)gi * m;
+
+    if (tid == 0) {
+        s_allowed = 0;
+        s_cnt = 0;
+    }
+    __syncthreads();
+    {
+        const float qi = q_inv[gi];
+        const int64_t qg = q_group ? q_group[gi] : -1;
+        unsigned local = 0;
+        for (int64_t mm = tid; mm < m; mm += RS_NT) {
+            float dot = part[(int64_t)gi * m + mm];
+            for (int s = 1; s < nsplit; ++s) dot += part[((int64_t)s * g + gi) * m + mm];      // slice order
+            const float sim = dot * qi * db_inv[mm];
+            const bool allowed = !(qg != -1 && db_group[mm] == qg);
+            keys[mm] = allowed ? sim_key(sim) : KEY_EXCLUDED;
+            local += allowed;
+        }
+        if (local) atomicAdd(&s_allowed, local);
+    }
+    __syncthreads();
+    if (tid == 0) {
+        // ranks of this query: each clamped below min(allowed rows, R_MAX); bad entries and a non-ascending row are counted
+        const unsigned n_allowed = s_allowed;
+        const int lim = (int)(n_allowed < (unsigned)R_MAX ? n_allowed : (unsigned)R_MAX);
+        int bad = 0, top = -1, prev = 0;
+        bool ascending = true;
+        for (int j = 0; j < k; ++j) {
+            const int raw = ranks[(int64_t)gi * k + j];
+            if (j > 0 && raw <= prev) ascending = false;
+            prev = raw;
+            int r = raw;
+            if (r < 0 || r >= lim) {
+                ++bad;
+                r = r < 0 ? 0 : lim - 1;
+                if (r < 0) r = 0;
+            }
+            s_rank[j] = r;
+            if (r > top) top = r;
+        }
+        if (!ascending) ++bad;
+        if (bad) atomicAdd(status, bad);
+        s_r = lim > 0 ? top + 1 : 0;
+    }
+    __syncthreads();
+    const int R = s_r;
+    if (R == 0) {                                         // no allowed row: nothing to pick, row 0 keeps the output inside [0, m)
+        if (tid < k) {
+            nbrs[(int64_t)gi * k + tid] = 0;
+            if (sims) sims[(int64_t)gi * k + tid] = __builtin_nanf("");
+        }
+        return;
+    }
+
+    // radix select of the R-th smallest (key << 32 | row): the pairs are distinct, so the last digit leaves exactly one
+    unsigned long long prefix = 0, mask = 0;
+    unsigned need = (unsigned)R;
+    for (int shift = 56; shift >= 0; shift -= 8) {
+        if (shift < 32 && ((unsigned long long)(m - 1) >> shift) == 0) {      // every row index has digit 0 here
+            mask |= 0xFFull << shift;
+            continue;
+        }
+        if (tid < 256) hist[tid] = 0;
+        __syncthreads();
+        for (int64_t mm = tid; mm < m; mm += RS_NT) {
+            const unsigned long long comp = ((unsigned long long)keys[mm] << 32) | (unsigned long long)mm;
+            if ((comp & mask) == prefix) atomicAdd(&hist[(unsigned)(comp >> shift) & 255u], 1u);
+        }
+        __syncthreads();
+        if (tid == 0) {
+            unsigned cum = 0;
+            int b = 0;
+            for (; b < 255; ++b) {
+                const unsigned h = hist[b];
+                if (cum + h >= need) break;
+                cum += h;
+            }
+            s_bucket = (unsigned)b;
+            s_need = need - cum;
+        }
+        __syncthreads();
+        prefix |= (unsigned long long)s_bucket << shift;
+        mask |= 0xFFull << shift;
+        need = s_need;
+    }
+    // collect the R pairs <= the threshold (slot order is arbitrary: the sort below fixes it), pad, sort ascending
+    if (tid < R_MAX) list[tid] = ~0ull;
+    __syncthreads();
+    for (int64_t mm = tid; mm < m; mm += RS_NT) {
+        const unsigned long long comp = ((unsigned long long)keys[mm] << 32) | (unsigned long long)mm;
+        if (comp <= prefix) {
+            const unsigned slot = atomicAdd(&s_cnt, 1u);
+            if (slot < (unsigned)R_MAX) list[slot] = comp;
+        }
+    }
+    for (int size = 2; size <= R_MAX; size <<= 1) {
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            __syncthreads();
+            if (tid < R_MAX / 2) {
+                const int i = 2 * tid - (tid & (stride - 1));
+                const int j = i + stride;
+                const bool up = (i & size) == 0;
+                const unsigned long long a = list[i], b = list[j];
+                if ((a > b) == up) {
+                    list[i] = b;
+                    list[j] = a;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    if (tid < k) {
+        const unsigned long long comp = list[s_rank[tid]];
+        int64_t row = (int64_t)(comp & 0xFFFFFFFFull);
+        if (row >= m) row = m - 1;                        // (a padding entry cannot be reached: ranks are clamped below R)
+        nbrs[(int64_t)gi * k + tid] = row;
+        if (sims) sims[(int64_t)gi * k + tid] = key_sim((uint32_t)(comp >> 32));
+    }
+}
+
+// ---- host side -----------------------------------------------------------------------------------------------------------------
+size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// Column slices of the dot kernel: enough workgroups to keep every CU streaming when the map has few 16-row tiles, at least 8
+// column blocks per slice.  A function of (m, d) ONLY: the slice count is part of the summation order.
+void split_plan(int64_t m, int d, int* nsplit, int* blocks_per_split) {
+    const int64_t tiles = (m + RT_ROWS - 1) / RT_ROWS;
+    const int nblk = (d + RT_BLK - 1) / RT_BLK;
+    int64_t s = (1024 + tiles - 1) / tiles;
+    const int cap = nblk / 8 < 1 ? 1 : nblk / 8;
+    if (s > cap) s = cap;
+    if (s > 16) s = 16;
+    if (s < 1) s = 1;
+    const int bps = (int)((nblk + s - 1) / s);
+    *blocks_per_split = bps;
+    *nsplit = (nblk + bps - 1) / bps;
+}
+
+struct WsLayout {
+    size_t q_inv, db_inv, part, total;
+};
+
+WsLayout ws_layout(int g, int64_t m, int d) {
+    int ns, bps;
+    split_plan(m, d, &ns, &bps);
+    WsLayout w;
+    w.q_inv = 0;
+    w.db_inv = round_up((size_t)g * sizeof(float), 256);
+    w.part = w.db_inv + round_up((size_t)m * sizeof(float), 256);
+    w.total = w.part + round_up((size_t)ns * (size_t)g * (size_t)m * sizeof(float), 256);
+    return w;
+}
+
+int launch_inv_norms(const float* x, int64_t rows, int d, float* inv, hipStream_t s) {
+    const int grid = (int)(rows < 65536 ? rows : 65536);
+    hipLaunchKernelGGL(row_inv_norms_kernel, dim3(grid), dim3(NORM_NT), 0, s, reinterpret_cast<const float4*>(x), rows, d / 4, inv);
+    RPG_CHECK_LAUNCH("row_inv_norms");
+    return RPG_OK;
+}
+
+}  // namespace
+
+extern "C" int rpg_retrieve_max_rank(void) { return R_MAX; }
+
+extern "C" size_t rpg_retrieve_workspace_bytes(int g, int64_t m, int d) {
+    if (g <= 0 || m <= 0 || d <= 0) return 0;
+    return ws_layout(g, m, d).total;
+}
+
+extern "C" int rpg_row_inv_norms_f32(const float* x, int64_t m, int d, float* inv_norm, void* stream) {
+    if (!x || !inv_norm || m <= 0 || d <= 0 || (d & 3) || !rpg::aligned16(x) || (reinterpret_cast<uintptr_t>(inv_norm) & 3u))
+        return RPG_ERR_BAD_ARG;
+    return launch_inv_norms(x, m, d, inv_norm, rpg::as_stream(stream));
+}
+
+extern "C" int rpg_retrieve_cosine_f32(const float* q, const float* db, const float* db_inv_norm, const int64_t* q_group,
+                                       const int64_t* db_group, const int32_t* ranks, int g, int k, int64_t m, int d,
+                                       int64_t* neighbours, float* sims, void* workspace, size_t workspace_bytes,
+                                       int32_t* status, void* stream) {
+    if (!q || !db || !ranks || !neighbours || !workspace || !status || g < 1 || k < 1 || k > K_MAX || m < k ||
+        m >= ((int64_t)1 << 31) || d <= 0 || (d & 3) || !rpg::aligned16(q) || !rpg::aligned16(db) || !rpg::aligned16(workspace) ||
+        ((q_group == nullptr) != (db_group == nullptr)) || (reinterpret_cast<uintptr_t>(neighbours) & 7u) ||
+        (reinterpret_cast<uintptr_t>(q_group) & 7u) || (reinterpret_cast<uintptr_t>(db_group) & 7u) ||
+        (reinterpret_cast<uintptr_t>(ranks) & 3u) || (reinterpret_cast<uintptr_t>(status) & 3u) ||
+        (reinterpret_cast<uintptr_t>(sims) & 3u) || (reinterpret_cast<uintptr_t>(db_inv_norm) & 3u) ||
+        (g + RT_QCHUNK - 1) / RT_QCHUNK > 65535)
+        return RPG_ERR_BAD_ARG;
+    const WsLayout w = ws_layout(g, m, d);
+    if (workspace_bytes < w.total) return RPG_ERR_WORKSPACE;
+    hipStream_t s = rpg::as_stream(stream);
+    char* base = static_cast<char*>(workspace);
+    float* q_inv = reinterpret_cast<float*>(base + w.q_inv);
+    float* part = reinterpret_cast<float*>(base + w.part);
+    int rc = launch_inv_norms(q, g, d, q_inv, s);
+    if (rc != RPG_OK) return rc;
+    if (!db_inv_norm) {
+        float* db_inv = reinterpret_cast<float*>(base + w.db_inv);
+        rc = launch_inv_norms(db, m, d, db_inv, s);
+        if (rc != RPG_OK) return rc;
+        db_inv_norm = db_inv;
+    }
+    int ns, bps;
+    split_plan(m, d, &ns, &bps);
+    const dim3 grid((unsigned)((m + RT_ROWS - 1) / RT_ROWS), (unsigned)ns, (unsigned)((g + RT_QCHUNK - 1) / RT_QCHUNK));
+    const int tiles = ((g < RT_QCHUNK ? g : RT_QCHUNK) + 15) / 16;
+    if (tiles <= 1)
+        hipLaunchKernelGGL(retrieve_dot_kernel<1>, grid, dim3(RT_NT), 0, s, q, db, g, m, d, bps, part);
+    else if (tiles == 2)
+        hipLaunchKernelGGL(retrieve_dot_kernel<2>, grid, dim3(RT_NT), 0, s, q, db, g, m, d, bps, part);
+    else
+        hipLaunchKernelGGL(retrieve_dot_kernel<4>, grid, dim3(RT_NT), 0, s, q, db, g, m, d, bps, part);
+    RPG_CHECK_LAUNCH("retrieve_dot");
+    hipLaunchKernelGGL(retrieve_select_kernel, dim3(g), dim3(RS_NT), 0, s, part, ns, q_inv, db_inv_norm, q_group, db_group, ranks,
+                       g, k, m, neighbours, sims, status);
+    RPG_CHECK_LAUNCH("retrieve_select");
+    return RPG_OK;
+}

@@ -506,9 +506,9 @@ def load_pose_stats(path):
 
 
 @torch.no_grad()
-def relocalize(model, fmap, queries: torch.Tensor, neighbours, micro_batch: int = 64, pose_m=(0.0, 0.0, 0.0),
+def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch: int = 64, pose_m=(0.0, 0.0, 0.0),
                pose_s=(1.0, 1.0, 1.0), ref_node: int = 0, stats: Optional[dict] = None, targets=None,
-               bf16_input: Optional[bool] = None):
+               bf16_input: Optional[bool] = None, *, rule=None, query_descriptors=None, query_groups=None):
     """The evaluation stream of the map path (``PoseNetX_R2.forward_map``): query g's graph is the query followed by the map
     rows ``neighbours[g]`` (its retrieved database images, dataset_7Scenes_multi.py:340-345).  Single process.
 
@@ -520,22 +520,47 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours, micro_batch: int 
     Returns, per query, the predicted pose [G, 7] by the rule of test.py:227-251 (``query_pose``), the "target" of the
     reference edge's source node being ``fmap.poses[neighbours[g][src - 1]]``; with ``targets`` ([G, 6], the queries' own
     ``[t, log q]``) an ``EvalResult`` instead (its ``pred_poses`` are those poses).  A map without poses gives the raw
-    ``(abs_pose [G*(K+1), 6], rel_pose [E, 6])`` host tensors.  ``stats`` as in ``evaluate_stream``."""
+    ``(abs_pose [G*(K+1), 6], rel_pose [E, 6])`` host tensors.  ``stats`` as in ``evaluate_stream``.
+
+    ``neighbours=None`` with a ``rule`` (retrieval.RetrievalRule) retrieves them on the GPU inside ``forward_map`` (which see
+    for ``query_descriptors`` [G, Dd] -- host or device, staged per micro-batch -- and ``query_groups`` [G], host integers): the
+    neighbours of micro-batch i come back to the host with its poses, by the same pinned non-blocking copy behind the same
+    event.  The chosen rows, int64 [G, K], are left in ``stats["neighbours"]`` and on an ``EvalResult`` as ``.neighbours``."""
     import time
     from .graph import Data, fc_edge_index
     device = fmap.device
     if not torch.is_tensor(queries):
         raise TypeError("relocalize: queries must be a tensor [G, ...]")
-    nb = torch.as_tensor(neighbours)
-    if nb.dtype != torch.int64 or nb.dim() != 2 or nb.shape[0] != queries.shape[0] or nb.shape[1] < 1:
-        raise ValueError(f"relocalize: neighbours must be int64 [G, K >= 1] with G = {queries.shape[0]} queries, got "
-                         f"{tuple(nb.shape)} {nb.dtype}")
+    if (neighbours is None) == (rule is None):
+        raise ValueError("relocalize: give neighbours or a retrieval rule (exactly one of them)")
+    if rule is None and (query_descriptors is not None or query_groups is not None):
+        raise ValueError("relocalize: query_descriptors / query_groups belong to retrieval: pass a rule (and no neighbours)")
     if micro_batch < 1:
         raise ValueError("relocalize: micro_batch must be >= 1")
-    g_all, kk = nb.shape
+    qd_all = qg_all = None
+    if rule is None:
+        nb = torch.as_tensor(neighbours)
+        if nb.dtype != torch.int64 or nb.dim() != 2 or nb.shape[0] != queries.shape[0] or nb.shape[1] < 1:
+            raise ValueError(f"relocalize: neighbours must be int64 [G, K >= 1] with G = {queries.shape[0]} queries, got "
+                             f"{tuple(nb.shape)} {nb.dtype}")
+        g_all, kk = nb.shape
+        nb_dev = nb.to(device).contiguous()
+        nb_h = nb.cpu().numpy()
+    else:
+        g_all, kk = int(queries.shape[0]), rule.k
+        if fmap.descriptors is not None and query_descriptors is None:
+            raise ValueError("relocalize: the map holds its own retrieval descriptors, so query_descriptors [G, Dd] must be given")
+        if query_descriptors is not None:
+            qd_all = torch.as_tensor(query_descriptors)
+            if qd_all.dim() != 2 or qd_all.shape[0] != g_all or qd_all.dtype != torch.float32:
+                raise ValueError(f"relocalize: query_descriptors must be fp32 [{g_all}, Dd], got {tuple(qd_all.shape)} {qd_all.dtype}")
+        if query_groups is not None:
+            qg_all = torch.as_tensor(query_groups).cpu()
+            if qg_all.dim() != 1 or qg_all.shape[0] != g_all:
+                raise ValueError(f"relocalize: query_groups must be integers [{g_all}], got {tuple(qg_all.shape)}")
+        nb_dev = None
+        nb_h = np.zeros((g_all, kk), dtype=np.int64)          # filled micro-batch by micro-batch as the copies land
     n_per = kk + 1
-    nb_dev = nb.to(device).contiguous()
-    nb_h = nb.cpu().numpy()
     pose_m, pose_s = np.asarray(pose_m, dtype=np.float64), np.asarray(pose_s, dtype=np.float64)
     poses_h = None if fmap.poses is None else fmap.poses.cpu().numpy().astype(np.float64)
     targ_h = None if targets is None else np.asarray(torch.as_tensor(targets).cpu(), dtype=np.float64).reshape(g_all, 6)
@@ -567,9 +592,11 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours, micro_batch: int 
     h2d = 0
 
     def finish(item):
-        b0, host_abs, host_rel, host_ei, ev = item
+        b0, host_abs, host_rel, host_ei, host_nb, ev = item
         ev.synchronize()
         model.check_edge_index(wait=False)       # this micro-batch's counters were copied before `ev`
+        if host_nb is not None:
+            nb_h[b0:b0 + host_nb.shape[0]] = host_nb.numpy()
         if poses_h is None:
             raw_abs.append(host_abs)
             raw_rel.append(host_rel)
@@ -606,7 +633,19 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours, micro_batch: int 
             pipe.acquire(i & 1)
         else:
             x = queries[b0:b1]
-        ab, rel, ei = model.forward_map(x, nb_dev[b0:b1], fmap)
+        host_nb = None
+        if rule is None:
+            ab, rel, ei = model.forward_map(x, nb_dev[b0:b1], fmap)
+        else:
+            qd = None
+            if qd_all is not None:
+                qd = qd_all[b0:b1]
+                if not qd.is_cuda:
+                    qd = (qd if qd.is_pinned() else qd.pin_memory()).to(device, non_blocking=True)
+            ab, rel, ei, nb_mb = model.forward_map(x, None, fmap, rule=rule, query_descriptors=qd,
+                                                   query_groups=None if qg_all is None else qg_all[b0:b1])
+            host_nb = torch.empty(nb_mb.shape, dtype=nb_mb.dtype, pin_memory=True)
+            host_nb.copy_(nb_mb, non_blocking=True)
         if on_host:
             pipe.release(i & 1)
         host_abs = torch.empty(ab.shape, dtype=ab.dtype, pin_memory=True)
@@ -623,7 +662,7 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours, micro_batch: int 
             handle = begin(i + 1)
         if pending is not None:
             finish(pending)
-        pending = (b0, host_abs, host_rel, host_ei, ev)
+        pending = (b0, host_abs, host_rel, host_ei, host_nb, ev)
     if pending is not None:
         finish(pending)
     model.check_edge_index()
@@ -634,9 +673,12 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours, micro_batch: int 
         stats["staged_bytes"] = pipe.staged_bytes if pipe else 0
         stats["direct_bytes"] = pipe.direct_bytes if pipe else 0
         stats["staging_workers"] = pipe.workers if pipe else 0
+        stats["neighbours"] = nb_h
     if poses_h is None:
         return torch.cat(raw_abs), torch.cat(raw_rel)
     pred = np.stack(preds) if preds else np.zeros((0, 7))
     if targ_h is None:
         return pred
-    return errors(pred, np.stack(targs) if targs else np.zeros((0, 7)))
+    res = errors(pred, np.stack(targs) if targs else np.zeros((0, 7)))
+    res.neighbours = nb_h
+    return res

@@ -35,6 +35,21 @@ def _chunks(images: ImageSource, chunk: int):
             yield part[i:i + chunk]
 
 
+def _descriptors_tensor(desc, n: int, device) -> torch.Tensor:
+    d = torch.as_tensor(desc)
+    if d.dim() != 2 or d.shape[0] != n or d.shape[1] == 0 or d.shape[1] % 4:
+        raise ValueError(f"descriptors must be [{n}, Dd] with Dd % 4 == 0 (one retrieval descriptor per row), got {tuple(d.shape)}")
+    return d.to(device=device, dtype=torch.float32).contiguous()
+
+
+def _groups_tensor(groups, n: int) -> torch.Tensor:
+    """Host int64 [n]: the rows' exclusion groups (the device copy is made from it)."""
+    g = torch.as_tensor(groups)
+    if g.dim() != 1 or g.shape[0] != n or g.dtype.is_floating_point or g.dtype == torch.bool:
+        raise ValueError(f"groups must be integers [{n}] (one exclusion group id per row), got {tuple(g.shape)} {g.dtype}")
+    return g.to(device="cpu", dtype=torch.int64).contiguous()
+
+
 def _poses_tensor(poses, n: int, device) -> torch.Tensor:
     p = torch.as_tensor(poses)
     if p.dim() != 2 or p.shape[1] != 6 or p.shape[0] != n:
@@ -44,9 +59,14 @@ def _poses_tensor(poses, n: int, device) -> torch.Tensor:
 
 class FeatureMap:
     """``features`` fp32 [M, feat_dim] on the device; optional ``poses`` fp32 [M, 6] (the database images' ``y``, in the
-    reference's ``[t, log q]`` target layout); ``meta`` = {"feat_dim", "precision", "encoder_digest"}."""
+    reference's ``[t, log q]`` target layout); ``meta`` = {"feat_dim", "precision", "encoder_digest"}.
 
-    def __init__(self, features: torch.Tensor, meta: dict, poses: Optional[torch.Tensor] = None):
+    For retrieval (``retrieve``, ``forward_map(..., rule=...)``): optional ``descriptors`` fp32 [M, Dd] on the device (``None``:
+    the map's own ``features`` are the descriptors) and ``groups`` int64 [M] (``None``: no exclusion; kept on the host as
+    ``groups_host`` too, because a rule with random draws needs each query's allowed-row count before the launch).  The
+    inverse norms of whichever matrix is the descriptor are cached on first use and never saved."""
+
+    def __init__(self, features: torch.Tensor, meta: dict, poses: Optional[torch.Tensor] = None, descriptors=None, groups=None):
         if not torch.is_tensor(features) or features.dim() != 2 or features.dtype != torch.float32:
             raise ValueError("features must be an fp32 tensor [M, feat_dim]")
         for key in ("feat_dim", "precision", "encoder_digest"):
@@ -58,6 +78,11 @@ class FeatureMap:
             poses = _poses_tensor(poses, features.shape[0], features.device)
         self.features = features.contiguous()
         self.poses = poses
+        self.descriptors = None if descriptors is None else _descriptors_tensor(descriptors, features.shape[0], features.device)
+        self.groups_host = None if groups is None else _groups_tensor(groups, features.shape[0])
+        self.groups = None if groups is None else self.groups_host.to(features.device)
+        self._inv_norms = None
+        self._group_counts = None
         self.meta = {"feat_dim": int(meta["feat_dim"]), "precision": str(meta["precision"]),
                      "encoder_digest": str(meta["encoder_digest"])}
 
@@ -74,7 +99,9 @@ class FeatureMap:
 
     def __repr__(self) -> str:
         return (f"FeatureMap(rows={len(self)}, feat_dim={self.feat_dim}, precision={self.meta['precision']!r}, "
-                f"poses={'yes' if self.poses is not None else 'no'}, device={self.device})")
+                f"poses={'yes' if self.poses is not None else 'no'}, "
+                f"descriptors={'own features' if self.descriptors is None else self.descriptors.shape[1]}, "
+                f"groups={'yes' if self.groups is not None else 'no'}, device={self.device})")
 
     # ---- building --------------------------------------------------------------------------------------------------
     @staticmethod
@@ -96,27 +123,107 @@ class FeatureMap:
         return torch.cat(feats) if feats else torch.empty((0, d), dtype=torch.float32, device=device)
 
     @classmethod
-    def build(cls, model, images: ImageSource, poses=None, chunk: int = 256) -> "FeatureMap":
+    def build(cls, model, images: ImageSource, poses=None, chunk: int = 256, descriptors=None, groups=None) -> "FeatureMap":
         """Encode ``images`` through ``model``'s encoder in chunks of ``chunk`` images.  ``images``: fp32 (or bf16, for the bf16
         encoder) processed images [n, 3*H*W] / [n, 3, H, W], or uint8 frames [n, H, W, 3] through ``model.frame_transform``;
-        a host or device tensor, or an iterable of such chunks."""
+        a host or device tensor, or an iterable of such chunks.  ``descriptors`` [n, Dd] / ``groups`` [n]: see the class."""
         device = cls._model_device(model)
         meta = cls.model_meta(model)
         feats = cls._encode(model, images, chunk, device)
         if feats.shape[0] == 0:
             raise ValueError("FeatureMap.build: no images")
-        return cls(feats, meta, None if poses is None else _poses_tensor(poses, feats.shape[0], device))
+        return cls(feats, meta, None if poses is None else _poses_tensor(poses, feats.shape[0], device), descriptors, groups)
 
-    def extend(self, model, images: ImageSource, poses=None, chunk: int = 256) -> "FeatureMap":
-        """Append the features of more database images (same encoder; poses given iff the map has poses).  Returns self."""
+    def extend(self, model, images: ImageSource, poses=None, chunk: int = 256, descriptors=None, groups=None) -> "FeatureMap":
+        """Append the features of more database images (same encoder; poses / descriptors / groups given iff the map has them).
+        Returns self."""
         self.check(model)
-        if (poses is None) != (self.poses is None):
-            raise ValueError("extend: poses must be given exactly when the map holds poses (every row has one or none has)")
+        self._check_extend(poses, descriptors, groups)
         feats = self._encode(model, images, chunk, self.device)
-        if poses is not None:
-            self.poses = torch.cat([self.poses, _poses_tensor(poses, feats.shape[0], self.device)])
+        return self._append(feats, poses, descriptors, groups)
+
+    def _check_extend(self, poses, descriptors, groups) -> None:
+        for name, given, held in (("poses", poses, self.poses), ("descriptors", descriptors, self.descriptors),
+                                  ("groups", groups, self.groups)):
+            if (given is None) != (held is None):
+                raise ValueError(f"extend: {name} must be given exactly when the map holds {name} (every row has one or none has)")
+
+    def _append(self, feats: torch.Tensor, poses, descriptors, groups) -> "FeatureMap":
+        n = feats.shape[0]
+        new_poses = None if poses is None else _poses_tensor(poses, n, self.device)
+        new_desc = None if descriptors is None else _descriptors_tensor(descriptors, n, self.device)
+        new_groups = None if groups is None else _groups_tensor(groups, n)
+        if new_desc is not None and new_desc.shape[1] != self.descriptors.shape[1]:
+            raise ValueError(f"extend: descriptors have {new_desc.shape[1]} columns, the map's have {self.descriptors.shape[1]}")
+        if new_poses is not None:
+            self.poses = torch.cat([self.poses, new_poses])
+        if new_desc is not None:
+            self.descriptors = torch.cat([self.descriptors, new_desc])
+        if new_groups is not None:
+            self.groups_host = torch.cat([self.groups_host, new_groups])
+            self.groups = self.groups_host.to(self.device)
         self.features = torch.cat([self.features, feats])
+        self._inv_norms, self._group_counts = None, None      # of the rows as they were: recomputed on the next retrieval
         return self
+
+    # ---- retrieval ------------------------------------------------------------------------------------------------------
+    @property
+    def descriptor_matrix(self) -> torch.Tensor:
+        """What queries are matched against: ``descriptors``, or the map's own ``features``."""
+        return self.features if self.descriptors is None else self.descriptors
+
+    def inv_norms(self) -> torch.Tensor:
+        """1 / |row| of ``descriptor_matrix`` (fp32 [M], on the device), computed once per set of rows."""
+        if self._inv_norms is None or self._inv_norms.shape[0] != len(self):
+            from . import ops
+            self._inv_norms = ops.row_inv_norms(self.descriptor_matrix)
+        return self._inv_norms
+
+    def _query_groups(self, query_groups, g: int):
+        """(host int64 [g] or None, device int64 [g] or None) of the queries' exclusion groups."""
+        if query_groups is None or self.groups is None:
+            if query_groups is not None:
+                raise ValueError("retrieve: query_groups given, but the map has no groups to exclude by")
+            return None, None
+        qg = torch.as_tensor(query_groups)
+        if qg.dim() != 1 or qg.shape[0] != g or qg.dtype.is_floating_point or qg.dtype == torch.bool:
+            raise ValueError(f"retrieve: query_groups must be integers [{g}] (-1: exclude nothing), got {tuple(qg.shape)} {qg.dtype}")
+        host = qg.to(device="cpu", dtype=torch.int64)                 # (a device tensor is read back here: pass host ids)
+        if qg.is_cuda and qg.dtype == torch.int64 and qg.device == self.device:
+            dev = qg.contiguous()
+        else:
+            dev = (host if host.is_pinned() else host.pin_memory()).to(self.device, non_blocking=True)
+        return host, dev
+
+    def n_allowed(self, query_groups_host, g: int):
+        """Per query the number of map rows its group leaves (numpy int64 [g]): M - count(groups == query_group), all M rows
+        for group -1 or without groups.  On the host: the rule's random draws are sized by it (retrieval.py)."""
+        import numpy as np
+        m = len(self)
+        if query_groups_host is None or self.groups_host is None:
+            return np.full(g, m, dtype=np.int64)
+        if self._group_counts is None:
+            ids, counts = np.unique(self.groups_host.numpy(), return_counts=True)
+            self._group_counts = dict(zip(ids.tolist(), counts.tolist()))
+        return np.asarray([m if q == -1 else m - self._group_counts.get(q, 0) for q in query_groups_host.tolist()], dtype=np.int64)
+
+    def retrieve(self, query_descriptors: torch.Tensor, rule, query_groups=None, status=None, workspace=None) -> torch.Tensor:
+        """int64 [G, K] on the map's device: per query the map rows ``rule`` picks from the ranking of ``descriptor_matrix`` by
+        cosine similarity to ``query_descriptors`` fp32 [G, Dd] (on the map's device), rows of the query's group left out
+        (``query_groups`` [G], host integers; -1 or None: nothing left out).  ``status`` / ``workspace``: as ``ops.retrieve``."""
+        from . import ops
+        if not torch.is_tensor(query_descriptors) or query_descriptors.dim() != 2:
+            raise ValueError("retrieve: query_descriptors must be a tensor [G, Dd]")
+        db = self.descriptor_matrix
+        g = query_descriptors.shape[0]
+        if query_descriptors.shape[1] != db.shape[1]:
+            raise ValueError(f"retrieve: query descriptors have {query_descriptors.shape[1]} columns, the map's have {db.shape[1]}")
+        if rule.k > len(self):
+            raise ValueError(f"retrieve: the rule picks {rule.k} rows, the map has {len(self)}")
+        qg_host, qg_dev = self._query_groups(query_groups, g)
+        ranks = rule.device_ranks(self.n_allowed(qg_host, g), self.device)
+        return ops.retrieve(query_descriptors, db, ranks, db_inv_norm=self.inv_norms(), q_group=qg_dev,
+                            db_group=None if qg_dev is None else self.groups, status=status, workspace=workspace)
 
     @staticmethod
     def _model_device(model) -> torch.device:
@@ -144,6 +251,10 @@ class FeatureMap:
         obj = {"format": FORMAT, "meta": dict(self.meta), "features": self.features.detach().cpu()}
         if self.poses is not None:
             obj["poses"] = self.poses.detach().cpu()
+        if self.descriptors is not None:
+            obj["descriptors"] = self.descriptors.detach().cpu()
+        if self.groups_host is not None:
+            obj["groups"] = self.groups_host
         torch.save(obj, path)
 
     @classmethod
@@ -151,5 +262,6 @@ class FeatureMap:
         obj = torch.load(path, map_location="cpu", weights_only=True)
         if not isinstance(obj, dict) or obj.get("format") != FORMAT:
             raise ValueError(f"{path}: not a saved FeatureMap (format {FORMAT!r})")
-        poses = obj.get("poses")
-        return cls(obj["features"].to(device), obj["meta"], None if poses is None else poses.to(device))
+        poses = obj.get("poses")                  # optional keys: a file written before they existed loads as before
+        return cls(obj["features"].to(device), obj["meta"], None if poses is None else poses.to(device),
+                   obj.get("descriptors"), obj.get("groups"))

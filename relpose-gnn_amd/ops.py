@@ -439,6 +439,82 @@ def gather_graph_nodes(query_feat: torch.Tensor, map_feat: torch.Tensor, neighbo
     return out
 
 
+def row_inv_norms(x: torch.Tensor) -> torch.Tensor:
+    """1 / |x_r| per row of x [M, d] (rpg_row_inv_norms_f32; 0 for a zero row): what ``retrieve`` takes as ``db_inv_norm``."""
+    x = _req(x, "x")
+    if x.dim() != 2 or x.shape[0] == 0 or x.shape[1] == 0 or x.shape[1] % 4:
+        raise ValueError(f"row_inv_norms: needs x [M >= 1, d] with d % 4 == 0, got {tuple(x.shape)}")
+    out = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
+    L.check(L.lib().rpg_row_inv_norms_f32(_p(x), x.shape[0], x.shape[1], _p(out), _stream()), "row_inv_norms")
+    return out
+
+
+def retrieve(q: torch.Tensor, db: torch.Tensor, ranks, db_inv_norm: Optional[torch.Tensor] = None,
+             q_group: Optional[torch.Tensor] = None, db_group: Optional[torch.Tensor] = None, return_sims: bool = False,
+             status: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
+             out: Optional[torch.Tensor] = None):
+    """Per query the database rows at positions ``ranks[g]`` of its ranking (rpg_retrieve_cosine_f32): q [G, d], db [M, d] fp32,
+    ranks int32 [G, K] (a tensor on the GPU, or host integers), strictly ascending per query -> neighbours int64 [G, K] (and
+    their similarities [G, K] with ``return_sims``).  Row m is skipped for query g when ``db_group[m] == q_group[g]`` (int64
+    [M] / [G]; both or neither; ``q_group[g] == -1`` skips nothing).  A rank outside query g's allowed rows or the kernel's
+    ``R_MAX``, or a row of ranks that does not ascend, is counted into ``status`` (int32 device tensor, accumulates; the rank
+    is clamped) -- with ``status=None`` the count is read back here (one synchronisation) and a non-zero count raises
+    IndexError.  ``workspace``: a uint8 device tensor to use instead of allocating one; ``out``: the neighbours' tensor."""
+    q, db = _req(q, "q"), _req(db, "db")
+    if q.dim() != 2 or db.dim() != 2:
+        raise ValueError("retrieve: q [G, d] and db [M, d] must be 2-D")
+    (g, d), (m, dm) = q.shape, db.shape
+    if dm != d:
+        raise ValueError(f"retrieve: shapes do not agree: q {tuple(q.shape)}, db {tuple(db.shape)}")
+    if db.device != q.device:
+        raise RuntimeError("retrieve: q and db must be on the same GPU")
+    if not torch.is_tensor(ranks):
+        ranks = torch.as_tensor(ranks, dtype=torch.int32).to(q.device)
+    ranks = _req(ranks, "ranks", torch.int32)
+    if ranks.dim() != 2 or ranks.shape[0] != g or ranks.device != q.device:
+        raise ValueError(f"retrieve: ranks must be int32 [G = {g}, K] on the inputs' GPU, got {tuple(ranks.shape)}")
+    k = ranks.shape[1]
+    if g == 0 or not 1 <= k <= 64 or m < k or m >= 1 << 31 or d == 0 or d % 4:
+        raise ValueError(f"retrieve: needs G >= 1, 1 <= K <= 64, K <= M < 2^31 and d % 4 == 0 (G={g}, K={k}, M={m}, d={d})")
+    if (q_group is None) != (db_group is None):
+        raise ValueError("retrieve: q_group and db_group go together (both or neither)")
+    if q_group is not None:
+        q_group, db_group = _req(q_group, "q_group", torch.int64), _req(db_group, "db_group", torch.int64)
+        if q_group.shape != (g,) or db_group.shape != (m,) or q_group.device != q.device or db_group.device != q.device:
+            raise ValueError(f"retrieve: q_group must be int64 [{g}] and db_group int64 [{m}] on the inputs' GPU")
+    if db_inv_norm is not None:
+        db_inv_norm = _req(db_inv_norm, "db_inv_norm")
+        if db_inv_norm.shape != (m,) or db_inv_norm.device != q.device:
+            raise ValueError(f"retrieve: db_inv_norm must be fp32 [{m}] on the inputs' GPU")
+    lib = L.lib()
+    need = int(lib.rpg_retrieve_workspace_bytes(g, m, d))
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=q.device)
+    elif workspace.dtype != torch.uint8 or workspace.device != q.device or not workspace.is_contiguous():
+        raise ValueError("retrieve: workspace must be a contiguous uint8 tensor on the inputs' GPU")
+    if out is None:
+        nbrs = torch.empty((g, k), dtype=torch.int64, device=q.device)
+    elif out.shape != (g, k) or out.dtype != torch.int64 or not out.is_contiguous() or out.device != q.device:
+        raise ValueError(f"retrieve: out must be a contiguous int64 [{g}, {k}] tensor on the inputs' GPU")
+    else:
+        nbrs = out
+    sims = torch.empty((g, k), dtype=torch.float32, device=q.device) if return_sims else None
+    sync = status is None
+    if sync:
+        status = torch.zeros(1, dtype=torch.int32, device=q.device)
+    elif status.dtype != torch.int32 or status.device != q.device or status.numel() < 1:
+        raise ValueError("retrieve: status must be an int32 tensor on the inputs' GPU")
+    L.check(lib.rpg_retrieve_cosine_f32(_p(q), _p(db), _p(db_inv_norm), _p(q_group), _p(db_group), _p(ranks), g, k, m, d,
+                                        _p(nbrs), _p(sims), workspace.data_ptr(), workspace.numel(), status.data_ptr(),
+                                        _stream()), "retrieve")
+    if sync:
+        bad = int(status.item())
+        if bad:
+            raise IndexError(f"ranks has {bad} entry(ies) outside a query's allowed rows / the kernel's R_MAX, or rows that do "
+                             "not ascend")
+    return (nbrs, sims) if return_sims else nbrs
+
+
 def linear_gather(sources: Sequence[Tuple[torch.Tensor, Optional[torch.Tensor]]], weight: torch.Tensor,
                   bias: Optional[torch.Tensor], m: int, residual: Optional[torch.Tensor] = None, relu: bool = False) -> torch.Tensor:
     """out[m] = act(cat_k(a_k[idx_k[m]]) @ weight.T + bias (+ residual)); sources = [(a_k, idx_k or None), ...]."""

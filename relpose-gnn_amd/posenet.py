@@ -516,14 +516,28 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
         return hit
 
     @torch.no_grad()
-    def forward_map(self, queries: torch.Tensor, neighbours: torch.Tensor, fmap, k=None):
+    def forward_map(self, queries: torch.Tensor, neighbours: Optional[torch.Tensor], fmap, k=None, *, rule=None,
+                    query_descriptors: Optional[torch.Tensor] = None, query_groups=None):
         """The forward of G graphs, each query g followed by the K database images ``neighbours[g]`` of the feature map ``fmap``
         (dataset_7Scenes_multi.py:340-345) -- with only the G queries through the encoder.  Returns what
         ``forward(fc_batch(assembled, K + 1), k)`` returns for the assembled images: (abs_pose [G*(K+1), 6], rel_pose [E, 6],
         edge_index [2, E]), fully-connected edges per graph in fc_edge_index order, or the kNN graph over the assembled node
         features with ``knn > 0`` / ``k``.  ``queries``: images as ``encode`` takes them; ``neighbours``: int64 [G, K] on the
         same GPU, K >= 1, rows of ``fmap`` (an index outside [0, M) raises IndexError under ``index_check``, as a bad edge does).
-        Every flag of ``forward`` applies; ``fmap.check(self)`` refuses a map of other encoder weights or precision."""
+        Every flag of ``forward`` applies; ``fmap.check(self)`` refuses a map of other encoder weights or precision.
+
+        ``neighbours=None`` with a ``rule`` (retrieval.RetrievalRule) retrieves them on the GPU (dataset_7Scenes_multi.py:238-264)
+        and returns them as a FOURTH element, int64 [G, rule.k]: without ``query_descriptors`` the query's own encoder feature,
+        which this call has just computed, is matched against ``fmap.features``; a map that holds ``descriptors`` needs
+        ``query_descriptors`` fp32 [G, Dd] on the same GPU.  ``query_groups`` [G] (host integers): rows of ``fmap.groups`` equal
+        to a query's group are left out; -1 leaves nothing out.  Nothing blocks: the ranks are made on the host before the
+        launch, and a rank the map cannot serve is reported like a bad neighbour."""
+        if neighbours is not None and rule is not None:
+            raise ValueError("forward_map: give neighbours or a retrieval rule, not both")
+        if rule is None and (query_descriptors is not None or query_groups is not None):
+            raise ValueError("forward_map: query_descriptors / query_groups belong to retrieval: pass a rule (and neighbours=None)")
+        if rule is not None:
+            return self._forward_map_retrieve(queries, fmap, k, rule, query_descriptors, query_groups)
         if not torch.is_tensor(queries) or not torch.is_tensor(neighbours):
             raise TypeError("forward_map: queries and neighbours must be tensors")
         if neighbours.dtype != torch.int64 or neighbours.dim() != 2:
@@ -539,6 +553,53 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
         if neighbours.device != queries.device or fmap.device != queries.device:
             raise RuntimeError(f"forward_map: queries ({queries.device}), neighbours ({neighbours.device}) and the feature map "
                                f"({fmap.device}) must be on the same GPU")
+        nb = neighbours.contiguous()
+        return self._forward_map_run(queries, fmap, k, g, kk, lambda qf, g0, g1, st, wkey: nb[g0:g1])
+
+    def _forward_map_retrieve(self, queries, fmap, k, rule, query_descriptors, query_groups):
+        """``forward_map`` with the neighbours retrieved per stream slot from that slot's query features (or descriptors)."""
+        if not torch.is_tensor(queries):
+            raise TypeError("forward_map: queries must be a tensor")
+        if fmap.descriptors is not None and query_descriptors is None:
+            raise ValueError("forward_map: the map holds its own retrieval descriptors, so the queries' descriptors must be given "
+                             "(query_descriptors [G, Dd]); only a map without descriptors is matched by encoder features")
+        if fmap.descriptors is None and query_descriptors is not None:
+            raise ValueError("forward_map: query_descriptors given, but the map holds no descriptors to match them against")
+        g, kk = queries.size(0), rule.k
+        if g < 1:
+            raise ValueError("forward_map: no queries")
+        if kk > len(fmap):
+            raise ValueError(f"forward_map: the rule picks {kk} rows, the map has {len(fmap)}")
+        qd = None
+        if query_descriptors is not None:
+            qd = query_descriptors
+            if not torch.is_tensor(qd) or qd.dtype != torch.float32 or qd.dim() != 2 or qd.shape != (g, fmap.descriptors.shape[1]):
+                raise ValueError(f"forward_map: query_descriptors must be fp32 [{g}, {fmap.descriptors.shape[1]}]")
+        if not queries.is_cuda:
+            raise RuntimeError("forward_map: queries must be on the GPU (there is no CPU fallback)")
+        if fmap.device != queries.device or (qd is not None and qd.device != queries.device):
+            raise RuntimeError(f"forward_map: queries ({queries.device}), query_descriptors and the feature map ({fmap.device}) "
+                               f"must be on the same GPU")
+        dev = queries.device
+        # everything the slots share is made here, on the caller's stream, before any side stream is forked off it
+        qd = None if qd is None else qd.contiguous()
+        qg_host, qg_dev = fmap._query_groups(query_groups, g)
+        ranks = rule.device_ranks(fmap.n_allowed(qg_host, g), dev)
+        inv, db = fmap.inv_norms(), fmap.descriptor_matrix
+        db_groups = None if qg_dev is None else fmap.groups
+        nb_out = torch.empty((g, kk), dtype=torch.int64, device=dev)
+        ws_bytes = _L.lib().rpg_retrieve_workspace_bytes
+
+        def neighbours_of(qf, g0, g1, st, wkey):
+            ws = self._ws_pool.get((400 + wkey[0], wkey[1]), int(ws_bytes(g1 - g0, db.shape[0], db.shape[1])), dev)
+            return ops.retrieve(qf if qd is None else qd[g0:g1], db, ranks[g0:g1], db_inv_norm=inv,
+                                q_group=None if qg_dev is None else qg_dev[g0:g1], db_group=db_groups, status=st, workspace=ws,
+                                out=nb_out[g0:g1])
+        return (*self._forward_map_run(queries, fmap, k, g, kk, neighbours_of), nb_out)
+
+    def _forward_map_run(self, queries, fmap, k, g, kk, neighbours_of):
+        """``neighbours_of(qf, g0, g1, status, wkey)``: the map rows int64 [g1 - g0, K] of queries g0..g1, whose encoder features
+        are ``qf``, made on the current (slot) stream."""
         fmap.check(self)
         x = self._encoder_input(queries, "queries")
         lib = _L.lib()
@@ -547,7 +608,6 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
         self._pack_gnn()
         self._enc.ensure_packed(self.feature_extractor.state_dict, "", dev)
         status = self._status_buffers(dev)
-        nb = neighbours.contiguous()
         n_per = kk + 1
         edge_index, batch = self._map_graph(g, n_per, dev)
         edge_index = edge_index.clone()           # the caller's to keep (the cached copy serves the next call)
@@ -564,9 +624,11 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
             def features(n0, n1, wkey):           # the slot's queries through the encoder, then its graphs' nodes
                 g0, g1 = n0 // n_per, n1 // n_per
                 qf = self._enc.run(enc_sd, "", x[g0:g1], slot=wkey)
-                return ops.gather_graph_nodes(qf, fmap.features, nb[g0:g1], status=status[8 + wkey[0]:9 + wkey[0]])
+                st = status[8 + wkey[0]:9 + wkey[0]]
+                return ops.gather_graph_nodes(qf, fmap.features, neighbours_of(qf, g0, g1, st, wkey), status=st)
             return self._forward_streams(lib, features, g * n_per, dev, edge_index, parts, batch)
-        feat = ops.gather_graph_nodes(self._encode_small(x), fmap.features, nb, status=status[8:9])
+        qf = self._encode_small(x)
+        feat = ops.gather_graph_nodes(qf, fmap.features, neighbours_of(qf, 0, g, status[8:9], (-1, 0)), status=status[8:9])
         return self._forward_tail(lib, feat, edge_index, batch, k)
 
     def _encoder_input(self, x: torch.Tensor, what: str) -> torch.Tensor:
