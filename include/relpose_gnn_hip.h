@@ -215,6 +215,35 @@ int rpg_retrieve_cosine_f32(const float* q, const float* db, const float* db_inv
                             int64_t* neighbours, float* sims, void* workspace, size_t workspace_bytes, int32_t* status,
                             void* stream);
 
+/* Pose recovery of an evaluation stream: per graph of ONE forward's output the query's pose and its errors, what eval_RP does
+ * on the host with the model outputs (testing/test.py:213-267; pose_utils.py:340-348 qexp, :420-431 the angular error).  In
+ * float64 arithmetic on the fp32 inputs, for graph i of g:
+ *   ref     = the ref_node-th column, in column order, whose target is the graph's first node          (test.py:227-229)
+ *   o       = pose[source of ref] - rel_pose[ref]                                                          (test.py:231)
+ *   pred    = (o[:3] * pose_s + pose_m, qexp(o[3:])),  targ = the same map of the query's own target row   (test.py:248-251)
+ *   out[i]  = pred[7], targ[7], |pred_t - targ_t|, 2 acos(min(1.0, max(-1.0, |<q_pred, q_targ>|))) * 180 / pi   (16 doubles)
+ * with Python's min / max (a NaN dot gives -1 and an error of 360); other non-finite inputs propagate as in numpy.
+ *   edge_src, edge_dst [e] int64  the two rows of the edge list the forward used (stored, or model-built), batch node ids
+ *   edge_first [g + 1] or NULL    graph i's columns are [edge_first[i], edge_first[i + 1]) (clamped into [0, e]); NULL: a column
+ *                                 belongs to the graph whose node range holds its target (a model-built kNN list)
+ * The graphs' nodes and poses come in one of two forms:
+ *   targets  node_first [g + 1] int64 (graph i owns nodes [node_first[i], node_first[i + 1])) and node_targets [n][6] fp32, the
+ *            collated `data.y`; map_poses, neighbours and query_targets NULL
+ *   map      node_first and node_targets NULL: graph i owns nodes [i (k + 1), (i + 1)(k + 1)), its node j >= 1 has the pose
+ *            map_poses[neighbours[i][j - 1]] (map_poses [m][6] fp32, neighbours [g][k] int64; an index outside [0, m) is
+ *            clamped -- rpg_gather_graph_nodes_f32 has counted it), its node 0 query_targets[i] ([g][6] fp32, or NULL: zeros)
+ * A graph with fewer than ref_node + 1 edges into its first node, with a reference edge whose source lies outside the graph, or
+ * (targets form) with nodes outside [0, n) gets a row of NaN and status [1] += 1 (the caller zeroes it; the host mirror raises
+ * ValueError on a non-zero count, the error evaluate.reference_edge raises).  Nothing reads out of bounds.
+ * out 16-byte aligned, e >= 1, g >= 1, ref_node >= 0 (RPG_ERR_BAD_ARG otherwise).  One wave per graph stepping over its columns
+ * 64 at a time (ballot + popcount, stops at the hit); no floating-point atomics: the chosen column and the bits of the row do
+ * not depend on arrival order.  One launch, no allocation, no synchronisation (graph-capturable).                        */
+int rpg_query_pose_f64(const float* rel_pose, const int64_t* edge_src, const int64_t* edge_dst, int64_t e,
+                       const int64_t* node_first, const int64_t* edge_first, int g, const float* node_targets, int64_t n,
+                       const float* map_poses, int64_t m, const int64_t* neighbours, int k, const float* query_targets,
+                       double pose_m0, double pose_m1, double pose_m2, double pose_s0, double pose_s1, double pose_s2,
+                       int ref_node, double* out, int32_t* status, void* stream);
+
 /* torch_cluster.knn_graph(x, k, batch, loop=False, flow='source_to_target') (posenet.py:1043-1050): for every node
  * the k nearest OTHER nodes of its graph by squared Euclidean distance (k+1 nearest including itself by
  * (distance, index), self match dropped).  x [n][d]; batch [n] int64 graph id per node, nodes of a graph contiguous,

@@ -10,6 +10,9 @@ def __getattr__(name):          # lazy: importing the package must not require t
     if name in ("PoseNetX_R2",):
         from .posenet import PoseNetX_R2
         return PoseNetX_R2
+    if name == "QueryPose":
+        from .query_pose import QueryPose
+        return QueryPose
     if name in ("resnet34", "ResNet"):
         from . import resnet
         return getattr(resnet, name)

@@ -1,0 +1,200 @@
+// Pose recovery of the evaluation streams: per graph of one forward's output the reference edge, the query's absolute pose
+// (t, q) and its translation / rotation error -- what eval_RP does on the host with the model outputs (testing/test.py:213-267:
+// the first edge into the query node, `target[source] - rel_pose`, qexp, translation * std + mean, the two losses;
+// evaluate.query_pose / evaluate.errors restate it in numpy).  float64 arithmetic on the fp32 inputs, like the host code.
+//
+// One wave per graph.  The wave steps over the graph's columns 64 at a time: every lane tests one column's target against the
+// graph's first node, a ballot gathers the 64 answers in COLUMN order, popcounts are accumulated until the `ref_node`-th hit is
+// inside the current step, and the wave stops there.  Which column is chosen is a function of the column order only.  Lane 0
+// then does the few dozen double operations of one pose and stores the row of 16 doubles as eight 16-byte stores.  The only
+// atomic is the integer count of bad graphs.  One launch, no allocation, no synchronisation.
+#include "rpg_common.h"
+
+#include <math.h>
+
+namespace {
+
+constexpr int QP_NT = 256;            // 4 waves = 4 graphs per workgroup
+
+struct QpArgs {
+    const float* rel_pose;            // [e][6]
+    const int64_t* edge_src;          // [e]
+    const int64_t* edge_dst;          // [e]
+    int64_t e;
+    const int64_t* node_first;        // [g + 1] (targets form) | null (map form: graph i owns nodes [i (k+1), (i+1)(k+1)))
+    const int64_t* edge_first;        // [g + 1] | null: the graph's columns are those whose target lies in its node range
+    int g;
+    const float* node_targets;        // [n][6] | null
+    int64_t n;
+    const float* map_poses;           // [m][6] | null
+    int64_t m;
+    const int64_t* neighbours;        // [g][k]
+    int k;
+    const float* query_targets;       // [g][6] | null (zeros)
+    double pose_m[3], pose_s[3];
+    int ref_node;
+    double* out;                      // [g][16]
+    int32_t* status;
+};
+
+__device__ __forceinline__ int64_t clamp_i64(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// (cos|v|, sin|v| / |v| * v), (1, 0, 0, 0) at |v| = 0   (pose_utils.py:340-348).  Non-finite input: |v| is NaN or inf, cos and
+// sin / |v| are NaN, and NaN * v is NaN in every component -- what numpy gives.
+__device__ __forceinline__ void qexp(const double* v, double* q) {
+#pragma clang fp contract(off)
+    const double n = sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+    const double s = n == 0.0 ? 1.0 : sin(n) / n;
+    q[0] = cos(n);
+    q[1] = s * v[0];
+    q[2] = s * v[1];
+    q[3] = s * v[2];
+}
+
+__global__ __launch_bounds__(QP_NT) void query_pose_kernel(const QpArgs a) {
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x & 63;
+    const int64_t gi = (int64_t)blockIdx.x * (QP_NT / 64) + (threadIdx.x >> 6);
+    if (gi >= a.g) return;                                // (the whole wave)
+    int64_t first, last;
+    if (a.node_first) {
+        first = a.node_first[gi];
+        last = a.node_first[gi + 1];
+    } else {
+        first = gi * (a.k + 1);
+        last = first + a.k + 1;
+    }
+    int64_t lo = 0, hi = a.e;
+    if (a.edge_first) {                                   // clamped: a wrong offset gives a wrong or bad row, never a read outside [0, e)
+        lo = clamp_i64(a.edge_first[gi], 0, a.e);
+        hi = clamp_i64(a.edge_first[gi + 1], 0, a.e);
+    }
+    // the ref_node-th column, in column order, whose target is the graph's first node (test.py:227-229)
+    int64_t ref = -1;
+    if (last > first) {                                   // (a graph without nodes owns no column)
+        int need = a.ref_node;
+        for (int64_t c0 = lo; c0 < hi; c0 += 64) {
+            const int64_t c = c0 + lane;
+            const bool hit = c < hi && a.edge_dst[c] == first;
+            unsigned long long mask = __ballot(hit);
+            const int cnt = __popcll(mask);
+            if (cnt > need) {
+                for (int i = 0; i < need; ++i) mask &= mask - 1;      // drop the hits before the wanted one
+                ref = c0 + (__ffsll((long long)mask) - 1);
+                break;
+            }
+            need -= cnt;
+        }
+    }
+    if (lane != 0) return;
+
+    double2* orow = reinterpret_cast<double2*>(a.out + gi * 16);
+    bool bad = ref < 0;
+    int64_t src = first;
+    if (!bad) {
+        src = a.edge_src[ref];
+        bad = src < first || src >= last;                 // the reference edge's source lies outside the graph
+    }
+    const float* trow = nullptr;                          // the query's own target row (null: zeros)
+    const float* srow = nullptr;                          // the target row of the reference edge's source node
+    if (a.node_targets) {
+        bad = bad || first < 0 || last > a.n;
+        if (!bad) {
+            trow = a.node_targets + first * 6;
+            srow = a.node_targets + src * 6;
+        }
+    } else if (!bad) {
+        trow = a.query_targets ? a.query_targets + gi * 6 : nullptr;
+        const int64_t s = src - first;                    // in [0, k]
+        if (s == 0) {
+            srow = trow;
+        } else {
+            // forward_map has counted a neighbour outside [0, m) already; here it is clamped like there
+            const int64_t idx = clamp_i64(a.neighbours[gi * a.k + (s - 1)], 0, a.m - 1);
+            srow = a.map_poses + idx * 6;
+        }
+    }
+    if (bad) {
+        atomicAdd(a.status, 1);
+        const double nan = __builtin_nan("");
+        for (int i = 0; i < 8; ++i) orow[i] = make_double2(nan, nan);
+        return;
+    }
+
+    const float* rrow = a.rel_pose + ref * 6;
+    double o[6], tg[6];
+    for (int i = 0; i < 6; ++i) {
+        o[i] = (srow ? (double)srow[i] : 0.0) - (double)rrow[i];      // test.py:231
+        tg[i] = trow ? (double)trow[i] : 0.0;
+    }
+    double pt[3], tt[3], pq[4], tq[4];
+    for (int i = 0; i < 3; ++i) {
+        pt[i] = o[i] * a.pose_s[i] + a.pose_m[i];                     // test.py:248-251
+        tt[i] = tg[i] * a.pose_s[i] + a.pose_m[i];
+    }
+    qexp(o + 3, pq);
+    qexp(tg + 3, tq);
+    const double dx = pt[0] - tt[0], dy = pt[1] - tt[1], dz = pt[2] - tt[2];
+    const double t_err = sqrt(dx * dx + dy * dy + dz * dz);
+    // 2 acos(|<q1, q2>|) in degrees (pose_utils.py:420-431); the clamp is Python's min(1.0, max(-1.0, d)): max keeps -1.0 unless
+    // d > -1.0, so a NaN dot becomes -1 and the error 360
+    double d = fabs(tq[0] * pq[0] + tq[1] * pq[1] + tq[2] * pq[2] + tq[3] * pq[3]);
+    d = d > -1.0 ? d : -1.0;
+    d = d < 1.0 ? d : 1.0;
+    const double q_err = 2.0 * acos(d) * 180.0 / M_PI;
+
+    orow[0] = make_double2(pt[0], pt[1]);
+    orow[1] = make_double2(pt[2], pq[0]);
+    orow[2] = make_double2(pq[1], pq[2]);
+    orow[3] = make_double2(pq[3], tt[0]);
+    orow[4] = make_double2(tt[1], tt[2]);
+    orow[5] = make_double2(tq[0], tq[1]);
+    orow[6] = make_double2(tq[2], tq[3]);
+    orow[7] = make_double2(t_err, q_err);
+}
+
+inline bool misaligned(const void* p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
+
+}  // namespace
+
+extern "C" int rpg_query_pose_f64(const float* rel_pose, const int64_t* edge_src, const int64_t* edge_dst, int64_t e,
+                                  const int64_t* node_first, const int64_t* edge_first, int g, const float* node_targets,
+                                  int64_t n, const float* map_poses, int64_t m, const int64_t* neighbours, int k,
+                                  const float* query_targets, double pose_m0, double pose_m1, double pose_m2, double pose_s0,
+                                  double pose_s1, double pose_s2, int ref_node, double* out, int32_t* status, void* stream) {
+    if (!rel_pose || !edge_src || !edge_dst || !out || !status || e < 1 || g < 1 || ref_node < 0) return RPG_ERR_BAD_ARG;
+    if ((node_targets == nullptr) == (map_poses == nullptr)) return RPG_ERR_BAD_ARG;      // one source of poses, not both
+    if (node_targets) {
+        if (!node_first || n < 1 || neighbours || query_targets) return RPG_ERR_BAD_ARG;
+    } else {
+        if (node_first || !neighbours || m < 1 || k < 1) return RPG_ERR_BAD_ARG;
+    }
+    if (misaligned(rel_pose, 3) || misaligned(node_targets, 3) || misaligned(map_poses, 3) || misaligned(query_targets, 3) ||
+        misaligned(edge_src, 7) || misaligned(edge_dst, 7) || misaligned(node_first, 7) || misaligned(edge_first, 7) ||
+        misaligned(neighbours, 7) || misaligned(status, 3) || !rpg::aligned16(out))
+        return RPG_ERR_BAD_ARG;
+    QpArgs a;
+    a.rel_pose = rel_pose;
+    a.edge_src = edge_src;
+    a.edge_dst = edge_dst;
+    a.e = e;
+    a.node_first = node_first;
+    a.edge_first = edge_first;
+    a.g = g;
+    a.node_targets = node_targets;
+    a.n = n;
+    a.map_poses = map_poses;
+    a.m = m;
+    a.neighbours = neighbours;
+    a.k = k;
+    a.query_targets = query_targets;
+    a.pose_m[0] = pose_m0, a.pose_m[1] = pose_m1, a.pose_m[2] = pose_m2;
+    a.pose_s[0] = pose_s0, a.pose_s[1] = pose_s1, a.pose_s[2] = pose_s2;
+    a.ref_node = ref_node;
+    a.out = out;
+    a.status = status;
+    const unsigned grid = (unsigned)((g + QP_NT / 64 - 1) / (QP_NT / 64));
+    hipLaunchKernelGGL(query_pose_kernel, dim3(grid), dim3(QP_NT), 0, rpg::as_stream(stream), a);
+    RPG_CHECK_LAUNCH("query_pose");
+    return RPG_OK;
+}

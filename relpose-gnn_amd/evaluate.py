@@ -244,8 +244,12 @@ class _MicroBatchRunner:
     edge list) into pinned host memory.  ``launch`` returns without waiting; ``item.ev`` marks the poses' arrival."""
 
     def __init__(self, model, device, micro_batch: int, h2d_dtype=torch.float32, local_world: int = 1, want_abs: bool = False,
-                 pinned_direct: bool = True):
+                 pinned_direct: bool = True, pose=None):
         self.model, self.device, self.micro_batch = model, device, int(micro_batch)
+        # pose (query_pose.QueryPose, GPU only): the pose rule of test.py:213-267 runs on the device behind the forward, and what
+        # comes back is its [G, 16] block (pred, targ, errors) INSTEAD of the relative poses and a model-built edge list
+        self.pose = pose
+        self.d2h_bytes = 0                 # payload copied back per micro-batch (poses / edge list / pose rows; not the status words)
         self.h2d_dtype, self.local_world, self.want_abs = h2d_dtype, local_world, want_abs
         # pinned_direct (when the caller did not force a staging dtype): a micro-batch whose fp32 images ALL sit in pinned host
         # memory -- what the reference's DataLoader(pin_memory=True) delivers, testing/test.py:193 -- goes to the device as it is,
@@ -297,9 +301,34 @@ class _MicroBatchRunner:
         pipe, handle = self._begin_staging(self.n_batches & 1, chunk)
         self._prefetched = (chunk, pipe, handle)
 
+    def _pose_inputs(self, chunk: Sequence[Data]):
+        """What the device pose rule reads besides the forward's output, sent from pinned memory on the current stream:
+        -> (node_first [G + 1], edge_first [G + 1] of the STORED edge lists, y [N, 6] fp32 = the chunk's collated targets)."""
+        device, n_g = self.device, len(chunk)
+        if any(g.y is None for g in chunk):
+            raise ValueError("postprocess='device': every graph needs its targets y [n, 6]")
+        ns = [int(g.x.shape[0]) for g in chunk]
+        idx = torch.empty(2 * (n_g + 1), dtype=torch.int64, pin_memory=True)
+        idx_np = idx.numpy()
+        idx_np[0] = idx_np[n_g + 1] = 0
+        np.cumsum(ns, out=idx_np[1:n_g + 1])
+        np.cumsum([int(g.edge_index.shape[1]) for g in chunk], out=idx_np[n_g + 2:])
+        if any(g.y.is_cuda for g in chunk):
+            y_dev = torch.cat([g.y.to(device=device, dtype=torch.float32).reshape(-1, 6) for g in chunk])
+        else:
+            y = torch.empty((sum(ns), 6), dtype=torch.float32, pin_memory=True)
+            off = 0
+            for g, n in zip(chunk, ns):
+                y[off:off + n].copy_(g.y.reshape(n, 6))
+                off += n
+            y_dev = y.to(device, non_blocking=True)
+        idx_dev = idx.to(device, non_blocking=True)
+        return idx_dev[:n_g + 1], idx_dev[n_g + 1:], y_dev
+
     def launch(self, chunk: Sequence[Data]):
         """-> (chunk, host_rel, host_ei | None, ev | None, host_abs | None, batch): batch = the collated micro-batch the forward
-        read (batch.x: the chunk's node images, rows in chunk order; batch.edge_index: batch node ids)."""
+        read (batch.x: the chunk's node images, rows in chunk order; batch.edge_index: batch node ids).  With ``pose`` host_rel
+        is the float64 [G, 16] block of the device pose rule and host_ei is None."""
         device, model = self.device, self.model
         k = self.n_batches & 1
         self.n_batches += 1
@@ -324,6 +353,7 @@ class _MicroBatchRunner:
                 batch = Batch.from_data_list([g.to(device, non_blocking=True) for g in chunk])
             else:
                 batch = Batch.from_data_list(chunk).to(device, non_blocking=True)
+        pose_in = self._pose_inputs(chunk) if self.pose is not None else None
         ab, rel, edge_index = model(batch)
         if staged:
             pipe.release(k)
@@ -332,15 +362,22 @@ class _MicroBatchRunner:
         model_built = edge_index is not batch.edge_index
         host_abs = None
         if self.on_gpu:
+            if self.pose is not None:
+                # a stored list is cut contiguously per graph; a model-built one is cut by its targets (edges_per_graph) in the kernel
+                rel = self.pose.from_targets(rel, edge_index, pose_in[0], pose_in[2], edge_first=None if model_built else pose_in[1])
+                model_built = False
             host = torch.empty(rel.shape, dtype=rel.dtype, pin_memory=True)
             host.copy_(rel, non_blocking=True)
+            self.d2h_bytes += host.numel() * host.element_size()
             if self.want_abs:
                 host_abs = torch.empty(ab.shape, dtype=ab.dtype, pin_memory=True)
                 host_abs.copy_(ab, non_blocking=True)
+                self.d2h_bytes += host_abs.numel() * host_abs.element_size()
             host_ei = None
             if model_built:
                 host_ei = torch.empty(edge_index.shape, dtype=edge_index.dtype, pin_memory=True)
                 host_ei.copy_(edge_index, non_blocking=True)
+                self.d2h_bytes += host_ei.numel() * host_ei.element_size()
             ev = torch.cuda.Event()
             ev.record()
         else:
@@ -360,7 +397,7 @@ def edges_per_graph(ei: np.ndarray, sizes: Sequence[int]):
 @torch.no_grad()
 def evaluate_stream(model, graphs: Sequence[Data], device, micro_batch: int = 64, pose_m=(0.0, 0.0, 0.0),
                     pose_s=(1.0, 1.0, 1.0), ref_node: int = 0, rank: int = 0, world: int = 1,
-                    stats: Optional[dict] = None, bf16_input: Optional[bool] = None) -> EvalResult:
+                    stats: Optional[dict] = None, bf16_input: Optional[bool] = None, postprocess: str = "host") -> EvalResult:
     """Run ``model`` over a stream of single-graph ``Data`` objects (x, edge_index, y) and post-process like test.py.
     With world > 1 every rank evaluates its contiguous block (shard_range) and the [G,7] rows are all-gathered.
 
@@ -379,8 +416,15 @@ def evaluate_stream(model, graphs: Sequence[Data], device, micro_batch: int = 64
     Graphs whose ``x`` is uint8 camera frames ``[n, H, W, 3]`` (one size per micro-batch) are sent as uint8 -- pinned sources
     straight from where they are, pageable ones through the staging threads as a plain copy -- and the model's
     ``frame_transform`` (frames.FrameTransform) runs the reference's image transform on the device; the byte counts in ``stats``
-    are then uint8 bytes."""
+    are then uint8 bytes.
+
+    ``postprocess``: ``"host"`` (default) copies every micro-batch's relative poses [E, 6] (and a model-built edge list) back and
+    applies the pose rule of test.py:213-267 in numpy, graph by graph.  ``"device"`` (GPU only) runs it as one kernel behind the
+    forward (``query_pose.QueryPose``: float64 on the fp32 outputs, the targets ``y`` taken as fp32) and copies 16 doubles per
+    graph back; the ``EvalResult`` is filled from those rows (under ``world > 1`` the gathered poses go through ``errors`` as
+    before).  ``stats`` also receives ``postprocess`` and ``d2h_bytes`` (the payload copied back)."""
     from .shard import rank_host_slice
+    _check_postprocess("evaluate_stream", postprocess, device)
     if world > 1 and torch.device(device).type == "cuda":
         import os
         # one process per GPU on a shared host: this rank's staging threads and pinned buffers stay on its share of the
@@ -389,19 +433,38 @@ def evaluate_stream(model, graphs: Sequence[Data], device, micro_batch: int = 64
         # from the launcher when it set them (ranks of other nodes do not share this host)
         local_world = int(os.environ.get("LOCAL_WORLD_SIZE", world))
         with rank_host_slice(int(os.environ.get("LOCAL_RANK", rank)), local_world, torch.device(device).index):
-            return _evaluate_stream(model, graphs, device, micro_batch, pose_m, pose_s, ref_node, rank, world, stats, bf16_input, local_world)
-    return _evaluate_stream(model, graphs, device, micro_batch, pose_m, pose_s, ref_node, rank, world, stats, bf16_input, 1)
+            return _evaluate_stream(model, graphs, device, micro_batch, pose_m, pose_s, ref_node, rank, world, stats, bf16_input, local_world,
+                                    postprocess)
+    return _evaluate_stream(model, graphs, device, micro_batch, pose_m, pose_s, ref_node, rank, world, stats, bf16_input, 1, postprocess)
 
 
-def _evaluate_stream(model, graphs, device, micro_batch, pose_m, pose_s, ref_node, rank, world, stats, bf16_input, local_world):
+def _check_postprocess(who: str, postprocess, device) -> None:
+    if postprocess not in ("host", "device"):
+        raise ValueError(f"{who}: postprocess must be 'host' or 'device', got {postprocess!r}")
+    if postprocess == "device" and torch.device(device).type != "cuda":
+        raise ValueError(f"{who}: postprocess='device' runs the pose rule on the GPU, the stream's device is {device}")
+
+
+def _result_from_rows(rows: np.ndarray) -> EvalResult:
+    """EvalResult of the device pose rule's rows [G, 16] = pred[7], targ[7], t_err, q_err."""
+    return EvalResult(np.ascontiguousarray(rows[:, :7]), np.ascontiguousarray(rows[:, 7:14]), rows[:, 14].copy(), rows[:, 15].copy())
+
+
+def _evaluate_stream(model, graphs, device, micro_batch, pose_m, pose_s, ref_node, rank, world, stats, bf16_input, local_world,
+                     postprocess="host"):
     from .shard import gather_rows, shard_counts, shard_range
+    qp = None
+    if postprocess == "device":
+        from .query_pose import QueryPose
+        qp = QueryPose(pose_m, pose_s, ref_node)
     pose_m, pose_s = np.asarray(pose_m, dtype=np.float64), np.asarray(pose_s, dtype=np.float64)
     lo, hi = shard_range(len(graphs), rank, world)
     preds: List[np.ndarray] = []
     targs: List[np.ndarray] = []
     # the bf16 encoder takes its node images in bf16 (rounded while they are staged: half the H2D bytes, identical results)
     h2d_dtype = torch.bfloat16 if (bf16_input if bf16_input is not None else getattr(model, "accepts_bf16_input", False)) else torch.float32
-    runner = _MicroBatchRunner(model, device, micro_batch, h2d_dtype, local_world, pinned_direct=bf16_input is None)
+    runner = _MicroBatchRunner(model, device, micro_batch, h2d_dtype, local_world, pinned_direct=bf16_input is None, pose=qp)
+    rows: List[np.ndarray] = []
 
     def finish(item):
         chunk, host, host_ei, ev = item[:4]
@@ -410,6 +473,10 @@ def _evaluate_stream(model, graphs, device, micro_batch, pose_m, pose_s, ref_nod
         check = getattr(model, "check_edge_index", None)
         if check is not None:
             check(wait=False)  # this batch's bad-edge counters were copied before `ev`: look, do not wait for the NEXT batch
+        if qp is not None:
+            qp.check(wait=False)   # likewise the pose rule's count of graphs without a reference edge
+            rows.append(host.numpy())
+            return
         rel = host.numpy()
         if host_ei is not None:
             ei = host_ei.numpy()
@@ -453,14 +520,23 @@ def _evaluate_stream(model, graphs, device, micro_batch, pose_m, pose_s, ref_nod
         finish(pending)
     if getattr(model, "check_edge_index", None) is not None:
         model.check_edge_index()                       # everything has been issued: wait for the last report
+    if qp is not None:
+        qp.check()
     if stats is not None:
         stats["local_seconds"] = time.perf_counter() - t_local      # this rank's own block, before the all-gather
         stats["h2d_bytes"] = runner.h2d_bytes
+        stats["postprocess"] = postprocess
+        stats["d2h_bytes"] = runner.d2h_bytes
         stats["micro_batches"] = runner.n_batches
         # bytes that went pageable -> pinned through the staging threads / straight out of the caller's own pinned tensors
         stats.update(runner.pipe_stats())
-    pred = np.stack(preds) if preds else np.zeros((0, 7))
-    targ = np.stack(targs) if targs else np.zeros((0, 7))
+    all_rows = None
+    if qp is not None:
+        all_rows = np.concatenate(rows) if rows else np.zeros((0, 16))
+        pred, targ = all_rows[:, :7], all_rows[:, 7:14]
+    else:
+        pred = np.stack(preds) if preds else np.zeros((0, 7))
+        targ = np.stack(targs) if targs else np.zeros((0, 7))
     import torch.distributed as dist
     grouped = dist.is_available() and dist.is_initialized() and dist.get_world_size() == world
     if grouped and world == 1:
@@ -473,6 +549,8 @@ def _evaluate_stream(model, graphs, device, micro_batch, pose_m, pose_s, ref_nod
         both = torch.from_numpy(np.concatenate([pred, targ], 1)).to(device)
         both = gather_rows(both, shard_counts(len(graphs), world), always=True).cpu().numpy()
         pred, targ = both[:, :7], both[:, 7:]
+    elif all_rows is not None:
+        return _result_from_rows(all_rows)
     return errors(pred, targ)
 
 
@@ -508,7 +586,8 @@ def load_pose_stats(path):
 @torch.no_grad()
 def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch: int = 64, pose_m=(0.0, 0.0, 0.0),
                pose_s=(1.0, 1.0, 1.0), ref_node: int = 0, stats: Optional[dict] = None, targets=None,
-               bf16_input: Optional[bool] = None, *, rule=None, query_descriptors=None, query_groups=None):
+               bf16_input: Optional[bool] = None, *, rule=None, query_descriptors=None, query_groups=None,
+               postprocess: str = "host"):
     """The evaluation stream of the map path (``PoseNetX_R2.forward_map``): query g's graph is the query followed by the map
     rows ``neighbours[g]`` (its retrieved database images, dataset_7Scenes_multi.py:340-345).  Single process.
 
@@ -525,7 +604,13 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
     ``neighbours=None`` with a ``rule`` (retrieval.RetrievalRule) retrieves them on the GPU inside ``forward_map`` (which see
     for ``query_descriptors`` [G, Dd] -- host or device, staged per micro-batch -- and ``query_groups`` [G], host integers): the
     neighbours of micro-batch i come back to the host with its poses, by the same pinned non-blocking copy behind the same
-    event.  The chosen rows, int64 [G, K], are left in ``stats["neighbours"]`` and on an ``EvalResult`` as ``.neighbours``."""
+    event.  The chosen rows, int64 [G, K], are left in ``stats["neighbours"]`` and on an ``EvalResult`` as ``.neighbours``.
+
+    ``postprocess="device"`` (default ``"host"``): the pose rule runs on the GPU behind every ``forward_map``
+    (``query_pose.QueryPose.from_map`` on the map's poses and the device neighbours -- with a rule the rows ``forward_map`` has
+    just chosen -- and on ``targets``, staged once as fp32), and 16 doubles per query come back instead of the absolute and
+    relative poses and a model-built edge list.  Same return types; a map without poses returns its raw tensors either way.
+    ``stats`` also receives ``postprocess`` and ``d2h_bytes``."""
     import time
     from .graph import Data, fc_edge_index
     device = fmap.device
@@ -537,6 +622,7 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
         raise ValueError("relocalize: query_descriptors / query_groups belong to retrieval: pass a rule (and no neighbours)")
     if micro_batch < 1:
         raise ValueError("relocalize: micro_batch must be >= 1")
+    _check_postprocess("relocalize", postprocess, device)
     qd_all = qg_all = None
     if rule is None:
         nb = torch.as_tensor(neighbours)
@@ -565,6 +651,15 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
     poses_h = None if fmap.poses is None else fmap.poses.cpu().numpy().astype(np.float64)
     targ_h = None if targets is None else np.asarray(torch.as_tensor(targets).cpu(), dtype=np.float64).reshape(g_all, 6)
     fc_edges = fc_edge_index(n_per).numpy()
+    qp = targ_dev = fc_first = None
+    if postprocess == "device" and poses_h is not None:
+        from .query_pose import QueryPose
+        qp = QueryPose(pose_m, pose_s, ref_node)
+        if targets is not None:
+            t32 = torch.as_tensor(targets).detach().to(dtype=torch.float32).reshape(g_all, 6)
+            targ_dev = t32 if t32.is_cuda else (t32 if t32.is_pinned() else t32.pin_memory()).to(device, non_blocking=True)
+        if model.knn <= 0:         # forward_map's own FC list: n (n - 1) columns per graph, graph after graph
+            fc_first = torch.arange(min(micro_batch, g_all) + 1, dtype=torch.int64, device=device) * fc_edges.shape[1]
 
     # the staging dtype: uint8 frames as they are; otherwise the rule of _MicroBatchRunner (bf16 for the bf16 encoder, except
     # pinned fp32 sources sent as they are when this rank cannot spend >= 8 rounding threads)
@@ -588,8 +683,8 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
         step = -(-xq.shape[0] // w)
         return pipe.stage_begin(i & 1, [Data(x=xq[j:j + step]) for j in range(0, xq.shape[0], step)])
 
-    raw_abs, raw_rel, preds, targs = [], [], [], []
-    h2d = 0
+    raw_abs, raw_rel, preds, targs, rows = [], [], [], [], []
+    h2d = d2h = 0
 
     def finish(item):
         b0, host_abs, host_rel, host_ei, host_nb, ev = item
@@ -597,6 +692,10 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
         model.check_edge_index(wait=False)       # this micro-batch's counters were copied before `ev`
         if host_nb is not None:
             nb_h[b0:b0 + host_nb.shape[0]] = host_nb.numpy()
+        if qp is not None:
+            qp.check(wait=False)                 # likewise the pose rule's count of graphs without a reference edge
+            rows.append(host_rel.numpy())        # the [G, 16] block of the device pose rule
+            return
         if poses_h is None:
             raw_abs.append(host_abs)
             raw_rel.append(host_rel)
@@ -648,14 +747,24 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
             host_nb.copy_(nb_mb, non_blocking=True)
         if on_host:
             pipe.release(i & 1)
-        host_abs = torch.empty(ab.shape, dtype=ab.dtype, pin_memory=True)
-        host_abs.copy_(ab, non_blocking=True)
+        if host_nb is not None:
+            d2h += host_nb.numel() * host_nb.element_size()
+        host_abs = host_ei = None
+        if qp is not None:
+            rel = qp.from_map(rel, ei, fmap, nb_dev[b0:b1] if rule is None else nb_mb,
+                              query_targets=None if targ_dev is None else targ_dev[b0:b1],
+                              edge_first=None if fc_first is None else fc_first[:b1 - b0 + 1])
+        else:
+            host_abs = torch.empty(ab.shape, dtype=ab.dtype, pin_memory=True)
+            host_abs.copy_(ab, non_blocking=True)
+            d2h += host_abs.numel() * host_abs.element_size()
         host_rel = torch.empty(rel.shape, dtype=rel.dtype, pin_memory=True)
         host_rel.copy_(rel, non_blocking=True)
-        host_ei = None
-        if model.knn > 0:
+        d2h += host_rel.numel() * host_rel.element_size()
+        if qp is None and model.knn > 0:
             host_ei = torch.empty(ei.shape, dtype=ei.dtype, pin_memory=True)
             host_ei.copy_(ei, non_blocking=True)
+            d2h += host_ei.numel() * host_ei.element_size()
         ev = torch.cuda.Event()
         ev.record()
         if on_host and i + 1 < n_mb:
@@ -666,9 +775,13 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
     if pending is not None:
         finish(pending)
     model.check_edge_index()
+    if qp is not None:
+        qp.check()
     if stats is not None:
         stats["local_seconds"] = time.perf_counter() - t0
         stats["h2d_bytes"] = h2d
+        stats["postprocess"] = postprocess
+        stats["d2h_bytes"] = d2h
         stats["micro_batches"] = n_mb
         stats["staged_bytes"] = pipe.staged_bytes if pipe else 0
         stats["direct_bytes"] = pipe.direct_bytes if pipe else 0
@@ -676,6 +789,13 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
         stats["neighbours"] = nb_h
     if poses_h is None:
         return torch.cat(raw_abs), torch.cat(raw_rel)
+    if qp is not None:
+        all_rows = np.concatenate(rows) if rows else np.zeros((0, 16))
+        if targ_h is None:
+            return np.ascontiguousarray(all_rows[:, :7])
+        res = _result_from_rows(all_rows)
+        res.neighbours = nb_h
+        return res
     pred = np.stack(preds) if preds else np.zeros((0, 7))
     if targ_h is None:
         return pred

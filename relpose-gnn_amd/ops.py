@@ -7,6 +7,7 @@ tensors, allocates its output with ``torch.empty`` and launches the HIP kernel o
 from __future__ import annotations
 
 import ctypes as C
+import numbers
 from typing import Dict, Optional, Sequence, Tuple
 
 import torch
@@ -513,6 +514,129 @@ def retrieve(q: torch.Tensor, db: torch.Tensor, ranks, db_inv_norm: Optional[tor
             raise IndexError(f"ranks has {bad} entry(ies) outside a query's allowed rows / the kernel's R_MAX, or rows that do "
                              "not ascend")
     return (nbrs, sims) if return_sims else nbrs
+
+
+def _qp_tensor(t, name: str, dtype, shape) -> torch.Tensor:
+    """Host-side check of one ``query_pose`` argument: TypeError for a non-tensor / wrong dtype, ValueError for a wrong shape
+    (``shape``: ints, or None for an axis that is free)."""
+    if not torch.is_tensor(t):
+        raise TypeError(f"query_pose: {name} must be a tensor, got {type(t).__name__}")
+    if t.dtype != dtype:
+        raise TypeError(f"query_pose: {name} must be {dtype}, got {t.dtype}")
+    if t.dim() != len(shape) or any(s is not None and int(d) != s for d, s in zip(t.shape, shape)):
+        want = ", ".join("*" if s is None else str(s) for s in shape)
+        raise ValueError(f"query_pose: {name} must be [{want}], got {tuple(t.shape)}")
+    return t
+
+
+def _qp_triple(v, name: str) -> Tuple[float, float, float]:
+    try:
+        out = tuple(float(x) for x in v)
+    except TypeError:
+        raise TypeError(f"query_pose: {name} must be three numbers") from None
+    if len(out) != 3:
+        raise ValueError(f"query_pose: {name} must be three numbers, got {len(out)}")
+    return out
+
+
+def query_pose(rel_pose: torch.Tensor, edge_index: torch.Tensor, *, node_first: Optional[torch.Tensor] = None,
+               node_targets: Optional[torch.Tensor] = None, map_poses: Optional[torch.Tensor] = None,
+               neighbours: Optional[torch.Tensor] = None, query_targets: Optional[torch.Tensor] = None,
+               edge_first: Optional[torch.Tensor] = None, pose_m=(0.0, 0.0, 0.0), pose_s=(1.0, 1.0, 1.0), ref_node: int = 0,
+               status: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Per graph of one forward's output the query's pose and errors (rpg_query_pose_f64; evaluate.query_pose + evaluate.errors
+    on the device): rel_pose fp32 [E, 6] and edge_index int64 [2, E] as the forward returned them -> float64 [G, 16] =
+    pred (t, q) [7], targ (t, q) [7], translation error, rotation error in degrees.
+
+    The graphs come in one of two forms.  Targets: ``node_first`` int64 [G + 1] (graph g owns nodes node_first[g] ..
+    node_first[g + 1]) and ``node_targets`` fp32 [N, 6], the collated ``data.y``.  Map: ``map_poses`` fp32 [M, 6] and
+    ``neighbours`` int64 [G, K] (graph g is a query followed by those map rows; an index outside [0, M) is clamped), with
+    ``query_targets`` fp32 [G, 6] or None (zeros).  ``edge_first`` int64 [G + 1]: the columns of graph g when the edge list is
+    cut contiguously; None for a model-built list (a column then belongs to the graph whose nodes hold its target).
+
+    A graph without a ``ref_node``-th edge into its first node, or whose reference edge starts outside the graph, gets a row of
+    NaN and one count in ``status`` (int32 device tensor, accumulates) -- with ``status=None`` the count is read back here (one
+    synchronisation) and a non-zero count raises the ValueError of ``evaluate.reference_edge``.  Every argument is checked on
+    the host before anything is launched: TypeError for a wrong type or dtype, ValueError for a wrong shape or device."""
+    rel = _qp_tensor(rel_pose, "rel_pose", torch.float32, (None, 6))
+    e = int(rel.shape[0])
+    ei = _qp_tensor(edge_index, "edge_index", torch.int64, (2, e))
+    if e < 1:
+        raise ValueError("query_pose: needs at least one edge")
+    pm, ps = _qp_triple(pose_m, "pose_m"), _qp_triple(pose_s, "pose_s")
+    if isinstance(ref_node, bool) or not isinstance(ref_node, numbers.Integral):
+        raise TypeError(f"query_pose: ref_node must be an int, got {type(ref_node).__name__}")
+    if ref_node < 0:
+        raise ValueError(f"query_pose: ref_node must be >= 0, got {ref_node}")
+    ref_node = int(ref_node)
+    if (node_targets is None) == (map_poses is None):
+        raise ValueError("query_pose: give node_first + node_targets (the collated targets) or map_poses + neighbours (the map "
+                         "form): exactly one of the two")
+    n = m = k = 0
+    if node_targets is not None:
+        if neighbours is not None or query_targets is not None:
+            raise ValueError("query_pose: neighbours / query_targets belong to the map form (map_poses)")
+        if node_first is None:
+            raise ValueError("query_pose: node_targets needs node_first [G + 1]")
+        nf = _qp_tensor(node_first, "node_first", torch.int64, (None,))
+        g = int(nf.shape[0]) - 1
+        nt = _qp_tensor(node_targets, "node_targets", torch.float32, (None, 6))
+        n = int(nt.shape[0])
+        if n < 1:
+            raise ValueError("query_pose: node_targets is empty")
+        parts = [("node_first", nf), ("node_targets", nt)]
+    else:
+        if node_first is not None:
+            raise ValueError("query_pose: node_first belongs to the targets form (graph g of the map form owns nodes g (K + 1) ..)")
+        if neighbours is None:
+            raise ValueError("query_pose: map_poses needs neighbours [G, K]")
+        nb = _qp_tensor(neighbours, "neighbours", torch.int64, (None, None))
+        g, k = int(nb.shape[0]), int(nb.shape[1])
+        mp = _qp_tensor(map_poses, "map_poses", torch.float32, (None, 6))
+        m = int(mp.shape[0])
+        if k < 1 or m < 1:
+            raise ValueError(f"query_pose: needs K >= 1 neighbours per query and M >= 1 map rows (K={k}, M={m})")
+        parts = [("map_poses", mp), ("neighbours", nb)]
+        if query_targets is not None:
+            parts.append(("query_targets", _qp_tensor(query_targets, "query_targets", torch.float32, (g, 6))))
+    if g < 1:
+        raise ValueError("query_pose: no graphs")
+    if edge_first is not None:
+        parts.append(("edge_first", _qp_tensor(edge_first, "edge_first", torch.int64, (g + 1,))))
+    if out is not None:
+        _qp_tensor(out, "out", torch.float64, (g, 16))
+        if not out.is_contiguous():
+            raise ValueError("query_pose: out must be contiguous")
+    if status is not None:
+        if not torch.is_tensor(status) or status.dtype != torch.int32:
+            raise TypeError("query_pose: status must be an int32 tensor")
+        if status.numel() < 1:
+            raise ValueError("query_pose: status must hold one counter")
+    dev = rel.device
+    if dev.type != "cuda":
+        raise ValueError(f"query_pose: rel_pose must be on the GPU (the HIP kernel is the only compute path), got {dev}")
+    for name, t in [("edge_index", ei)] + parts + [("out", out), ("status", status)]:
+        if t is not None and t.device != dev:
+            raise ValueError(f"query_pose: {name} is on {t.device}, rel_pose on {dev}: everything must be on the same GPU")
+
+    rel, ei = rel.contiguous(), ei.contiguous()
+    by_name = {name: t.contiguous() for name, t in parts}
+    if out is None:
+        out = torch.empty((g, 16), dtype=torch.float64, device=dev)
+    sync = status is None
+    if sync:
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+    L.check(L.lib().rpg_query_pose_f64(_p(rel), ei.data_ptr(), ei.data_ptr() + 8 * e, e, _p(by_name.get("node_first")),
+                                       _p(by_name.get("edge_first")), g, _p(by_name.get("node_targets")), n,
+                                       _p(by_name.get("map_poses")), m, _p(by_name.get("neighbours")), k,
+                                       _p(by_name.get("query_targets")), *pm, *ps, ref_node, _p(out), status.data_ptr(),
+                                       _stream()), "query_pose")
+    if sync:
+        bad = int(status.item())
+        if bad:
+            raise ValueError(f"graph has no edge into node 0: cannot derive the query pose ({bad} graph(s) of this call lack "
+                             "the reference edge, or its source lies outside the graph)")
+    return out
 
 
 def linear_gather(sources: Sequence[Tuple[torch.Tensor, Optional[torch.Tensor]]], weight: torch.Tensor,

@@ -1,0 +1,114 @@
+"""``QueryPose``: the pose rule of the reference's evaluation (testing/test.py:213-267) on the device.
+
+``evaluate.query_pose`` / ``evaluate.errors`` do this on the host, graph by graph, from a copy of every relative pose.  A
+``QueryPose`` runs it as one kernel launch over all graphs of a forward's output (``ops.query_pose``, rpg_query_pose_f64) and
+returns a device tensor float64 [G, 16] per call: pred (t, q) [7], targ (t, q) [7], translation error, rotation error in degrees
+-- so a caller whose images, map poses and neighbours already live on the GPU gets the evaluation's products without a host
+round trip, and an evaluation stream copies 128 bytes per graph back instead of the [E, 6] relative poses.
+
+A graph that has no ``ref_node``-th edge into its query node (or whose reference edge starts outside the graph) cannot be
+evaluated: its row is NaN and it is counted in a status word this object owns.  ``check`` turns a non-zero count into the
+``ValueError`` of ``evaluate.reference_edge``, by the look-now / wait contract of ``PoseNetX_R2.check_edge_index``: the count
+travels to pinned host memory with an asynchronous copy behind every call, so nothing blocks unless the caller asks it to.
+"""
+from __future__ import annotations
+
+import numbers
+from typing import Optional
+
+import torch
+
+from . import ops
+
+
+class QueryPose:
+    def __init__(self, pose_m=(0.0, 0.0, 0.0), pose_s=(1.0, 1.0, 1.0), ref_node: int = 0):
+        """``pose_m`` / ``pose_s``: translation mean / std (test.py:126-130, 248-251); ``ref_node``: which of the edges into the
+        query node is the reference edge (test.py:227-229)."""
+        self.pose_m, self.pose_s = ops._qp_triple(pose_m, "pose_m"), ops._qp_triple(pose_s, "pose_s")
+        if isinstance(ref_node, bool) or not isinstance(ref_node, numbers.Integral):
+            raise TypeError(f"QueryPose: ref_node must be an int, got {type(ref_node).__name__}")
+        if ref_node < 0:
+            raise ValueError(f"QueryPose: ref_node must be >= 0, got {ref_node}")
+        self.ref_node = int(ref_node)
+        self._status: Optional[torch.Tensor] = None
+        self._status_host: Optional[torch.Tensor] = None      # pinned mirror
+        self._event: Optional[torch.cuda.Event] = None
+        self._pending = False
+
+    # ---- the two forms ---------------------------------------------------------------------------------------------------
+    def from_targets(self, rel_pose, edge_index, node_first, node_targets, edge_first=None, out=None) -> torch.Tensor:
+        """Graphs with collated targets (``evaluate_stream``): ``node_first`` int64 [G + 1], ``node_targets`` fp32 [N, 6] =
+        the batch's ``data.y``.  -> float64 [G, 16] on the device."""
+        return self._run(rel_pose, dict(edge_index=edge_index, node_first=node_first, node_targets=node_targets,
+                                        edge_first=edge_first, out=out))
+
+    def from_map(self, rel_pose, edge_index, fmap, neighbours, query_targets=None, edge_first=None, out=None) -> torch.Tensor:
+        """Graphs of the map path (``forward_map`` / ``relocalize``): graph g is query g followed by the rows ``neighbours[g]``
+        of ``fmap``, whose ``poses`` are the database images' targets; ``query_targets`` fp32 [G, 6] are the queries' own (None:
+        zeros, the rows' ``targ`` part and errors then mean nothing).  -> float64 [G, 16] on the device."""
+        poses = getattr(fmap, "poses", None)
+        if poses is None:
+            raise ValueError("QueryPose.from_map: the feature map holds no poses (build it with poses=...): a query's pose is "
+                             "its database image's pose minus the predicted relative pose")
+        return self._run(rel_pose, dict(edge_index=edge_index, map_poses=poses, neighbours=neighbours,
+                                        query_targets=query_targets, edge_first=edge_first, out=out))
+
+    def _run(self, rel_pose, kw) -> torch.Tensor:
+        status = None
+        if torch.is_tensor(rel_pose) and rel_pose.is_cuda:      # (anything else is refused by ops.query_pose below)
+            status = self._status_buffers(rel_pose.device)
+        elif self._status is not None:
+            status = self._status
+        if status is None:
+            status = torch.zeros(1, dtype=torch.int32)          # placeholder for the host-side checks, which refuse the call
+        rows = ops.query_pose(rel_pose, pose_m=self.pose_m, pose_s=self.pose_s, ref_node=self.ref_node, status=status, **kw)
+        self._publish()
+        return rows
+
+    # ---- bad graphs, without a host synchronisation -----------------------------------------------------------------------
+    def _status_buffers(self, dev) -> torch.Tensor:
+        if self._status is None or self._status.device != dev:
+            self._status = torch.zeros(1, dtype=torch.int32, device=dev)
+            self._status_host = torch.zeros(1, dtype=torch.int32).pin_memory()
+            self._event = torch.cuda.Event()
+            self._pending = False
+        return self._status
+
+    def _publish(self) -> None:
+        """Enqueue the counter's copy to pinned memory behind this call's kernel (current stream)."""
+        if torch.cuda.is_current_stream_capturing():
+            return                                # a replayed launch keeps counting on the device: call publish() behind the replay
+        self._status_host.copy_(self._status, non_blocking=True)
+        self._event.record()
+        self._pending = True
+
+    def publish(self) -> None:
+        """For callers that replay a captured launch: enqueue the counter's copy behind the replay."""
+        if self._status is not None:
+            self._publish()
+
+    def _raise(self) -> None:
+        bad = int(self._status_host[0])
+        self._status.zero_()                      # (stream-ordered: after every call issued so far)
+        self._status_host.zero_()                 # the mirror too, or a look without waiting would report it again
+        self._pending = False
+        raise ValueError(f"graph has no edge into node 0: cannot derive the query pose ({bad} graph(s) lack edge number "
+                         f"{self.ref_node} into their query node, or its source lies outside the graph; detected on the device, "
+                         "their rows are NaN)")
+
+    def check(self, wait: bool = True) -> None:
+        """Raise the ValueError of ``evaluate.reference_edge`` if a call issued so far met a graph it could not evaluate.
+        ``wait=True`` blocks until every call issued so far has reported.  ``wait=False`` only looks at what has already arrived
+        in the pinned mirror: for a caller that has just synchronised on a later event of the same stream that covers the call
+        in question without waiting for the next one; the counter accumulates on the device, so a report that is not in yet is
+        seen by the next look."""
+        if self._status_host is None:
+            return
+        if wait:
+            if self._pending:
+                self._event.synchronize()
+                self._pending = False
+        if int(self._status_host[0]):
+            self._event.synchronize()
+            self._raise()

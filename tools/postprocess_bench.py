@@ -1,0 +1,171 @@
+#!/usr/bin/env python3
+"""The evaluation streams with the pose rule on the host against the pose rule on the device (opt-in; bench.py does not call it).
+
+  * ``relocalize`` over 1024 queries in pinned host memory against a 256-row map, K = 7, micro-batches of 64, at
+    {224x224, 256x341} x {fp32, bf16 encoder + GNN} x postprocess {"host", "device"};
+  * ``evaluate_stream`` over 8-node graphs at 256x341 bf16, the same two modes.
+
+Every leg: one warm-up call, then ``--reps`` timed calls (wall clock around the call, which ends with everything on the host);
+reported are the rates, their median and the spread (max - min) / median.  ``--baseline-root DIR`` also measures ``relocalize``
+as ANOTHER checkout of this package has it (the parent commit's tree, with its own built library), in a child process, called
+without the ``postprocess`` argument: the baseline the device mode is held against -- "not slower beyond the run-to-run spread".
+``--only LEG`` runs one leg in one mode in a loop, for a profiler (``rocprofv3 --kernel-trace --stats -- python
+tools/postprocess_bench.py --only 256x341_bf16:device``), and prints the wall time of the timed loop to relate kernel time to.
+
+usage: tools/postprocess_bench.py [--reps 3] [--baseline-root DIR] [--out profiles/query_pose_bench.json]"""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+import time
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+
+D, K, MAP_ROWS = 2048, 7, 256
+GEOMS = ((224, 224), (256, 341))
+
+
+def _arg_root():
+    for i, a in enumerate(sys.argv):
+        if a == "--root" and i + 1 < len(sys.argv):
+            return os.path.abspath(sys.argv[i + 1])
+    return os.path.dirname(HERE)
+
+
+ROOT = _arg_root()
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+
+def rates(fn, n, reps):
+    fn()                                                   # warm-up: pipeline buffers, workspaces, pinned blocks
+    out = []
+    for _ in range(reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        out.append(n / (time.perf_counter() - t0))
+    med = statistics.median(out)
+    return {"graphs_per_s": [round(r, 1) for r in out], "median": round(med, 1), "spread": round((max(out) - min(out)) / med, 4)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--queries", type=int, default=1024)
+    ap.add_argument("--stream-graphs", type=int, default=256)
+    ap.add_argument("--root", default=None, help="the checkout whose package is measured (default: this one)")
+    ap.add_argument("--modes", default="host,device", help="comma list of host, device, baseline (= no postprocess argument)")
+    ap.add_argument("--baseline-root", default=None, help="another checkout (the parent commit, built) to measure as the baseline")
+    ap.add_argument("--only", default=None, help="LEG:MODE, e.g. 256x341_bf16:device -- that leg alone, for a profiler")
+    ap.add_argument("--out", default=None, help="also write the JSON document to this file")
+    args = ap.parse_args()
+
+    import relpose_gnn_amd.synth as S
+    from relpose_gnn_amd import build as B
+    from relpose_gnn_amd.evaluate import evaluate_stream, relocalize
+    from relpose_gnn_amd.featmap import FeatureMap
+    from relpose_gnn_amd.graph import Data, fc_edge_index
+    from relpose_gnn_amd.posenet import PoseNetX_R2
+    from relpose_gnn_amd.resnet import resnet34
+
+    modes = [m for m in args.modes.split(",") if m]
+    only_leg, only_mode = (args.only.split(":") + [None])[:2] if args.only else (None, None)
+    if only_mode:
+        modes = [only_mode]
+    dev = torch.device("cuda:0")
+    m = PoseNetX_R2(resnet34(), droprate=0.0, pretrained=False, feat_dim=D, edge_feat_dim=D, node_dim=D, input_img_height=224,
+                    use_gnn=True, knn=-1, use_AP=True, gnn_recursion=2)
+    m.load_state_dict(S.synth_state_dict(S.posenet_r2_param_shapes(D, D, D), seed=1))
+    m = m.to(dev).eval()
+    gen = torch.Generator(device=dev).manual_seed(0)
+    doc = {"metric": "query_pose_postprocess", "K": K, "map_rows": MAP_ROWS, "queries": args.queries, "micro_batch": 64,
+           "reps": args.reps, "root": "this checkout" if args.root is None else "another checkout",
+           "library_digest": B.source_digest(), "device": torch.cuda.get_device_name(0), "host": os.uname().nodename,
+           "cpus": len(os.sched_getaffinity(0)), "relocalize": {}, "evaluate_stream": {}}
+
+    def kw_of(mode):
+        return {} if mode == "baseline" else {"postprocess": mode}
+
+    n = args.queries
+    for prec in ("f32", "bf16"):
+        m.encoder_dtype, m.gnn_dtype = prec, prec
+        for h, w in GEOMS:
+            key = f"{h}x{w}_{prec}"
+            if only_leg and only_leg != key:
+                continue
+            m.input_img_height = h
+            fmap = FeatureMap.build(m, torch.randn((MAP_ROWS, 3 * h * w), device=dev, generator=gen),
+                                    poses=torch.randn((MAP_ROWS, 6), generator=torch.Generator().manual_seed(3)) * 0.3)
+            qh = torch.randn((n, 3 * h * w), generator=torch.Generator().manual_seed(1)).pin_memory()
+            nbh = torch.randint(0, MAP_ROWS, (n, K), generator=torch.Generator().manual_seed(2))
+            tg = torch.randn((n, 6), generator=torch.Generator().manual_seed(4)) * 0.3
+            leg = {}
+            for mode in modes:
+                st = {}
+                fn = lambda: relocalize(m, fmap, qh, nbh, micro_batch=64, targets=tg, stats=st, **kw_of(mode))  # noqa: E731
+                if only_mode:
+                    fn()
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    for _ in range(10):
+                        fn()
+                    wall = time.perf_counter() - t0
+                    print(json.dumps({"only": args.only, "calls": 10, "wall_s": round(wall, 4),
+                                      "graphs_per_s": round(10 * n / wall, 1)}), flush=True)
+                    return
+                leg[mode] = rates(fn, n, args.reps)
+                leg[mode]["d2h_bytes"] = st.get("d2h_bytes")
+            doc["relocalize"][key] = leg
+            del qh, fmap
+            torch.cuda.empty_cache()
+
+    # evaluate_stream: all 8 images of a graph cross the host link (pinned, as the reference's loader delivers them)
+    if not only_leg and "baseline" not in modes:
+        h, w = 256, 341
+        m.input_img_height = h
+        g_n = args.stream_graphs
+        ei = fc_edge_index(K + 1)
+        xs = torch.randn((g_n, K + 1, 3 * h * w), generator=torch.Generator().manual_seed(5)).pin_memory()
+        ys = torch.randn((g_n, K + 1, 6), generator=torch.Generator().manual_seed(6)) * 0.3
+        graphs = [Data(x=xs[i], edge_index=ei, y=ys[i]) for i in range(g_n)]
+        leg = {}
+        for mode in modes:
+            st = {}
+            leg[mode] = rates(lambda: evaluate_stream(m, graphs, dev, micro_batch=64, stats=st, postprocess=mode), g_n, args.reps)
+            leg[mode]["d2h_bytes"] = st.get("d2h_bytes")
+        doc["evaluate_stream"][f"{h}x{w}_bf16"] = leg
+        del xs, graphs
+    m.encoder_dtype, m.gnn_dtype = "f32", "f32"
+
+    if args.baseline_root:
+        # the parent commit's relocalize, on this box, in this visit: a fresh child process on the other checkout
+        cmd = [sys.executable, os.path.abspath(__file__), "--root", os.path.abspath(args.baseline_root), "--modes", "baseline",
+               "--reps", str(args.reps), "--queries", str(args.queries)]
+        res = subprocess.run(cmd, stdout=subprocess.PIPE, text=True, timeout=600)
+        if res.returncode != 0:
+            raise SystemExit(f"baseline run failed with exit status {res.returncode}")
+        base = json.loads(res.stdout.strip().splitlines()[-1])
+        doc["baseline_library_digest"] = base["library_digest"]
+        verdict = {}
+        for key, leg in doc["relocalize"].items():
+            b = base["relocalize"][key]["baseline"]
+            leg["baseline"] = b
+            if "device" in leg:
+                d = leg["device"]
+                spread = max(b["spread"], d["spread"])
+                verdict[key] = {"device_over_baseline": round(d["median"] / b["median"], 3), "spread": spread,
+                                "not_slower": bool(d["median"] >= b["median"] * (1.0 - spread))}
+        doc["device_vs_baseline"] = verdict
+    line = json.dumps(doc)
+    print(line, flush=True)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(json.dumps(doc, indent=1) + "\n")
+
+
+if __name__ == "__main__":
+    main()
