@@ -10,7 +10,7 @@ test.py:213-286) and changes ONE line in front of it::
     loader, self.model = lookahead(loader, self.model, self.device, micro_batch=64)      # after test.py:193-194
 
 The wrapped loader reads ``micro_batch`` graphs AHEAD of the loop, sends their node images through the pinned double
-buffers of ``evaluate._InputPipeline``, runs ONE forward over them and copies the poses to pinned host memory -- while the
+buffers of ``pipeline._InputPipeline``, runs ONE forward over them and copies the poses to pinned host memory -- while the
 loop is still consuming the previous micro-batch -- and then yields the graphs one by one; the wrapped model hands each
 ``model(data.to(device))`` call that graph's rows of the batched result (results per graph do not depend on the batching:
 ``tests/test_hip_model.py::test_batch_independence_full_width``).  What the loop sees:
@@ -30,11 +30,10 @@ from __future__ import annotations
 import copy
 from typing import Iterable, Optional
 
-import numpy as np
 import torch
 
-from .evaluate import _MicroBatchRunner, edges_per_graph
 from .graph import Data
+from .pipeline import _MicroBatchRunner, cut_per_graph
 
 
 class _Ticket:
@@ -91,9 +90,8 @@ class Lookahead:
     def __init__(self, model, device, micro_batch: int = 64, bf16_input: Optional[bool] = None):
         if micro_batch < 1:
             raise ValueError("micro_batch must be >= 1")
-        h2d = torch.bfloat16 if (bf16_input if bf16_input is not None else getattr(model, "accepts_bf16_input", False)) else torch.float32
         self.__dict__["_model"] = model
-        self.__dict__["_runner"] = _MicroBatchRunner(model, device, micro_batch, h2d, want_abs=True, pinned_direct=bf16_input is None)
+        self.__dict__["_runner"] = _MicroBatchRunner(model, device, micro_batch, bf16_input, want_abs=True)
         self.__dict__["_expect"] = None      # (device pointer of the yielded graph's x, its (abs, rel, edge_index))
         # The batched forwards run on a stream of their own: the loop's own device traffic (data.to(device) sends y and
         # edge_index of every graph, test.py:211) is ordered on the CURRENT stream and would otherwise queue behind the forward
@@ -195,34 +193,23 @@ class Lookahead:
         cur = start()
         while cur is not None:
             nxt = start()                    # micro-batch i + 1 is staged and enqueued before micro-batch i is handed out
-            items, (chunk, host_rel, host_ei, ev, host_abs, batch) = cur
-            x_dev = batch.x
-            if ev is not None:
-                ev.synchronize()
-            check = getattr(self._model, "check_edge_index", None)
-            if check is not None:
-                check(wait=False)            # raises the IndexError of a bad edge_index in THIS micro-batch (evaluate.finish)
+            items, launched = cur
+            self._runner.arrived(launched)   # raises the IndexError of a bad edge_index in THIS micro-batch
+            chunk, host, x_dev = launched.chunk, launched.host, launched.batch.x
             sizes = [g.num_nodes for g in chunk]
-            cols = None
-            if host_ei is not None:          # model-built edge list (kNN): cut at graph boundaries, local node ids
-                ei = host_ei.numpy()
-                first, cols = edges_per_graph(ei, sizes)
-                rel_np = host_rel.numpy()
-            n0 = e0 = 0
-            for j, (item, g) in enumerate(zip(items, chunk)):
-                n = sizes[j]
-                if cols is None:
-                    e = int(g.edge_index.shape[1])
-                    rel_j, ei_j = host_rel[e0:e0 + e], g.edge_index if not g.edge_index.is_cuda else g.edge_index.cpu()
-                    e0 += e
-                else:
-                    rel_j = torch.from_numpy(rel_np[cols[j]])
-                    ei_j = torch.from_numpy(ei[:, cols[j]] - first[j])
+            # stored edge lists are handed back as they are; a model-built one (kNN) is cut at graph boundaries, local node ids
+            cut = cut_per_graph(sizes, None if host["ei"] is None else host["ei"].numpy(),
+                                (g.edge_index if not g.edge_index.is_cuda else g.edge_index.cpu() for g in chunk))
+            rel = host["rel"] if host["ei"] is None else host["rel"].numpy()
+            n0 = 0
+            for item, n, (cols, ei_j) in zip(items, sizes, cut):
+                rel_j = torch.as_tensor(rel[cols])
+                ei_j = torch.as_tensor(ei_j)
                 inner = copy.copy(item)
                 xj = x_dev[n0:n0 + n]
                 inner.x = xj.view((n,) + tuple(item.x.shape[1:])) if item.x.dim() != 2 else xj
                 ticket = _Ticket(inner)
-                self.__dict__["_expect"] = (ticket.x.data_ptr(), (host_abs[n0:n0 + n], rel_j, ei_j))
+                self.__dict__["_expect"] = (ticket.x.data_ptr(), (host["abs"][n0:n0 + n], rel_j, ei_j))
                 n0 += n
                 yield ticket
             self.__dict__["_expect"] = None

@@ -52,7 +52,7 @@ def gather_rows(local: torch.Tensor, counts: List[int], group=None, always: bool
 
 # ---- host placement of a rank (round 5) -------------------------------------------------------------------------------
 # The reference is one process (testing/test.py:78-80,192-194); eight ranks on a two-socket GPU host are eight processes whose
-# staging threads (evaluate._InputPipeline: 8-16 per rank) and pinned buffers would otherwise float over both sockets: a
+# staging threads (pipeline._InputPipeline: 8-16 per rank) and pinned buffers would otherwise float over both sockets: a
 # rank's pageable -> pinned copy and the DMA out of the pinned buffer then cross the socket link for half of the ranks.
 
 _BOUND = None        # ((local_rank, local_world), cpus) once bind_rank_to_host_slice has narrowed this process's mask
@@ -185,7 +185,7 @@ def bind_rank_to_host_slice(local_rank: int, local_world: int, device_index: Opt
 class rank_host_slice:
     """``with rank_host_slice(local_rank, local_world, device_index):`` -- bind_rank_to_host_slice for the duration of the block
     (a library call must not narrow its caller's CPU mask for good).  The threads started inside (the staging pool of
-    ``evaluate._InputPipeline``) keep the slice; the calling thread gets its previous mask back on exit.  A process its entry
+    ``pipeline._InputPipeline``) keep the slice; the calling thread gets its previous mask back on exit.  A process its entry
     script has already bound (``_BOUND`` set before the block) is left alone both ways."""
 
     def __init__(self, local_rank: int, local_world: int, device_index: Optional[int] = None):

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Host staging at scale (round 5): can eight ranks' input pipelines share one two-socket host?
 
-Starts W processes (default 8) that each run ONLY the producer side of relpose_gnn_amd.evaluate._InputPipeline -- collate
+Starts W processes (default 8) that each run ONLY the producer side of relpose_gnn_amd.pipeline._InputPipeline -- collate
 micro-batches of pageable host images into pinned memory with the staging threads (memcpy for fp32, rpg_host_f32_to_bf16 for
 bf16) and send them host -> device on a copy stream; no forward -- and reports the aggregate GB/s of pageable bytes consumed,
 
@@ -27,7 +27,7 @@ def child(args):
     sys.path.insert(0, ROOT)
     import torch
     from relpose_gnn_amd import shard
-    from relpose_gnn_amd.evaluate import _InputPipeline
+    from relpose_gnn_amd.pipeline import _InputPipeline
     from relpose_gnn_amd.graph import Data, fc_edge_index
     rank, world = args.rank, args.ranks
     cpus = shard.bind_rank_to_host_slice(rank, world, 0) if args.bind else None
