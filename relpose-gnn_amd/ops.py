@@ -29,8 +29,40 @@ def _req(t: torch.Tensor, name: str, dtype=torch.float32) -> torch.Tensor:
     return t if t.is_contiguous() else t.contiguous()
 
 
+def _opt(t: Optional[torch.Tensor], name: str, dtype=torch.float32) -> Optional[torch.Tensor]:
+    return None if t is None else _req(t, name, dtype)
+
+
+def _out(out: Optional[torch.Tensor], shape, dtype, dev, what: str) -> torch.Tensor:
+    """The ``out`` argument of ``what``: checked when given, allocated otherwise."""
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=dev)
+    if tuple(out.shape) != tuple(shape) or out.dtype != dtype or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"{what}: out must be a contiguous {dtype} {list(shape)} tensor on the inputs' GPU")
+    return out
+
+
 def _p(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
+
+
+def _status_arg(status: Optional[torch.Tensor], dev, what: str, bad_dtype=ValueError) -> Tuple[torch.Tensor, bool]:
+    """The ``status`` argument of ``what``: a given tensor must be int32 (``bad_dtype`` otherwise) and hold a counter on ``dev``
+    (ValueError otherwise); None becomes a zeroed counter of this call's own.  -> (status, whether it is this call's own)."""
+    if status is None:
+        return torch.zeros(1, dtype=torch.int32, device=dev), True
+    if not torch.is_tensor(status) or status.dtype != torch.int32:
+        raise bad_dtype(f"{what}: status must be an int32 tensor on the inputs' GPU")
+    if status.numel() < 1 or status.device != dev:
+        raise ValueError(f"{what}: status must be an int32 tensor holding one counter on the inputs' GPU, got "
+                         f"{status.numel()} element(s) on {status.device}")
+    return status, False
+
+
+def _own_count(status: torch.Tensor, own: bool) -> int:
+    """What a call without a ``status`` argument counted (read back here: one synchronisation); 0 for the caller's counter,
+    which the caller reads."""
+    return int(status.item()) if own else 0
 
 
 def nchw3_to_nhwc4(x: torch.Tensor) -> torch.Tensor:
@@ -52,9 +84,9 @@ def conv2d_bn_act_nhwc(x: torch.Tensor, w_ohwi: torch.Tensor, scale: Optional[to
         raise ValueError(f"channel mismatch: x has {cin}, weight has {cin_w}")
     ho, wo = (h + 2 * pad - kh) // stride + 1, (w + 2 * pad - kw) // stride + 1
     y = torch.empty((n, ho, wo, cout), dtype=torch.float32, device=x.device)
-    scale = None if scale is None else _req(scale, "scale")
-    shift = None if shift is None else _req(shift, "shift")
-    residual = None if residual is None else _req(residual, "residual")
+    scale = _opt(scale, "scale")
+    shift = _opt(shift, "shift")
+    residual = _opt(residual, "residual")
     if residual is not None and residual.shape != y.shape:
         raise ValueError("residual shape mismatch")
     L.check(L.lib().rpg_conv2d_bn_act_nhwc_f32(_p(x), _p(w_ohwi), _p(scale), _p(shift), _p(residual), _p(y), n, h, w, cin,
@@ -91,9 +123,9 @@ def conv3x3_wino43_bn_act_nhwc(x: torch.Tensor, u: torch.Tensor, scale: Optional
     else:                                                          # flat buffer of a probe build: Cout from its size
         cout = u.numel() // (per * cin)
     y = torch.empty((n, h, w, cout), dtype=torch.float32, device=x.device)
-    scale = None if scale is None else _req(scale, "scale")
-    shift = None if shift is None else _req(shift, "shift")
-    residual = None if residual is None else _req(residual, "residual")
+    scale = _opt(scale, "scale")
+    shift = _opt(shift, "shift")
+    residual = _opt(residual, "residual")
     for name, t in (("scale", scale), ("shift", shift)):
         if t is not None and t.numel() != cout:
             raise ValueError(f"{name} must have Cout = {cout} elements, got {t.numel()}")
@@ -115,9 +147,9 @@ def conv2d_bn_act_nhwc_bf16(x: torch.Tensor, w_ohwi: torch.Tensor, scale: Option
         raise ValueError(f"channel mismatch: x has {cin}, weight has {cin_w}")
     ho, wo = (h + 2 * pad - kh) // stride + 1, (w + 2 * pad - kw) // stride + 1
     y = torch.empty((n, ho, wo, cout), dtype=torch.float32 if out_f32 else torch.bfloat16, device=x.device)
-    scale = None if scale is None else _req(scale, "scale")
-    shift = None if shift is None else _req(shift, "shift")
-    residual = None if residual is None else _req(residual, "residual", torch.bfloat16)
+    scale = _opt(scale, "scale")
+    shift = _opt(shift, "shift")
+    residual = _opt(residual, "residual", torch.bfloat16)
     L.check(L.lib().rpg_conv2d_bn_act_nhwc_bf16(_p(x), _p(w_ohwi), _p(scale), _p(shift), _p(residual), _p(y), n, h, w, cin,
                                                  cout, kh, kw, stride, pad, int(relu), int(out_f32), _stream()),
             "conv2d_bn_act_nhwc_bf16")
@@ -184,22 +216,13 @@ def f32_to_bf16(x: torch.Tensor, out: Optional[torch.Tensor] = None, col_off: in
 
 def _frames(frames: torch.Tensor, out_hw: Tuple[int, int], tables, mean: Sequence[float], std: Sequence[float],
             dtype, out: Optional[torch.Tensor]) -> torch.Tensor:
-    if not torch.is_tensor(frames):
-        raise TypeError("frames: expected a tensor")
-    if not frames.is_cuda:
-        raise RuntimeError(f"frames: expected a tensor on the GPU (the HIP kernels are the only compute path), got {frames.device}")
-    if frames.dtype != torch.uint8:
-        raise TypeError(f"frames: expected uint8, got {frames.dtype}")
+    frames = _req(frames, "frames", torch.uint8)
     if frames.dim() != 4 or frames.shape[3] != 3:
         raise ValueError(f"frames: expected uint8 [n, H, W, 3] (RGB, HWC), got {tuple(frames.shape)}")
-    frames = frames if frames.is_contiguous() else frames.contiguous()
     n, h, w, _ = frames.shape
     oh, ow = int(out_hw[0]), int(out_hw[1])
     hb, hw, vb, vw = tables
-    if out is None:
-        out = torch.empty((n, 3, oh, ow), dtype=dtype, device=frames.device)
-    if out.shape != (n, 3, oh, ow) or out.dtype != dtype or not out.is_contiguous() or out.device != frames.device:
-        raise ValueError(f"out must be a contiguous {dtype} [{n}, 3, {oh}, {ow}] tensor on the frames' device")
+    out = _out(out, (n, 3, oh, ow), dtype, frames.device, "frames")
     fn = L.lib().rpg_frames_u8_to_bf16 if dtype == torch.bfloat16 else L.lib().rpg_frames_u8_to_f32
     L.check(fn(_p(frames), n, h, w, oh, ow, _p(hb), _p(hw), _p(vb), _p(vw), *[float(v) for v in mean], *[float(v) for v in std],
                _p(out), None, 0, _stream()), "frames_u8")
@@ -234,24 +257,36 @@ def resize_table(n_in: int, n_out: int):
     return bounds, weights
 
 
+def _linear_bf16_args(a, weight, bias, residual, res_idx, residual2, res2_idx, strided: bool = False):
+    """The checked operands of linear_bf16 / linear_bf16_ex -> (a, weight, bias, residual, res_idx, residual2, res2_idx, m, k,
+    n_out, the residuals' row pitch).  ``strided``: the optional tensors are taken as they are (dtype and device checked, never
+    copied), so that ``residual2`` may be a view of ``residual``'s storage; the row pitch is then their stride."""
+    a, weight = _req(a, "a", torch.bfloat16), _req(weight, "weight", torch.bfloat16)
+    m, k = a.shape
+    if weight.shape[1] != k:
+        raise ValueError("a.shape[1] != weight.shape[1]")
+    opt = ((bias, "bias", torch.float32), (residual, "residual", torch.float32), (residual2, "residual2", torch.float32),
+           (res_idx, "res_idx", torch.int64), (res2_idx, "res2_idx", torch.int64))
+    if strided:
+        for t, nm, dt in opt:
+            if t is not None and (t.dtype != dt or not t.is_cuda):
+                raise TypeError(f"{nm}: expected {dt} on the GPU")
+    else:
+        bias, residual, residual2, res_idx, res2_idx = (_opt(t, nm, dt) for t, nm, dt in opt)
+    pitch = (lambda t: t.stride(0)) if strided else (lambda t: t.shape[1])
+    if residual2 is not None and (residual is None or pitch(residual2) != pitch(residual)):
+        raise ValueError("residual2 needs residual with the same row pitch")
+    return (a, weight, bias, residual, res_idx, residual2, res2_idx, m, k, weight.shape[0],
+            0 if residual is None else pitch(residual))
+
+
 def linear_bf16(a: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None,
                 residual: Optional[torch.Tensor] = None, res_idx: Optional[torch.Tensor] = None,
                 residual2: Optional[torch.Tensor] = None, res2_idx: Optional[torch.Tensor] = None, relu: bool = False) -> torch.Tensor:
     """out (fp32) = act(a (bf16) @ weight.T (bf16) + bias + residual[res_idx or arange] + residual2[res2_idx]); the
     residual matrices are fp32 with a common row pitch."""
-    a, weight = _req(a, "a", torch.bfloat16), _req(weight, "weight", torch.bfloat16)
-    m, k = a.shape
-    n_out = weight.shape[0]
-    if weight.shape[1] != k:
-        raise ValueError("a.shape[1] != weight.shape[1]")
-    bias = None if bias is None else _req(bias, "bias")
-    residual = None if residual is None else _req(residual, "residual")
-    residual2 = None if residual2 is None else _req(residual2, "residual2")
-    res_idx = None if res_idx is None else _req(res_idx, "res_idx", torch.int64)
-    res2_idx = None if res2_idx is None else _req(res2_idx, "res2_idx", torch.int64)
-    if residual2 is not None and (residual is None or residual2.shape[1] != residual.shape[1]):
-        raise ValueError("residual2 needs residual with the same row pitch")
-    ldr = 0 if residual is None else residual.shape[1]
+    a, weight, bias, residual, res_idx, residual2, res2_idx, m, k, n_out, ldr = _linear_bf16_args(
+        a, weight, bias, residual, res_idx, residual2, res2_idx)
     out = torch.empty((m, n_out), dtype=torch.float32, device=a.device)
     L.check(L.lib().rpg_linear_bf16(_p(a), _p(weight), _p(bias), _p(residual), _p(res_idx), _p(residual2), _p(res2_idx), ldr,
                                     _p(out), m, k, n_out, int(relu), _stream()), "linear_bf16")
@@ -266,20 +301,10 @@ def linear_bf16_ex(a: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.T
     """linear_bf16 in its general form (rpg_linear_bf16_ex): primary output fp32 / bf16 / none (``out_dtype``), and with ``out2`` a
     second bf16 output = bf16(relu2 ? max(y, 0) : y), y taken before the primary's ReLU.  ``residual2`` may be a column-offset view
     of ``residual``'s storage (common row pitch)."""
-    a, weight = _req(a, "a", torch.bfloat16), _req(weight, "weight", torch.bfloat16)
-    m, k = a.shape
-    n_out = weight.shape[0]
-    if weight.shape[1] != k:
-        raise ValueError("a.shape[1] != weight.shape[1]")
     if out_dtype not in (torch.float32, torch.bfloat16, None) or (out_dtype is None and not out2):
         raise ValueError("out_dtype: float32 | bfloat16 | None (then out2 must be set)")
-    for t, nm, dt in ((bias, "bias", torch.float32), (residual, "residual", torch.float32), (residual2, "residual2", torch.float32),
-                      (res_idx, "res_idx", torch.int64), (res2_idx, "res2_idx", torch.int64)):
-        if t is not None and (t.dtype != dt or not t.is_cuda):
-            raise TypeError(f"{nm}: expected {dt} on the GPU")
-    if residual2 is not None and (residual is None or residual2.stride(0) != residual.stride(0)):
-        raise ValueError("residual2 needs residual with the same row pitch")
-    ldr = 0 if residual is None else residual.stride(0)
+    a, weight, bias, residual, res_idx, residual2, res2_idx, m, k, n_out, ldr = _linear_bf16_args(
+        a, weight, bias, residual, res_idx, residual2, res2_idx, strided=True)
     y = None if out_dtype is None else torch.empty((m, n_out), dtype=out_dtype, device=a.device)
     y2 = torch.empty((m, n_out), dtype=torch.bfloat16, device=a.device) if out2 else None
     L.check(L.lib().rpg_linear_bf16_ex(_p(a), k, _p(weight), _p(bias), _p(residual), _p(res_idx), _p(residual2), _p(res2_idx), ldr,
@@ -376,7 +401,7 @@ def knn_graph_launch(x: torch.Tensor, k: int, batch: Optional[torch.Tensor] = No
     the stream has run; knn_graph() below reads E right away, PoseNetX_R2's multi-stream path reads it behind an event."""
     x = _req(x, "x")
     n, d = x.shape
-    batch = None if batch is None else _req(batch, "batch", torch.int64)
+    batch = _opt(batch, "batch", torch.int64)
     cap = n * (k + 1)
     ei = torch.empty((2, cap), dtype=torch.int64, device=x.device)
     cand = torch.empty((n, k + 1), dtype=torch.int32, device=x.device)
@@ -422,21 +447,13 @@ def gather_graph_nodes(query_feat: torch.Tensor, map_feat: torch.Tensor, neighbo
         raise ValueError(f"gather_graph_nodes: needs G >= 1, K >= 1, M >= 1 and d % 4 == 0 (G={g}, K={k}, M={m}, d={d})")
     if mp.device != q.device or nb.device != q.device:
         raise RuntimeError("gather_graph_nodes: query_feat, map_feat and neighbours must be on the same GPU")
-    if out is None:
-        out = torch.empty((g * (k + 1), d), dtype=torch.float32, device=q.device)
-    elif out.shape != (g * (k + 1), d) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != q.device:
-        raise ValueError(f"gather_graph_nodes: out must be a contiguous fp32 [{g * (k + 1)}, {d}] tensor on the inputs' GPU")
-    sync = status is None
-    if sync:
-        status = torch.zeros(1, dtype=torch.int32, device=q.device)
-    elif status.dtype != torch.int32 or status.device != q.device or status.numel() < 1:
-        raise ValueError("gather_graph_nodes: status must be an int32 tensor on the inputs' GPU")
+    out = _out(out, (g * (k + 1), d), torch.float32, q.device, "gather_graph_nodes")
+    status, own = _status_arg(status, q.device, "gather_graph_nodes")
     L.check(L.lib().rpg_gather_graph_nodes_f32(_p(q), _p(mp), _p(nb), g, k, m, d, _p(out), status.data_ptr(), _stream()),
             "gather_graph_nodes")
-    if sync:
-        bad = int(status.item())
-        if bad:
-            raise IndexError(f"neighbours has {bad} index(es) outside the map's rows [0, {m})")
+    bad = _own_count(status, own)
+    if bad:
+        raise IndexError(f"neighbours has {bad} index(es) outside the map's rows [0, {m})")
     return out
 
 
@@ -493,26 +510,16 @@ def retrieve(q: torch.Tensor, db: torch.Tensor, ranks, db_inv_norm: Optional[tor
         workspace = torch.empty(need, dtype=torch.uint8, device=q.device)
     elif workspace.dtype != torch.uint8 or workspace.device != q.device or not workspace.is_contiguous():
         raise ValueError("retrieve: workspace must be a contiguous uint8 tensor on the inputs' GPU")
-    if out is None:
-        nbrs = torch.empty((g, k), dtype=torch.int64, device=q.device)
-    elif out.shape != (g, k) or out.dtype != torch.int64 or not out.is_contiguous() or out.device != q.device:
-        raise ValueError(f"retrieve: out must be a contiguous int64 [{g}, {k}] tensor on the inputs' GPU")
-    else:
-        nbrs = out
+    nbrs = _out(out, (g, k), torch.int64, q.device, "retrieve")
     sims = torch.empty((g, k), dtype=torch.float32, device=q.device) if return_sims else None
-    sync = status is None
-    if sync:
-        status = torch.zeros(1, dtype=torch.int32, device=q.device)
-    elif status.dtype != torch.int32 or status.device != q.device or status.numel() < 1:
-        raise ValueError("retrieve: status must be an int32 tensor on the inputs' GPU")
+    status, own = _status_arg(status, q.device, "retrieve")
     L.check(lib.rpg_retrieve_cosine_f32(_p(q), _p(db), _p(db_inv_norm), _p(q_group), _p(db_group), _p(ranks), g, k, m, d,
                                         _p(nbrs), _p(sims), workspace.data_ptr(), workspace.numel(), status.data_ptr(),
                                         _stream()), "retrieve")
-    if sync:
-        bad = int(status.item())
-        if bad:
-            raise IndexError(f"ranks has {bad} entry(ies) outside a query's allowed rows / the kernel's R_MAX, or rows that do "
-                             "not ascend")
+    bad = _own_count(status, own)
+    if bad:
+        raise IndexError(f"ranks has {bad} entry(ies) outside a query's allowed rows / the kernel's R_MAX, or rows that do "
+                         "not ascend")
     return (nbrs, sims) if return_sims else nbrs
 
 
@@ -527,6 +534,14 @@ def _qp_tensor(t, name: str, dtype, shape) -> torch.Tensor:
         want = ", ".join("*" if s is None else str(s) for s in shape)
         raise ValueError(f"query_pose: {name} must be [{want}], got {tuple(t.shape)}")
     return t
+
+
+def _qp_ref_node(v) -> int:
+    if isinstance(v, bool) or not isinstance(v, numbers.Integral):
+        raise TypeError(f"query_pose: ref_node must be an int, got {type(v).__name__}")
+    if v < 0:
+        raise ValueError(f"query_pose: ref_node must be >= 0, got {v}")
+    return int(v)
 
 
 def _qp_triple(v, name: str) -> Tuple[float, float, float]:
@@ -564,11 +579,7 @@ def query_pose(rel_pose: torch.Tensor, edge_index: torch.Tensor, *, node_first: 
     if e < 1:
         raise ValueError("query_pose: needs at least one edge")
     pm, ps = _qp_triple(pose_m, "pose_m"), _qp_triple(pose_s, "pose_s")
-    if isinstance(ref_node, bool) or not isinstance(ref_node, numbers.Integral):
-        raise TypeError(f"query_pose: ref_node must be an int, got {type(ref_node).__name__}")
-    if ref_node < 0:
-        raise ValueError(f"query_pose: ref_node must be >= 0, got {ref_node}")
-    ref_node = int(ref_node)
+    ref_node = _qp_ref_node(ref_node)
     if (node_targets is None) == (map_poses is None):
         raise ValueError("query_pose: give node_first + node_targets (the collated targets) or map_poses + neighbours (the map "
                          "form): exactly one of the two")
@@ -607,15 +618,11 @@ def query_pose(rel_pose: torch.Tensor, edge_index: torch.Tensor, *, node_first: 
         _qp_tensor(out, "out", torch.float64, (g, 16))
         if not out.is_contiguous():
             raise ValueError("query_pose: out must be contiguous")
-    if status is not None:
-        if not torch.is_tensor(status) or status.dtype != torch.int32:
-            raise TypeError("query_pose: status must be an int32 tensor")
-        if status.numel() < 1:
-            raise ValueError("query_pose: status must hold one counter")
     dev = rel.device
+    status, own = _status_arg(status, dev, "query_pose", bad_dtype=TypeError)
     if dev.type != "cuda":
         raise ValueError(f"query_pose: rel_pose must be on the GPU (the HIP kernel is the only compute path), got {dev}")
-    for name, t in [("edge_index", ei)] + parts + [("out", out), ("status", status)]:
+    for name, t in [("edge_index", ei)] + parts + [("out", out)]:
         if t is not None and t.device != dev:
             raise ValueError(f"query_pose: {name} is on {t.device}, rel_pose on {dev}: everything must be on the same GPU")
 
@@ -623,39 +630,40 @@ def query_pose(rel_pose: torch.Tensor, edge_index: torch.Tensor, *, node_first: 
     by_name = {name: t.contiguous() for name, t in parts}
     if out is None:
         out = torch.empty((g, 16), dtype=torch.float64, device=dev)
-    sync = status is None
-    if sync:
-        status = torch.zeros(1, dtype=torch.int32, device=dev)
     L.check(L.lib().rpg_query_pose_f64(_p(rel), ei.data_ptr(), ei.data_ptr() + 8 * e, e, _p(by_name.get("node_first")),
                                        _p(by_name.get("edge_first")), g, _p(by_name.get("node_targets")), n,
                                        _p(by_name.get("map_poses")), m, _p(by_name.get("neighbours")), k,
                                        _p(by_name.get("query_targets")), *pm, *ps, ref_node, _p(out), status.data_ptr(),
                                        _stream()), "query_pose")
-    if sync:
-        bad = int(status.item())
-        if bad:
-            raise ValueError(f"graph has no edge into node 0: cannot derive the query pose ({bad} graph(s) of this call lack "
-                             "the reference edge, or its source lies outside the graph)")
+    bad = _own_count(status, own)
+    if bad:
+        raise ValueError(f"graph has no edge into node 0: cannot derive the query pose ({bad} graph(s) of this call lack "
+                         "the reference edge, or its source lies outside the graph)")
     return out
+
+
+def _gather_sources(sources, weight: torch.Tensor, widths: Optional[Sequence[int]] = None):
+    """The checked A operands of linear_gather / linear_gather_ex, and their C arrays: sources = [(a_k, idx_k or None), ...],
+    ``widths[k]`` columns of a_k are read (all of them by default) and together they are weight's columns.
+    -> (the tensors kept alive, (pointers, index pointers, row pitches, widths) as the C entry points take them)."""
+    keep = [(_req(a, f"a{i}"), _opt(ix, f"idx{i}", torch.int64)) for i, (a, ix) in enumerate(sources)]
+    wd_l = [a.shape[1] for a, _ in keep] if widths is None else [int(v) for v in widths]
+    if len(wd_l) != len(keep) or any(w <= 0 or w > a.shape[1] for w, (a, _) in zip(wd_l, keep)):
+        raise ValueError("widths: one positive entry per source, at most the source's row pitch")
+    if sum(wd_l) != weight.shape[1]:
+        raise ValueError("sum of source widths != weight.shape[1]")
+    return keep, (L.ptr_array([a.data_ptr() for a, _ in keep]), L.ptr_array([_p(ix) for _, ix in keep]),
+                  L.int_array([a.shape[1] for a, _ in keep]), L.int_array(wd_l))
 
 
 def linear_gather(sources: Sequence[Tuple[torch.Tensor, Optional[torch.Tensor]]], weight: torch.Tensor,
                   bias: Optional[torch.Tensor], m: int, residual: Optional[torch.Tensor] = None, relu: bool = False) -> torch.Tensor:
     """out[m] = act(cat_k(a_k[idx_k[m]]) @ weight.T + bias (+ residual)); sources = [(a_k, idx_k or None), ...]."""
-    ns = len(sources)
-    keep = [(_req(a, f"a{i}"), None if ix is None else _req(ix, f"idx{i}", torch.int64)) for i, (a, ix) in enumerate(sources)]
-    weight = _req(weight, "weight")
-    bias = None if bias is None else _req(bias, "bias")
-    residual = None if residual is None else _req(residual, "residual")
+    weight, bias, residual = _req(weight, "weight"), _opt(bias, "bias"), _opt(residual, "residual")
+    keep, arrays = _gather_sources(sources, weight)
     n_out = weight.shape[0]
-    if sum(a.shape[1] for a, _ in keep) != weight.shape[1]:
-        raise ValueError("sum of source widths != weight.shape[1]")
     out = torch.empty((m, n_out), dtype=torch.float32, device=weight.device)
-    a_arr = L.ptr_array([a.data_ptr() for a, _ in keep])
-    i_arr = L.ptr_array([None if ix is None else ix.data_ptr() for _, ix in keep])
-    ld = L.int_array([a.shape[1] for a, _ in keep])
-    wd = L.int_array([a.shape[1] for a, _ in keep])
-    L.check(L.lib().rpg_linear_gather_f32(ns, a_arr, i_arr, ld, wd, _p(weight), _p(bias), _p(residual), _p(out), m, n_out,
+    L.check(L.lib().rpg_linear_gather_f32(len(keep), *arrays, _p(weight), _p(bias), _p(residual), _p(out), m, n_out,
                                            int(relu), _stream()), "linear_gather")
     return out
 
@@ -667,20 +675,11 @@ def linear_gather_ex(sources: Sequence[Tuple[torch.Tensor, Optional[torch.Tensor
     """rpg_linear_gather_ex_f32: linear_gather with gathered residual rows, an optional max(out, 0) copy and A operands that are
     column blocks of wider tensors (``widths[k]`` < a_k.shape[1]: row pitch a_k.shape[1], the first widths[k] columns are read).
     -> out, or (out, out_relu) with ``want_relu_copy``."""
-    ns = len(sources)
-    keep = [(_req(a, f"a{i}"), None if ix is None else _req(ix, f"idx{i}", torch.int64)) for i, (a, ix) in enumerate(sources)]
-    wd_l = [a.shape[1] for a, _ in keep] if widths is None else [int(v) for v in widths]
-    if len(wd_l) != ns or any(w <= 0 or w > a.shape[1] for w, (a, _) in zip(wd_l, keep)):
-        raise ValueError("widths: one positive entry per source, at most the source's row pitch")
-    weight = _req(weight, "weight")
-    bias = None if bias is None else _req(bias, "bias")
-    residual = None if residual is None else _req(residual, "residual")
-    residual2 = None if residual2 is None else _req(residual2, "residual2")
-    res_idx = None if res_idx is None else _req(res_idx, "res_idx", torch.int64)
-    res2_idx = None if res2_idx is None else _req(res2_idx, "res2_idx", torch.int64)
+    weight, bias = _req(weight, "weight"), _opt(bias, "bias")
+    residual, residual2 = _opt(residual, "residual"), _opt(residual2, "residual2")
+    res_idx, res2_idx = _opt(res_idx, "res_idx", torch.int64), _opt(res2_idx, "res2_idx", torch.int64)
+    keep, arrays = _gather_sources(sources, weight, widths)
     n_out = weight.shape[0]
-    if sum(wd_l) != weight.shape[1]:
-        raise ValueError("sum of source widths != weight.shape[1]")
     for r_, i_ in ((residual, res_idx), (residual2, res2_idx)):
         if r_ is not None and (r_.shape[1] < n_out or (i_ is None and r_.shape[0] != m) or (i_ is not None and i_.numel() != m)):
             raise ValueError("residual: [rows][>= n_out] with one (gathered) row per output row")
@@ -688,13 +687,8 @@ def linear_gather_ex(sources: Sequence[Tuple[torch.Tensor, Optional[torch.Tensor
         raise ValueError("residual and residual2 share one row pitch")
     out = torch.empty((m, n_out), dtype=torch.float32, device=weight.device)
     out_relu = torch.empty_like(out) if want_relu_copy else None
-    a_arr = L.ptr_array([a.data_ptr() for a, _ in keep])
-    i_arr = L.ptr_array([None if ix is None else ix.data_ptr() for _, ix in keep])
-    ld = L.int_array([a.shape[1] for a, _ in keep])
-    wd = L.int_array(wd_l)
-    import ctypes as C
-    rows = (C.c_long * ns)(*[a.shape[0] if ix is not None else 0 for a, ix in keep])
-    L.check(L.lib().rpg_linear_gather_ex_f32(ns, a_arr, i_arr, ld, wd, rows, _p(weight), _p(bias), _p(residual), _p(res_idx), _p(residual2),
+    rows = (C.c_long * len(keep))(*[a.shape[0] if ix is not None else 0 for a, ix in keep])
+    L.check(L.lib().rpg_linear_gather_ex_f32(len(keep), *arrays, rows, _p(weight), _p(bias), _p(residual), _p(res_idx), _p(residual2),
                                               _p(res2_idx), 0 if residual is None else residual.shape[1], _p(out), _p(out_relu), m, n_out,
                                               int(relu), _stream()), "linear_gather_ex")
     return (out, out_relu) if want_relu_copy else out
@@ -724,7 +718,7 @@ def attention_aggregate(gtp: torch.Tensor, msg: torch.Tensor, rowptr: torch.Tens
     with incoming edges), ascending edge order; see rpg_attention_aggregate_f32."""
     gtp, msg = _req(gtp, "gtp"), _req(msg, "msg")
     rowptr, perm = _req(rowptr, "rowptr", torch.int32), _req(perm, "perm", torch.int32)
-    bias = None if bias is None else _req(bias, "bias")
+    bias = _opt(bias, "bias")
     e, c3 = gtp.shape
     c, d = c3 // 3, msg.shape[1]
     ybar = torch.empty((n, c), dtype=torch.float32, device=gtp.device)
@@ -737,10 +731,7 @@ def attention_aggregate(gtp: torch.Tensor, msg: torch.Tensor, rowptr: torch.Tens
 def pose_heads(x: torch.Tensor, w6: torch.Tensor, b6: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     x, w6, b6 = _req(x, "x"), _req(w6, "w6"), _req(b6, "b6")
     r, d = x.shape
-    if out is None:
-        out = torch.empty((r, 6), dtype=torch.float32, device=x.device)
-    elif tuple(out.shape) != (r, 6) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != x.device:
-        raise ValueError("pose_heads: out must be a contiguous fp32 [rows, 6] tensor on x's device")
+    out = _out(out, (r, 6), torch.float32, x.device, "pose_heads")
     L.check(L.lib().rpg_pose_heads_f32(_p(x), _p(w6), _p(b6), r, d, _p(out), _stream()), "pose_heads")
     return out
 

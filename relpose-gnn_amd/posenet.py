@@ -19,7 +19,7 @@ the result; parity tests use ``droprate=0``.  Everything runs on the GPU; CPU te
 Index validation.  The reference's aten indexing raises ``IndexError`` for a node id outside ``[0, N)``.  Here every call
 is validated on the device (``rpg_graph_prepare`` counts the offending edges, clamps them and leaves them out of the
 aggregation, so nothing reads out of bounds) and the count travels to pinned host memory with an asynchronous copy
-behind the kernels.  ``index_check = "deferred"`` (default) never blocks inside ``forward``: the count of call i is looked
+behind the kernels (``status.DeferredCounters``, which ``QueryPose`` uses too).  ``index_check = "deferred"`` (default) never blocks inside ``forward``: the count of call i is looked
 at when call i+1 starts (by then a reference-style caller has already synchronised through ``.cpu()``), in
 ``check_edge_index()`` and by ``evaluate_stream`` right after its own device-to-host event; ``index_check = "sync"``
 reads it back before returning, like the reference, at the price of one device synchronisation per call.
@@ -36,6 +36,7 @@ from . import _lib as _L
 from . import ops
 from .params import pack_gnn, pack_gnn_bf16
 from .resnet import EncoderRunner, WorkspacePool
+from .status import DeferredCounters
 
 
 class AttentionBlock(nn.Module):
@@ -65,6 +66,18 @@ class simpleConvEdge_upt(nn.Module):  # noqa: N801 - reference spelling (my_gnn_
                                           nn.Linear(out_channels, out_channels))
         self.edge_model = simpleEdgeModel(in_channels, edge_channels, edge_channels)
         self.att = AttentionBlock(in_channels)
+
+
+def _bad_index_error(counts: torch.Tensor) -> IndexError:
+    """``counts``: host int32 [16], the bad-edge counters (slots 0..7) and forward_map's bad-neighbour counters (8..15)."""
+    edges, nbrs = int(counts[:8].sum()), int(counts[8:].sum())
+    what = []
+    if edges:
+        what.append(f"edge_index has {edges} edge(s) with a node id outside its graph group / [0, N)")
+    if nbrs:
+        what.append(f"neighbours has {nbrs} index(es) outside the feature map's rows [0, M)")
+    return IndexError("; ".join(what) + " (detected on the device; with index_check='deferred' this refers to an EARLIER "
+                      "forward call)")
 
 
 class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
@@ -138,10 +151,7 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
         self._extra: Dict[str, torch.Tensor] = {}
         self.index_check = "deferred"            # "deferred" | "sync" (see the module docstring)
         # device int32 [16]: bad-edge counters, one per stream slot, then the map path's bad-neighbour counters, one per slot
-        self._status: Optional[torch.Tensor] = None
-        self._status_host: Optional[torch.Tensor] = None     # pinned mirror
-        self._status_event: Optional[torch.cuda.Event] = None
-        self._status_pending = False
+        self._counters = DeferredCounters(16, _bad_index_error)
         # optional frames.FrameTransform: with it forward() also takes uint8 frames data.x [n, H, W, 3] (RGB, HWC) on the GPU and
         # runs the reference's image transform there (a plain attribute: not a module, parameter or buffer -- state_dict unchanged)
         self.frame_transform = None
@@ -221,59 +231,13 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
             self._gnn_bf16 = pack_gnn_bf16(self._gnn_packed)
             self._gnn_bf16_ptrs = _L.ptr_array([t.data_ptr() for t in self._gnn_bf16])
 
-    # ---- edge_index validation without a host synchronisation ----------------------------------------------------
-    def _status_buffers(self, dev) -> torch.Tensor:
-        if self._status is None or self._status.device != dev:
-            self._status = torch.zeros(16, dtype=torch.int32, device=dev)
-            self._status_host = torch.zeros(16, dtype=torch.int32).pin_memory()
-            self._status_event = torch.cuda.Event()
-            self._status_pending = False
-        return self._status
-
-    def _raise_bad_edges(self, counts: torch.Tensor):
-        """``counts``: host int32 [16], the bad-edge counters (slots 0..7) and forward_map's bad-neighbour counters (8..15)."""
-        edges, nbrs = int(counts[:8].sum()), int(counts[8:].sum())
-        self._status.zero_()                      # (stream-ordered: after every forward issued so far)
-        self._status_host.zero_()                 # the mirror too, or a look without waiting would report it again
-        self._status_pending = False
-        what = []
-        if edges:
-            what.append(f"edge_index has {edges} edge(s) with a node id outside its graph group / [0, N)")
-        if nbrs:
-            what.append(f"neighbours has {nbrs} index(es) outside the feature map's rows [0, M)")
-        raise IndexError("; ".join(what) + " (detected on the device; with index_check='deferred' this refers to an EARLIER "
-                         "forward call)")
-
-    def _poll_status(self, block: bool) -> None:
-        """Look at the counters of the previous call(s) if their copy has landed (or wait for it when ``block``)."""
-        if not self._status_pending or torch.cuda.is_current_stream_capturing():
-            return
-        if block:
-            self._status_event.synchronize()
-        elif not self._status_event.query():
-            return
-        self._status_pending = False
-        if int(self._status_host.sum()):
-            self._raise_bad_edges(self._status_host)
-
+    # ---- edge_index validation without a host synchronisation (status.DeferredCounters) ------------------------------
     def publish_status(self) -> None:
-        """For callers that replay a captured forward (graphed.GraphedForward): the replayed kernels keep counting bad
-        edges on the device; this enqueues the copy of the counters behind the replay."""
-        if self._status is not None:
-            self._publish_status()
-
-    def _publish_status(self) -> None:
-        """Enqueue the counters' copy to pinned memory behind this call's kernels (current stream)."""
-        if torch.cuda.is_current_stream_capturing():
-            return                                # a captured forward is validated by its eager warm-up call
-        if self.index_check == "sync":
-            counts = self._status.cpu()
-            if int(counts.sum()):
-                self._raise_bad_edges(counts)
-            return
-        self._status_host.copy_(self._status, non_blocking=True)
-        self._status_event.record()
-        self._status_pending = True
+        """Enqueue the counters' copy to pinned memory behind the kernels issued so far (current stream); with
+        ``index_check = "sync"`` read them back instead.  Every forward ends with it.  Also for callers that replay a captured
+        forward (graphed.GraphedForward): the replayed kernels keep counting bad edges on the device; this enqueues the copy
+        of the counters behind the replay."""
+        self._counters.publish(sync=self.index_check == "sync")
 
     def check_edge_index(self, wait: bool = True) -> None:
         """Raise IndexError if a forward issued so far had an edge with a node id out of range (the error the reference's
@@ -282,34 +246,51 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
         on a later event of the same stream (``evaluate_stream`` after its device-to-host copy of batch i, with batch i+1
         already enqueued) that covers batch i without waiting for batch i+1; the counters accumulate on the device, so a
         report that is not in yet is seen by the next look."""
-        if wait:
-            self._poll_status(block=True)
-            return
-        if self._status_host is not None:
-            if int(self._status_host.sum()):
-                self._status_event.synchronize()
-                self._raise_bad_edges(self._status_host)
+        self._counters.check(wait)
+
+    def _prepare(self, x: torch.Tensor, what: str):
+        """The start of every forward: images as the encoder takes them, the bad-edge report of the previous call if it has
+        landed, packed weights.  -> (x [n, 3, H, W], the library, the device counters int32 [16])."""
+        x = self._encoder_input(x, what)                                          # posenet.py:1035
+        lib = _L.lib()
+        self._counters.poll()                     # bad-edge report of the previous call, if it has landed
+        # all weight packing happens here, on the caller's stream, BEFORE any side stream is forked off it
+        self._pack_gnn()
+        self._enc.ensure_packed(self.feature_extractor.state_dict, "", x.device)
+        return x, lib, self._counters.tensor(x.device)
+
+    def _fast(self, k, knn_ok: bool = True) -> bool:
+        """Whether the multi-stream schedule (_forward_streams) applies.  ``knn_ok``: the caller's batch vector can serve the
+        per-slot kNN build."""
+        return bool(self.use_AP and not self.use_attention and k is None and knn_ok
+                    and not (self.knn > 0 and self._gnn_dtype == "bf16"))
 
     def _gnn_call(self, lib, feat, esrc_ptr, edst_ptr, node_off, n, e, abs_pose, rel_pose, node_f, edge_f, status, slot):
         d = feat.shape[1]
         # the slot's workspace (resnet.WorkspacePool): the SAME buffer the encoder call of this slot used a moment ago on
         # this stream -- stream order makes the reuse safe, and the split-K scratch slice exists once per slot
         ws = self._ws_pool.get(slot, lib.rpg_gnn_workspace_bytes(n, e, d), feat.device)
+        weights = (self._gnn_ptrs, len(self._gnn_packed))
+        fn, name = lib.rpg_gnn_forward_f32, "gnn_forward"
         if self._gnn_dtype == "bf16":
-            rc = lib.rpg_gnn_forward_bf16(self._gnn_ptrs, len(self._gnn_packed), self._gnn_bf16_ptrs, len(self._gnn_bf16),
-                                          feat.data_ptr(), esrc_ptr, edst_ptr, node_off, n, e, d, int(self.gnn_recursion),
-                                          abs_pose.data_ptr(), rel_pose.data_ptr(),
-                                          None if node_f is None else node_f.data_ptr(),
-                                          None if edge_f is None else edge_f.data_ptr(), status.data_ptr(), ws.data_ptr(),
-                                          ws.numel(), torch.cuda.current_stream().cuda_stream)
-            _L.check(rc, "gnn_forward_bf16")
-            return
-        rc = lib.rpg_gnn_forward_f32(self._gnn_ptrs, len(self._gnn_packed), feat.data_ptr(), esrc_ptr, edst_ptr, node_off, n,
-                                     e, d, int(self.gnn_recursion), abs_pose.data_ptr(), rel_pose.data_ptr(),
-                                     None if node_f is None else node_f.data_ptr(),
-                                     None if edge_f is None else edge_f.data_ptr(), status.data_ptr(), ws.data_ptr(),
-                                     ws.numel(), torch.cuda.current_stream().cuda_stream)
-        _L.check(rc, "gnn_forward")
+            weights += (self._gnn_bf16_ptrs, len(self._gnn_bf16))
+            fn, name = lib.rpg_gnn_forward_bf16, "gnn_forward_bf16"
+        rc = fn(*weights, feat.data_ptr(), esrc_ptr, edst_ptr, node_off, n, e, d, int(self.gnn_recursion), abs_pose.data_ptr(),
+                rel_pose.data_ptr(), None if node_f is None else node_f.data_ptr(),
+                None if edge_f is None else edge_f.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(),
+                torch.cuda.current_stream().cuda_stream)
+        _L.check(rc, name)
+
+    def _drop_heads(self, node_f, edge_f, abs_out, rel_out):
+        """The reference's always-on dropout (posenet.py:1073-1075), then the heads kernel on the dropped features, which
+        overwrites the poses the GNN call made from the undropped ones (the node heads only with ``use_AP``: without it the
+        caller makes abs_pose from the returned, dropped node features)."""
+        t = self._gnn_packed
+        node_f = F.dropout(node_f, p=self.droprate)
+        if self.use_AP:
+            ops.pose_heads(node_f, t[18], t[19], out=abs_out)
+        ops.pose_heads(F.dropout(edge_f, p=self.droprate), t[20], t[21], out=rel_out)
+        return node_f
 
     @staticmethod
     def _graph_sizes(data, n_total: int, e_total: Optional[int]):
@@ -357,7 +338,7 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
     def _partition(self, data, n_total: int, e_total: Optional[int]):
         """Contiguous groups of whole graphs, one per stream: [(n0, n1, e0, e1, slot), ...] or None (single stream).
         ``e_total=None``: the caller replaces ``data.edge_index`` (kNN graph) -- only the node ranges matter then."""
-        parts = min(int(self.hip_streams), 8)                  # one bad-edge counter per slot (self._status)
+        parts = min(int(self.hip_streams), 8)                  # one bad-edge counter per slot (self._counters)
         if parts < 2:
             return None
         ng = getattr(data, "num_graphs", None)
@@ -404,20 +385,13 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
                                "(there is no CPU fallback)")
         if not torch.is_tensor(edge_index) or edge_index.device != x.device:
             raise RuntimeError("data.edge_index must be a tensor on the same GPU as data.x")
-        x = self._encoder_input(x, "data.x")                                      # posenet.py:1035
-        lib = _L.lib()
-        self._poll_status(block=False)            # bad-edge report of the previous call, if it has landed
-        # all weight packing happens here, on the caller's stream, BEFORE any side stream is forked off it
-        self._pack_gnn()
-        self._enc.ensure_packed(self.feature_extractor.state_dict, "", x.device)
-        self._status_buffers(x.device)
+        x, lib, _ = self._prepare(x, "data.x")
         # The multi-stream schedule serves the reference's default CLI flags too (round 5; testing/test.py:308-309: --knn 4
         # --droprate 0.5): the kNN graph is built per stream slot from that slot's encoder output, dropout + heads run per slot.
         batch_t = getattr(data, "batch", None)
         knn_ok = self.knn <= 0 or (torch.is_tensor(batch_t) and batch_t.dtype == torch.int64 and batch_t.device == x.device
                                    and batch_t.dim() == 1 and batch_t.numel() == x.size(0))
-        fast = self.use_AP and not self.use_attention and k is None and knn_ok and not (self.knn > 0 and self._gnn_dtype == "bf16")
-        parts = self._partition(data, x.size(0), edge_index.size(1) if self.knn <= 0 else None) if fast else None
+        parts = self._partition(data, x.size(0), edge_index.size(1) if self.knn <= 0 else None) if self._fast(k, knn_ok) else None
         if parts is not None and edge_index.dtype == torch.int64 and edge_index.dim() == 2 and edge_index.is_contiguous():
             enc_sd = self.feature_extractor.state_dict
             return self._forward_streams(lib, lambda n0, n1, wkey: self._enc.run(enc_sd, "", x[n0:n1], slot=wkey), x.size(0),
@@ -448,22 +422,17 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
         dev = feat.device
         abs_pose = torch.empty((n, 6), dtype=torch.float32, device=dev)
         rel_pose = torch.empty((e, 6), dtype=torch.float32, device=dev)
-        status = self._status[0:1]
+        status = self._counters.counters[0:1]
         drop = self.droprate > 0
         want_feats = drop or not self.use_AP
         node_f = torch.empty((n, d), dtype=torch.float32, device=dev) if want_feats else None
         edge_f = torch.empty((e, d), dtype=torch.float32, device=dev) if drop else None
         self._gnn_call(lib, feat, ei.data_ptr(), ei.data_ptr() + 8 * e, 0, n, e, abs_pose, rel_pose, node_f, edge_f, status, 0)
 
-        self._publish_status()                    # every call is validated; nothing blocks in "deferred" mode
+        self.publish_status()                     # every call is validated; nothing blocks in "deferred" mode
 
-        t = self._gnn_packed
-        if drop:                                                                  # posenet.py:1073-1075 (always on)
-            node_f = F.dropout(node_f, p=self.droprate)
-            edge_f = F.dropout(edge_f, p=self.droprate)
-            rel_pose = ops.pose_heads(edge_f, t[20], t[21])
-            if self.use_AP:
-                abs_pose = ops.pose_heads(node_f, t[18], t[19])
+        if drop:
+            node_f = self._drop_heads(node_f, edge_f, abs_pose, rel_pose)
         if not self.use_AP:                                                       # posenet.py:1080-1083
             # index plumbing (compute_edge_features).  Clamped like the GNN's own copy of the end points (rpg_graph_prepare):
             # with index_check="deferred" an out-of-range node id is REPORTED by the device-side counter (IndexError at the
@@ -548,13 +517,19 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
             raise ValueError("forward_map: neighbours needs K >= 1 database images per query")
         if g < 1 or queries.size(0) != g:
             raise ValueError(f"forward_map: {queries.size(0)} queries but neighbours has {g} rows")
-        if not queries.is_cuda:
-            raise RuntimeError("forward_map: queries must be on the GPU (there is no CPU fallback)")
-        if neighbours.device != queries.device or fmap.device != queries.device:
-            raise RuntimeError(f"forward_map: queries ({queries.device}), neighbours ({neighbours.device}) and the feature map "
-                               f"({fmap.device}) must be on the same GPU")
+        self._map_devices(queries, fmap, "neighbours", neighbours)
         nb = neighbours.contiguous()
         return self._forward_map_run(queries, fmap, k, g, kk, lambda qf, g0, g1, st, wkey: nb[g0:g1])
+
+    @staticmethod
+    def _map_devices(queries, fmap, name: str, t: Optional[torch.Tensor]) -> None:
+        """``forward_map``'s device rules: the queries on a GPU, the feature map and the tensor ``t`` (if given) on the same one."""
+        if not queries.is_cuda:
+            raise RuntimeError("forward_map: queries must be on the GPU (there is no CPU fallback)")
+        if fmap.device != queries.device or (t is not None and t.device != queries.device):
+            where = "" if t is None else f" ({t.device})"
+            raise RuntimeError(f"forward_map: queries ({queries.device}), {name}{where} and the feature map ({fmap.device}) "
+                               f"must be on the same GPU")
 
     def _forward_map_retrieve(self, queries, fmap, k, rule, query_descriptors, query_groups):
         """``forward_map`` with the neighbours retrieved per stream slot from that slot's query features (or descriptors)."""
@@ -575,11 +550,7 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
             qd = query_descriptors
             if not torch.is_tensor(qd) or qd.dtype != torch.float32 or qd.dim() != 2 or qd.shape != (g, fmap.descriptors.shape[1]):
                 raise ValueError(f"forward_map: query_descriptors must be fp32 [{g}, {fmap.descriptors.shape[1]}]")
-        if not queries.is_cuda:
-            raise RuntimeError("forward_map: queries must be on the GPU (there is no CPU fallback)")
-        if fmap.device != queries.device or (qd is not None and qd.device != queries.device):
-            raise RuntimeError(f"forward_map: queries ({queries.device}), query_descriptors and the feature map ({fmap.device}) "
-                               f"must be on the same GPU")
+        self._map_devices(queries, fmap, "query_descriptors", qd)
         dev = queries.device
         # everything the slots share is made here, on the caller's stream, before any side stream is forked off it
         qd = None if qd is None else qd.contiguous()
@@ -601,21 +572,15 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
         """``neighbours_of(qf, g0, g1, status, wkey)``: the map rows int64 [g1 - g0, K] of queries g0..g1, whose encoder features
         are ``qf``, made on the current (slot) stream."""
         fmap.check(self)
-        x = self._encoder_input(queries, "queries")
-        lib = _L.lib()
-        self._poll_status(block=False)
+        x, lib, status = self._prepare(queries, "queries")
         dev = x.device
-        self._pack_gnn()
-        self._enc.ensure_packed(self.feature_extractor.state_dict, "", dev)
-        status = self._status_buffers(dev)
         n_per = kk + 1
         edge_index, batch = self._map_graph(g, n_per, dev)
         edge_index = edge_index.clone()           # the caller's to keep (the cached copy serves the next call)
         enc_sd = self.feature_extractor.state_dict
 
-        fast = self.use_AP and not self.use_attention and k is None and not (self.knn > 0 and self._gnn_dtype == "bf16")
         parts = None
-        if fast:
+        if self._fast(k):
             from .graph import Data
             spec = Data()
             spec.graph_sizes = ([n_per] * g, [n_per * kk] * g)
@@ -668,21 +633,32 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
         k = min(int(self.small_batch_streams), n)
         if k < 2 or n > 32:
             return self._enc.run(self.feature_extractor.state_dict, "", x)
-        dev = x.device
-        while len(self._streams) < k:
+        feat = torch.empty((n, self.feature_extractor.fc.out_features), dtype=torch.float32, device=x.device)
+        cur, streams = self._fork(k, x.device)
+        for p, st in enumerate(streams):
+            i0, i1 = n * p // k, n * (p + 1) // k
+            with torch.cuda.stream(st):
+                self._enc.run(self.feature_extractor.state_dict, "", x[i0:i1], slot=(100, p), out=feat[i0:i1])
+        self._join(cur, streams)
+        return feat
+
+    def _fork(self, n: int, dev) -> Tuple[torch.cuda.Stream, List[torch.cuda.Stream]]:
+        """(the caller's stream, the first ``n`` side streams): every side stream waits for what the caller's stream has been
+        given so far (inputs, packed weights, the outputs allocated on it) before it runs anything issued from here on."""
+        while len(self._streams) < n:
             self._streams.append(torch.cuda.Stream(device=dev))
-        feat = torch.empty((n, self.feature_extractor.fc.out_features), dtype=torch.float32, device=dev)
         cur = torch.cuda.current_stream()
         ready = torch.cuda.Event()
         ready.record(cur)
-        for p in range(k):
-            i0, i1 = n * p // k, n * (p + 1) // k
-            st = self._streams[p]
+        for st in self._streams[:n]:
             st.wait_event(ready)
-            with torch.cuda.stream(st):
-                self._enc.run(self.feature_extractor.state_dict, "", x[i0:i1], slot=(100, p), out=feat[i0:i1])
+        return cur, self._streams[:n]
+
+    @staticmethod
+    def _join(cur: torch.cuda.Stream, streams: List[torch.cuda.Stream]) -> None:
+        """The caller's stream waits for everything issued to the side streams so far."""
+        for st in streams:
             cur.wait_stream(st)
-        return feat
 
     def _forward_streams(self, lib, features, n_total, dev, edge_index, parts, batch=None):
         """use_AP / no extra attention / no explicit k, on ``len(parts)`` concurrent streams.  ``features(n0, n1, wkey)`` makes the
@@ -695,27 +671,18 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
         (posenet.py:1073-1086) run per slot on the slot's stream."""
         knn = int(self.knn) if self.knn > 0 else 0
         drop = self.droprate > 0
-        n_slots = 1 + max(p[4] for p in parts)
-        while len(self._streams) < n_slots:
-            self._streams.append(torch.cuda.Stream(device=dev))
-        cur = torch.cuda.current_stream()
         abs_pose = torch.empty((n_total, 6), dtype=torch.float32, device=dev)
-        status = self._status
-        ready = torch.cuda.Event()
-        ready.record(cur)
-        for st in self._streams[:n_slots]:
-            st.wait_event(ready)
+        status = self._counters.counters
+        cur, streams = self._fork(1 + max(p[4] for p in parts), dev)
         d = self.feature_extractor.fc.out_features
-        t = self._gnn_packed
 
         def heads(feat, n0, n1, ei_ptrs, node_off, e, rel_out, slot, wkey):
             node_f = torch.empty((n1 - n0, d), dtype=torch.float32, device=dev) if drop else None
             edge_f = torch.empty((e, d), dtype=torch.float32, device=dev) if drop else None
             self._gnn_call(lib, feat, ei_ptrs[0], ei_ptrs[1], node_off, n1 - n0, e, abs_pose[n0:n1], rel_out, node_f, edge_f,
                            status[slot:slot + 1], wkey)
-            if drop:                                                              # posenet.py:1073-1075 (always on)
-                ops.pose_heads(F.dropout(node_f, p=self.droprate), t[18], t[19], out=abs_pose[n0:n1])
-                ops.pose_heads(F.dropout(edge_f, p=self.droprate), t[20], t[21], out=rel_out)
+            if drop:
+                self._drop_heads(node_f, edge_f, abs_pose[n0:n1], rel_out)
                 for buf in (node_f, edge_f):
                     buf.record_stream(torch.cuda.current_stream())
 
@@ -724,7 +691,7 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
             rel_pose = torch.empty((e_total, 6), dtype=torch.float32, device=dev)
             base = edge_index.data_ptr()
             for gi, (n0, n1, e0, e1, slot) in enumerate(parts):
-                st = self._streams[slot]
+                st = streams[slot]
                 with torch.cuda.stream(st):
                     # workspaces are per (slot, position in the slot's queue): groups of a slot run in order, so they could share,
                     # but a different shape would re-allocate every call
@@ -732,15 +699,14 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
                     feat = features(n0, n1, wkey)
                     heads(feat, n0, n1, (base + 8 * e0, base + 8 * (e_total + e0)), n0, e1 - e0, rel_pose[e0:e1], slot, wkey)
                     feat.record_stream(st)
-            for st in self._streams[:n_slots]:
-                cur.wait_stream(st)
-            self._publish_status()
+            self._join(cur, streams)
+            self.publish_status()
             return abs_pose, rel_pose, edge_index
 
         # ---- knn > 0: phase 1 = encoder + kNN build per slot (no host wait), phase 2 = GNN per slot once its edge count is in
         pend = []
         for gi, (n0, n1, _, _, slot) in enumerate(parts):
-            st = self._streams[slot]
+            st = streams[slot]
             with torch.cuda.stream(st):
                 wkey = (slot, gi)
                 feat = features(n0, n1, wkey)
@@ -757,10 +723,9 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
             if bad:
                 # every slot's encoder + kNN work is already enqueued on the side streams and reads the caller's x (e.g. a
                 # staging buffer the caller refills once this call returns OR raises): join them before leaving
-                for st_ in self._streams[:n_slots]:
-                    cur.wait_stream(st_)
+                self._join(cur, streams)
                 raise ValueError("knn_graph: a graph has more than 2048 nodes (unsupported)")
-            st = self._streams[slot]
+            st = streams[slot]
             with torch.cuda.stream(st):
                 cap = ei_buf.size(1)
                 rel = torch.empty((total, 6), dtype=torch.float32, device=dev)
@@ -772,7 +737,6 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
                     buf.record_stream(st)
                 for buf in (rel, ei_g):                # allocated on the slot's stream, concatenated on the caller's below
                     buf.record_stream(cur)
-        for st in self._streams[:n_slots]:
-            cur.wait_stream(st)
-        self._publish_status()
+        self._join(cur, streams)
+        self.publish_status()
         return abs_pose, torch.cat(rels), torch.cat(eis, dim=1)

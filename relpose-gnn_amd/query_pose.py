@@ -8,17 +8,16 @@ round trip, and an evaluation stream copies 128 bytes per graph back instead of 
 
 A graph that has no ``ref_node``-th edge into its query node (or whose reference edge starts outside the graph) cannot be
 evaluated: its row is NaN and it is counted in a status word this object owns.  ``check`` turns a non-zero count into the
-``ValueError`` of ``evaluate.reference_edge``, by the look-now / wait contract of ``PoseNetX_R2.check_edge_index``: the count
-travels to pinned host memory with an asynchronous copy behind every call, so nothing blocks unless the caller asks it to.
+``ValueError`` of ``evaluate.reference_edge``.  The status word is a ``status.DeferredCounters`` with one counter, the class
+behind ``PoseNetX_R2.check_edge_index`` too: the count travels to pinned host memory with an asynchronous copy behind every
+call, so nothing blocks unless the caller asks it to.
 """
 from __future__ import annotations
-
-import numbers
-from typing import Optional
 
 import torch
 
 from . import ops
+from .status import DeferredCounters
 
 
 class QueryPose:
@@ -26,15 +25,8 @@ class QueryPose:
         """``pose_m`` / ``pose_s``: translation mean / std (test.py:126-130, 248-251); ``ref_node``: which of the edges into the
         query node is the reference edge (test.py:227-229)."""
         self.pose_m, self.pose_s = ops._qp_triple(pose_m, "pose_m"), ops._qp_triple(pose_s, "pose_s")
-        if isinstance(ref_node, bool) or not isinstance(ref_node, numbers.Integral):
-            raise TypeError(f"QueryPose: ref_node must be an int, got {type(ref_node).__name__}")
-        if ref_node < 0:
-            raise ValueError(f"QueryPose: ref_node must be >= 0, got {ref_node}")
-        self.ref_node = int(ref_node)
-        self._status: Optional[torch.Tensor] = None
-        self._status_host: Optional[torch.Tensor] = None      # pinned mirror
-        self._event: Optional[torch.cuda.Event] = None
-        self._pending = False
+        self.ref_node = ops._qp_ref_node(ref_node)
+        self._bad = DeferredCounters(1, self._error)          # graphs that could not be evaluated
 
     # ---- the two forms ---------------------------------------------------------------------------------------------------
     def from_targets(self, rel_pose, edge_index, node_first, node_targets, edge_first=None, out=None) -> torch.Tensor:
@@ -55,60 +47,29 @@ class QueryPose:
                                         query_targets=query_targets, edge_first=edge_first, out=out))
 
     def _run(self, rel_pose, kw) -> torch.Tensor:
-        status = None
         if torch.is_tensor(rel_pose) and rel_pose.is_cuda:      # (anything else is refused by ops.query_pose below)
-            status = self._status_buffers(rel_pose.device)
-        elif self._status is not None:
-            status = self._status
+            status = self._bad.tensor(rel_pose.device)
+        else:
+            status = self._bad.counters
         if status is None:
             status = torch.zeros(1, dtype=torch.int32)          # placeholder for the host-side checks, which refuse the call
         rows = ops.query_pose(rel_pose, pose_m=self.pose_m, pose_s=self.pose_s, ref_node=self.ref_node, status=status, **kw)
-        self._publish()
+        self._bad.publish()                       # the counter's copy to pinned memory, behind this call's kernel
         return rows
 
-    # ---- bad graphs, without a host synchronisation -----------------------------------------------------------------------
-    def _status_buffers(self, dev) -> torch.Tensor:
-        if self._status is None or self._status.device != dev:
-            self._status = torch.zeros(1, dtype=torch.int32, device=dev)
-            self._status_host = torch.zeros(1, dtype=torch.int32).pin_memory()
-            self._event = torch.cuda.Event()
-            self._pending = False
-        return self._status
-
-    def _publish(self) -> None:
-        """Enqueue the counter's copy to pinned memory behind this call's kernel (current stream)."""
-        if torch.cuda.is_current_stream_capturing():
-            return                                # a replayed launch keeps counting on the device: call publish() behind the replay
-        self._status_host.copy_(self._status, non_blocking=True)
-        self._event.record()
-        self._pending = True
+    # ---- bad graphs, without a host synchronisation (status.DeferredCounters) ----------------------------------------------
+    def _error(self, counts: torch.Tensor) -> ValueError:
+        return ValueError(f"graph has no edge into node 0: cannot derive the query pose ({int(counts[0])} graph(s) lack edge "
+                          f"number {self.ref_node} into their query node, or its source lies outside the graph; detected on the "
+                          "device, their rows are NaN)")
 
     def publish(self) -> None:
-        """For callers that replay a captured launch: enqueue the counter's copy behind the replay."""
-        if self._status is not None:
-            self._publish()
-
-    def _raise(self) -> None:
-        bad = int(self._status_host[0])
-        self._status.zero_()                      # (stream-ordered: after every call issued so far)
-        self._status_host.zero_()                 # the mirror too, or a look without waiting would report it again
-        self._pending = False
-        raise ValueError(f"graph has no edge into node 0: cannot derive the query pose ({bad} graph(s) lack edge number "
-                         f"{self.ref_node} into their query node, or its source lies outside the graph; detected on the device, "
-                         "their rows are NaN)")
+        """For callers that replay a captured launch (a replayed launch keeps counting on the device): enqueue the counter's
+        copy behind the replay."""
+        self._bad.publish()
 
     def check(self, wait: bool = True) -> None:
         """Raise the ValueError of ``evaluate.reference_edge`` if a call issued so far met a graph it could not evaluate.
-        ``wait=True`` blocks until every call issued so far has reported.  ``wait=False`` only looks at what has already arrived
-        in the pinned mirror: for a caller that has just synchronised on a later event of the same stream that covers the call
-        in question without waiting for the next one; the counter accumulates on the device, so a report that is not in yet is
-        seen by the next look."""
-        if self._status_host is None:
-            return
-        if wait:
-            if self._pending:
-                self._event.synchronize()
-                self._pending = False
-        if int(self._status_host[0]):
-            self._event.synchronize()
-            self._raise()
+        ``wait=True`` blocks until every call issued so far has reported, ``wait=False`` only looks at what has already arrived
+        in the pinned mirror (``status.DeferredCounters.check``; the contract of ``PoseNetX_R2.check_edge_index``)."""
+        self._bad.check(wait)

@@ -208,6 +208,33 @@ def test_module_contract(dev):
     assert torch.equal(a3, a) and torch.equal(r3, r)
 
 
+def test_bad_edge_is_reported_once_by_a_look(dev):
+    """The look-without-waiting half of the deferred check: once the counters' copy has landed, ``check_edge_index(wait=False)``
+    reports the bad edge, exactly once, and the next clean forward is untouched by it.  One 8-node graph runs on the caller's
+    stream and counts in slot 0; four 8-node graphs on two streams, the bad edge in the second half, count in slot 1 and go
+    through the fork / join of the side streams."""
+    import relpose_gnn_amd.synth as S
+    m, _ = _build(64, 32, (8, 16, 32, 64), (1, 1, 1, 1), dev)
+    for graphs in (1, 4):
+        m.hip_streams = 2
+        x = S.synth_images(8 * graphs, 32, 40, seed=3)
+        d = _data(x, 8, dev)
+        a, r, _ = m(d)
+        m.check_edge_index()
+        bad = _data(x, 8, dev)
+        bad.edge_index = bad.edge_index.clone()
+        bad.edge_index[0, 56 * (graphs // 2) + 5] = 99          # past every node; in the second half of the 4-graph batch
+        m(bad)                                                  # returns: the bad edge is clamped and counted on the device
+        torch.cuda.synchronize()
+        with pytest.raises(IndexError, match="edge_index has 1 edge"):
+            m.check_edge_index(wait=False)                      # the report has landed: a look is enough
+        m.check_edge_index(wait=False)                          # reported once; device counter and mirror are cleared
+        m.check_edge_index()
+        a_ok, r_ok, _ = m(d)
+        m.check_edge_index()
+        assert torch.equal(a_ok, a) and torch.equal(r_ok, r)
+
+
 @pytest.mark.parametrize("use_AP", [True, False])
 def test_dropout_always_on_with_seeded_mask(dev, use_AP):
     """A11 (posenet.py:1073-1075): F.dropout(x, p) / F.dropout(edge_feat, p) with training=True regardless of eval().

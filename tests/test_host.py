@@ -188,6 +188,40 @@ def test_stream_partition_from_pyg_batch_tables():
     m.stream_schedule = None
 
 
+def test_deferred_counters_are_idle_until_a_call_runs(monkeypatch):
+    """A model and a QueryPose on which nothing has run have nothing to report and nothing to publish: every public entry of the
+    deferred check returns without touching CUDA, and status.DeferredCounters creates no buffer at construction."""
+    from relpose_gnn_amd.posenet import PoseNetX_R2
+    from relpose_gnn_amd.query_pose import QueryPose
+    from relpose_gnn_amd.resnet import ResNet
+    from relpose_gnn_amd.status import DeferredCounters
+
+    def touched(*a, **k):
+        raise AssertionError("CUDA was touched")
+    for name in ("_lazy_init", "is_current_stream_capturing", "current_stream", "Event", "Stream"):
+        monkeypatch.setattr(torch.cuda, name, touched)
+    monkeypatch.setattr(torch.Tensor, "pin_memory", touched)
+    c = DeferredCounters(3, lambda counts: IndexError(str(counts.tolist())))
+    assert c.counters is None and c._host is None and c._event is None and not c._pending
+    m = PoseNetX_R2(ResNet((1, 1, 1, 1), (8, 16, 32, 64)), droprate=0.0, pretrained=False, feat_dim=64, edge_feat_dim=64,
+                    node_dim=64, use_gnn=True)
+    qp = QueryPose()
+    for index_check in ("deferred", "sync"):
+        m.index_check = index_check
+        m.check_edge_index()
+        m.check_edge_index(wait=False)
+        m.publish_status()
+    qp.check()
+    qp.check(wait=False)
+    qp.publish()
+    c.check()
+    c.check(wait=False)
+    c.poll()
+    c.publish()
+    c.publish(sync=True)
+    assert m._counters.counters is None and qp._bad.counters is None and c.counters is None
+
+
 def test_stem_pair_table_matches_the_kernel():
     """params.stem_pair_table (what pack_stem_pairs packs by) == rpg_stem_pair_table (what csrc/stem.hip reads by)."""
     import ctypes as C
