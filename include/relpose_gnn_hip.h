@@ -244,6 +244,35 @@ int rpg_query_pose_f64(const float* rel_pose, const int64_t* edge_src, const int
                        double pose_m0, double pose_m1, double pose_m2, double pose_s0, double pose_s1, double pose_s2,
                        int ref_node, double* out, int32_t* status, void* stream);
 
+/* All of a query's reference edges fused into one pose.  rpg_query_pose_f64 keeps one of the edges into the query node; here every
+ * such edge is one estimate of the query's pose and the row holds their combination.  Arguments, the two forms of the graphs,
+ * arithmetic (float64 on the fp32 inputs, no contraction) and the row layout are those of rpg_query_pose_f64.  For graph i:
+ *   used    = the first max_edges columns, in column order, whose target is the graph's first node and whose source is NOT that
+ *             node (a self-edge would carry the query's own target into its estimate); C of them
+ *   t_c, q_c = the pred part of the single-edge rule for used column c;  targ is unchanged
+ *   fuse 0 (mean)    t = (t_0 + .. + t_{C-1}) / C;  q = S / |S| with S = sum of (q_c if <q_c, q_0> >= 0 else -q_c), both sums in
+ *                    column order; q_0 where |S| = 0
+ *   fuse 1 (median)  t = the component-wise median (the mean of the two middle values for even C);  q = q_c* , the medoid: c*
+ *                    minimises the sum over d != c, in column order, of the angular error between q_c and q_d; ties: the lowest c
+ *   C = 1            the candidate as it is: the row of rpg_query_pose_f64 at ref_node = 0, bit for bit
+ *   C >= 2 and a used candidate with a non-finite component: pred[7] and both errors NaN (targ as always); not a bad graph
+ *   the errors are those of the fused pose against targ, by the formulas of rpg_query_pose_f64
+ * A graph without a usable edge, with a used edge whose source lies outside the graph, or (targets form) with nodes outside
+ * [0, n) gets a row of NaN and status [1] += 1.  Nothing reads out of bounds.
+ *   cand  [g][max_edges][16] float64 or NULL  used candidate c as a full row (pred, targ, its own errors): the row of
+ *                                             rpg_query_pose_f64 at ref_node = c on a graph without self-edges; NaN past C and
+ *                                             for a bad graph
+ *   count [g] int32 or NULL                   the usable edges found BEFORE the cut at max_edges
+ * out and cand 16-byte aligned, e >= 1, g >= 1, fuse 0 or 1, 1 <= max_edges <= 64 (RPG_ERR_BAD_ARG otherwise).  One wave per
+ * graph, lane c computes candidate c; every reduction is a function of the column order only (sequential sums, ranks with ties
+ * by slot, a lexicographic minimum through cross-lane moves); no floating-point atomics.  One launch, no allocation, no
+ * synchronisation (graph-capturable).                                                                                    */
+int rpg_query_pose_fused_f64(const float* rel_pose, const int64_t* edge_src, const int64_t* edge_dst, int64_t e,
+                             const int64_t* node_first, const int64_t* edge_first, int g, const float* node_targets, int64_t n,
+                             const float* map_poses, int64_t m, const int64_t* neighbours, int k, const float* query_targets,
+                             double pose_m0, double pose_m1, double pose_m2, double pose_s0, double pose_s1, double pose_s2,
+                             int fuse, int max_edges, double* out, double* cand, int32_t* count, int32_t* status, void* stream);
+
 /* torch_cluster.knn_graph(x, k, batch, loop=False, flow='source_to_target') (posenet.py:1043-1050): for every node
  * the k nearest OTHER nodes of its graph by squared Euclidean distance (k+1 nearest including itself by
  * (distance, index), self match dropped).  x [n][d]; batch [n] int64 graph id per node, nodes of a graph contiguous,

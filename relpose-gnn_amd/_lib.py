@@ -31,7 +31,7 @@ SYMBOLS = (
     "rpg_resize_table_ksize", "rpg_resize_table_bilinear", "rpg_frames_workspace_bytes", "rpg_frames_u8_to_f32",
     "rpg_frames_u8_to_bf16", "rpg_gather_graph_nodes_f32", "rpg_linear_bf16_ex", "rpg_conv_pair_bf16",
     "rpg_retrieve_workspace_bytes", "rpg_retrieve_max_rank", "rpg_row_inv_norms_f32", "rpg_retrieve_cosine_f32",
-    "rpg_query_pose_f64",
+    "rpg_query_pose_f64", "rpg_query_pose_fused_f64",
 )
 
 
@@ -117,6 +117,8 @@ def _declare(lib: C.CDLL) -> None:
     lib.rpg_retrieve_cosine_f32.argtypes = [_vp] * 6 + [_i, _i, C.c_int64, _i, _vp, _vp, _vp, _sz, _vp, _vp]
     lib.rpg_query_pose_f64.argtypes = [_vp, _vp, _vp, C.c_int64, _vp, _vp, _i, _vp, C.c_int64, _vp, C.c_int64, _vp, _i, _vp] + [C.c_double] * 6 + [
         _i, _vp, _vp, _vp]
+    lib.rpg_query_pose_fused_f64.argtypes = [_vp, _vp, _vp, C.c_int64, _vp, _vp, _i, _vp, C.c_int64, _vp, C.c_int64, _vp, _i, _vp] + [
+        C.c_double] * 6 + [_i, _i, _vp, _vp, _vp, _vp, _vp]
     for name in SYMBOLS:
         getattr(lib, name)         # AttributeError here = the library does not export a declared symbol
 

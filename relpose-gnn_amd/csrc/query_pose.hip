@@ -153,6 +153,236 @@ __global__ __launch_bounds__(QP_NT) void query_pose_kernel(const QpArgs a) {
     orow[7] = make_double2(t_err, q_err);
 }
 
+// ---- all of a query's reference edges fused into one pose ---------------------------------------------------------------------
+// Every column into the query node is one estimate of its pose (the single-edge rule above keeps one and drops the rest).  One
+// wave per graph again.  The wave steps over the graph's columns 64 at a time; a hit whose source is not the query itself takes
+// the next candidate slot (ballot + popcounts in column order) until `max_edges` slots are filled, and the scan goes on to the
+// end so that `count` tells what the limit cut.  Lane c then computes candidate c -- the sin / cos / sqrt of the candidates run
+// side by side -- and writes its 7 doubles to LDS (4 waves x 64 x 7 doubles = 14 KB, plus 2 KB of column indices).  Every
+// reduction is a function of the column order only: the sums of `mean` run sequentially over LDS in lane 0; for `median` every
+// lane ranks its own value (smaller values, ties by slot) and the lane(s) of the middle rank(s) are read with a cross-lane move;
+// for the medoid lane c adds up its own row of angles in slot order and a butterfly of cross-lane moves takes the lexicographic
+// minimum of (sum, c).  No floating-point atomics; the only atomic is the integer count of bad graphs.
+constexpr int QF_MEAN = 0, QF_MEDIAN = 1;
+constexpr int QF_MAX = 64;            // candidates per graph: one per lane
+
+struct QfArgs {
+    QpArgs q;                         // (ref_node unused)
+    int fuse, max_edges;
+    double* cand;                     // [g][max_edges][16] | null
+    int32_t* count;                   // [g] | null
+};
+
+// 2 acos(|<p, q>|) in degrees (pose_utils.py:420-431) with Python's min(1.0, max(-1.0, d)), as in the kernel above
+__device__ __forceinline__ double quat_angle(const double* p, const double* q) {
+#pragma clang fp contract(off)
+    double d = fabs(q[0] * p[0] + q[1] * p[1] + q[2] * p[2] + q[3] * p[3]);
+    d = d > -1.0 ? d : -1.0;
+    d = d < 1.0 ? d : 1.0;
+    return 2.0 * acos(d) * 180.0 / M_PI;
+}
+
+__device__ __forceinline__ double trans_dist(const double* p, const double* t) {
+#pragma clang fp contract(off)
+    const double dx = p[0] - t[0], dy = p[1] - t[1], dz = p[2] - t[2];
+    return sqrt(dx * dx + dy * dy + dz * dz);
+}
+
+__device__ __forceinline__ void store_row(double* row, const double* pt, const double* pq, const double* tt, const double* tq,
+                                          double t_err, double q_err) {
+    double2* orow = reinterpret_cast<double2*>(row);
+    orow[0] = make_double2(pt[0], pt[1]);
+    orow[1] = make_double2(pt[2], pq[0]);
+    orow[2] = make_double2(pq[1], pq[2]);
+    orow[3] = make_double2(pq[3], tt[0]);
+    orow[4] = make_double2(tt[1], tt[2]);
+    orow[5] = make_double2(tq[0], tq[1]);
+    orow[6] = make_double2(tq[2], tq[3]);
+    orow[7] = make_double2(t_err, q_err);
+}
+
+__device__ __forceinline__ void store_nan_row(double* row) {
+    const double nan = __builtin_nan("");
+    double2* orow = reinterpret_cast<double2*>(row);
+    for (int i = 0; i < 8; ++i) orow[i] = make_double2(nan, nan);
+}
+
+__global__ __launch_bounds__(QP_NT) void query_pose_fused_kernel(const QfArgs f) {
+#pragma clang fp contract(off)
+    __shared__ double s_cand[QP_NT / 64][QF_MAX][7];      // per wave: candidate c = t[3], q[4]
+    __shared__ long long s_col[QP_NT / 64][QF_MAX];       // per wave: the column of candidate c
+    const QpArgs& a = f.q;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int64_t gi = (int64_t)blockIdx.x * (QP_NT / 64) + w;
+    const bool active = gi < a.g;                         // (wave-uniform; no wave leaves before the last barrier)
+
+    // ---- the usable columns, in column order: target = the graph's first node, source != that node -------------------------------
+    int64_t first = 0, last = 0, found = 0;
+    if (active) {
+        if (a.node_first) {
+            first = a.node_first[gi];
+            last = a.node_first[gi + 1];
+        } else {
+            first = gi * (a.k + 1);
+            last = first + a.k + 1;
+        }
+        int64_t lo = 0, hi = a.e;
+        if (a.edge_first) {                               // clamped, as above
+            lo = clamp_i64(a.edge_first[gi], 0, a.e);
+            hi = clamp_i64(a.edge_first[gi + 1], 0, a.e);
+        }
+        if (last > first) {
+            for (int64_t c0 = lo; c0 < hi; c0 += 64) {
+                const int64_t c = c0 + lane;
+                const bool hit = c < hi && a.edge_dst[c] == first && a.edge_src[c] != first;
+                const unsigned long long mask = __ballot(hit);
+                if (hit) {
+                    const int64_t slot = found + __popcll(mask & ((1ull << lane) - 1ull));
+                    if (slot < f.max_edges) s_col[w][slot] = c;
+                }
+                found += __popcll(mask);
+            }
+        }
+    }
+    __syncthreads();
+
+    // ---- lane c: candidate c --------------------------------------------------------------------------------------------------------
+    const int cn = (int)(found < f.max_edges ? found : f.max_edges);      // C, the candidates used
+    const bool mine = active && lane < cn;
+    bool bad = false, void_row = false;
+    double pt[3], pq[4], tt[3], tq[4], t_err = 0.0, q_err = 0.0;
+    for (int i = 0; i < 3; ++i) pt[i] = tt[i] = 0.0;
+    for (int i = 0; i < 4; ++i) pq[i] = tq[i] = 0.0;
+    if (active) {
+        int64_t col = 0, src = first;
+        bool bad_lane = false;
+        if (mine) {
+            col = s_col[w][lane];
+            src = a.edge_src[col];
+            bad_lane = src < first || src >= last;        // a used edge's source lies outside the graph
+        }
+        bad = cn == 0 || __ballot(bad_lane) != 0ull;
+        if (a.node_targets) bad = bad || first < 0 || last > a.n;
+        if (!bad) {
+            const float* trow;                            // the query's own target row (null: zeros)
+            const float* srow = nullptr;                  // the target row of this candidate's source node
+            if (a.node_targets) {
+                trow = a.node_targets + first * 6;
+                if (mine) srow = a.node_targets + src * 6;
+            } else {
+                trow = a.query_targets ? a.query_targets + gi * 6 : nullptr;
+                if (mine) {                               // src - first in [1, k]: the query's own node is never a source here
+                    const int64_t idx = clamp_i64(a.neighbours[gi * a.k + (src - first - 1)], 0, a.m - 1);
+                    srow = a.map_poses + idx * 6;
+                }
+            }
+            double tg[6];
+            for (int i = 0; i < 6; ++i) tg[i] = trow ? (double)trow[i] : 0.0;
+            for (int i = 0; i < 3; ++i) tt[i] = tg[i] * a.pose_s[i] + a.pose_m[i];
+            qexp(tg + 3, tq);
+            bool nf_lane = false;
+            if (mine) {
+                const float* rrow = a.rel_pose + col * 6;
+                double o[6];
+                for (int i = 0; i < 6; ++i) o[i] = (double)srow[i] - (double)rrow[i];
+                for (int i = 0; i < 3; ++i) pt[i] = o[i] * a.pose_s[i] + a.pose_m[i];
+                qexp(o + 3, pq);
+                t_err = trans_dist(pt, tt);
+                q_err = quat_angle(pq, tq);
+                for (int i = 0; i < 3; ++i) {
+                    s_cand[w][lane][i] = pt[i];
+                    nf_lane = nf_lane || !isfinite(pt[i]);
+                }
+                for (int i = 0; i < 4; ++i) {
+                    s_cand[w][lane][3 + i] = pq[i];
+                    nf_lane = nf_lane || !isfinite(pq[i]);
+                }
+            }
+            void_row = cn > 1 && __ballot(nf_lane) != 0ull;       // a non-finite candidate voids the fused pose (not C = 1)
+        }
+        if (f.cand && lane < f.max_edges) {
+            double* crow = f.cand + (gi * f.max_edges + lane) * 16;
+            if (mine && !bad) {
+                store_row(crow, pt, pq, tt, tq, t_err, q_err);
+            } else {
+                store_nan_row(crow);
+            }
+        }
+        if (f.count && lane == 0) f.count[gi] = (int32_t)(found < 0x7fffffff ? found : 0x7fffffff);
+    }
+    __syncthreads();
+    if (!active) return;
+    if (bad) {
+        if (lane == 0) {
+            atomicAdd(a.status, 1);
+            store_nan_row(a.out + gi * 16);
+        }
+        return;
+    }
+    if (cn == 1) {                                        // the candidate as it is: the single-edge rule's row
+        if (lane == 0) store_row(a.out + gi * 16, pt, pq, tt, tq, t_err, q_err);
+        return;
+    }
+    if (void_row) {
+        if (lane == 0) {
+            const double nan = __builtin_nan("");
+            const double nt[3] = {nan, nan, nan}, nq[4] = {nan, nan, nan, nan};
+            store_row(a.out + gi * 16, nt, nq, tt, tq, nan, nan);
+        }
+        return;
+    }
+
+    // ---- the fused pose (the whole wave is here: cross-lane moves below) ----------------------------------------------------------
+    double ft[3], fq[4];
+    if (f.fuse == QF_MEAN) {
+        if (lane != 0) return;
+        double st[3] = {0.0, 0.0, 0.0}, sq[4] = {0.0, 0.0, 0.0, 0.0};
+        for (int d = 0; d < cn; ++d) {
+            const double* cd = s_cand[w][d];
+            for (int i = 0; i < 3; ++i) st[i] = st[i] + cd[i];
+            const double dot = cd[3] * pq[0] + cd[4] * pq[1] + cd[5] * pq[2] + cd[6] * pq[3];    // <q_d, q_0>
+            for (int i = 0; i < 4; ++i) sq[i] = dot >= 0.0 ? sq[i] + cd[3 + i] : sq[i] - cd[3 + i];
+        }
+        for (int i = 0; i < 3; ++i) ft[i] = st[i] / (double)cn;
+        const double norm = sqrt(sq[0] * sq[0] + sq[1] * sq[1] + sq[2] * sq[2] + sq[3] * sq[3]);
+        for (int i = 0; i < 4; ++i) fq[i] = norm == 0.0 ? pq[i] : sq[i] / norm;
+    } else {
+        // component-wise median of t: every lane ranks its own value, ties by slot, and the middle rank(s) are read
+        for (int j = 0; j < 3; ++j) {
+            const double v = pt[j];
+            int rank = 0;
+            for (int d = 0; d < cn; ++d) {
+                const double vd = s_cand[w][d][j];
+                rank += (vd < v || (vd == v && d < lane)) ? 1 : 0;
+            }
+            const unsigned long long m_lo = __ballot(mine && rank == (cn - 1) / 2);
+            const unsigned long long m_hi = __ballot(mine && rank == cn / 2);
+            const double v_lo = __shfl(v, __ffsll((long long)m_lo) - 1);
+            const double v_hi = __shfl(v, __ffsll((long long)m_hi) - 1);
+            ft[j] = (cn & 1) ? v_lo : (v_lo + v_hi) / 2.0;
+        }
+        // medoid of q: lane c's sum of angles to the others in slot order, then the lexicographic minimum of (sum, c)
+        double sum = __builtin_inf();
+        int best = lane;
+        if (mine) {
+            sum = 0.0;
+            for (int d = 0; d < cn; ++d)
+                if (d != lane) sum = sum + quat_angle(pq, &s_cand[w][d][3]);
+        }
+        for (int off = 32; off > 0; off >>= 1) {
+            const double so = __shfl_xor(sum, off);
+            const int bo = __shfl_xor(best, off);
+            if (so < sum || (so == sum && bo < best)) {
+                sum = so;
+                best = bo;
+            }
+        }
+        if (lane != 0) return;
+        for (int i = 0; i < 4; ++i) fq[i] = s_cand[w][best][3 + i];
+    }
+    store_row(a.out + gi * 16, ft, fq, tt, tq, trans_dist(ft, tt), quat_angle(fq, tq));
+}
+
 inline bool misaligned(const void* p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
 
 }  // namespace
@@ -196,5 +426,55 @@ extern "C" int rpg_query_pose_f64(const float* rel_pose, const int64_t* edge_src
     const unsigned grid = (unsigned)((g + QP_NT / 64 - 1) / (QP_NT / 64));
     hipLaunchKernelGGL(query_pose_kernel, dim3(grid), dim3(QP_NT), 0, rpg::as_stream(stream), a);
     RPG_CHECK_LAUNCH("query_pose");
+    return RPG_OK;
+}
+
+extern "C" int rpg_query_pose_fused_f64(const float* rel_pose, const int64_t* edge_src, const int64_t* edge_dst, int64_t e,
+                                        const int64_t* node_first, const int64_t* edge_first, int g, const float* node_targets,
+                                        int64_t n, const float* map_poses, int64_t m, const int64_t* neighbours, int k,
+                                        const float* query_targets, double pose_m0, double pose_m1, double pose_m2,
+                                        double pose_s0, double pose_s1, double pose_s2, int fuse, int max_edges, double* out,
+                                        double* cand, int32_t* count, int32_t* status, void* stream) {
+    if (!rel_pose || !edge_src || !edge_dst || !out || !status || e < 1 || g < 1) return RPG_ERR_BAD_ARG;
+    if ((fuse != QF_MEAN && fuse != QF_MEDIAN) || max_edges < 1 || max_edges > QF_MAX) return RPG_ERR_BAD_ARG;
+    if ((node_targets == nullptr) == (map_poses == nullptr)) return RPG_ERR_BAD_ARG;      // one source of poses, not both
+    if (node_targets) {
+        if (!node_first || n < 1 || neighbours || query_targets) return RPG_ERR_BAD_ARG;
+    } else {
+        if (node_first || !neighbours || m < 1 || k < 1) return RPG_ERR_BAD_ARG;
+    }
+    if (misaligned(rel_pose, 3) || misaligned(node_targets, 3) || misaligned(map_poses, 3) || misaligned(query_targets, 3) ||
+        misaligned(edge_src, 7) || misaligned(edge_dst, 7) || misaligned(node_first, 7) || misaligned(edge_first, 7) ||
+        misaligned(neighbours, 7) || misaligned(status, 3) || misaligned(count, 3) || !rpg::aligned16(out) ||
+        (cand && !rpg::aligned16(cand)))
+        return RPG_ERR_BAD_ARG;
+    QfArgs f;
+    QpArgs& a = f.q;
+    a.rel_pose = rel_pose;
+    a.edge_src = edge_src;
+    a.edge_dst = edge_dst;
+    a.e = e;
+    a.node_first = node_first;
+    a.edge_first = edge_first;
+    a.g = g;
+    a.node_targets = node_targets;
+    a.n = n;
+    a.map_poses = map_poses;
+    a.m = m;
+    a.neighbours = neighbours;
+    a.k = k;
+    a.query_targets = query_targets;
+    a.pose_m[0] = pose_m0, a.pose_m[1] = pose_m1, a.pose_m[2] = pose_m2;
+    a.pose_s[0] = pose_s0, a.pose_s[1] = pose_s1, a.pose_s[2] = pose_s2;
+    a.ref_node = 0;
+    a.out = out;
+    a.status = status;
+    f.fuse = fuse;
+    f.max_edges = max_edges;
+    f.cand = cand;
+    f.count = count;
+    const unsigned grid = (unsigned)((g + QP_NT / 64 - 1) / (QP_NT / 64));
+    hipLaunchKernelGGL(query_pose_fused_kernel, dim3(grid), dim3(QP_NT), 0, rpg::as_stream(stream), f);
+    RPG_CHECK_LAUNCH("query_pose_fused");
     return RPG_OK;
 }

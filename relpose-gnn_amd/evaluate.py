@@ -57,6 +57,94 @@ def query_pose(rel_pose: np.ndarray, target: np.ndarray, edges: np.ndarray, pose
     return pred, targ
 
 
+FUSE_MODES = ("mean", "median")
+_NO_EDGE = "graph has no edge into node 0: cannot derive the query pose"       # reference_edge's message
+
+
+def pose_candidates(rel_pose: np.ndarray, target: np.ndarray, edges: np.ndarray, pose_m, pose_s, max_edges: int = 64):
+    """Every usable edge into node 0 of ONE graph as an estimate of the query's pose: -> (cands [C, 7], targ [7], count).  Usable:
+    target 0 and a source that is not node 0 (a self-edge would carry the query's own target into its estimate); used: the first
+    ``max_edges`` of them in column order; ``count``: how many there were before that cut.  Row c is ``query_pose`` over used
+    edge c -- on a graph without self-edges ``query_pose(..., ref_node=c)``, bit for bit.  ValueError (``reference_edge``'s) for a
+    graph without a usable edge or with a used edge whose source is not one of its nodes."""
+    rel_pose, target, edges = np.asarray(rel_pose, dtype=np.float64), np.asarray(target, dtype=np.float64), np.asarray(edges)
+    hits = np.flatnonzero((edges[1] == 0) & (edges[0] != 0))
+    if hits.size == 0:
+        raise ValueError(_NO_EDGE)
+    used = hits[:max_edges]
+    src = edges[0, used]
+    if ((src < 0) | (src >= target.shape[0])).any():
+        raise ValueError(_NO_EDGE + " (a used edge's source lies outside the graph)")
+    cands = []
+    for c, s in zip(used, src):
+        out = target[s] - rel_pose[c]
+        cands.append(np.hstack((out[:3] * pose_s + pose_m, qexp(out[3:]))))
+    targ = np.hstack((target[0, :3] * pose_s + pose_m, qexp(target[0, 3:])))
+    return np.stack(cands), targ, int(hits.size)
+
+
+def medoid_angle_sums(q: np.ndarray) -> np.ndarray:
+    """[C]: for every quaternion of q [C, 4] the sum of its angular errors to the others, added up in row order."""
+    c = q.shape[0]
+    sums = np.zeros(c)
+    for i in range(c):
+        acc = 0.0                                       # (an explicit loop: the order of the additions is part of the rule)
+        for d in range(c):
+            if d != i:
+                acc = acc + quaternion_angular_error(q[i], q[d])
+        sums[i] = acc
+    return sums
+
+
+def fuse_poses(cands: np.ndarray, fuse: str) -> np.ndarray:
+    """cands [C, 7] = (t, q) -> the one pose [7] (float64; every sum in row order).
+    ``"mean"``: t = (t_0 + .. + t_{C-1}) / C; q = S / |S| with S the sum of q_c where <q_c, q_0> >= 0 and of -q_c elsewhere (q and
+    -q are one rotation), q_0 where |S| = 0.  ``"median"``: the component-wise median of t (``np.median``: the mean of the two
+    middle values for even C) and the medoid q_c*, c* the lowest c that minimises ``medoid_angle_sums``.
+    One candidate is returned as it is.  Two or more of which one has a non-finite component give NaN in every component, so
+    that neither mode depends on how NaN orders."""
+    if fuse not in FUSE_MODES:
+        raise ValueError(f"fuse must be 'mean' or 'median', got {fuse!r}")
+    cands = np.asarray(cands, dtype=np.float64)
+    c = cands.shape[0]
+    if c == 1:
+        return cands[0].copy()
+    if not np.isfinite(cands).all():
+        return np.full(7, np.nan)
+    t, q = cands[:, :3], cands[:, 3:]
+    if fuse == "median":
+        return np.hstack((np.median(t, axis=0), q[int(np.argmin(medoid_angle_sums(q)))]))      # argmin: the first of equals
+    st, sq = np.zeros(3), np.zeros(4)
+    for d in range(c):
+        st = st + t[d]
+        dot = q[d, 0] * q[0, 0] + q[d, 1] * q[0, 1] + q[d, 2] * q[0, 2] + q[d, 3] * q[0, 3]
+        sq = sq + q[d] if dot >= 0.0 else sq - q[d]
+    norm = np.sqrt(sq[0] * sq[0] + sq[1] * sq[1] + sq[2] * sq[2] + sq[3] * sq[3])
+    return np.hstack((st / c, q[0] if norm == 0.0 else sq / norm))
+
+
+def fused_query_pose(rel_pose: np.ndarray, target: np.ndarray, edges: np.ndarray, pose_m, pose_s, fuse: str, max_edges: int = 64):
+    """(pred[7], targ[7]) of the query node of ONE graph from ALL its usable reference edges (``pose_candidates``) combined by
+    ``fuse_poses``: ``query_pose`` keeps one of these estimates, this is the rule that uses them all.  The host path of
+    ``fuse=`` in the two streams and the statement the device kernel (rpg_query_pose_fused_f64) is held to."""
+    cands, targ, _ = pose_candidates(rel_pose, target, edges, pose_m, pose_s, max_edges)
+    return fuse_poses(cands, fuse), targ
+
+
+def fused_query_row(rel_pose, target, edges, pose_m, pose_s, fuse: str, max_edges: int = 64) -> np.ndarray:
+    """The device rule's row of 16 = pred[7], targ[7], translation error, rotation error for ONE graph.  The errors are
+    ``errors`` of the fused pose, except that a pose voided by a non-finite candidate (two or more candidates) has NaN for both
+    -- the rotation error of a NaN quaternion would be 360 by the reference's clamp."""
+    cands, targ, _ = pose_candidates(rel_pose, target, edges, pose_m, pose_s, max_edges)
+    pred = fuse_poses(cands, fuse)
+    with np.errstate(invalid="ignore"):
+        r = errors(pred[None], targ[None])
+    t_err, q_err = r.t_loss[0], r.q_loss[0]
+    if cands.shape[0] > 1 and np.isnan(pred).any():
+        t_err = q_err = np.nan
+    return np.hstack((pred, targ, t_err, q_err))
+
+
 @dataclass
 class EvalResult:
     pred_poses: np.ndarray      # [G, 7]
@@ -85,17 +173,25 @@ def errors(pred_poses: np.ndarray, targ_poses: np.ndarray) -> EvalResult:
 
 class _PoseRows:
     """What a stream collects micro-batch by micro-batch, and the result made of it: the [G, 16] blocks of the device pose
-    rule (``on_device``), or the (pred, targ) rows of the host rule of test.py:213-251."""
+    rule (``on_device``), or the (pred, targ) rows of the host rule of test.py:213-251.  With ``fuse`` the host rule is
+    ``fused_query_row`` and collects the same [G, 16] blocks as the device."""
 
-    def __init__(self, pose_m, pose_s, ref_node: int, on_device: bool):
+    def __init__(self, pose_m, pose_s, ref_node: int, on_device: bool, fuse=None, max_edges: int = 64):
         self.pose_m, self.pose_s = np.asarray(pose_m, dtype=np.float64), np.asarray(pose_s, dtype=np.float64)
         self.ref_node = ref_node
-        self.rows: Optional[List[np.ndarray]] = [] if on_device else None
+        self.fuse, self.max_edges = fuse, max_edges
+        self.rows: Optional[List[np.ndarray]] = [] if on_device or fuse is not None else None
         self.preds: List[np.ndarray] = []
         self.targs: List[np.ndarray] = []
 
     def add(self, rel: np.ndarray, targets: Iterable, cut: Iterable) -> None:
         """The host rule over one micro-batch: per graph its targets [n, 6] and its (columns of ``rel``, local edge list)."""
+        if self.fuse is not None:
+            rows = [fused_query_row(rel[cols], target, edges, self.pose_m, self.pose_s, self.fuse, self.max_edges)
+                    for target, (cols, edges) in zip(targets, cut)]
+            if rows:
+                self.rows.append(np.stack(rows))
+            return
         for target, (cols, edges) in zip(targets, cut):
             p, t = query_pose(rel[cols], target, edges, self.pose_m, self.pose_s, self.ref_node)
             self.preds.append(p)
@@ -121,7 +217,8 @@ class _PoseRows:
 @torch.no_grad()
 def evaluate_stream(model, graphs: Sequence[Data], device, micro_batch: int = 64, pose_m=(0.0, 0.0, 0.0),
                     pose_s=(1.0, 1.0, 1.0), ref_node: int = 0, rank: int = 0, world: int = 1,
-                    stats: Optional[dict] = None, bf16_input: Optional[bool] = None, postprocess: str = "host") -> EvalResult:
+                    stats: Optional[dict] = None, bf16_input: Optional[bool] = None, postprocess: str = "host",
+                    fuse: Optional[str] = None, max_edges: int = 64) -> EvalResult:
     """Run ``model`` over a stream of single-graph ``Data`` objects (x, edge_index, y) and post-process like test.py.
     With world > 1 every rank evaluates its contiguous block (shard_range) and the [G,7] rows are all-gathered.
 
@@ -146,9 +243,15 @@ def evaluate_stream(model, graphs: Sequence[Data], device, micro_batch: int = 64
     applies the pose rule of test.py:213-267 in numpy, graph by graph.  ``"device"`` (GPU only) runs it as one kernel behind the
     forward (``query_pose.QueryPose``: float64 on the fp32 outputs, the targets ``y`` taken as fp32) and copies 16 doubles per
     graph back; the ``EvalResult`` is filled from those rows (under ``world > 1`` the gathered poses go through ``errors`` as
-    before).  ``stats`` also receives ``postprocess`` and ``d2h_bytes`` (the payload copied back)."""
+    before).  ``stats`` also receives ``postprocess`` and ``d2h_bytes`` (the payload copied back).
+
+    ``fuse``: None (default) derives the query's pose from the ``ref_node``-th edge into it, as the reference does.  ``"mean"``
+    / ``"median"`` combine the estimates of ALL the edges into it (the first ``max_edges`` <= 64 in column order, self-edges
+    skipped; ``fused_query_pose``): with ``postprocess="host"`` in numpy, with ``"device"`` in the fused kernel
+    (``QueryPose(fuse=...)``), still 16 doubles per graph back.  ``ref_node`` must stay 0 then."""
     from .shard import rank_host_slice
     _check_postprocess("evaluate_stream", postprocess, device)
+    _check_fuse("evaluate_stream", fuse, max_edges, ref_node)
     if world > 1 and torch.device(device).type == "cuda":
         # one process per GPU on a shared host: this rank's staging threads and pinned buffers stay on its share of the
         # cores / its GPU's NUMA node for the duration of the call (shard.rank_host_slice puts the caller's mask back on
@@ -157,8 +260,9 @@ def evaluate_stream(model, graphs: Sequence[Data], device, micro_batch: int = 64
         local_world = int(os.environ.get("LOCAL_WORLD_SIZE", world))
         with rank_host_slice(int(os.environ.get("LOCAL_RANK", rank)), local_world, torch.device(device).index):
             return _evaluate_stream(model, graphs, device, micro_batch, pose_m, pose_s, ref_node, rank, world, stats, bf16_input, local_world,
-                                    postprocess)
-    return _evaluate_stream(model, graphs, device, micro_batch, pose_m, pose_s, ref_node, rank, world, stats, bf16_input, 1, postprocess)
+                                    postprocess, fuse, max_edges)
+    return _evaluate_stream(model, graphs, device, micro_batch, pose_m, pose_s, ref_node, rank, world, stats, bf16_input, 1, postprocess,
+                            fuse, max_edges)
 
 
 def _check_postprocess(who: str, postprocess, device) -> None:
@@ -168,20 +272,32 @@ def _check_postprocess(who: str, postprocess, device) -> None:
         raise ValueError(f"{who}: postprocess='device' runs the pose rule on the GPU, the stream's device is {device}")
 
 
+def _check_fuse(who: str, fuse, max_edges, ref_node) -> None:
+    if fuse is None:
+        return
+    if fuse not in FUSE_MODES:
+        raise ValueError(f"{who}: fuse must be None, 'mean' or 'median', got {fuse!r}")
+    if isinstance(max_edges, bool) or not isinstance(max_edges, (int, np.integer)) or not 1 <= max_edges <= 64:
+        raise ValueError(f"{who}: max_edges must be an int in 1..64, got {max_edges!r}")
+    if ref_node != 0:
+        raise ValueError(f"{who}: fuse={fuse!r} combines every edge into the query node, ref_node={ref_node} selects one: give "
+                         "one of the two")
+
+
 def _result_from_rows(rows: np.ndarray) -> EvalResult:
     """EvalResult of the device pose rule's rows [G, 16] = pred[7], targ[7], t_err, q_err."""
     return EvalResult(np.ascontiguousarray(rows[:, :7]), np.ascontiguousarray(rows[:, 7:14]), rows[:, 14].copy(), rows[:, 15].copy())
 
 
 def _evaluate_stream(model, graphs, device, micro_batch, pose_m, pose_s, ref_node, rank, world, stats, bf16_input, local_world,
-                     postprocess="host"):
+                     postprocess="host", fuse=None, max_edges=64):
     from .shard import gather_rows, shard_counts, shard_range
     qp = None
     if postprocess == "device":
         from .query_pose import QueryPose
-        qp = QueryPose(pose_m, pose_s, ref_node)
+        qp = QueryPose(pose_m, pose_s, ref_node, fuse=fuse, max_edges=max_edges)
     lo, hi = shard_range(len(graphs), rank, world)
-    acc = _PoseRows(pose_m, pose_s, ref_node, on_device=qp is not None)
+    acc = _PoseRows(pose_m, pose_s, ref_node, on_device=qp is not None, fuse=fuse, max_edges=max_edges)
     runner = _MicroBatchRunner(model, device, micro_batch, bf16_input, local_world, pose=qp)
 
     def finish(item):
@@ -244,7 +360,7 @@ def load_pose_stats(path):
 def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch: int = 64, pose_m=(0.0, 0.0, 0.0),
                pose_s=(1.0, 1.0, 1.0), ref_node: int = 0, stats: Optional[dict] = None, targets=None,
                bf16_input: Optional[bool] = None, *, rule=None, query_descriptors=None, query_groups=None,
-               postprocess: str = "host"):
+               postprocess: str = "host", fuse: Optional[str] = None, max_edges: int = 64):
     """The evaluation stream of the map path (``PoseNetX_R2.forward_map``): query g's graph is the query followed by the map
     rows ``neighbours[g]`` (its retrieved database images, dataset_7Scenes_multi.py:340-345).  Single process.
 
@@ -268,7 +384,10 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
     (``query_pose.QueryPose.from_map`` on the map's poses and the device neighbours -- with a rule the rows ``forward_map`` has
     just chosen -- and on ``targets``, staged once as fp32), and 16 doubles per query come back instead of the absolute and
     relative poses and a model-built edge list.  Same return types; a map without poses returns its raw tensors either way.
-    ``stats`` also receives ``postprocess`` and ``d2h_bytes``."""
+    ``stats`` also receives ``postprocess`` and ``d2h_bytes``.
+
+    ``fuse`` (None, ``"mean"``, ``"median"``) and ``max_edges``: as in ``evaluate_stream`` -- one pose per query from the
+    estimates of all its K database images instead of the ``ref_node``-th one, on the host or on the device."""
     device = fmap.device
     if not torch.is_tensor(queries):
         raise TypeError("relocalize: queries must be a tensor [G, ...]")
@@ -279,6 +398,7 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
     if micro_batch < 1:
         raise ValueError("relocalize: micro_batch must be >= 1")
     _check_postprocess("relocalize", postprocess, device)
+    _check_fuse("relocalize", fuse, max_edges, ref_node)
     qd_all = qg_all = None
     if rule is None:
         nb = torch.as_tensor(neighbours)
@@ -310,13 +430,14 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
     qp = targ_dev = fc_first = None
     if postprocess == "device" and poses_h is not None:
         from .query_pose import QueryPose
-        qp = QueryPose(np.asarray(pose_m, dtype=np.float64), np.asarray(pose_s, dtype=np.float64), ref_node)
+        qp = QueryPose(np.asarray(pose_m, dtype=np.float64), np.asarray(pose_s, dtype=np.float64), ref_node, fuse=fuse,
+                       max_edges=max_edges)
         if targets is not None:
             t32 = torch.as_tensor(targets).detach().to(dtype=torch.float32).reshape(g_all, 6)
             targ_dev = t32 if t32.is_cuda else (t32 if t32.is_pinned() else t32.pin_memory()).to(device, non_blocking=True)
         if model.knn <= 0:         # forward_map's own FC list: n (n - 1) columns per graph, graph after graph
             fc_first = torch.arange(min(micro_batch, g_all) + 1, dtype=torch.int64, device=device) * fc_edges.shape[1]
-    acc = _PoseRows(pose_m, pose_s, ref_node, on_device=qp is not None)
+    acc = _PoseRows(pose_m, pose_s, ref_node, on_device=qp is not None, fuse=fuse, max_edges=max_edges)
     raw_abs, raw_rel = [], []
 
     def forward(chunk, x):

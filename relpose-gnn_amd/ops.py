@@ -523,16 +523,16 @@ def retrieve(q: torch.Tensor, db: torch.Tensor, ranks, db_inv_norm: Optional[tor
     return (nbrs, sims) if return_sims else nbrs
 
 
-def _qp_tensor(t, name: str, dtype, shape) -> torch.Tensor:
-    """Host-side check of one ``query_pose`` argument: TypeError for a non-tensor / wrong dtype, ValueError for a wrong shape
-    (``shape``: ints, or None for an axis that is free)."""
+def _qp_tensor(t, name: str, dtype, shape, who: str = "query_pose") -> torch.Tensor:
+    """Host-side check of one ``query_pose`` / ``query_pose_fused`` argument: TypeError for a non-tensor / wrong dtype, ValueError
+    for a wrong shape (``shape``: ints, or None for an axis that is free)."""
     if not torch.is_tensor(t):
-        raise TypeError(f"query_pose: {name} must be a tensor, got {type(t).__name__}")
+        raise TypeError(f"{who}: {name} must be a tensor, got {type(t).__name__}")
     if t.dtype != dtype:
-        raise TypeError(f"query_pose: {name} must be {dtype}, got {t.dtype}")
+        raise TypeError(f"{who}: {name} must be {dtype}, got {t.dtype}")
     if t.dim() != len(shape) or any(s is not None and int(d) != s for d, s in zip(t.shape, shape)):
         want = ", ".join("*" if s is None else str(s) for s in shape)
-        raise ValueError(f"query_pose: {name} must be [{want}], got {tuple(t.shape)}")
+        raise ValueError(f"{who}: {name} must be [{want}], got {tuple(t.shape)}")
     return t
 
 
@@ -573,63 +573,14 @@ def query_pose(rel_pose: torch.Tensor, edge_index: torch.Tensor, *, node_first: 
     NaN and one count in ``status`` (int32 device tensor, accumulates) -- with ``status=None`` the count is read back here (one
     synchronisation) and a non-zero count raises the ValueError of ``evaluate.reference_edge``.  Every argument is checked on
     the host before anything is launched: TypeError for a wrong type or dtype, ValueError for a wrong shape or device."""
-    rel = _qp_tensor(rel_pose, "rel_pose", torch.float32, (None, 6))
-    e = int(rel.shape[0])
-    ei = _qp_tensor(edge_index, "edge_index", torch.int64, (2, e))
-    if e < 1:
-        raise ValueError("query_pose: needs at least one edge")
+    rel, ei, e, g, (n, m, k), by_name, out, status, own = _qp_graphs(
+        "query_pose", rel_pose, edge_index, node_first, node_targets, map_poses, neighbours, query_targets, edge_first, status, out)
     pm, ps = _qp_triple(pose_m, "pose_m"), _qp_triple(pose_s, "pose_s")
     ref_node = _qp_ref_node(ref_node)
-    if (node_targets is None) == (map_poses is None):
-        raise ValueError("query_pose: give node_first + node_targets (the collated targets) or map_poses + neighbours (the map "
-                         "form): exactly one of the two")
-    n = m = k = 0
-    if node_targets is not None:
-        if neighbours is not None or query_targets is not None:
-            raise ValueError("query_pose: neighbours / query_targets belong to the map form (map_poses)")
-        if node_first is None:
-            raise ValueError("query_pose: node_targets needs node_first [G + 1]")
-        nf = _qp_tensor(node_first, "node_first", torch.int64, (None,))
-        g = int(nf.shape[0]) - 1
-        nt = _qp_tensor(node_targets, "node_targets", torch.float32, (None, 6))
-        n = int(nt.shape[0])
-        if n < 1:
-            raise ValueError("query_pose: node_targets is empty")
-        parts = [("node_first", nf), ("node_targets", nt)]
-    else:
-        if node_first is not None:
-            raise ValueError("query_pose: node_first belongs to the targets form (graph g of the map form owns nodes g (K + 1) ..)")
-        if neighbours is None:
-            raise ValueError("query_pose: map_poses needs neighbours [G, K]")
-        nb = _qp_tensor(neighbours, "neighbours", torch.int64, (None, None))
-        g, k = int(nb.shape[0]), int(nb.shape[1])
-        mp = _qp_tensor(map_poses, "map_poses", torch.float32, (None, 6))
-        m = int(mp.shape[0])
-        if k < 1 or m < 1:
-            raise ValueError(f"query_pose: needs K >= 1 neighbours per query and M >= 1 map rows (K={k}, M={m})")
-        parts = [("map_poses", mp), ("neighbours", nb)]
-        if query_targets is not None:
-            parts.append(("query_targets", _qp_tensor(query_targets, "query_targets", torch.float32, (g, 6))))
-    if g < 1:
-        raise ValueError("query_pose: no graphs")
-    if edge_first is not None:
-        parts.append(("edge_first", _qp_tensor(edge_first, "edge_first", torch.int64, (g + 1,))))
-    if out is not None:
-        _qp_tensor(out, "out", torch.float64, (g, 16))
-        if not out.is_contiguous():
-            raise ValueError("query_pose: out must be contiguous")
-    dev = rel.device
-    status, own = _status_arg(status, dev, "query_pose", bad_dtype=TypeError)
-    if dev.type != "cuda":
-        raise ValueError(f"query_pose: rel_pose must be on the GPU (the HIP kernel is the only compute path), got {dev}")
-    for name, t in [("edge_index", ei)] + parts + [("out", out)]:
-        if t is not None and t.device != dev:
-            raise ValueError(f"query_pose: {name} is on {t.device}, rel_pose on {dev}: everything must be on the same GPU")
-
+    _qp_on_one_gpu("query_pose", rel, ei, by_name, [("out", out)])
     rel, ei = rel.contiguous(), ei.contiguous()
-    by_name = {name: t.contiguous() for name, t in parts}
     if out is None:
-        out = torch.empty((g, 16), dtype=torch.float64, device=dev)
+        out = torch.empty((g, 16), dtype=torch.float64, device=rel.device)
     L.check(L.lib().rpg_query_pose_f64(_p(rel), ei.data_ptr(), ei.data_ptr() + 8 * e, e, _p(by_name.get("node_first")),
                                        _p(by_name.get("edge_first")), g, _p(by_name.get("node_targets")), n,
                                        _p(by_name.get("map_poses")), m, _p(by_name.get("neighbours")), k,
@@ -639,6 +590,126 @@ def query_pose(rel_pose: torch.Tensor, edge_index: torch.Tensor, *, node_first: 
     if bad:
         raise ValueError(f"graph has no edge into node 0: cannot derive the query pose ({bad} graph(s) of this call lack "
                          "the reference edge, or its source lies outside the graph)")
+    return out
+
+
+def _qp_graphs(who, rel_pose, edge_index, node_first, node_targets, map_poses, neighbours, query_targets, edge_first, status, out):
+    """The checks ``query_pose`` and ``query_pose_fused`` share: the forward's output, the two forms of the graphs, ``out`` and
+    ``status``.  -> (rel, ei, E, G, (N, M, K), the form's tensors by
+    name -- still as given --, out, status, whether the status word is this call's own)."""
+    rel = _qp_tensor(rel_pose, "rel_pose", torch.float32, (None, 6), who)
+    e = int(rel.shape[0])
+    ei = _qp_tensor(edge_index, "edge_index", torch.int64, (2, e), who)
+    if e < 1:
+        raise ValueError(f"{who}: needs at least one edge")
+    if (node_targets is None) == (map_poses is None):
+        raise ValueError(f"{who}: give node_first + node_targets (the collated targets) or map_poses + neighbours (the map "
+                         "form): exactly one of the two")
+    n = m = k = 0
+    if node_targets is not None:
+        if neighbours is not None or query_targets is not None:
+            raise ValueError(f"{who}: neighbours / query_targets belong to the map form (map_poses)")
+        if node_first is None:
+            raise ValueError(f"{who}: node_targets needs node_first [G + 1]")
+        nf = _qp_tensor(node_first, "node_first", torch.int64, (None,), who)
+        g = int(nf.shape[0]) - 1
+        nt = _qp_tensor(node_targets, "node_targets", torch.float32, (None, 6), who)
+        n = int(nt.shape[0])
+        if n < 1:
+            raise ValueError(f"{who}: node_targets is empty")
+        parts = [("node_first", nf), ("node_targets", nt)]
+    else:
+        if node_first is not None:
+            raise ValueError(f"{who}: node_first belongs to the targets form (graph g of the map form owns nodes g (K + 1) ..)")
+        if neighbours is None:
+            raise ValueError(f"{who}: map_poses needs neighbours [G, K]")
+        nb = _qp_tensor(neighbours, "neighbours", torch.int64, (None, None), who)
+        g, k = int(nb.shape[0]), int(nb.shape[1])
+        mp = _qp_tensor(map_poses, "map_poses", torch.float32, (None, 6), who)
+        m = int(mp.shape[0])
+        if k < 1 or m < 1:
+            raise ValueError(f"{who}: needs K >= 1 neighbours per query and M >= 1 map rows (K={k}, M={m})")
+        parts = [("map_poses", mp), ("neighbours", nb)]
+        if query_targets is not None:
+            parts.append(("query_targets", _qp_tensor(query_targets, "query_targets", torch.float32, (g, 6), who)))
+    if g < 1:
+        raise ValueError(f"{who}: no graphs")
+    if edge_first is not None:
+        parts.append(("edge_first", _qp_tensor(edge_first, "edge_first", torch.int64, (g + 1,), who)))
+    if out is not None:
+        _qp_tensor(out, "out", torch.float64, (g, 16), who)
+        if not out.is_contiguous():
+            raise ValueError(f"{who}: out must be contiguous")
+    status, own = _status_arg(status, rel.device, who, bad_dtype=TypeError)
+    return rel, ei, e, g, (n, m, k), dict(parts), out, status, own
+
+
+def _qp_on_one_gpu(who, rel, ei, by_name, outputs) -> None:
+    """Everything on rel_pose's GPU; then the inputs made contiguous in place of the given ones (``by_name`` is updated)."""
+    dev = rel.device
+    if dev.type != "cuda":
+        raise ValueError(f"{who}: rel_pose must be on the GPU (the HIP kernel is the only compute path), got {dev}")
+    for name, t in [("edge_index", ei)] + list(by_name.items()) + list(outputs):
+        if t is not None and t.device != dev:
+            raise ValueError(f"{who}: {name} is on {t.device}, rel_pose on {dev}: everything must be on the same GPU")
+    for name in by_name:
+        by_name[name] = by_name[name].contiguous()
+
+
+FUSE_MODES = ("mean", "median")            # the C entry point's `fuse` is the index
+
+
+def _qp_fuse(fuse, max_edges, who: str = "query_pose_fused"):
+    if fuse not in FUSE_MODES:
+        raise ValueError(f"{who}: fuse must be 'mean' or 'median', got {fuse!r}")
+    if isinstance(max_edges, bool) or not isinstance(max_edges, numbers.Integral):
+        raise TypeError(f"{who}: max_edges must be an int, got {type(max_edges).__name__}")
+    if not 1 <= max_edges <= 64:
+        raise ValueError(f"{who}: max_edges must be in 1..64 (one candidate per lane of a wave), got {max_edges}")
+    return FUSE_MODES.index(fuse), int(max_edges)
+
+
+def query_pose_fused(rel_pose: torch.Tensor, edge_index: torch.Tensor, *, fuse: str, max_edges: int = 64,
+                     node_first: Optional[torch.Tensor] = None, node_targets: Optional[torch.Tensor] = None,
+                     map_poses: Optional[torch.Tensor] = None, neighbours: Optional[torch.Tensor] = None,
+                     query_targets: Optional[torch.Tensor] = None, edge_first: Optional[torch.Tensor] = None,
+                     pose_m=(0.0, 0.0, 0.0), pose_s=(1.0, 1.0, 1.0), status: Optional[torch.Tensor] = None,
+                     out: Optional[torch.Tensor] = None, candidates: Optional[torch.Tensor] = None,
+                     counts: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``query_pose`` over ALL the edges into every graph's query node (rpg_query_pose_fused_f64; evaluate.fused_query_pose on
+    the device): each such edge whose source is not the query itself is one estimate of the query's pose, the first
+    ``max_edges`` (1..64) of them in column order are combined by ``fuse`` -- ``"mean"`` (mean translation, sign-aligned
+    normalised quaternion sum) or ``"median"`` (component-wise median translation, medoid quaternion) -- and the row's errors are
+    those of the fused pose.  The graphs' two forms, ``edge_first``, ``status``, ``out`` and the row layout are ``query_pose``'s.
+
+    ``candidates`` float64 [G, max_edges, 16] (optional output): used candidate c as a full row, NaN past the graph's count;
+    ``counts`` int32 [G] (optional output): the usable edges found before the cut at ``max_edges``.  A graph without a usable
+    edge, or with a used edge whose source lies outside the graph, gets a NaN row and one count in ``status``."""
+    who = "query_pose_fused"
+    rel, ei, e, g, (n, m, k), by_name, out, status, own = _qp_graphs(
+        who, rel_pose, edge_index, node_first, node_targets, map_poses, neighbours, query_targets, edge_first, status, out)
+    pm, ps = _qp_triple(pose_m, "pose_m"), _qp_triple(pose_s, "pose_s")
+    mode, max_edges = _qp_fuse(fuse, max_edges)
+    if candidates is not None:
+        _qp_tensor(candidates, "candidates", torch.float64, (g, max_edges, 16), who)
+    if counts is not None:
+        _qp_tensor(counts, "counts", torch.int32, (g,), who)
+    for name, t in (("candidates", candidates), ("counts", counts)):
+        if t is not None and not t.is_contiguous():
+            raise ValueError(f"{who}: {name} must be contiguous")
+    _qp_on_one_gpu(who, rel, ei, by_name, [("out", out), ("candidates", candidates), ("counts", counts)])
+    rel, ei = rel.contiguous(), ei.contiguous()
+    if out is None:
+        out = torch.empty((g, 16), dtype=torch.float64, device=rel.device)
+    L.check(L.lib().rpg_query_pose_fused_f64(_p(rel), ei.data_ptr(), ei.data_ptr() + 8 * e, e, _p(by_name.get("node_first")),
+                                             _p(by_name.get("edge_first")), g, _p(by_name.get("node_targets")), n,
+                                             _p(by_name.get("map_poses")), m, _p(by_name.get("neighbours")), k,
+                                             _p(by_name.get("query_targets")), *pm, *ps, mode, max_edges, _p(out),
+                                             _p(candidates), _p(counts), status.data_ptr(), _stream()), who)
+    bad = _own_count(status, own)
+    if bad:
+        raise ValueError(f"graph has no edge into node 0: cannot derive the query pose ({bad} graph(s) of this call have no "
+                         "usable edge into their query node, or a used edge's source lies outside the graph)")
     return out
 
 

@@ -11,6 +11,11 @@ evaluated: its row is NaN and it is counted in a status word this object owns.  
 ``ValueError`` of ``evaluate.reference_edge``.  The status word is a ``status.DeferredCounters`` with one counter, the class
 behind ``PoseNetX_R2.check_edge_index`` too: the count travels to pinned host memory with an asynchronous copy behind every
 call, so nothing blocks unless the caller asks it to.
+
+``QueryPose(fuse="mean" | "median")`` keeps none of the edges into the query node to itself: every one of them (whose source is
+not the query) is an estimate of the query's pose, and the row holds their combination (``ops.query_pose_fused``,
+rpg_query_pose_fused_f64; ``evaluate.fused_query_pose`` is the rule in numpy).  Same row layout, same status word, same
+``publish`` / ``check`` contract; a bad graph is then one without a usable edge or with a used edge from outside the graph.
 """
 from __future__ import annotations
 
@@ -21,44 +26,66 @@ from .status import DeferredCounters
 
 
 class QueryPose:
-    def __init__(self, pose_m=(0.0, 0.0, 0.0), pose_s=(1.0, 1.0, 1.0), ref_node: int = 0):
+    def __init__(self, pose_m=(0.0, 0.0, 0.0), pose_s=(1.0, 1.0, 1.0), ref_node: int = 0, fuse=None, max_edges: int = 64):
         """``pose_m`` / ``pose_s``: translation mean / std (test.py:126-130, 248-251); ``ref_node``: which of the edges into the
-        query node is the reference edge (test.py:227-229)."""
+        query node is the reference edge (test.py:227-229).  ``fuse``: None (that one edge), or ``"mean"`` / ``"median"``: the
+        first ``max_edges`` (1..64) edges into the query node combined -- there is no reference edge then, so ``ref_node`` must
+        stay 0."""
         self.pose_m, self.pose_s = ops._qp_triple(pose_m, "pose_m"), ops._qp_triple(pose_s, "pose_s")
         self.ref_node = ops._qp_ref_node(ref_node)
+        self.fuse, self.max_edges = fuse, max_edges
+        if fuse is not None:
+            ops._qp_fuse(fuse, max_edges, "QueryPose")
+            if self.ref_node != 0:
+                raise ValueError(f"QueryPose: fuse={fuse!r} combines every edge into the query node, ref_node={ref_node} selects "
+                                 "one: give one of the two")
         self._bad = DeferredCounters(1, self._error)          # graphs that could not be evaluated
 
     # ---- the two forms ---------------------------------------------------------------------------------------------------
-    def from_targets(self, rel_pose, edge_index, node_first, node_targets, edge_first=None, out=None) -> torch.Tensor:
+    def from_targets(self, rel_pose, edge_index, node_first, node_targets, edge_first=None, out=None, candidates=None,
+                     counts=None) -> torch.Tensor:
         """Graphs with collated targets (``evaluate_stream``): ``node_first`` int64 [G + 1], ``node_targets`` fp32 [N, 6] =
-        the batch's ``data.y``.  -> float64 [G, 16] on the device."""
+        the batch's ``data.y``.  -> float64 [G, 16] on the device.  With ``fuse``, optional outputs: ``candidates`` float64
+        [G, max_edges, 16] (every used candidate as a row) and ``counts`` int32 [G] (usable edges before the cut)."""
         return self._run(rel_pose, dict(edge_index=edge_index, node_first=node_first, node_targets=node_targets,
-                                        edge_first=edge_first, out=out))
+                                        edge_first=edge_first, out=out), candidates, counts)
 
-    def from_map(self, rel_pose, edge_index, fmap, neighbours, query_targets=None, edge_first=None, out=None) -> torch.Tensor:
+    def from_map(self, rel_pose, edge_index, fmap, neighbours, query_targets=None, edge_first=None, out=None, candidates=None,
+                 counts=None) -> torch.Tensor:
         """Graphs of the map path (``forward_map`` / ``relocalize``): graph g is query g followed by the rows ``neighbours[g]``
         of ``fmap``, whose ``poses`` are the database images' targets; ``query_targets`` fp32 [G, 6] are the queries' own (None:
-        zeros, the rows' ``targ`` part and errors then mean nothing).  -> float64 [G, 16] on the device."""
+        zeros, the rows' ``targ`` part and errors then mean nothing).  -> float64 [G, 16] on the device.  ``candidates`` /
+        ``counts``: as in ``from_targets``."""
         poses = getattr(fmap, "poses", None)
         if poses is None:
             raise ValueError("QueryPose.from_map: the feature map holds no poses (build it with poses=...): a query's pose is "
                              "its database image's pose minus the predicted relative pose")
         return self._run(rel_pose, dict(edge_index=edge_index, map_poses=poses, neighbours=neighbours,
-                                        query_targets=query_targets, edge_first=edge_first, out=out))
+                                        query_targets=query_targets, edge_first=edge_first, out=out), candidates, counts)
 
-    def _run(self, rel_pose, kw) -> torch.Tensor:
+    def _run(self, rel_pose, kw, candidates=None, counts=None) -> torch.Tensor:
+        if self.fuse is None and (candidates is not None or counts is not None):
+            raise ValueError("QueryPose: candidates / counts are outputs of the fused rule (fuse='mean' or 'median')")
         if torch.is_tensor(rel_pose) and rel_pose.is_cuda:      # (anything else is refused by ops.query_pose below)
             status = self._bad.tensor(rel_pose.device)
         else:
             status = self._bad.counters
         if status is None:
             status = torch.zeros(1, dtype=torch.int32)          # placeholder for the host-side checks, which refuse the call
-        rows = ops.query_pose(rel_pose, pose_m=self.pose_m, pose_s=self.pose_s, ref_node=self.ref_node, status=status, **kw)
+        if self.fuse is None:
+            rows = ops.query_pose(rel_pose, pose_m=self.pose_m, pose_s=self.pose_s, ref_node=self.ref_node, status=status, **kw)
+        else:
+            rows = ops.query_pose_fused(rel_pose, fuse=self.fuse, max_edges=self.max_edges, pose_m=self.pose_m, pose_s=self.pose_s,
+                                        status=status, candidates=candidates, counts=counts, **kw)
         self._bad.publish()                       # the counter's copy to pinned memory, behind this call's kernel
         return rows
 
     # ---- bad graphs, without a host synchronisation (status.DeferredCounters) ----------------------------------------------
     def _error(self, counts: torch.Tensor) -> ValueError:
+        if self.fuse is not None:
+            return ValueError(f"graph has no edge into node 0: cannot derive the query pose ({int(counts[0])} graph(s) have no "
+                              "usable edge into their query node, or a used edge's source lies outside the graph; detected on "
+                              "the device, their rows are NaN)")
         return ValueError(f"graph has no edge into node 0: cannot derive the query pose ({int(counts[0])} graph(s) lack edge "
                           f"number {self.ref_node} into their query node, or its source lies outside the graph; detected on the "
                           "device, their rows are NaN)")

@@ -9,10 +9,14 @@ Every leg: one warm-up call, then ``--reps`` timed calls (wall clock around the 
 reported are the rates, their median and the spread (max - min) / median.  ``--baseline-root DIR`` also measures ``relocalize``
 as ANOTHER checkout of this package has it (the parent commit's tree, with its own built library), in a child process, called
 without the ``postprocess`` argument: the baseline the device mode is held against -- "not slower beyond the run-to-run spread".
+``--fuse mean,median`` adds, per mode, a row ``MODE+FUSE`` with the streams' ``fuse=`` argument (every edge into the query
+combined, not one: the fused kernel behind the forward for "device", the numpy rule for "host"), held against the same baseline;
+``--legs`` keeps only the named ``relocalize`` legs (and drops the ``evaluate_stream`` one).
 ``--only LEG`` runs one leg in one mode in a loop, for a profiler (``rocprofv3 --kernel-trace --stats -- python
 tools/postprocess_bench.py --only 256x341_bf16:device``), and prints the wall time of the timed loop to relate kernel time to.
 
-usage: tools/postprocess_bench.py [--reps 3] [--baseline-root DIR] [--out profiles/query_pose_bench.json]"""
+usage: tools/postprocess_bench.py [--reps 3] [--baseline-root DIR] [--out profiles/query_pose_bench.json]
+       tools/postprocess_bench.py --fuse mean,median --baseline-root DIR --out profiles/query_pose_fused_bench.json"""
 import argparse
 import json
 import os
@@ -60,6 +64,8 @@ def main():
     ap.add_argument("--root", default=None, help="the checkout whose package is measured (default: this one)")
     ap.add_argument("--modes", default="host,device", help="comma list of host, device, baseline (= no postprocess argument)")
     ap.add_argument("--baseline-root", default=None, help="another checkout (the parent commit, built) to measure as the baseline")
+    ap.add_argument("--fuse", default="", help="comma list of mean, median: also measure every mode with fuse= (rows MODE+FUSE)")
+    ap.add_argument("--legs", default=None, help="comma list of relocalize legs to keep, e.g. 256x341_bf16 (default: all four)")
     ap.add_argument("--only", default=None, help="LEG:MODE, e.g. 256x341_bf16:device -- that leg alone, for a profiler")
     ap.add_argument("--out", default=None, help="also write the JSON document to this file")
     args = ap.parse_args()
@@ -73,6 +79,8 @@ def main():
     from relpose_gnn_amd.resnet import resnet34
 
     modes = [m for m in args.modes.split(",") if m]
+    modes += [f"{m}+{f}" for f in args.fuse.split(",") if f for m in modes if m != "baseline"]
+    legs = args.legs.split(",") if args.legs else None
     only_leg, only_mode = (args.only.split(":") + [None])[:2] if args.only else (None, None)
     if only_mode:
         modes = [only_mode]
@@ -88,14 +96,17 @@ def main():
            "cpus": len(os.sched_getaffinity(0)), "relocalize": {}, "evaluate_stream": {}}
 
     def kw_of(mode):
-        return {} if mode == "baseline" else {"postprocess": mode}
+        if mode == "baseline":
+            return {}
+        mode, _, fuse = mode.partition("+")
+        return {"postprocess": mode, "fuse": fuse} if fuse else {"postprocess": mode}
 
     n = args.queries
     for prec in ("f32", "bf16"):
         m.encoder_dtype, m.gnn_dtype = prec, prec
         for h, w in GEOMS:
             key = f"{h}x{w}_{prec}"
-            if only_leg and only_leg != key:
+            if (only_leg and only_leg != key) or (legs and key not in legs):
                 continue
             m.input_img_height = h
             fmap = FeatureMap.build(m, torch.randn((MAP_ROWS, 3 * h * w), device=dev, generator=gen),
@@ -124,7 +135,7 @@ def main():
             torch.cuda.empty_cache()
 
     # evaluate_stream: all 8 images of a graph cross the host link (pinned, as the reference's loader delivers them)
-    if not only_leg and "baseline" not in modes:
+    if not only_leg and not legs and "baseline" not in modes:
         h, w = 256, 341
         m.input_img_height = h
         g_n = args.stream_graphs
@@ -135,7 +146,7 @@ def main():
         leg = {}
         for mode in modes:
             st = {}
-            leg[mode] = rates(lambda: evaluate_stream(m, graphs, dev, micro_batch=64, stats=st, postprocess=mode), g_n, args.reps)
+            leg[mode] = rates(lambda: evaluate_stream(m, graphs, dev, micro_batch=64, stats=st, **kw_of(mode)), g_n, args.reps)
             leg[mode]["d2h_bytes"] = st.get("d2h_bytes")
         doc["evaluate_stream"][f"{h}x{w}_bf16"] = leg
         del xs, graphs
@@ -144,7 +155,7 @@ def main():
     if args.baseline_root:
         # the parent commit's relocalize, on this box, in this visit: a fresh child process on the other checkout
         cmd = [sys.executable, os.path.abspath(__file__), "--root", os.path.abspath(args.baseline_root), "--modes", "baseline",
-               "--reps", str(args.reps), "--queries", str(args.queries)]
+               "--reps", str(args.reps), "--queries", str(args.queries)] + (["--legs", args.legs] if args.legs else [])
         res = subprocess.run(cmd, stdout=subprocess.PIPE, text=True, timeout=600)
         if res.returncode != 0:
             raise SystemExit(f"baseline run failed with exit status {res.returncode}")
@@ -159,6 +170,14 @@ def main():
                 spread = max(b["spread"], d["spread"])
                 verdict[key] = {"device_over_baseline": round(d["median"] / b["median"], 3), "spread": spread,
                                 "not_slower": bool(d["median"] >= b["median"] * (1.0 - spread))}
+            for mode, d in leg.items():                    # the fused rows: against the same baseline and against plain "device"
+                if mode.startswith("device+"):
+                    spread = max(b["spread"], d["spread"])
+                    v = {"over_baseline": round(d["median"] / b["median"], 3), "spread": spread,
+                         "not_slower": bool(d["median"] >= b["median"] * (1.0 - spread))}
+                    if "device" in leg:
+                        v["over_device"] = round(d["median"] / leg["device"]["median"], 3)
+                    verdict[f"{key}:{mode}"] = v
         doc["device_vs_baseline"] = verdict
     line = json.dumps(doc)
     print(line, flush=True)
