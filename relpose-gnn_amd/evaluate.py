@@ -360,7 +360,7 @@ def load_pose_stats(path):
 def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch: int = 64, pose_m=(0.0, 0.0, 0.0),
                pose_s=(1.0, 1.0, 1.0), ref_node: int = 0, stats: Optional[dict] = None, targets=None,
                bf16_input: Optional[bool] = None, *, rule=None, query_descriptors=None, query_groups=None,
-               postprocess: str = "host", fuse: Optional[str] = None, max_edges: int = 64):
+               postprocess: str = "host", fuse: Optional[str] = None, max_edges: int = 64, capture: bool = False):
     """The evaluation stream of the map path (``PoseNetX_R2.forward_map``): query g's graph is the query followed by the map
     rows ``neighbours[g]`` (its retrieved database images, dataset_7Scenes_multi.py:340-345).  Single process.
 
@@ -387,8 +387,18 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
     ``stats`` also receives ``postprocess`` and ``d2h_bytes``.
 
     ``fuse`` (None, ``"mean"``, ``"median"``) and ``max_edges``: as in ``evaluate_stream`` -- one pose per query from the
-    estimates of all its K database images instead of the ``ref_node``-th one, on the host or on the device."""
+    estimates of all its K database images instead of the ``ref_node``-th one, on the host or on the device.
+
+    ``capture=True`` (GPU map only): a micro-batch's device step -- ``forward_map`` with its retrieval, and the device pose rule
+    behind it -- is captured into a HIP graph once per shape (``graphed.GraphedForwardMap``: the full micro-batch and a ragged
+    tail) and replayed with one launch per micro-batch instead of ~137.  Same kernels, same launch geometry, same order: the
+    results are bit-identical to ``capture=False``.  The captured steps are kept on the model (``refresh_packed`` drops them; a
+    step whose map has been extended is captured again), so a second call with the same shapes captures nothing.  What that
+    class refuses (``droprate > 0``, ``knn > 0``, ``use_attention``, ``use_AP=False``, uint8 queries) raises here, before any
+    work is queued.  ``stats`` also receives ``graphs_captured`` (by this call) and ``graph_replays``."""
     device = fmap.device
+    if not isinstance(capture, bool):
+        raise TypeError(f"relocalize: capture must be a bool, got {type(capture).__name__}")
     if not torch.is_tensor(queries):
         raise TypeError("relocalize: queries must be a tensor [G, ...]")
     if (neighbours is None) == (rule is None):
@@ -399,6 +409,11 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
         raise ValueError("relocalize: micro_batch must be >= 1")
     _check_postprocess("relocalize", postprocess, device)
     _check_fuse("relocalize", fuse, max_edges, ref_node)
+    if capture:
+        if torch.device(device).type != "cuda":
+            raise ValueError(f"relocalize: capture=True replays a HIP graph, the feature map is on {device}")
+        from .graphed import GraphedForwardMap
+        GraphedForwardMap.refuse(model, queries)
     qd_all = qg_all = None
     if rule is None:
         nb = torch.as_tensor(neighbours)
@@ -428,10 +443,18 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
     targ_h = None if targets is None else np.asarray(torch.as_tensor(targets).cpu(), dtype=np.float64).reshape(g_all, 6)
     fc_edges = fc_edge_index(n_per).numpy()
     qp = targ_dev = fc_first = None
+    captured = model._map_captures if capture else None
+    n_captured = n_replays = 0
     if postprocess == "device" and poses_h is not None:
         from .query_pose import QueryPose
-        qp = QueryPose(np.asarray(pose_m, dtype=np.float64), np.asarray(pose_s, dtype=np.float64), ref_node, fuse=fuse,
-                       max_edges=max_edges)
+        # a captured step counts its bad graphs in the status word of the rule it was captured with: that rule is kept with it
+        qp_key = ("pose", tuple(float(v) for v in pose_m), tuple(float(v) for v in pose_s), ref_node, fuse, max_edges)
+        qp = captured.get(qp_key) if capture else None
+        if qp is None:
+            qp = QueryPose(np.asarray(pose_m, dtype=np.float64), np.asarray(pose_s, dtype=np.float64), ref_node, fuse=fuse,
+                           max_edges=max_edges)
+            if capture:
+                captured[qp_key] = qp
         if targets is not None:
             t32 = torch.as_tensor(targets).detach().to(dtype=torch.float32).reshape(g_all, 6)
             targ_dev = t32 if t32.is_cuda else (t32 if t32.is_pinned() else t32.pin_memory()).to(device, non_blocking=True)
@@ -440,28 +463,66 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
     acc = _PoseRows(pose_m, pose_s, ref_node, on_device=qp is not None, fuse=fuse, max_edges=max_edges)
     raw_abs, raw_rel = [], []
 
+    def captured_step(x, qd, targ):
+        """The captured step of this micro-batch's shape and of this call's configuration: from the model's cache, or captured
+        now with the micro-batch itself as the example."""
+        nonlocal n_captured
+        key = ("step", tuple(x.shape), x.dtype, kk, None if rule is None else (rule.sampling_period, rule.random), postprocess,
+               fuse, max_edges, qd is not None, targ is not None)
+        step = captured.get(key)
+        if step is None or step.fmap is not fmap or step.pose is not qp or step.stale():
+            if len(captured) >= 16:
+                captured.clear()
+                if qp is not None:
+                    captured[qp_key] = qp
+            step = captured[key] = GraphedForwardMap(model, fmap, x, kk, rule=rule, query_descriptors=qd, pose=qp,
+                                                     pose_kwargs=None if targ is None else {"query_targets": targ})
+            n_captured += 1
+        return step
+
     def forward(chunk, x):
-        """-> (abs, rel, edge list, the neighbours on the device, the retrieved ones on their way to the host | None)"""
+        """-> (abs, rel, edge list, the neighbours on the device, the retrieved ones on their way to the host | None, the pose
+        rule's rows when a captured step has already made them | None)"""
+        nonlocal n_replays
         b0, b1 = chunk[0].first, chunk[0].first + x.shape[0]
-        if rule is None:
+        if rule is None and not capture:
             ab, rel, ei = model.forward_map(x, nb_dev[b0:b1], fmap)
-            return ab, rel, ei, nb_dev[b0:b1], None
+            return ab, rel, ei, nb_dev[b0:b1], None, None
         qd = None
         if qd_all is not None:
             qd = qd_all[b0:b1]
             if on_gpu and not qd.is_cuda:
                 qd = (qd if qd.is_pinned() else qd.pin_memory()).to(device, non_blocking=True)
-        ab, rel, ei, nb_mb = model.forward_map(x, None, fmap, rule=rule, query_descriptors=qd,
-                                               query_groups=None if qg_all is None else qg_all[b0:b1])
-        return ab, rel, ei, nb_mb, runner.read_back(nb_mb)
+        qg = None if qg_all is None else qg_all[b0:b1]
+        if capture:
+            targ = None if qp is None or targ_dev is None else targ_dev[b0:b1]
+            step = captured_step(x, qd, targ)
+            ranks = None
+            if rule is not None and (rule.random or qg is not None):
+                # this call's rule draws, in query order, exactly what forward_map would have drawn from it
+                ranks = rule.ranks(fmap.n_allowed(fmap._query_groups(qg, b1 - b0)[0], b1 - b0))
+            # x is one of the pipeline's two staging buffers (the copy of micro-batch i + 1 into the other one runs under this
+            # replay), so the step copies it into its one static input: a device copy of the queries, ~1 % of the step
+            out = step(x, None if rule is not None else nb_dev[b0:b1], ranks=ranks, query_descriptors=qd, query_groups=qg,
+                       query_targets=targ)
+            n_replays += 1
+            # The outputs are the step's STATIC tensors, which the replay of the next micro-batch overwrites.  Their copies to
+            # pinned memory (read_back here and in _MicroBatchRunner.launch, right after this returns) are enqueued on the stream
+            # the replay ran on BEFORE the next launch() enqueues its replay there: stream order keeps micro-batch i's results.
+            return (out.abs_pose, out.rel_pose, out.edge_index, out.neighbours,
+                    None if rule is None else runner.read_back(out.neighbours), out.rows)
+        ab, rel, ei, nb_mb = model.forward_map(x, None, fmap, rule=rule, query_descriptors=qd, query_groups=qg)
+        return ab, rel, ei, nb_mb, runner.read_back(nb_mb), None
 
     def outputs(chunk, x, fwd):
-        ab, rel, ei, nb_mb, host_nb = fwd
+        ab, rel, ei, nb_mb, host_nb, rows = fwd
         if qp is None:
             return {"nb": host_nb, "abs": ab, "rel": rel, "ei": ei if model.knn > 0 else None}
-        b0, n = chunk[0].first, x.shape[0]
-        return {"nb": host_nb, "rel": qp.from_map(rel, ei, fmap, nb_mb, query_targets=None if targ_dev is None else targ_dev[b0:b0 + n],
-                                                  edge_first=None if fc_first is None else fc_first[:n + 1])}
+        if rows is None:
+            b0, n = chunk[0].first, x.shape[0]
+            rows = qp.from_map(rel, ei, fmap, nb_mb, query_targets=None if targ_dev is None else targ_dev[b0:b0 + n],
+                               edge_first=None if fc_first is None else fc_first[:n + 1])
+        return {"nb": host_nb, "rel": rows}
 
     def target_block(g):
         target = np.zeros((n_per, 6))
@@ -491,6 +552,8 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
                finish, stats, postprocess)
     if stats is not None:
         stats["neighbours"] = nb_h
+        if capture:
+            stats.update(graphs_captured=n_captured, graph_replays=n_replays)
     if poses_h is None:
         return torch.cat(raw_abs), torch.cat(raw_rel)
     res = acc.result(with_targets=targ_h is not None)

@@ -11,9 +11,21 @@ graph is for hosts whose CPU is busy (8 ranks, data loading) and as the fixed-sh
     abs_pose, rel_pose, edge_index = runner(batch)       # copies batch.x into the static input, replays, returns views
 
 The returned tensors are the graph's static outputs: they are overwritten by the next call (clone them to keep them).
+
+``GraphedForwardMap`` is the same for the map path (``PoseNetX_R2.forward_map``, optionally followed by the device pose rule
+``QueryPose.from_map``).  That step is the opposite case: one encoder image per graph, ~137 launches of 5-50 us per 64 queries,
+bound by launch issue from Python -- the case a replay is for -- and, captured for one query, the serving entry point of a
+camera that sends one frame at a time.
+
+    step = GraphedForwardMap(model, fmap, example_queries, k=7, pose=QueryPose(...), pose_kwargs={"query_targets": t0})
+    out = step(queries, neighbours, query_targets=t)     # out.rows: float64 [G, 16]; out.abs_pose, out.rel_pose, ...
 """
 from __future__ import annotations
 
+from collections import namedtuple
+from typing import Optional
+
+import numpy as np
 import torch
 
 
@@ -51,4 +63,238 @@ class GraphedForward:
         self.graph.replay()
         if hasattr(self.model, "publish_status"):
             self.model.publish_status()           # bad-edge counters of the replayed kernels -> model.check_edge_index()
+        return self.out
+
+
+# what a GraphedForwardMap call returns: forward_map's outputs, the neighbours the graphs were built from (the static input, or
+# the rows the retrieval chose) and the pose rule's rows float64 [G, 16] (None without a pose rule) -- all static
+MapStep = namedtuple("MapStep", "abs_pose rel_pose edge_index neighbours rows")
+
+_FC_ONLY = "graph capture covers the deterministic fully-connected path (droprate=0, knn<=0)"
+
+
+def _storage(t: Optional[torch.Tensor]):
+    return None if t is None else (t.data_ptr(), int(t.shape[0]))
+
+
+class GraphedForwardMap:
+    """``model.forward_map(...)`` -- and ``pose.from_map(...)`` behind it when a ``QueryPose`` is given -- for ONE shape, captured
+    once and replayed with one launch.
+
+    ``example_queries`` [G, ...] fp32 (bf16 for the bf16 encoder) on the map's GPU give the shape; ``k`` is the number of
+    database images per query (with a ``rule``, ``rule.k``; it may be None then).  Without a rule the neighbours are an input,
+    int64 [G, K].  With a rule (``retrieval.RetrievalRule``) they are retrieved inside the graph from the static ``ranks`` int32
+    [G, K] and query groups int64 [G]: everything the host draws per call (the rule's half-drop mask and start) stays on the host
+    and is only copied in, so a seeded random rule gives other neighbours on every replay, as it does eagerly.  The forward's
+    own explicit-``k`` kNN graph is not offered at all (there is no argument for it).
+    ``query_descriptors`` fp32 [G, Dd]: an example, for a map that holds its own retrieval descriptors.
+    ``pose_kwargs``: ``query_targets`` (an example fp32 [G, 6]; absent: the rows' target part is zeros) and ``edge_first`` (int64
+    [G + 1]; absent: the cut of forward_map's own fully-connected list, K (K + 1) columns per graph).
+
+    The graph reads the packed weights, the workspaces, the map's tensors and the counters in place.  All of them are held
+    here, so nothing it reads is freed under it, and every call compares them with what the model and the map hold NOW:
+    after ``refresh_packed()`` / ``load_state_dict`` / ``.to()`` / a dtype switch / ``FeatureMap.extend`` the call raises
+    ``RuntimeError`` instead of replaying over storage that is no longer the model's or the map's."""
+
+    def __init__(self, model, fmap, example_queries: torch.Tensor, k: Optional[int] = None, *, rule=None, query_descriptors=None,
+                 pose=None, pose_kwargs: Optional[dict] = None, warmup: int = 2):
+        self.refuse(model, example_queries)
+        q = example_queries
+        if not q.is_cuda or q.device != fmap.device:
+            raise RuntimeError("GraphedForwardMap needs the queries and the feature map on the same GPU")
+        g = int(q.shape[0])
+        if rule is not None:
+            if k is not None and int(k) != rule.k:
+                raise ValueError(f"GraphedForwardMap: k = {k}, but the rule picks {rule.k} rows")
+            k = rule.k
+        if k is None or int(k) < 1 or g < 1:
+            raise ValueError("GraphedForwardMap: needs G >= 1 queries and K >= 1 database images per query")
+        k = int(k)
+        if rule is not None and k > len(fmap):
+            raise ValueError(f"GraphedForwardMap: the rule picks {k} rows, the map has {len(fmap)}")
+        if rule is None and query_descriptors is not None:
+            raise ValueError("GraphedForwardMap: query_descriptors belong to retrieval: pass a rule")
+        if rule is not None and (fmap.descriptors is None) != (query_descriptors is None):
+            raise ValueError("GraphedForwardMap: query_descriptors must be given exactly when the map holds its own descriptors")
+        pose_kwargs = dict(pose_kwargs or {})
+        if pose is None and pose_kwargs:
+            raise ValueError("GraphedForwardMap: pose_kwargs without a pose rule")
+        if pose is not None and fmap.poses is None:
+            raise ValueError("GraphedForwardMap: the pose rule needs a feature map with poses")
+        unknown = set(pose_kwargs) - {"query_targets", "edge_first"}
+        if unknown:
+            raise ValueError(f"GraphedForwardMap: pose_kwargs takes query_targets and edge_first, got {sorted(unknown)}")
+        dev = q.device
+        self.model, self.fmap, self.rule, self.pose = model, fmap, rule, pose
+        self.g, self.k = g, k
+
+        # ---- the static inputs --------------------------------------------------------------------------------------------------
+        self.queries = q.detach().clone(memory_format=torch.contiguous_format)
+        self.neighbours = self.ranks = self.query_groups = self.query_descriptors = self.query_targets = self.edge_first = None
+        if rule is None:
+            self.neighbours = torch.zeros((g, k), dtype=torch.int64, device=dev)          # row 0: valid for any map
+        else:
+            # A rule without random draws picks the same positions for every query that no group restricts: they are made once,
+            # here, and stay in the static buffer.  A random rule's draws are made per call, on the host, in query order; the
+            # warm-up and the capture run on positions 0..K-1 (K <= M rows and no group set: valid) so that they do not advance
+            # a seeded rule's generator.
+            self._fixed_ranks = None if rule.random else torch.from_numpy(rule.ranks(fmap.n_allowed(None, g))).pin_memory()
+            self._ranks_fixed = not rule.random
+            self.ranks = (torch.arange(k, dtype=torch.int32).repeat(g, 1) if rule.random else self._fixed_ranks).to(dev)
+            if fmap.groups is not None:
+                self.query_groups = torch.full((g,), -1, dtype=torch.int64, device=dev)   # -1: nothing left out
+            if query_descriptors is not None:
+                qd = query_descriptors
+                if not torch.is_tensor(qd) or qd.dtype != torch.float32 or tuple(qd.shape) != (g, fmap.descriptors.shape[1]):
+                    raise ValueError(f"GraphedForwardMap: query_descriptors must be fp32 [{g}, {fmap.descriptors.shape[1]}]")
+                self.query_descriptors = qd.detach().to(dev).contiguous().clone()
+            fmap.inv_norms()                      # cached on the map: made here, outside the capture, and held below
+        if pose is not None:
+            qt = pose_kwargs.get("query_targets")
+            if qt is not None:
+                if not torch.is_tensor(qt) or qt.dtype != torch.float32 or tuple(qt.shape) != (g, 6):
+                    raise ValueError(f"GraphedForwardMap: pose_kwargs['query_targets'] must be fp32 [{g}, 6]")
+                self.query_targets = qt.detach().to(dev).contiguous().clone()
+            if "edge_first" in pose_kwargs:
+                ef = pose_kwargs["edge_first"]
+                self.edge_first = None if ef is None else ef.detach().to(device=dev, dtype=torch.int64).contiguous().clone()
+            else:
+                self.edge_first = torch.arange(g + 1, dtype=torch.int64, device=dev) * (k * (k + 1))
+
+        # ---- warm-up, validation, capture (the pattern of GraphedForward) ---------------------------------------------------------
+        self.graph = torch.cuda.CUDAGraph()
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(max(1, warmup)):       # packs weights, sizes the workspace pool, builds the _map_graph edge list
+                self._step()
+            model.check_edge_index()              # one sync, before the capture: the warm-up's inputs were valid
+            if pose is not None:
+                pose.check()
+            with torch.cuda.graph(self.graph, stream=side):
+                self.out = self._step()
+        torch.cuda.current_stream().wait_stream(side)
+        # everything the graph reads besides its static inputs, held so that it outlives the graph, and what a call compares
+        self._held = self._reads()
+        self._signature = self._sign(self._held)
+
+    @staticmethod
+    def refuse(model, queries) -> None:
+        """Raise for what a captured map step does not cover -- before anything is queued."""
+        if not torch.is_tensor(queries):
+            raise TypeError("GraphedForwardMap: queries must be a tensor [G, ...]")
+        if queries.dtype == torch.uint8:
+            raise TypeError("GraphedForwardMap does not take uint8 frames: capture the model on its fp32 / bf16 input "
+                            "(frame_transform.apply(frames) outside the graph)")
+        if getattr(model, "droprate", 0) > 0 or getattr(model, "knn", -1) > 0:
+            raise NotImplementedError(_FC_ONLY)
+        if getattr(model, "use_attention", False) or not getattr(model, "use_AP", True):
+            raise NotImplementedError(_FC_ONLY + "; use_attention and use_AP=False take the one-stream path, which allocates and "
+                                      "publishes between its launches")
+
+    def _step(self) -> MapStep:
+        m = self.model
+        if self.rule is None:
+            ab, rel, ei = m.forward_map(self.queries, self.neighbours, self.fmap)
+            nb = self.neighbours
+        else:
+            ab, rel, ei, nb = m.forward_map(self.queries, None, self.fmap, rule=self.rule, query_descriptors=self.query_descriptors,
+                                            _static=(self.ranks, self.query_groups))
+        rows = None
+        if self.pose is not None:
+            rows = self.pose.from_map(rel, ei, self.fmap, nb, query_targets=self.query_targets, edge_first=self.edge_first)
+        return MapStep(ab, rel, ei, nb, rows)
+
+    # ---- validity ------------------------------------------------------------------------------------------------------------------
+    def _reads(self) -> dict:
+        from . import _lib as L
+        m, f = self.model, self.fmap
+        return {"library": L.lib(), "encoder": m._enc._packed, "gnn": m._gnn_packed, "gnn_bf16": m._gnn_bf16,
+                "dtypes": (m.encoder_dtype, m.gnn_dtype), "workspaces": list(m._ws_pool._buf.values()),
+                "fc_graph": m._map_graphs.get((self.g, self.k + 1, str(self.queries.device))),
+                "counters": m._counters.counters, "pose_counters": None if self.pose is None else self.pose._bad.counters,
+                "features": f.features, "poses": f.poses, "descriptors": f.descriptors, "groups": f.groups,
+                "inv_norms": f._inv_norms if self.rule is not None else None}
+
+    @staticmethod
+    def _sign(r: dict) -> tuple:
+        """Objects by identity, the map's storage by (address, rows): what must be unchanged for the graph to be replayed."""
+        return (id(r["library"]), id(r["encoder"]), id(r["gnn"]), id(r["gnn_bf16"]), r["dtypes"], id(r["counters"]),
+                id(r["pose_counters"]), _storage(r["features"]), _storage(r["poses"]), _storage(r["descriptors"]),
+                _storage(r["groups"]), _storage(r["inv_norms"]))
+
+    def stale(self) -> bool:
+        """True once the model or the map no longer hold what the graph was captured over."""
+        now = self._reads()
+        if now["encoder"] is None or now["gnn"] is None:
+            return True
+        if self.rule is not None and now["inv_norms"] is None:
+            return True
+        return self._sign(now) != self._signature
+
+    # ---- replay ------------------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _copy_in(static: torch.Tensor, given: torch.Tensor) -> None:
+        if given.data_ptr() != static.data_ptr():             # the static buffer itself: nothing to copy
+            static.copy_(given, non_blocking=True)
+
+    @torch.no_grad()
+    def __call__(self, queries: torch.Tensor, neighbours: Optional[torch.Tensor] = None, ranks=None, query_descriptors=None,
+                 query_groups=None, query_targets=None) -> MapStep:
+        """Copy the given inputs into the static buffers (non-blocking, on the current stream; a tensor that IS the static buffer
+        -- ``self.queries`` filled by the caller -- is not copied), replay, publish the deferred counters.  ``ranks``: int32 [G, K]
+        (tensor or array) in place of the rule's own, which are otherwise drawn here, on the host, as ``forward_map`` draws them;
+        ``query_groups`` [G]: host integers, as ``forward_map`` takes them."""
+        if self.stale():
+            raise RuntimeError("GraphedForwardMap is stale: the model's packed weights / precision or the feature map's storage "
+                               "have changed since the capture (refresh_packed, load_state_dict, .to(), FeatureMap.extend): "
+                               "capture again")
+        # every check before the first copy: a refused call leaves the static inputs as they were
+        for static, given, name in ((self.queries, queries, "queries"), (self.neighbours, neighbours, "neighbours"),
+                                    (self.query_descriptors, query_descriptors, "query_descriptors"),
+                                    (self.query_targets, query_targets, "query_targets")):
+            if static is None and given is not None:
+                raise ValueError(f"GraphedForwardMap: {name} given, but the graph was captured without")
+            if static is not None and given is None:
+                raise ValueError(f"GraphedForwardMap: the graph was captured with {name}: give them")
+            if static is not None and not torch.is_tensor(given):
+                raise TypeError(f"GraphedForwardMap: {name} must be a tensor")
+            if static is not None and (given.shape != static.shape or given.dtype != static.dtype):
+                raise ValueError(f"GraphedForwardMap was captured for {name} {static.dtype} {tuple(static.shape)}, got "
+                                 f"{given.dtype} {tuple(given.shape)}")
+        if self.rule is None and (ranks is not None or query_groups is not None):
+            raise ValueError("GraphedForwardMap: ranks / query_groups belong to retrieval: the graph was captured without a rule")
+        self.model._counters.poll()               # as the eager call starts: the report of the previous call, if it has landed
+        host_ranks, qg_dev, fixed = None, None, False
+        if self.rule is not None:
+            qg_host, qg_dev = self.fmap._query_groups(query_groups, self.g)
+            if ranks is None:
+                if self.rule.random or qg_host is not None:
+                    ranks = self.rule.ranks(self.fmap.n_allowed(qg_host, self.g))
+                elif not self._ranks_fixed:       # an earlier call left its own ranks in the static buffer
+                    ranks = self._fixed_ranks
+            fixed = ranks is self._fixed_ranks and ranks is not None
+            if ranks is not None:
+                host_ranks = ranks if torch.is_tensor(ranks) else torch.from_numpy(np.ascontiguousarray(ranks, dtype=np.int32))
+                if host_ranks.dtype != torch.int32 or tuple(host_ranks.shape) != (self.g, self.k):
+                    raise ValueError(f"GraphedForwardMap: ranks must be int32 [{self.g}, {self.k}], got {host_ranks.dtype} "
+                                     f"{tuple(host_ranks.shape)}")
+                if not host_ranks.is_cuda and not host_ranks.is_pinned():
+                    host_ranks = host_ranks.pin_memory()
+        for static, given in ((self.queries, queries), (self.neighbours, neighbours),
+                              (self.query_descriptors, query_descriptors), (self.query_targets, query_targets)):
+            if static is not None:
+                self._copy_in(static, given)
+        if host_ranks is not None:
+            self.ranks.copy_(host_ranks, non_blocking=True)
+            self._ranks_fixed = fixed
+        if self.query_groups is not None:
+            if qg_dev is None:
+                self.query_groups.fill_(-1)
+            else:
+                self.query_groups.copy_(qg_dev, non_blocking=True)
+        self.graph.replay()
+        self.model.publish_status()               # bad neighbours / ranks / edges counted by the replayed kernels
+        if self.pose is not None:
+            self.pose.publish()                   # ... and graphs without a usable reference edge
         return self.out

@@ -348,6 +348,9 @@ class _MicroBatchRunner:
         fwd = self.forward(chunk, batch)
         if staged:
             pipe.release(k)
+        # enqueued on the forward's stream, behind it and ahead of whatever the next launch() enqueues there: a client whose
+        # forward replays a captured graph (relocalize(capture=True)) hands over that graph's static outputs, which the next
+        # replay overwrites -- only after these copies have read them, by stream order
         host = {name: self.read_back(t) for name, t in self.outputs(chunk, batch, fwd).items()}
         ev = None
         if self.on_gpu:

@@ -157,6 +157,9 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
         self.frame_transform = None
         self._enc_digest: Optional[str] = None        # encoder_digest() cache (cleared wherever the packed weights are)
         self._map_graphs: Dict[tuple, Tuple[torch.Tensor, torch.Tensor]] = {}   # forward_map: (G, K+1, device) -> (edges, batch)
+        # relocalize(capture=True): its captured micro-batch steps (graphed.GraphedForwardMap) and the pose rules they were
+        # captured with, by shape / configuration; dropped with the packed weights, which every captured step reads
+        self._map_captures: Dict[tuple, object] = {}
 
     @property
     def encoder_dtype(self) -> str:
@@ -198,6 +201,7 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
         self._extra = {}
         self._ws_pool.clear()
         self._enc_digest = None
+        self._map_captures = {}
 
     def _apply(self, fn, *a, **k):
         if hasattr(self, "_enc"):
@@ -486,7 +490,7 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
 
     @torch.no_grad()
     def forward_map(self, queries: torch.Tensor, neighbours: Optional[torch.Tensor], fmap, k=None, *, rule=None,
-                    query_descriptors: Optional[torch.Tensor] = None, query_groups=None):
+                    query_descriptors: Optional[torch.Tensor] = None, query_groups=None, _static=None):
         """The forward of G graphs, each query g followed by the K database images ``neighbours[g]`` of the feature map ``fmap``
         (dataset_7Scenes_multi.py:340-345) -- with only the G queries through the encoder.  Returns what
         ``forward(fc_batch(assembled, K + 1), k)`` returns for the assembled images: (abs_pose [G*(K+1), 6], rel_pose [E, 6],
@@ -500,13 +504,16 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
         which this call has just computed, is matched against ``fmap.features``; a map that holds ``descriptors`` needs
         ``query_descriptors`` fp32 [G, Dd] on the same GPU.  ``query_groups`` [G] (host integers): rows of ``fmap.groups`` equal
         to a query's group are left out; -1 leaves nothing out.  Nothing blocks: the ranks are made on the host before the
-        launch, and a rank the map cannot serve is reported like a bad neighbour."""
+        launch, and a rank the map cannot serve is reported like a bad neighbour.
+
+        ``_static`` (graphed.GraphedForwardMap only): ``(ranks int32 [G, K], query groups int64 [G] or None)`` already on the
+        device, read in place of the two per-call host products above, so that nothing of the call depends on host data."""
         if neighbours is not None and rule is not None:
             raise ValueError("forward_map: give neighbours or a retrieval rule, not both")
         if rule is None and (query_descriptors is not None or query_groups is not None):
             raise ValueError("forward_map: query_descriptors / query_groups belong to retrieval: pass a rule (and neighbours=None)")
         if rule is not None:
-            return self._forward_map_retrieve(queries, fmap, k, rule, query_descriptors, query_groups)
+            return self._forward_map_retrieve(queries, fmap, k, rule, query_descriptors, query_groups, _static)
         if not torch.is_tensor(queries) or not torch.is_tensor(neighbours):
             raise TypeError("forward_map: queries and neighbours must be tensors")
         if neighbours.dtype != torch.int64 or neighbours.dim() != 2:
@@ -531,8 +538,9 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
             raise RuntimeError(f"forward_map: queries ({queries.device}), {name}{where} and the feature map ({fmap.device}) "
                                f"must be on the same GPU")
 
-    def _forward_map_retrieve(self, queries, fmap, k, rule, query_descriptors, query_groups):
-        """``forward_map`` with the neighbours retrieved per stream slot from that slot's query features (or descriptors)."""
+    def _forward_map_retrieve(self, queries, fmap, k, rule, query_descriptors, query_groups, static=None):
+        """``forward_map`` with the neighbours retrieved per stream slot from that slot's query features (or descriptors).
+        ``static``: see ``forward_map``'s ``_static``."""
         if not torch.is_tensor(queries):
             raise TypeError("forward_map: queries must be a tensor")
         if fmap.descriptors is not None and query_descriptors is None:
@@ -554,8 +562,11 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
         dev = queries.device
         # everything the slots share is made here, on the caller's stream, before any side stream is forked off it
         qd = None if qd is None else qd.contiguous()
-        qg_host, qg_dev = fmap._query_groups(query_groups, g)
-        ranks = rule.device_ranks(fmap.n_allowed(qg_host, g), dev)
+        if static is None:
+            qg_host, qg_dev = fmap._query_groups(query_groups, g)
+            ranks = rule.device_ranks(fmap.n_allowed(qg_host, g), dev)
+        else:                                     # the host's per-call products, already in the caller's device buffers
+            ranks, qg_dev = static
         inv, db = fmap.inv_norms(), fmap.descriptor_matrix
         db_groups = None if qg_dev is None else fmap.groups
         nb_out = torch.empty((g, kk), dtype=torch.int64, device=dev)

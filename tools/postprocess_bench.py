@@ -12,11 +12,16 @@ without the ``postprocess`` argument: the baseline the device mode is held again
 ``--fuse mean,median`` adds, per mode, a row ``MODE+FUSE`` with the streams' ``fuse=`` argument (every edge into the query
 combined, not one: the fused kernel behind the forward for "device", the numpy rule for "host"), held against the same baseline;
 ``--legs`` keeps only the named ``relocalize`` legs (and drops the ``evaluate_stream`` one).
+``--capture`` adds, per mode, a row ``MODE+capture`` with ``relocalize(..., capture=True)`` (the micro-batch step replayed from a
+captured HIP graph), measures the baseline checkout's ``device`` mode next to its default one -- the row ``device+capture`` is
+held against -- and adds ``latency_g1``: one query per call, the median of 200 synchronised calls of ``GraphedForwardMap``
+against eager ``forward_map`` (here and in the baseline checkout).
 ``--only LEG`` runs one leg in one mode in a loop, for a profiler (``rocprofv3 --kernel-trace --stats -- python
 tools/postprocess_bench.py --only 256x341_bf16:device``), and prints the wall time of the timed loop to relate kernel time to.
 
 usage: tools/postprocess_bench.py [--reps 3] [--baseline-root DIR] [--out profiles/query_pose_bench.json]
-       tools/postprocess_bench.py --fuse mean,median --baseline-root DIR --out profiles/query_pose_fused_bench.json"""
+       tools/postprocess_bench.py --fuse mean,median --baseline-root DIR --out profiles/query_pose_fused_bench.json
+       tools/postprocess_bench.py --capture --baseline-root DIR --out profiles/relocalize_capture_bench.json"""
 import argparse
 import json
 import os
@@ -56,6 +61,22 @@ def rates(fn, n, reps):
     return {"graphs_per_s": [round(r, 1) for r in out], "median": round(med, 1), "spread": round((max(out) - min(out)) / med, 4)}
 
 
+def latency_ms(fn, calls=200):
+    """Median wall time of ``calls`` synchronised calls, in ms, and the spread (p90 - p10) / median."""
+    for _ in range(10):
+        fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(calls):
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        ts.append((time.perf_counter() - t0) * 1e3)
+    ts.sort()
+    med = statistics.median(ts)
+    return {"median_ms": round(med, 4), "spread": round((ts[int(0.9 * len(ts))] - ts[int(0.1 * len(ts))]) / med, 4)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=3)
@@ -65,6 +86,10 @@ def main():
     ap.add_argument("--modes", default="host,device", help="comma list of host, device, baseline (= no postprocess argument)")
     ap.add_argument("--baseline-root", default=None, help="another checkout (the parent commit, built) to measure as the baseline")
     ap.add_argument("--fuse", default="", help="comma list of mean, median: also measure every mode with fuse= (rows MODE+FUSE)")
+    ap.add_argument("--capture", action="store_true", help="also measure every mode with capture=True (rows MODE+capture) and "
+                    "the one-query latency of GraphedForwardMap")
+    ap.add_argument("--g1", action="store_true", help="measure the one-query latency of eager forward_map (the baseline child "
+                    "of --capture)")
     ap.add_argument("--legs", default=None, help="comma list of relocalize legs to keep, e.g. 256x341_bf16 (default: all four)")
     ap.add_argument("--only", default=None, help="LEG:MODE, e.g. 256x341_bf16:device -- that leg alone, for a profiler")
     ap.add_argument("--out", default=None, help="also write the JSON document to this file")
@@ -80,6 +105,8 @@ def main():
 
     modes = [m for m in args.modes.split(",") if m]
     modes += [f"{m}+{f}" for f in args.fuse.split(",") if f for m in modes if m != "baseline"]
+    if args.capture:
+        modes += [f"{m}+capture" for m in modes if m != "baseline"]
     legs = args.legs.split(",") if args.legs else None
     only_leg, only_mode = (args.only.split(":") + [None])[:2] if args.only else (None, None)
     if only_mode:
@@ -98,8 +125,11 @@ def main():
     def kw_of(mode):
         if mode == "baseline":
             return {}
-        mode, _, fuse = mode.partition("+")
-        return {"postprocess": mode, "fuse": fuse} if fuse else {"postprocess": mode}
+        mode, *extra = mode.split("+")
+        kw = {"postprocess": mode}
+        for e in extra:                                    # "capture", or the fuse mode
+            kw.update({"capture": True} if e == "capture" else {"fuse": e})
+        return kw
 
     n = args.queries
     for prec in ("f32", "bf16"):
@@ -131,6 +161,17 @@ def main():
                 leg[mode] = rates(fn, n, args.reps)
                 leg[mode]["d2h_bytes"] = st.get("d2h_bytes")
             doc["relocalize"][key] = leg
+            if args.capture or args.g1:
+                # one query per call, everything on the device: a camera that sends one frame at a time
+                q1, nb1 = qh[:1].to(dev), nbh[:1].to(dev)
+                lat = {"eager": latency_ms(lambda: m.forward_map(q1, nb1, fmap))}
+                if args.capture:
+                    from relpose_gnn_amd.graphed import GraphedForwardMap
+                    step = GraphedForwardMap(m, fmap, q1, K)
+                    lat["captured"] = latency_ms(lambda: step(q1, nb1))
+                    del step
+                m.check_edge_index()
+                doc.setdefault("latency_g1", {})[key] = lat
             del qh, fmap
             torch.cuda.empty_cache()
 
@@ -144,7 +185,7 @@ def main():
         ys = torch.randn((g_n, K + 1, 6), generator=torch.Generator().manual_seed(6)) * 0.3
         graphs = [Data(x=xs[i], edge_index=ei, y=ys[i]) for i in range(g_n)]
         leg = {}
-        for mode in modes:
+        for mode in (mo for mo in modes if "capture" not in mo):       # capture is relocalize's alone
             st = {}
             leg[mode] = rates(lambda: evaluate_stream(m, graphs, dev, micro_batch=64, stats=st, **kw_of(mode)), g_n, args.reps)
             leg[mode]["d2h_bytes"] = st.get("d2h_bytes")
@@ -154,8 +195,9 @@ def main():
 
     if args.baseline_root:
         # the parent commit's relocalize, on this box, in this visit: a fresh child process on the other checkout
-        cmd = [sys.executable, os.path.abspath(__file__), "--root", os.path.abspath(args.baseline_root), "--modes", "baseline",
-               "--reps", str(args.reps), "--queries", str(args.queries)] + (["--legs", args.legs] if args.legs else [])
+        cmd = [sys.executable, os.path.abspath(__file__), "--root", os.path.abspath(args.baseline_root), "--modes",
+               "baseline,device" if args.capture else "baseline", "--reps", str(args.reps), "--queries", str(args.queries)]
+        cmd += (["--legs", args.legs] if args.legs else []) + (["--g1"] if args.capture else [])
         res = subprocess.run(cmd, stdout=subprocess.PIPE, text=True, timeout=600)
         if res.returncode != 0:
             raise SystemExit(f"baseline run failed with exit status {res.returncode}")
@@ -178,6 +220,19 @@ def main():
                     if "device" in leg:
                         v["over_device"] = round(d["median"] / leg["device"]["median"], 3)
                     verdict[f"{key}:{mode}"] = v
+            if "device+capture" in leg and "device" in base["relocalize"][key]:
+                # the captured step against the BASELINE checkout's device mode; a gain only beyond both rows' spreads
+                bd, d = base["relocalize"][key]["device"], leg["device+capture"]
+                leg["baseline_device"] = bd
+                spread = max(bd["spread"], d["spread"])
+                ratio = d["median"] / bd["median"]
+                verdict[f"{key}:device+capture"] = {"over_baseline_device": round(ratio, 3), "spread": spread,
+                                                    "gain": bool(ratio - 1.0 > spread), "not_slower": bool(ratio >= 1.0 - spread)}
+            if key in doc.get("latency_g1", {}) and key in base.get("latency_g1", {}):
+                lat = doc["latency_g1"][key]
+                lat["baseline_eager"] = base["latency_g1"][key]["eager"]
+                if "captured" in lat:
+                    lat["captured_over_baseline_eager"] = round(lat["baseline_eager"]["median_ms"] / lat["captured"]["median_ms"], 3)
         doc["device_vs_baseline"] = verdict
     line = json.dumps(doc)
     print(line, flush=True)
