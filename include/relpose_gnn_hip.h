@@ -286,6 +286,13 @@ int rpg_knn_graph_f32(const float* x, const int64_t* batch, int n, int d, int k,
 /* compute_edge_features (posenet.py:999-1019): out[e] = [x[min(s,t)], x[max(s,t)]], [e][2d]. */
 int rpg_edge_concat_gather_f32(const float* x, const int64_t* edge_index, int e, int d, float* out, void* stream);
 
+/* proj_edge (posenet.py:1053-1055) after its weight is split into the two node halves, W [x_lo, x_hi] = W_lo x_lo + W_hi x_hi
+ * with both products computed once per node: out[e][:] = relu((pq[lo[e]][0:d] + pq[hi[e]][d:2d]) + bias), in that association.
+ * pq [rows][2d] = [W_lo x | W_hi x] per node, lo / hi [e] int64 row ids in [0, rows) (NOT checked: the composite forward passes
+ * the clamped end points of rpg_graph_prepare), bias [d], out [e][d]; d % 4 == 0, all float pointers 16-byte aligned.      */
+int rpg_gather_add2_relu_f32(const float* pq, const int64_t* lo, const int64_t* hi, const float* bias, int e, int d, float* out,
+                             void* stream);
+
 /* out[m][n_out] = act( cat_k( a_k[idx_k[m]] ) @ W^T + bias ) (+ residual): nn.Linear over a row-wise
  * concatenation of up to three gathered sources that is never materialised
  * (my_gnn_layer.py:238, :305, :310; posenet.py:1053-1055).  idx_k == NULL means row m itself.

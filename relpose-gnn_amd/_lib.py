@@ -31,7 +31,7 @@ SYMBOLS = (
     "rpg_resize_table_ksize", "rpg_resize_table_bilinear", "rpg_frames_workspace_bytes", "rpg_frames_u8_to_f32",
     "rpg_frames_u8_to_bf16", "rpg_gather_graph_nodes_f32", "rpg_linear_bf16_ex", "rpg_conv_pair_bf16",
     "rpg_retrieve_workspace_bytes", "rpg_retrieve_max_rank", "rpg_row_inv_norms_f32", "rpg_retrieve_cosine_f32",
-    "rpg_query_pose_f64", "rpg_query_pose_fused_f64",
+    "rpg_query_pose_f64", "rpg_query_pose_fused_f64", "rpg_gather_add2_relu_f32",
 )
 
 
@@ -60,6 +60,7 @@ def _declare(lib: C.CDLL) -> None:
                                            _vp, _sz, _vp]
     lib.rpg_graph_prepare.argtypes = [_vp, _vp, C.c_int64, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]
     lib.rpg_edge_concat_gather_f32.argtypes = [_vp, _vp, _i, _i, _vp, _vp]
+    lib.rpg_gather_add2_relu_f32.argtypes = [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp]
     lib.rpg_linear_gather_f32.argtypes = [_i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i), C.POINTER(_i), _vp, _vp,
                                           _vp, _vp, _i, _i, _i, _vp]
     lib.rpg_linear_gather_ex_f32.argtypes = [_i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i), C.POINTER(_i), C.POINTER(C.c_long),

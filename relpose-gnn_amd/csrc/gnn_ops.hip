@@ -495,6 +495,12 @@ extern "C" int rpg_edge_concat_gather_f32(const float* x, const int64_t* edge_in
     return RPG_OK;
 }
 
+extern "C" int rpg_gather_add2_relu_f32(const float* pq, const int64_t* lo, const int64_t* hi, const float* bias, int e, int d,
+                                        float* out, void* stream) {
+    if (!rpg::aligned16(pq) || !rpg::aligned16(bias) || !rpg::aligned16(out)) return RPG_ERR_BAD_ARG;
+    return rpg::launch_gather_add2_relu(pq, lo, hi, bias, out, e, d, rpg::as_stream(stream));
+}
+
 extern "C" int rpg_attention_rows_f32(const float* gtp, int r, int c, float* y, void* stream) {
     if (!gtp || !y || r <= 0 || c <= 0 || (c & 3) || c > 8192 || !rpg::aligned16(gtp)) return RPG_ERR_BAD_ARG;
     hipStream_t s = rpg::as_stream(stream);

@@ -430,6 +430,22 @@ def edge_concat_gather(x: torch.Tensor, edge_index: torch.Tensor) -> torch.Tenso
     return out
 
 
+def gather_add2_relu(pq: torch.Tensor, lo: torch.Tensor, hi: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
+    """relu((pq[lo][:, :d] + pq[hi][:, d:]) + bias) (rpg_gather_add2_relu_f32; proj_edge on per-node products): pq [rows, 2d],
+    lo / hi int64 [E] row ids (checked here against ``rows``: one synchronisation), bias [d] -> [E, d]."""
+    pq, bias = _req(pq, "pq"), _req(bias, "bias")
+    lo, hi = _req(lo, "lo", torch.int64), _req(hi, "hi", torch.int64)
+    if pq.dim() != 2 or pq.shape[1] % 8 or lo.dim() != 1 or lo.shape != hi.shape or bias.shape != (pq.shape[1] // 2,):
+        raise ValueError(f"gather_add2_relu: needs pq [rows, 2d] with d % 4 == 0, lo / hi [E] and bias [d], got "
+                         f"{tuple(pq.shape)}, {tuple(lo.shape)}, {tuple(hi.shape)}, {tuple(bias.shape)}")
+    rows, e, d = pq.shape[0], lo.shape[0], pq.shape[1] // 2
+    if e and (int(torch.minimum(lo.min(), hi.min())) < 0 or int(torch.maximum(lo.max(), hi.max())) >= rows):
+        raise IndexError(f"gather_add2_relu: lo / hi hold a row id outside [0, {rows})")
+    out = torch.empty((e, d), dtype=torch.float32, device=pq.device)
+    L.check(L.lib().rpg_gather_add2_relu_f32(_p(pq), _p(lo), _p(hi), _p(bias), e, d, _p(out), _stream()), "gather_add2_relu")
+    return out
+
+
 def gather_graph_nodes(query_feat: torch.Tensor, map_feat: torch.Tensor, neighbours: torch.Tensor,
                        out: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Node features of G graphs, each its query followed by K map rows (rpg_gather_graph_nodes_f32): query_feat [G, d],
