@@ -372,6 +372,32 @@ int rpg_gnn_forward_bf16(const float* const* tensors, int n_tensors, const void*
                          int gnn_recursion, float* abs_pose, float* rel_pose, float* node_out, float* edge_out,
                          int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The query-only output mode of the two forwards above, for callers whose pose rule reads only the relative poses on the edges
+ * INTO some nodes (the queries) and those nodes' own absolute poses (test.py:227-232).  The last recursion of simpleConvEdge_upt
+ * (my_gnn_layer.py:293-311) has no consumer behind it, so its edge update, message MLP, attention and aggregation run on the
+ * e_sel selected columns only and att.W / mlp_updating on the q query rows only; every recursion before it, proj_edge and the
+ * last recursion's three per-node terms run in full.  Dead-code elimination: every value still computed is the value of the full
+ * forward up to the summation order of the differently tiled GEMMs.
+ *   sel    [e_sel] int64, ascending columns of the edge list: exactly the valid columns (those rpg_graph_prepare keeps) whose
+ *          target is in qnodes, so that every query node's aggregate is complete
+ *   qnodes [q] int64, ascending and distinct node ids in the edge list's numbering (node_offset is subtracted)
+ * -> abs_pose [q][6] of qnodes, rel_pose [e_sel][6] of the sel columns in sel order; node_out [q][d] / edge_out [e_sel][d]
+ * optional, the heads' inputs.  The selection's CSR keeps rpg_graph_prepare's ascending-edge order.  Index contract, as
+ * rpg_graph_prepare: status += violations -- a column outside [0, e), one rpg_graph_prepare left out, one whose target is no query
+ * node, a column that does not ascend, a qnode out of range or not ascending, and one more if the number of valid columns into
+ * the query nodes is not e_sel; everything is clamped, so nothing reads out of bounds.  1 <= e_sel <= e, 1 <= q <= n.
+ * No allocation, no synchronisation, capturable; workspace of rpg_gnn_query_workspace_bytes().                                  */
+size_t rpg_gnn_query_workspace_bytes(int n, int e, int d, int e_sel, int q);
+int rpg_gnn_forward_query_f32(const float* const* tensors, int n_tensors, const float* feat, const int64_t* src,
+                              const int64_t* dst, int64_t node_offset, int n, int e, int d, int gnn_recursion, const int64_t* sel,
+                              int e_sel, const int64_t* qnodes, int q, float* abs_pose, float* rel_pose, float* node_out,
+                              float* edge_out, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+int rpg_gnn_forward_query_bf16(const float* const* tensors, int n_tensors, const void* const* weights_bf16, int n_bf16,
+                               const float* feat, const int64_t* src, const int64_t* dst, int64_t node_offset, int n, int e, int d,
+                               int gnn_recursion, const int64_t* sel, int e_sel, const int64_t* qnodes, int q, float* abs_pose,
+                               float* rel_pose, float* node_out, float* edge_out, int32_t* status, void* workspace,
+                               size_t workspace_bytes, void* stream);
+
 /* One 64-channel identity BasicBlock of the bf16 encoder as a single kernel (round 5): y = relu(bn2(conv2(relu(bn1(conv1(x))))) + x),
  * both convolutions 3x3 / stride 1 / pad 1, 64 -> 64 channels, x / y bf16 NHWC [n][h][w][64] (y must not alias x), weights bf16
  * [64][3][3][64] (OHWI), folded BatchNorm scale / shift fp32 [64] (16-byte aligned).  Replaces the two aten conv2d + batch_norm +

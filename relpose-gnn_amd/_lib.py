@@ -32,6 +32,7 @@ SYMBOLS = (
     "rpg_frames_u8_to_bf16", "rpg_gather_graph_nodes_f32", "rpg_linear_bf16_ex", "rpg_conv_pair_bf16",
     "rpg_retrieve_workspace_bytes", "rpg_retrieve_max_rank", "rpg_row_inv_norms_f32", "rpg_retrieve_cosine_f32",
     "rpg_query_pose_f64", "rpg_query_pose_fused_f64", "rpg_gather_add2_relu_f32",
+    "rpg_gnn_query_workspace_bytes", "rpg_gnn_forward_query_f32", "rpg_gnn_forward_query_bf16",
 )
 
 
@@ -75,6 +76,12 @@ def _declare(lib: C.CDLL) -> None:
                                         _vp, _vp, _sz, _vp]
     lib.rpg_gnn_forward_bf16.argtypes = [C.POINTER(_vp), _i, C.POINTER(_vp), _i, _vp, _vp, _vp, C.c_int64, _i, _i, _i, _i, _vp,
                                          _vp, _vp, _vp, _vp, _vp, _sz, _vp]
+    lib.rpg_gnn_query_workspace_bytes.argtypes = [_i] * 5
+    lib.rpg_gnn_query_workspace_bytes.restype = _sz
+    lib.rpg_gnn_forward_query_f32.argtypes = [C.POINTER(_vp), _i, _vp, _vp, _vp, C.c_int64, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp,
+                                              _vp, _vp, _vp, _vp, _sz, _vp]
+    lib.rpg_gnn_forward_query_bf16.argtypes = [C.POINTER(_vp), _i, C.POINTER(_vp), _i, _vp, _vp, _vp, C.c_int64, _i, _i, _i, _i, _vp,
+                                               _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]
     lib.rpg_f32_to_bf16.argtypes = [_vp, _i, _vp, _i, _i, C.c_long, _i, _vp]
     lib.rpg_linear_bf16.argtypes = [_vp] * 7 + [_i, _vp, _i, _i, _i, _i, _vp]
     lib.rpg_linear_bf16_ex.argtypes = [_vp, _i] + [_vp] * 6 + [_i, _vp, _i, _vp] + [_i] * 6 + [_vp]

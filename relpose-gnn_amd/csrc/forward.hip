@@ -192,11 +192,36 @@ size_t gnn_bytes(int n, int e, int d) {
     add(rpg::split_scratch_bytes());                // stream-K partial tiles
     return b;
 }
+
+// The query-only output mode (rpg_gnn_forward_query_*): the selection and what the pruned last recursion keeps beside the buffers
+// of gnn_bytes(), which it reuses at e_sel / q rows.
+struct QuerySel {
+    const int64_t* sel;        // [e_sel] ascending columns of the edge list: every valid column whose target is a query node
+    int e_sel;
+    const int64_t* qnodes;     // [q] ascending node ids, in the numbering of the edge list (node_offset is subtracted)
+    int q;
+};
+size_t gnn_query_extra_bytes(int d, int e_sel, int q) {
+    size_t b = 0;
+    auto add = [&](size_t bytes) { b += align_up(bytes, 256) + rpg::kWorkspaceSkew; };
+    add(((size_t)3 * e_sel + 3 * (size_t)q + 1) * 4);    // clamped columns, query row per column, CSR of the selection, query nodes
+    add((size_t)2 * e_sel * 8);                         // end points of the selected columns
+    add((size_t)e_sel * d * 4);                         // the selected rows of the edge features (fp32)
+    add((size_t)e_sel * d * 2);                         // ... and their bf16 image (bf16 Linears)
+    add((size_t)q * d * 4);                             // the query rows of x
+    add((size_t)q * 2 * d * 2);                         // bf16 x | aggregate of the query rows (bf16 Linears)
+    return b;
+}
 }  // namespace
 
 extern "C" size_t rpg_gnn_workspace_bytes(int n, int e, int d) {
     if (n <= 0 || e <= 0 || d <= 0 || (d & 31)) return 0;
     return gnn_bytes(n, e, d);
+}
+
+extern "C" size_t rpg_gnn_query_workspace_bytes(int n, int e, int d, int e_sel, int q) {
+    if (n <= 0 || e <= 0 || d <= 0 || (d & 31) || e_sel <= 0 || e_sel > e || q <= 0 || q > n) return 0;
+    return gnn_bytes(n, e, d) + gnn_query_extra_bytes(d, e_sel, q);
 }
 
 namespace {
@@ -208,13 +233,14 @@ enum BfWeight { B_PROJN, B_NODE3, B_EDGE0E, B_EDGE2, B_MSG0E, B_MSG2, B_GTP, B_A
 int gnn_forward_impl(const float* const* tensors, int n_tensors, const void* const* wb, const float* feat, const int64_t* esrc,
                      const int64_t* edst, int64_t node_offset, int n, int e, int d, int gnn_recursion, float* abs_pose,
                      float* rel_pose, float* node_out, float* edge_out, int32_t* status, void* workspace,
-                     size_t workspace_bytes, void* stream) {
+                     size_t workspace_bytes, void* stream, const QuerySel* qs = nullptr) {
     if (!tensors || (n_tensors != T_COUNT && n_tensors != T_COUNT_SPLIT) || !feat || !esrc || !edst || !abs_pose || !rel_pose || !status || !workspace ||
         n <= 0 || e <= 0 || d <= 0 || (d & 31) || gnn_recursion < 0)
         return RPG_ERR_BAD_ARG;
     for (int i = 0; i < n_tensors; ++i)
         if (!tensors[i]) return RPG_ERR_BAD_ARG;
-    if (workspace_bytes < gnn_bytes(n, e, d)) return RPG_ERR_WORKSPACE;
+    if (qs && (!qs->sel || !qs->qnodes || qs->e_sel <= 0 || qs->e_sel > e || qs->q <= 0 || qs->q > n)) return RPG_ERR_BAD_ARG;
+    if (workspace_bytes < gnn_bytes(n, e, d) + (qs ? gnn_query_extra_bytes(d, qs->e_sel, qs->q) : 0)) return RPG_ERR_WORKSPACE;
     const bool split = (n_tensors == T_COUNT_SPLIT) && (wb || rpg::gnn_split_enabled());
     if (wb && !split) return RPG_ERR_BAD_ARG;            // the bf16 Linears exist for the split formulation only
     hipStream_t s = rpg::as_stream(stream);
@@ -239,6 +265,22 @@ int gnn_forward_impl(const float* const* tensors, int n_tensors, const void* con
     void* abf = cv.take<unsigned short>((size_t)(e > 2 * n ? e : 2 * n) * d);
     const size_t scratch_bytes = rpg::split_scratch_bytes();
     rpg::ScratchScope scratch(cv.take<char>(scratch_bytes), scratch_bytes, s);
+    // query-only mode: carved behind everything else, so the plan of the full forward is the same with and without it
+    const int es = qs ? qs->e_sel : 0, nq = qs ? qs->q : 0;
+    int32_t *selc = nullptr, *srow = nullptr, *perm_q = nullptr, *qn = nullptr, *rowptr_q = nullptr, *cursor_q = nullptr;
+    int64_t *ssrc = nullptr, *sdst = nullptr;
+    float *esel = nullptr, *xq = nullptr;
+    unsigned short *ebs = nullptr, *xabq = nullptr;
+    if (qs) {
+        int32_t* i32 = cv.take<int32_t>((size_t)3 * es + 3 * (size_t)nq + 1);
+        selc = i32; srow = selc + es; perm_q = srow + es; qn = perm_q + es; cursor_q = qn + nq; rowptr_q = cursor_q + nq;
+        ssrc = cv.take<int64_t>((size_t)2 * es);
+        sdst = ssrc + es;
+        esel = cv.take<float>((size_t)es * d);
+        ebs = cv.take<unsigned short>((size_t)es * d);
+        xq = cv.take<float>((size_t)nq * d);
+        xabq = cv.take<unsigned short>((size_t)nq * 2 * d);
+    }
 
     int rc;
     if ((rc = rpg_graph_prepare(esrc, edst, node_offset, e, n, ends, rowptr, cursor, perm, status, stream)) != RPG_OK) return rc;
@@ -246,6 +288,13 @@ int gnn_forward_impl(const float* const* tensors, int n_tensors, const void* con
     const int64_t* dst = ends + e;
     const int64_t* lo = ends + 2 * (size_t)e;
     const int64_t* hi = ends + 3 * (size_t)e;
+    // the selection: checked against its contract (counted into status, clamped), its end points, its CSR by query row.  `cursor`
+    // is free once graph_prepare has run: it holds the node -> query row table.
+    if (qs && (rc = rpg::launch_query_select(esrc, edst, node_offset, e, n, ends, qs->sel, es, qs->qnodes, nq, cursor, selc, ssrc, sdst,
+                                             srow, qn, rowptr_q, cursor_q, perm_q, status, s)) != RPG_OK)
+        return rc;
+    // rows of the heads' inputs: all of them, or the query nodes and the selected columns
+    const int n_head = qs ? nq : n, e_head = qs ? es : e;
 
     auto linear = [&](int ns, const float* a0, const int64_t* i0, int w0, const float* a1, const int64_t* i1, int w1,
                       const float* a2, const int64_t* i2, int w2, int wt, const float* residual, float* out, int m,
@@ -294,17 +343,17 @@ int gnn_forward_impl(const float* const* tensors, int n_tensors, const void* con
         return rpg::launch_linear(g, tensors[wt], nullptr, nullptr, node3, n, n_out, 0, s);
     };
     auto edge_gemm = [&](const float* ein, int wt, int bias_t, const float* r1, const int64_t* i1, const float* r2,
-                         const int64_t* i2, float* out) {
+                         const int64_t* i2, float* out, int m) {
         rpg::GatherSrc g{};
         g.n = 1; g.a[0] = ein; g.idx[0] = nullptr; g.ld[0] = d; g.width[0] = d;
         const rpg::GatherRes gr{r1, i1, r2, i2, 3 * d};
         if (wb) {
             int rcb;
-            if ((rcb = rpg::launch_f32_to_bf16(ein, d, abf, d, 0, e, d, s)) != RPG_OK) return rcb;
+            if ((rcb = rpg::launch_f32_to_bf16(ein, d, abf, d, 0, m, d, s)) != RPG_OK) return rcb;
             return rpg::launch_linear_bf16(abf, wb[wt == T_EDGE0E_W ? B_EDGE0E : B_MSG0E], tensors[bias_t], r1, i1, r2, i2, 3 * d,
-                                           out, e, d, d, 1, s);
+                                           out, m, d, d, 1, s);
         }
-        return rpg::launch_linear(g, tensors[wt], tensors[bias_t], nullptr, out, e, d, 1, s, &gr);
+        return rpg::launch_linear(g, tensors[wt], tensors[bias_t], nullptr, out, m, d, 1, s, &gr);
     };
 
     const bool fuse_agg = rpg::gnn_fuse_agg_enabled();
@@ -344,41 +393,69 @@ int gnn_forward_impl(const float* const* tensors, int n_tensors, const void* con
         if ((rc = rpg::launch_gather_add2_relu(node3, lo, hi, tensors[T_PROJ_B], ecur, e, d, s)) != RPG_OK) return rc;
         if ((rc = rpg::launch_f32_to_bf16(ecur, d, eb, d, 0, e, d, s)) != RPG_OK) return rc;
         const float* x = feat;
+        auto gather16 = [&](const void* in, int ld_in, const int32_t* idx, void* out, int ld_out, int row_bytes, int rows) {
+            return rpg::launch_gather_rows16(in, ld_in, idx, out, ld_out, row_bytes, rows, s);
+        };
         for (int r = 0; r < gnn_recursion; ++r) {                                       // posenet.py:1061-1069
             const bool last = r + 1 == gnn_recursion;
+            // query-only mode, last recursion: nothing reads its output but the heads, so the edge rows are the selected columns
+            // and the node rows the query nodes (the three node terms stay n rows: a selected edge's source is any node)
+            const bool prune = qs && last;
+            const int me = prune ? es : e, mn = prune ? nq : n;
+            const int64_t* rs = prune ? ssrc : src;
+            const int64_t* rd = prune ? sdst : dst;
             float* xnew = xbuf[r & 1];
             // edge update                                                              my_gnn_layer.py:296-297
             if ((rc = gemm(xab, 2 * d, d, B_NODE3, nullptr, nullptr, nullptr, nullptr, nullptr, 0, node3, 1, nullptr, 0, 0, n, 3 * d, 0)) != RPG_OK) return rc;
-            if ((rc = gemm(eb, d, d, B_EDGE0E, tensors[T_EDGE0_B], node3, src, node3 + d, dst, 3 * d, hb, 0, nullptr, 0, 0, e, d, 1)) != RPG_OK) return rc;
+            const bf* ein = eb;
+            if (prune) {
+                if ((rc = gather16(eb, d * 2, selc, ebs, d * 2, d * 2, es)) != RPG_OK) return rc;
+                ein = ebs;
+            }
+            if ((rc = gemm(ein, d, d, B_EDGE0E, tensors[T_EDGE0_B], node3, rs, node3 + d, rd, 3 * d, hb, 0, nullptr, 0, 0, me, d, 1)) != RPG_OK) return rc;
             // raw update -> enb (consumed by the message MLP); relu(update) (posenet.py:1065) -> the next recursion's bf16 edge
             // features, or on the last recursion the fp32 ones the heads read
-            if (last) rc = gemm(hb, d, d, B_EDGE2, tensors[T_EDGE2_B], nullptr, nullptr, nullptr, nullptr, 0, ebuf[1], 1, enb, d, 0, e, d, 1);
+            if (last) rc = gemm(hb, d, d, B_EDGE2, tensors[T_EDGE2_B], nullptr, nullptr, nullptr, nullptr, 0, ebuf[1], 1, enb, d, 0, me, d, 1);
             else rc = gemm(hb, d, d, B_EDGE2, tensors[T_EDGE2_B], nullptr, nullptr, nullptr, nullptr, 0, eb, 0, enb, d, 0, e, d, 1);
             if (rc != RPG_OK) return rc;
             if (last) ecur = ebuf[1];
             // message MLP, attention, aggregation                                      my_gnn_layer.py:301,304-307
-            if ((rc = gemm(enb, d, d, B_MSG0E, tensors[T_MSG0_B], node3 + 2 * d, src, nullptr, nullptr, 3 * d, hb, 0, nullptr, 0, 0, e, d, 1)) != RPG_OK) return rc;
-            if ((rc = gemm(hb, d, d, B_MSG2, tensors[T_MSG2_B], nullptr, nullptr, nullptr, nullptr, 0, msg, 1, mb, d, 0, e, d, 0)) != RPG_OK) return rc;
-            if ((rc = gemm(mb, d, d, B_GTP, tensors[T_GTP_B], nullptr, nullptr, nullptr, nullptr, 0, gtp, 1, nullptr, 0, 0, e, 3 * c, 0)) != RPG_OK) return rc;
-            if ((rc = rpg_attention_aggregate_f32(gtp, msg, rowptr, perm, tensors[T_ATTW_B], n, e, c, d, yat, att, stream)) != RPG_OK) return rc;
-            if ((rc = rpg::launch_f32_to_bf16(yat, c, yb, c, 0, n, c, s)) != RPG_OK) return rc;
+            if ((rc = gemm(enb, d, d, B_MSG0E, tensors[T_MSG0_B], node3 + 2 * d, rs, nullptr, nullptr, 3 * d, hb, 0, nullptr, 0, 0, me, d, 1)) != RPG_OK) return rc;
+            if ((rc = gemm(hb, d, d, B_MSG2, tensors[T_MSG2_B], nullptr, nullptr, nullptr, nullptr, 0, msg, 1, mb, d, 0, me, d, 0)) != RPG_OK) return rc;
+            if ((rc = gemm(mb, d, d, B_GTP, tensors[T_GTP_B], nullptr, nullptr, nullptr, nullptr, 0, gtp, 1, nullptr, 0, 0, me, 3 * c, 0)) != RPG_OK) return rc;
+            if ((rc = rpg_attention_aggregate_f32(gtp, msg, prune ? rowptr_q : rowptr, prune ? perm_q : perm, tensors[T_ATTW_B], mn, me, c, d,
+                                                  yat, att, stream)) != RPG_OK)
+                return rc;
+            if ((rc = rpg::launch_f32_to_bf16(yat, c, yb, c, 0, mn, c, s)) != RPG_OK) return rc;
+            bf* xa = xab;                                     // [mn][2d]: x | aggregate, the input of mlp_updating.0
+            if (prune) {
+                if ((rc = gather16(xab, 4 * d, qn, xabq, 4 * d, 2 * d, nq)) != RPG_OK) return rc;
+                xa = xabq;
+            }
             // att.W on node rows; the aggregate goes straight to the right half of mlp_updating.0's bf16 input
-            if ((rc = gemm(yb, c, c, B_ATTW, nullptr, att, nullptr, nullptr, nullptr, d, nullptr, 0, xab + d, 2 * d, 0, n, d, 0)) != RPG_OK) return rc;
+            if ((rc = gemm(yb, c, c, B_ATTW, nullptr, att, nullptr, nullptr, nullptr, d, nullptr, 0, xa + d, 2 * d, 0, mn, d, 0)) != RPG_OK) return rc;
             // node update                                                              my_gnn_layer.py:309-311
-            if ((rc = gemm(xab, 2 * d, 2 * d, B_UPD0, tensors[T_UPD0_B], nullptr, nullptr, nullptr, nullptr, 0, nhb, 0, nullptr, 0, 0, n, d, 1)) != RPG_OK) return rc;
-            if ((rc = gemm(nhb, d, d, B_UPD2, tensors[T_UPD2_B], nullptr, nullptr, nullptr, nullptr, 0, xnew, 1, xab, 2 * d, 1, n, d, 1)) != RPG_OK) return rc;
+            if ((rc = gemm(xa, 2 * d, 2 * d, B_UPD0, tensors[T_UPD0_B], nullptr, nullptr, nullptr, nullptr, 0, nhb, 0, nullptr, 0, 0, mn, d, 1)) != RPG_OK) return rc;
+            if ((rc = gemm(nhb, d, d, B_UPD2, tensors[T_UPD2_B], nullptr, nullptr, nullptr, nullptr, 0, xnew, 1, prune ? nullptr : xab,
+                           prune ? 0 : 2 * d, 1, mn, d, 1)) != RPG_OK)
+                return rc;
             x = xnew;
         }
-        if (node_out && hipMemcpyAsync(node_out, x, (size_t)n * d * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) {
+        if (qs && gnn_recursion == 0) {                       // no recursion to prune: the heads read rows of the inputs
+            if ((rc = gather16(ecur, d * 4, selc, esel, d * 4, d * 4, es)) != RPG_OK) return rc;
+            if ((rc = gather16(x, d * 4, qn, xq, d * 4, d * 4, nq)) != RPG_OK) return rc;
+            ecur = esel; x = xq;
+        }
+        if (node_out && hipMemcpyAsync(node_out, x, (size_t)n_head * d * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) {
             rpg::set_last_error("gnn_forward node_out", hipGetLastError());
             return RPG_ERR_LAUNCH;
         }
-        if (edge_out && hipMemcpyAsync(edge_out, ecur, (size_t)e * d * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) {
+        if (edge_out && hipMemcpyAsync(edge_out, ecur, (size_t)e_head * d * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) {
             rpg::set_last_error("gnn_forward edge_out", hipGetLastError());
             return RPG_ERR_LAUNCH;
         }
-        if ((rc = rpg_pose_heads_f32(x, tensors[T_HEADN_W], tensors[T_HEADN_B], n, d, abs_pose, stream)) != RPG_OK) return rc;
-        return rpg_pose_heads_f32(ecur, tensors[T_HEADE_W], tensors[T_HEADE_B], e, d, rel_pose, stream);
+        if ((rc = rpg_pose_heads_f32(x, tensors[T_HEADN_W], tensors[T_HEADN_B], n_head, d, abs_pose, stream)) != RPG_OK) return rc;
+        return rpg_pose_heads_f32(ecur, tensors[T_HEADE_W], tensors[T_HEADE_B], e_head, d, rel_pose, stream);
     }
 
     // edge_feat = relu(proj_edge(cat[x[min], x[max]]))                                   posenet.py:1053-1055
@@ -393,62 +470,85 @@ int gnn_forward_impl(const float* const* tensors, int n_tensors, const void* con
 
     const bool dual = !wb;                 // fp32: the edge update is stored twice, raw (for the message) and rectified
     for (int r = 0; r < gnn_recursion; ++r) {                                           // posenet.py:1061-1069
+        // query-only mode, last recursion: nothing reads its output but the heads, so the edge rows are the selected columns and
+        // the node rows the query nodes (the three node terms stay n rows: a selected edge's source is any node)
+        const bool prune = qs && r + 1 == gnn_recursion;
+        const int me = prune ? es : e, mn = prune ? nq : n;
+        const int64_t* rs = prune ? ssrc : src;
+        const int64_t* rd = prune ? sdst : dst;
+        const int32_t* rp = prune ? rowptr_q : rowptr;
+        const int32_t* pm = prune ? perm_q : perm;
         float* enext = (ecur == ebuf[0]) ? ebuf[1] : ebuf[0];    // relu(edge update): the next recursion's / the heads' input
         float* enew = dual ? eraw : enext;                        // the raw edge update (consumed by the message MLP)
         float* xnew = xbuf[r & 1];
+        const float* ein = ecur;
+        if (prune) {
+            if ((rc = rpg::launch_gather_rows16(ecur, d * 4, selc, esel, d * 4, d * 4, es, s)) != RPG_OK) return rc;
+            ein = esel;
+        }
         // edge update: edge_mlp(cat[x[src], x[dst], e])                                 my_gnn_layer.py:296-297
         if (split) {
             if ((rc = node_gemm(x, T_NODE3_W, 3 * d)) != RPG_OK) return rc;              // [n][3d] = [Ws x | Wd x | Wm x]
-            if ((rc = edge_gemm(ecur, T_EDGE0E_W, T_EDGE0_B, node3, src, node3 + d, dst, hid)) != RPG_OK) return rc;
-        } else if ((rc = linear(3, x, src, d, x, dst, d, ecur, nullptr, d, T_EDGE0_W, nullptr, hid, e, d, 1)) != RPG_OK) {
+            if ((rc = edge_gemm(ein, T_EDGE0E_W, T_EDGE0_B, node3, rs, node3 + d, rd, hid, me)) != RPG_OK) return rc;
+        } else if ((rc = linear(3, x, rs, d, x, rd, d, ein, nullptr, d, T_EDGE0_W, nullptr, hid, me, d, 1)) != RPG_OK) {
             return rc;
         }
         // edge_feat = relu(edge_feat) of posenet.py:1065 is the second output of this Linear's epilogue (fp32 path)
-        if ((rc = linear(1, hid, nullptr, d, nullptr, nullptr, 0, nullptr, nullptr, 0, T_EDGE2_W, nullptr, enew, e, d, 0,
+        if ((rc = linear(1, hid, nullptr, d, nullptr, nullptr, 0, nullptr, nullptr, 0, T_EDGE2_W, nullptr, enew, me, d, 0,
                          dual ? enext : nullptr)) != RPG_OK)
             return rc;
         // message: mlp(cat[x[src], e_new]) then AttentionBlock                          my_gnn_layer.py:304-307
         if (split) {
-            if ((rc = edge_gemm(enew, T_MSG0E_W, T_MSG0_B, node3 + 2 * d, src, nullptr, nullptr, hid)) != RPG_OK) return rc;
-        } else if ((rc = linear(2, x, src, d, enew, nullptr, d, nullptr, nullptr, 0, T_MSG0_W, nullptr, hid, e, d, 1)) != RPG_OK) {
+            if ((rc = edge_gemm(enew, T_MSG0E_W, T_MSG0_B, node3 + 2 * d, rs, nullptr, nullptr, hid, me)) != RPG_OK) return rc;
+        } else if ((rc = linear(2, x, rs, d, enew, nullptr, d, nullptr, nullptr, 0, T_MSG0_W, nullptr, hid, me, d, 1)) != RPG_OK) {
             return rc;
         }
-        if ((rc = linear(1, hid, nullptr, d, nullptr, nullptr, 0, nullptr, nullptr, 0, T_MSG2_W, nullptr, msg, e, d, 0)) != RPG_OK) return rc;
-        if ((rc = linear(1, msg, nullptr, d, nullptr, nullptr, 0, nullptr, nullptr, 0, T_GTP_W, nullptr, gtp, e, 3 * c, 0)) != RPG_OK) return rc;
+        if ((rc = linear(1, hid, nullptr, d, nullptr, nullptr, 0, nullptr, nullptr, 0, T_MSG2_W, nullptr, msg, me, d, 0)) != RPG_OK) return rc;
+        if ((rc = linear(1, msg, nullptr, d, nullptr, nullptr, 0, nullptr, nullptr, 0, T_GTP_W, nullptr, gtp, me, 3 * c, 0)) != RPG_OK) return rc;
         if (fuse_agg) {
             // aggregate FIRST (att = W y + b + msg is linear in (y, msg): mean(att) = W mean(y) + b + mean(msg)), in the
             // attention kernel itself, then att.W on the n node rows                    my_gnn_layer.py:301,304-307; att.py:32-33
-            if ((rc = rpg_attention_aggregate_f32(gtp, msg, rowptr, perm, tensors[T_ATTW_B], n, e, c, d, yat, att, stream)) != RPG_OK)
+            if ((rc = rpg_attention_aggregate_f32(gtp, msg, rp, pm, tensors[T_ATTW_B], mn, me, c, d, yat, att, stream)) != RPG_OK)
                 return rc;
-            if ((rc = linear(1, yat, nullptr, c, nullptr, nullptr, 0, nullptr, nullptr, 0, T_ATTW_W, att, agg, n, d, 0, nullptr,
+            if ((rc = linear(1, yat, nullptr, c, nullptr, nullptr, 0, nullptr, nullptr, 0, T_ATTW_W, att, agg, mn, d, 0, nullptr,
                              false)) != RPG_OK)
                 return rc;
         } else {
-            if ((rc = rpg_attention_rows_f32(gtp, e, c, yat, stream)) != RPG_OK) return rc;
-            if ((rc = linear(1, yat, nullptr, c, nullptr, nullptr, 0, nullptr, nullptr, 0, T_ATTW_W, msg, att, e, d, 0)) != RPG_OK) return rc;
+            if ((rc = rpg_attention_rows_f32(gtp, me, c, yat, stream)) != RPG_OK) return rc;
+            if ((rc = linear(1, yat, nullptr, c, nullptr, nullptr, 0, nullptr, nullptr, 0, T_ATTW_W, msg, att, me, d, 0)) != RPG_OK) return rc;
             // aggregate (mean over incoming edges)                                       my_gnn_layer.py:301
-            if ((rc = rpg_scatter_mean_f32(att, rowptr, perm, n, e, d, agg, stream)) != RPG_OK) return rc;
+            if ((rc = rpg_scatter_mean_f32(att, rp, pm, mn, me, d, agg, stream)) != RPG_OK) return rc;
         }
         // node update                                                                   my_gnn_layer.py:309-311
-        if ((rc = linear(2, x, nullptr, d, agg, nullptr, d, nullptr, nullptr, 0, T_UPD0_W, nullptr, nhid, n, d, 1)) != RPG_OK) return rc;
-        if ((rc = linear(1, nhid, nullptr, d, nullptr, nullptr, 0, nullptr, nullptr, 0, T_UPD2_W, nullptr, xnew, n, d, 1)) != RPG_OK) return rc;
+        const float* xin = x;
+        if (prune) {
+            if ((rc = rpg::launch_gather_rows16(x, d * 4, qn, xq, d * 4, d * 4, nq, s)) != RPG_OK) return rc;
+            xin = xq;
+        }
+        if ((rc = linear(2, xin, nullptr, d, agg, nullptr, d, nullptr, nullptr, 0, T_UPD0_W, nullptr, nhid, mn, d, 1)) != RPG_OK) return rc;
+        if ((rc = linear(1, nhid, nullptr, d, nullptr, nullptr, 0, nullptr, nullptr, 0, T_UPD2_W, nullptr, xnew, mn, d, 1)) != RPG_OK) return rc;
         // x = relu(x) is fused above; edge_feat = relu(edge_feat): dual-stored above, or in place now that the message has
         // consumed the raw one (bf16 Linears)
-        if (!dual && (rc = rpg::launch_relu_inplace(enext, (long)e * d, s)) != RPG_OK) return rc;
+        if (!dual && (rc = rpg::launch_relu_inplace(enext, (long)me * d, s)) != RPG_OK) return rc;
         x = xnew;
         ecur = enext;
     }
-    if (node_out && hipMemcpyAsync(node_out, x, (size_t)n * d * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) {
+    if (qs && gnn_recursion == 0) {                           // no recursion to prune: the heads read rows of the inputs
+        if ((rc = rpg::launch_gather_rows16(ecur, d * 4, selc, esel, d * 4, d * 4, es, s)) != RPG_OK) return rc;
+        if ((rc = rpg::launch_gather_rows16(x, d * 4, qn, xq, d * 4, d * 4, nq, s)) != RPG_OK) return rc;
+        ecur = esel; x = xq;
+    }
+    if (node_out && hipMemcpyAsync(node_out, x, (size_t)n_head * d * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) {
         rpg::set_last_error("gnn_forward node_out", hipGetLastError());
         return RPG_ERR_LAUNCH;
     }
-    if (edge_out && hipMemcpyAsync(edge_out, ecur, (size_t)e * d * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) {
+    if (edge_out && hipMemcpyAsync(edge_out, ecur, (size_t)e_head * d * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) {
         rpg::set_last_error("gnn_forward edge_out", hipGetLastError());
         return RPG_ERR_LAUNCH;
     }
     // heads (droprate == 0, use_AP)                                                     posenet.py:1077-1091
-    if ((rc = rpg_pose_heads_f32(x, tensors[T_HEADN_W], tensors[T_HEADN_B], n, d, abs_pose, stream)) != RPG_OK) return rc;
-    return rpg_pose_heads_f32(ecur, tensors[T_HEADE_W], tensors[T_HEADE_B], e, d, rel_pose, stream);
+    if ((rc = rpg_pose_heads_f32(x, tensors[T_HEADN_W], tensors[T_HEADN_B], n_head, d, abs_pose, stream)) != RPG_OK) return rc;
+    return rpg_pose_heads_f32(ecur, tensors[T_HEADE_W], tensors[T_HEADE_B], e_head, d, rel_pose, stream);
 }
 }  // namespace
 
@@ -469,4 +569,30 @@ extern "C" int rpg_gnn_forward_bf16(const float* const* tensors, int n_tensors, 
         if (!weights_bf16[i]) return RPG_ERR_BAD_ARG;
     return gnn_forward_impl(tensors, n_tensors, weights_bf16, feat, esrc, edst, node_offset, n, e, d, gnn_recursion, abs_pose,
                             rel_pose, node_out, edge_out, status, workspace, workspace_bytes, stream);
+}
+
+// The query-only output mode: abs_pose [q][6] of `qnodes`, rel_pose [e_sel][6] of the columns `sel` (node_out [q][d], edge_out
+// [e_sel][d]).  Everything up to the last recursion runs as in rpg_gnn_forward_*; the last recursion runs its edge rows on the
+// selection and its node rows on the query nodes (see query_select.hip).
+extern "C" int rpg_gnn_forward_query_f32(const float* const* tensors, int n_tensors, const float* feat, const int64_t* esrc,
+                                         const int64_t* edst, int64_t node_offset, int n, int e, int d, int gnn_recursion,
+                                         const int64_t* sel, int e_sel, const int64_t* qnodes, int q, float* abs_pose, float* rel_pose,
+                                         float* node_out, float* edge_out, int32_t* status, void* workspace, size_t workspace_bytes,
+                                         void* stream) {
+    const QuerySel qs{sel, e_sel, qnodes, q};
+    return gnn_forward_impl(tensors, n_tensors, nullptr, feat, esrc, edst, node_offset, n, e, d, gnn_recursion, abs_pose, rel_pose,
+                            node_out, edge_out, status, workspace, workspace_bytes, stream, &qs);
+}
+
+extern "C" int rpg_gnn_forward_query_bf16(const float* const* tensors, int n_tensors, const void* const* weights_bf16, int n_bf16,
+                                          const float* feat, const int64_t* esrc, const int64_t* edst, int64_t node_offset, int n, int e,
+                                          int d, int gnn_recursion, const int64_t* sel, int e_sel, const int64_t* qnodes, int q,
+                                          float* abs_pose, float* rel_pose, float* node_out, float* edge_out, int32_t* status,
+                                          void* workspace, size_t workspace_bytes, void* stream) {
+    if (!weights_bf16 || n_bf16 != B_COUNT || (d & 63)) return RPG_ERR_BAD_ARG;
+    for (int i = 0; i < B_COUNT; ++i)
+        if (!weights_bf16[i]) return RPG_ERR_BAD_ARG;
+    const QuerySel qs{sel, e_sel, qnodes, q};
+    return gnn_forward_impl(tensors, n_tensors, weights_bf16, feat, esrc, edst, node_offset, n, e, d, gnn_recursion, abs_pose,
+                            rel_pose, node_out, edge_out, status, workspace, workspace_bytes, stream, &qs);
 }

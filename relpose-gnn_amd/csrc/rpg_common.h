@@ -156,6 +156,15 @@ int launch_linear(const GatherSrc& src, const float* weight, const float* bias, 
                   int m, int n_out, int relu, hipStream_t s, const GatherRes* gres = nullptr, float* out_relu = nullptr);
 int launch_gather_add2_relu(const float* pq, const int64_t* lo, const int64_t* hi, const float* bias, float* out, int e,
                             int d, hipStream_t s);
+// query_select.hip: the query-only output mode of the GNN composite.  launch_query_select checks a selection of edge columns and
+// query nodes against its contract (violations counted into status, everything clamped) and builds its CSR by query row;
+// launch_gather_rows16 copies rows out[i] = in[idx[i]] in 16-byte units (row pitches and width in bytes, multiples of 16).
+int launch_query_select(const int64_t* esrc, const int64_t* edst, int64_t node_off, int e, int n, const int64_t* ends,
+                        const int64_t* sel, int e_sel, const int64_t* qnodes, int q, int32_t* qrow, int32_t* selc, int64_t* ssrc,
+                        int64_t* sdst, int32_t* srow, int32_t* qn, int32_t* rowptr, int32_t* cursor, int32_t* perm, int32_t* status,
+                        hipStream_t s);
+int launch_gather_rows16(const void* in, int ld_in_bytes, const int32_t* idx, void* out, int ld_out_bytes, int row_bytes, long rows,
+                         hipStream_t s);
 bool gnn_split_enabled();
 bool gnn_fuse_agg_enabled();
 void bf16_set_bk(int bk);

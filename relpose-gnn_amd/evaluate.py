@@ -360,7 +360,8 @@ def load_pose_stats(path):
 def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch: int = 64, pose_m=(0.0, 0.0, 0.0),
                pose_s=(1.0, 1.0, 1.0), ref_node: int = 0, stats: Optional[dict] = None, targets=None,
                bf16_input: Optional[bool] = None, *, rule=None, query_descriptors=None, query_groups=None,
-               postprocess: str = "host", fuse: Optional[str] = None, max_edges: int = 64, capture: bool = False):
+               postprocess: str = "host", fuse: Optional[str] = None, max_edges: int = 64, capture: bool = False,
+               outputs: str = "all"):
     """The evaluation stream of the map path (``PoseNetX_R2.forward_map``): query g's graph is the query followed by the map
     rows ``neighbours[g]`` (its retrieved database images, dataset_7Scenes_multi.py:340-345).  Single process.
 
@@ -395,8 +396,28 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
     results are bit-identical to ``capture=False``.  The captured steps are kept on the model (``refresh_packed`` drops them; a
     step whose map has been extended is captured again), so a second call with the same shapes captures nothing.  What that
     class refuses (``droprate > 0``, ``knn > 0``, ``use_attention``, ``use_AP=False``, uint8 queries) raises here, before any
-    work is queued.  ``stats`` also receives ``graphs_captured`` (by this call) and ``graph_replays``."""
+    work is queued.  ``stats`` also receives ``graphs_captured`` (by this call) and ``graph_replays``.
+
+    ``outputs="query"`` (default ``"all"``): every micro-batch runs ``forward_map(outputs="query")``, which computes only what
+    the pose rule reads -- the K relative poses into each query and the query's absolute pose -- and prunes the GNN's last
+    recursion accordingly (which see, also for what it does not serve: those raise here, before any work is queued; an unknown
+    value raises ValueError).  Same return types and, row for row, the poses of ``"all"`` up to GEMM summation order; the host
+    rule then reads the reduced list (K columns per query, sources 1..K), so ``postprocess="host"`` copies K (K + 1) / K times
+    fewer relative poses back (``stats["d2h_bytes"]``), and ``ref_node`` / ``fuse`` / ``rule`` / ``capture`` combine as before
+    (a captured ``"all"`` step is never replayed for ``"query"``, nor the reverse).  A map without poses then returns the REDUCED
+    raw tensors ``(abs_pose [G, 6], rel_pose [G*K, 6])``.  A map that is not on a GPU takes the synchronous path as for ``"all"``:
+    the model's ``forward_map`` is called with ``outputs="query"`` and the host rule reads what it returns (``PoseNetX_R2`` itself
+    has no CPU compute path and raises there)."""
     device = fmap.device
+    if outputs not in ("all", "query"):
+        raise ValueError(f"relocalize: outputs must be 'all' or 'query', got {outputs!r}")
+    if outputs == "query":
+        check = getattr(model, "_check_outputs", None)
+        if check is not None:
+            check(outputs, None)
+        elif getattr(model, "knn", -1) > 0:
+            raise NotImplementedError("relocalize(outputs='query') does not serve knn > 0 (a model-built kNN graph)")
+    okw = {} if outputs == "all" else {"outputs": outputs}          # a model without the argument keeps serving "all"
     if not isinstance(capture, bool):
         raise TypeError(f"relocalize: capture must be a bool, got {type(capture).__name__}")
     if not torch.is_tensor(queries):
@@ -442,6 +463,9 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
     poses_h = None if fmap.poses is None else fmap.poses.cpu().numpy().astype(np.float64)
     targ_h = None if targets is None else np.asarray(torch.as_tensor(targets).cpu(), dtype=np.float64).reshape(g_all, 6)
     fc_edges = fc_edge_index(n_per).numpy()
+    if outputs == "query":         # the columns forward_map(outputs="query") keeps of every graph: those into node 0, in order
+        fc_edges = fc_edges[:, fc_edges[1] == 0]
+    rows_per = 1 if outputs == "query" else n_per             # rows of abs_pose per graph
     qp = targ_dev = fc_first = None
     captured = model._map_captures if capture else None
     n_captured = n_replays = 0
@@ -468,7 +492,7 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
         now with the micro-batch itself as the example."""
         nonlocal n_captured
         key = ("step", tuple(x.shape), x.dtype, kk, None if rule is None else (rule.sampling_period, rule.random), postprocess,
-               fuse, max_edges, qd is not None, targ is not None)
+               fuse, max_edges, qd is not None, targ is not None, outputs)
         step = captured.get(key)
         if step is None or step.fmap is not fmap or step.pose is not qp or step.stale():
             if len(captured) >= 16:
@@ -476,7 +500,7 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
                 if qp is not None:
                     captured[qp_key] = qp
             step = captured[key] = GraphedForwardMap(model, fmap, x, kk, rule=rule, query_descriptors=qd, pose=qp,
-                                                     pose_kwargs=None if targ is None else {"query_targets": targ})
+                                                     pose_kwargs=None if targ is None else {"query_targets": targ}, **okw)
             n_captured += 1
         return step
 
@@ -486,7 +510,7 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
         nonlocal n_replays
         b0, b1 = chunk[0].first, chunk[0].first + x.shape[0]
         if rule is None and not capture:
-            ab, rel, ei = model.forward_map(x, nb_dev[b0:b1], fmap)
+            ab, rel, ei = model.forward_map(x, nb_dev[b0:b1], fmap, **okw)
             return ab, rel, ei, nb_dev[b0:b1], None, None
         qd = None
         if qd_all is not None:
@@ -511,10 +535,10 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
             # the replay ran on BEFORE the next launch() enqueues its replay there: stream order keeps micro-batch i's results.
             return (out.abs_pose, out.rel_pose, out.edge_index, out.neighbours,
                     None if rule is None else runner.read_back(out.neighbours), out.rows)
-        ab, rel, ei, nb_mb = model.forward_map(x, None, fmap, rule=rule, query_descriptors=qd, query_groups=qg)
+        ab, rel, ei, nb_mb = model.forward_map(x, None, fmap, rule=rule, query_descriptors=qd, query_groups=qg, **okw)
         return ab, rel, ei, nb_mb, runner.read_back(nb_mb), None
 
-    def outputs(chunk, x, fwd):
+    def read_back_of(chunk, x, fwd):
         ab, rel, ei, nb_mb, host_nb, rows = fwd
         if qp is None:
             return {"nb": host_nb, "abs": ab, "rel": rel, "ei": ei if model.knn > 0 else None}
@@ -541,13 +565,13 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
             raw_abs.append(host["abs"])
             raw_rel.append(host["rel"])
         else:
-            n_g = host["abs"].shape[0] // n_per
+            n_g = host["abs"].shape[0] // rows_per
             ei = None if host["ei"] is None else host["ei"].numpy()      # a model-built (kNN) edge list
             acc.add(host["rel"].numpy(), (target_block(g) for g in range(b0, b0 + n_g)), cut_per_graph([n_per] * n_g, ei, [fc_edges] * n_g))
 
     # only the queries are staged, by the rules of evaluate_stream; everything else of a micro-batch goes inside its launch
     runner = _MicroBatchRunner(model, device, micro_batch, bf16_input, pose=qp, collate=lambda chunk, x_dev: chunk[0].x if x_dev is None else x_dev,
-                               forward=forward, outputs=outputs, capacity=min(micro_batch, g_all))
+                               forward=forward, outputs=read_back_of, capacity=min(micro_batch, g_all))
     runner.run(-(-g_all // micro_batch), lambda i: runner.pieces(queries[i * micro_batch:(i + 1) * micro_batch], i * micro_batch),
                finish, stats, postprocess)
     if stats is not None:

@@ -24,6 +24,18 @@ def fc_edge_index(n: int) -> torch.Tensor:
     return torch.cat([torch.stack([src, dst]), torch.stack([dst, src])], dim=1).to(torch.int64)
 
 
+def query_edge_columns(edge_index, query_nodes) -> torch.Tensor:
+    """HOST: the columns of ``edge_index`` [2, E] whose target is one of ``query_nodes``, ascending, int64 -- what the pose rule of
+    test.py:227-232 reads when those nodes are the queries, and the ``sel`` of the query-only GNN forward
+    (rpg_gnn_forward_query_*).  Self-loops and repeated edges are columns like any other.  For ``fc_batch`` graphs of n = K + 1
+    nodes with the queries g n these are G K columns, graph after graph, with sources g n + 1 .. g n + K in that order."""
+    ei = torch.as_tensor(edge_index).cpu()
+    if ei.dim() != 2 or ei.shape[0] != 2:
+        raise ValueError(f"query_edge_columns: edge_index must be [2, E], got {tuple(ei.shape)}")
+    q = torch.as_tensor(query_nodes).cpu().reshape(-1).to(torch.int64)
+    return torch.isin(ei[1].to(torch.int64), q).nonzero().flatten()
+
+
 class Data:
     """One graph: x [n, 3*H*W], edge_index [2, E], y [n, 6], edge_attr [E, 6] (or None)."""
 

@@ -89,7 +89,10 @@ class GraphedForwardMap:
     own explicit-``k`` kNN graph is not offered at all (there is no argument for it).
     ``query_descriptors`` fp32 [G, Dd]: an example, for a map that holds its own retrieval descriptors.
     ``pose_kwargs``: ``query_targets`` (an example fp32 [G, 6]; absent: the rows' target part is zeros) and ``edge_first`` (int64
-    [G + 1]; absent: the cut of forward_map's own fully-connected list, K (K + 1) columns per graph).
+    [G + 1]; absent: the cut of forward_map's own fully-connected list, K (K + 1) columns per graph -- K per graph with
+    ``outputs="query"``).
+    ``outputs``: ``forward_map``'s -- ``"query"`` captures the query-only step, whose outputs are abs_pose [G, 6], rel_pose
+    [G K, 6] and the G K edges into the query nodes; what that mode does not serve raises as it does there.
 
     The graph reads the packed weights, the workspaces, the map's tensors and the counters in place.  All of them are held
     here, so nothing it reads is freed under it, and every call compares them with what the model and the map hold NOW:
@@ -97,8 +100,9 @@ class GraphedForwardMap:
     ``RuntimeError`` instead of replaying over storage that is no longer the model's or the map's."""
 
     def __init__(self, model, fmap, example_queries: torch.Tensor, k: Optional[int] = None, *, rule=None, query_descriptors=None,
-                 pose=None, pose_kwargs: Optional[dict] = None, warmup: int = 2):
+                 pose=None, pose_kwargs: Optional[dict] = None, warmup: int = 2, outputs: str = "all"):
         self.refuse(model, example_queries)
+        model._check_outputs(outputs, None)
         q = example_queries
         if not q.is_cuda or q.device != fmap.device:
             raise RuntimeError("GraphedForwardMap needs the queries and the feature map on the same GPU")
@@ -126,7 +130,7 @@ class GraphedForwardMap:
             raise ValueError(f"GraphedForwardMap: pose_kwargs takes query_targets and edge_first, got {sorted(unknown)}")
         dev = q.device
         self.model, self.fmap, self.rule, self.pose = model, fmap, rule, pose
-        self.g, self.k = g, k
+        self.g, self.k, self.outputs = g, k, outputs
 
         # ---- the static inputs --------------------------------------------------------------------------------------------------
         self.queries = q.detach().clone(memory_format=torch.contiguous_format)
@@ -159,7 +163,7 @@ class GraphedForwardMap:
                 ef = pose_kwargs["edge_first"]
                 self.edge_first = None if ef is None else ef.detach().to(device=dev, dtype=torch.int64).contiguous().clone()
             else:
-                self.edge_first = torch.arange(g + 1, dtype=torch.int64, device=dev) * (k * (k + 1))
+                self.edge_first = torch.arange(g + 1, dtype=torch.int64, device=dev) * (k if outputs == "query" else k * (k + 1))
 
         # ---- warm-up, validation, capture (the pattern of GraphedForward) ---------------------------------------------------------
         self.graph = torch.cuda.CUDAGraph()
@@ -195,11 +199,11 @@ class GraphedForwardMap:
     def _step(self) -> MapStep:
         m = self.model
         if self.rule is None:
-            ab, rel, ei = m.forward_map(self.queries, self.neighbours, self.fmap)
+            ab, rel, ei = m.forward_map(self.queries, self.neighbours, self.fmap, outputs=self.outputs)
             nb = self.neighbours
         else:
             ab, rel, ei, nb = m.forward_map(self.queries, None, self.fmap, rule=self.rule, query_descriptors=self.query_descriptors,
-                                            _static=(self.ranks, self.query_groups))
+                                            outputs=self.outputs, _static=(self.ranks, self.query_groups))
         rows = None
         if self.pose is not None:
             rows = self.pose.from_map(rel, ei, self.fmap, nb, query_targets=self.query_targets, edge_first=self.edge_first)
@@ -212,6 +216,8 @@ class GraphedForwardMap:
         return {"library": L.lib(), "encoder": m._enc._packed, "gnn": m._gnn_packed, "gnn_bf16": m._gnn_bf16,
                 "dtypes": (m.encoder_dtype, m.gnn_dtype), "workspaces": list(m._ws_pool._buf.values()),
                 "fc_graph": m._map_graphs.get((self.g, self.k + 1, str(self.queries.device))),
+                "query_sel": (m._map_queries.get((self.g, self.k + 1, str(self.queries.device)))
+                              if self.outputs == "query" else None),
                 "counters": m._counters.counters, "pose_counters": None if self.pose is None else self.pose._bad.counters,
                 "features": f.features, "poses": f.poses, "descriptors": f.descriptors, "groups": f.groups,
                 "inv_norms": f._inv_norms if self.rule is not None else None}

@@ -823,6 +823,60 @@ def pose_heads(x: torch.Tensor, w6: torch.Tensor, b6: torch.Tensor, out: Optiona
     return out
 
 
+def gnn_forward_query(tensors: Sequence[torch.Tensor], feat: torch.Tensor, edge_index: torch.Tensor, sel: torch.Tensor,
+                      qnodes: torch.Tensor, gnn_recursion: int = 2, weights_bf16: Optional[Sequence[torch.Tensor]] = None,
+                      node_offset: int = 0, want_features: bool = False, status: Optional[torch.Tensor] = None,
+                      workspace: Optional[torch.Tensor] = None):
+    """The GNN and its heads in the query-only output mode (rpg_gnn_forward_query_f32, or _bf16 with ``weights_bf16`` from
+    params.pack_gnn_bf16): ``tensors`` from params.pack_gnn (22 or 26), feat [n, d], edge_index int64 [2, e], ``sel`` int64
+    [e_sel] -- ascending, exactly the valid columns whose target is in ``qnodes`` (graph.query_edge_columns) -- and ``qnodes``
+    int64 [q], ascending node ids -> (abs_pose [q, 6] of qnodes, rel_pose [e_sel, 6] of the sel columns), and with
+    ``want_features`` also (node_out [q, d], edge_out [e_sel, d]), the heads' inputs.  Every row is what the full forward gives
+    there; the last recursion only runs on the selected columns and the query rows.
+
+    A selection that breaks the contract (a column outside [0, e), one graph_prepare leaves out, one whose target is no query
+    node, columns that do not ascend, a count other than the edges into the query nodes, qnodes not ascending / distinct / in
+    range) and a bad edge are counted into ``status`` (int32 device tensor, accumulates; everything is clamped) -- with
+    ``status=None`` the count is read back here (one synchronisation) and a non-zero count raises IndexError.  ``workspace``: a
+    uint8 device tensor to use instead of allocating one."""
+    feat, ei = _req(feat, "feat"), _req(edge_index, "edge_index", torch.int64)
+    sel, qnodes = _req(sel, "sel", torch.int64), _req(qnodes, "qnodes", torch.int64)
+    if feat.dim() != 2 or ei.dim() != 2 or ei.shape[0] != 2 or sel.dim() != 1 or qnodes.dim() != 1:
+        raise ValueError("gnn_forward_query: feat [n, d], edge_index [2, e], sel [e_sel] and qnodes [q]")
+    (n, d), e, es, q = feat.shape, ei.shape[1], sel.numel(), qnodes.numel()
+    if not (1 <= es <= e and 1 <= q <= n) or d % 32:
+        raise ValueError(f"gnn_forward_query: needs 1 <= e_sel <= e, 1 <= q <= n and d % 32 == 0 (e_sel={es}, e={e}, q={q}, n={n}, d={d})")
+    dev = feat.device
+    if any(t.device != dev for t in (ei, sel, qnodes)):
+        raise RuntimeError("gnn_forward_query: feat, edge_index, sel and qnodes must be on the same GPU")
+    keep = [_req(t, f"tensors[{i}]") for i, t in enumerate(tensors)]
+    lib = L.lib()
+    need = int(lib.rpg_gnn_query_workspace_bytes(n, e, d, es, q))
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif workspace.dtype != torch.uint8 or workspace.device != dev or not workspace.is_contiguous():
+        raise ValueError("gnn_forward_query: workspace must be a contiguous uint8 tensor on the inputs' GPU")
+    abs_pose = torch.empty((q, 6), dtype=torch.float32, device=dev)
+    rel_pose = torch.empty((es, 6), dtype=torch.float32, device=dev)
+    node_out = torch.empty((q, d), dtype=torch.float32, device=dev) if want_features else None
+    edge_out = torch.empty((es, d), dtype=torch.float32, device=dev) if want_features else None
+    status, own = _status_arg(status, dev, "gnn_forward_query")
+    weights = (L.ptr_array([t.data_ptr() for t in keep]), len(keep))
+    fn = lib.rpg_gnn_forward_query_f32
+    if weights_bf16 is not None:
+        keep_bf = [_req(t, f"weights_bf16[{i}]", torch.bfloat16) for i, t in enumerate(weights_bf16)]
+        weights += (L.ptr_array([t.data_ptr() for t in keep_bf]), len(keep_bf))
+        fn = lib.rpg_gnn_forward_query_bf16
+    L.check(fn(*weights, _p(feat), ei.data_ptr(), ei.data_ptr() + 8 * e, int(node_offset), n, e, d, int(gnn_recursion), _p(sel), es,
+               _p(qnodes), q, _p(abs_pose), _p(rel_pose), _p(node_out), _p(edge_out), status.data_ptr(), workspace.data_ptr(),
+               workspace.numel(), _stream()), "gnn_forward_query")
+    bad = _own_count(status, own)
+    if bad:
+        raise IndexError(f"gnn_forward_query: {bad} violation(s) of the index contract: an edge with a node id outside [0, n), or a "
+                         "selection that is not exactly the ascending valid columns into the ascending, distinct query nodes")
+    return (abs_pose, rel_pose, node_out, edge_out) if want_features else (abs_pose, rel_pose)
+
+
 def timing_enable(on: bool) -> None:
     L.check(L.lib().rpg_timing_enable(int(on)), "timing_enable")
 

@@ -157,6 +157,8 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
         self.frame_transform = None
         self._enc_digest: Optional[str] = None        # encoder_digest() cache (cleared wherever the packed weights are)
         self._map_graphs: Dict[tuple, Tuple[torch.Tensor, torch.Tensor]] = {}   # forward_map: (G, K+1, device) -> (edges, batch)
+        # forward_map(outputs="query"): same key -> (selected columns [G K], query nodes [G], the selected edges [2, G K])
+        self._map_queries: Dict[tuple, Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = {}
         # relocalize(capture=True): its captured micro-batch steps (graphed.GraphedForwardMap) and the pose rules they were
         # captured with, by shape / configuration; dropped with the packed weights, which every captured step reads
         self._map_captures: Dict[tuple, object] = {}
@@ -269,17 +271,27 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
         return bool(self.use_AP and not self.use_attention and k is None and knn_ok
                     and not (self.knn > 0 and self._gnn_dtype == "bf16"))
 
-    def _gnn_call(self, lib, feat, esrc_ptr, edst_ptr, node_off, n, e, abs_pose, rel_pose, node_f, edge_f, status, slot):
+    def _gnn_call(self, lib, feat, esrc_ptr, edst_ptr, node_off, n, e, abs_pose, rel_pose, node_f, edge_f, status, slot, query=None):
+        """``query``: None, or (sel int64 [e_sel], qnodes int64 [q]) -- the query-only output mode (rpg_gnn_forward_query_*):
+        the outputs then have q / e_sel rows."""
         d = feat.shape[1]
         # the slot's workspace (resnet.WorkspacePool): the SAME buffer the encoder call of this slot used a moment ago on
         # this stream -- stream order makes the reuse safe, and the split-K scratch slice exists once per slot
-        ws = self._ws_pool.get(slot, lib.rpg_gnn_workspace_bytes(n, e, d), feat.device)
+        bf16 = self._gnn_dtype == "bf16"
         weights = (self._gnn_ptrs, len(self._gnn_packed))
-        fn, name = lib.rpg_gnn_forward_f32, "gnn_forward"
-        if self._gnn_dtype == "bf16":
+        if bf16:
             weights += (self._gnn_bf16_ptrs, len(self._gnn_bf16))
-            fn, name = lib.rpg_gnn_forward_bf16, "gnn_forward_bf16"
-        rc = fn(*weights, feat.data_ptr(), esrc_ptr, edst_ptr, node_off, n, e, d, int(self.gnn_recursion), abs_pose.data_ptr(),
+        if query is None:
+            ws = self._ws_pool.get(slot, lib.rpg_gnn_workspace_bytes(n, e, d), feat.device)
+            fn, name = (lib.rpg_gnn_forward_bf16, "gnn_forward_bf16") if bf16 else (lib.rpg_gnn_forward_f32, "gnn_forward")
+            sel_args = ()
+        else:
+            sel, qn = query
+            ws = self._ws_pool.get(slot, lib.rpg_gnn_query_workspace_bytes(n, e, d, sel.numel(), qn.numel()), feat.device)
+            fn, name = ((lib.rpg_gnn_forward_query_bf16, "gnn_forward_query_bf16") if bf16
+                        else (lib.rpg_gnn_forward_query_f32, "gnn_forward_query"))
+            sel_args = (sel.data_ptr(), sel.numel(), qn.data_ptr(), qn.numel())
+        rc = fn(*weights, feat.data_ptr(), esrc_ptr, edst_ptr, node_off, n, e, d, int(self.gnn_recursion), *sel_args, abs_pose.data_ptr(),
                 rel_pose.data_ptr(), None if node_f is None else node_f.data_ptr(),
                 None if edge_f is None else edge_f.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(),
                 torch.cuda.current_stream().cuda_stream)
@@ -403,8 +415,9 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
         feat = self._encode_small(x)                                              # posenet.py:1037
         return self._forward_tail(lib, feat, edge_index, getattr(data, "batch", None), k)
 
-    def _forward_tail(self, lib, feat, edge_index, batch, k):
-        """Everything after the encoder on one stream (posenet.py:1040-1091): feat [N, d] are the node features."""
+    def _forward_tail(self, lib, feat, edge_index, batch, k, query=None):
+        """Everything after the encoder on one stream (posenet.py:1040-1091): feat [N, d] are the node features.  ``query``: None,
+        or forward_map's (selected columns, query nodes, selected edges) -- the outputs then cover those rows only."""
         n, d = feat.shape
         if self.use_attention:                                                    # posenet.py:1040-1041
             ex = self._extra
@@ -424,19 +437,23 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
         ei = edge_index.contiguous()
         e = ei.size(1)
         dev = feat.device
-        abs_pose = torch.empty((n, 6), dtype=torch.float32, device=dev)
-        rel_pose = torch.empty((e, 6), dtype=torch.float32, device=dev)
+        n_out, e_out = (n, e) if query is None else (query[1].numel(), query[0].numel())
+        abs_pose = torch.empty((n_out, 6), dtype=torch.float32, device=dev)
+        rel_pose = torch.empty((e_out, 6), dtype=torch.float32, device=dev)
         status = self._counters.counters[0:1]
         drop = self.droprate > 0
         want_feats = drop or not self.use_AP
-        node_f = torch.empty((n, d), dtype=torch.float32, device=dev) if want_feats else None
-        edge_f = torch.empty((e, d), dtype=torch.float32, device=dev) if drop else None
-        self._gnn_call(lib, feat, ei.data_ptr(), ei.data_ptr() + 8 * e, 0, n, e, abs_pose, rel_pose, node_f, edge_f, status, 0)
+        node_f = torch.empty((n_out, d), dtype=torch.float32, device=dev) if want_feats else None
+        edge_f = torch.empty((e_out, d), dtype=torch.float32, device=dev) if drop else None
+        self._gnn_call(lib, feat, ei.data_ptr(), ei.data_ptr() + 8 * e, 0, n, e, abs_pose, rel_pose, node_f, edge_f, status, 0,
+                       None if query is None else query[:2])
 
         self.publish_status()                     # every call is validated; nothing blocks in "deferred" mode
 
         if drop:
             node_f = self._drop_heads(node_f, edge_f, abs_pose, rel_pose)
+        if query is not None:                     # use_AP, no kNN graph: refused by forward_map otherwise
+            return abs_pose, rel_pose, query[2].clone()
         if not self.use_AP:                                                       # posenet.py:1080-1083
             # index plumbing (compute_edge_features).  Clamped like the GNN's own copy of the end points (rpg_graph_prepare):
             # with index_check="deferred" an out-of-range node id is REPORTED by the device-side counter (IndexError at the
@@ -488,9 +505,45 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
             self._map_graphs[key] = hit
         return hit
 
+    def _map_query(self, g: int, n_per: int, dev) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """(sel int64 [G K], qnodes int64 [G], edges [2, G K]) of ``_map_graph``'s list on ``dev``: the columns whose target is a
+        query node g n, ascending (graph.query_edge_columns), the query nodes, and those columns of the list.  Graph after graph
+        the list repeats one pattern, so the first j K entries of ``sel`` are the selection of any j consecutive graphs."""
+        key = (g, n_per, str(dev))
+        hit = self._map_queries.get(key)
+        if hit is None:
+            from .graph import query_edge_columns
+            edges = self._map_graph(g, n_per, dev)[0]
+            qn = torch.arange(g, dtype=torch.int64) * n_per
+            sel = query_edge_columns(edges.cpu(), qn).to(dev)
+            hit = (sel, qn.to(dev), edges[:, sel].contiguous())
+            if len(self._map_queries) >= 16:
+                self._map_queries.clear()
+            self._map_queries[key] = hit
+        return hit
+
+    def _check_outputs(self, outputs, k) -> None:
+        """``forward_map``'s ``outputs``: an unknown value and what the query-only mode does not serve raise here, before anything
+        is queued."""
+        if outputs not in ("all", "query"):
+            raise ValueError(f"forward_map: outputs must be 'all' or 'query', got {outputs!r}")
+        if outputs == "all":
+            return
+        why = "the selected columns would depend on the features"
+        if self.knn > 0:
+            raise NotImplementedError(f"forward_map(outputs='query') does not serve knn > 0 (a model-built kNN graph: {why})")
+        if k is not None:
+            raise NotImplementedError(f"forward_map(outputs='query') does not serve an explicit k (a kNN graph: {why})")
+        if self.use_attention:
+            raise NotImplementedError("forward_map(outputs='query') does not serve use_attention (the one-stream path, which "
+                                      "allocates between its launches)")
+        if not self.use_AP:
+            raise NotImplementedError("forward_map(outputs='query') does not serve use_AP=False (its absolute poses are per edge, "
+                                      "from pair features of all nodes)")
+
     @torch.no_grad()
     def forward_map(self, queries: torch.Tensor, neighbours: Optional[torch.Tensor], fmap, k=None, *, rule=None,
-                    query_descriptors: Optional[torch.Tensor] = None, query_groups=None, _static=None):
+                    query_descriptors: Optional[torch.Tensor] = None, query_groups=None, outputs: str = "all", _static=None):
         """The forward of G graphs, each query g followed by the K database images ``neighbours[g]`` of the feature map ``fmap``
         (dataset_7Scenes_multi.py:340-345) -- with only the G queries through the encoder.  Returns what
         ``forward(fc_batch(assembled, K + 1), k)`` returns for the assembled images: (abs_pose [G*(K+1), 6], rel_pose [E, 6],
@@ -506,14 +559,26 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
         to a query's group are left out; -1 leaves nothing out.  Nothing blocks: the ranks are made on the host before the
         launch, and a rank the map cannot serve is reported like a bad neighbour.
 
+        ``outputs="query"`` (default ``"all"``) returns only what the pose rule of the map path reads (test.py:227-232): (abs_pose
+        [G, 6] of the queries, rel_pose [G*K, 6], edge_index [2, G*K]) -- the columns of the full list whose target is a query node,
+        in the full list's order (graph g's sources are g(K+1)+1 .. g(K+1)+K, in that order), node ids unchanged, and with a
+        ``rule`` the neighbours as the fourth element, as before.  The last recursion of the GNN then runs its edge rows on those
+        K of K(K+1) columns per graph and its node rows on the queries only (rpg_gnn_forward_query_*): every value is the one
+        ``outputs="all"`` gives at the same row, up to the summation order of differently tiled GEMMs.  Same two-stream schedule,
+        same workspace pool.  ``droprate > 0`` is served as for ``"all"``, but ``F.dropout`` is drawn over [G, D] and [G*K, D], so a
+        seeded run draws OTHER masks than the full forward does.  ``knn > 0``, an explicit ``k``, ``use_attention`` and
+        ``use_AP=False`` raise NotImplementedError (the selection would depend on the data, or the path allocates between its
+        launches); an unknown value raises ValueError.
+
         ``_static`` (graphed.GraphedForwardMap only): ``(ranks int32 [G, K], query groups int64 [G] or None)`` already on the
         device, read in place of the two per-call host products above, so that nothing of the call depends on host data."""
+        self._check_outputs(outputs, k)
         if neighbours is not None and rule is not None:
             raise ValueError("forward_map: give neighbours or a retrieval rule, not both")
         if rule is None and (query_descriptors is not None or query_groups is not None):
             raise ValueError("forward_map: query_descriptors / query_groups belong to retrieval: pass a rule (and neighbours=None)")
         if rule is not None:
-            return self._forward_map_retrieve(queries, fmap, k, rule, query_descriptors, query_groups, _static)
+            return self._forward_map_retrieve(queries, fmap, k, rule, query_descriptors, query_groups, _static, outputs)
         if not torch.is_tensor(queries) or not torch.is_tensor(neighbours):
             raise TypeError("forward_map: queries and neighbours must be tensors")
         if neighbours.dtype != torch.int64 or neighbours.dim() != 2:
@@ -526,7 +591,7 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
             raise ValueError(f"forward_map: {queries.size(0)} queries but neighbours has {g} rows")
         self._map_devices(queries, fmap, "neighbours", neighbours)
         nb = neighbours.contiguous()
-        return self._forward_map_run(queries, fmap, k, g, kk, lambda qf, g0, g1, st, wkey: nb[g0:g1])
+        return self._forward_map_run(queries, fmap, k, g, kk, lambda qf, g0, g1, st, wkey: nb[g0:g1], outputs)
 
     @staticmethod
     def _map_devices(queries, fmap, name: str, t: Optional[torch.Tensor]) -> None:
@@ -538,7 +603,7 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
             raise RuntimeError(f"forward_map: queries ({queries.device}), {name}{where} and the feature map ({fmap.device}) "
                                f"must be on the same GPU")
 
-    def _forward_map_retrieve(self, queries, fmap, k, rule, query_descriptors, query_groups, static=None):
+    def _forward_map_retrieve(self, queries, fmap, k, rule, query_descriptors, query_groups, static=None, outputs="all"):
         """``forward_map`` with the neighbours retrieved per stream slot from that slot's query features (or descriptors).
         ``static``: see ``forward_map``'s ``_static``."""
         if not torch.is_tensor(queries):
@@ -577,9 +642,9 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
             return ops.retrieve(qf if qd is None else qd[g0:g1], db, ranks[g0:g1], db_inv_norm=inv,
                                 q_group=None if qg_dev is None else qg_dev[g0:g1], db_group=db_groups, status=st, workspace=ws,
                                 out=nb_out[g0:g1])
-        return (*self._forward_map_run(queries, fmap, k, g, kk, neighbours_of), nb_out)
+        return (*self._forward_map_run(queries, fmap, k, g, kk, neighbours_of, outputs), nb_out)
 
-    def _forward_map_run(self, queries, fmap, k, g, kk, neighbours_of):
+    def _forward_map_run(self, queries, fmap, k, g, kk, neighbours_of, outputs="all"):
         """``neighbours_of(qf, g0, g1, status, wkey)``: the map rows int64 [g1 - g0, K] of queries g0..g1, whose encoder features
         are ``qf``, made on the current (slot) stream."""
         fmap.check(self)
@@ -587,7 +652,9 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
         dev = x.device
         n_per = kk + 1
         edge_index, batch = self._map_graph(g, n_per, dev)
-        edge_index = edge_index.clone()           # the caller's to keep (the cached copy serves the next call)
+        query = self._map_query(g, n_per, dev) if outputs == "query" else None
+        if query is None:
+            edge_index = edge_index.clone()       # the caller's to keep (the cached copy serves the next call)
         enc_sd = self.feature_extractor.state_dict
 
         parts = None
@@ -602,10 +669,10 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
                 qf = self._enc.run(enc_sd, "", x[g0:g1], slot=wkey)
                 st = status[8 + wkey[0]:9 + wkey[0]]
                 return ops.gather_graph_nodes(qf, fmap.features, neighbours_of(qf, g0, g1, st, wkey), status=st)
-            return self._forward_streams(lib, features, g * n_per, dev, edge_index, parts, batch)
+            return self._forward_streams(lib, features, g * n_per, dev, edge_index, parts, batch, query=query, per_graph=(n_per, kk))
         qf = self._encode_small(x)
         feat = ops.gather_graph_nodes(qf, fmap.features, neighbours_of(qf, 0, g, status[8:9], (-1, 0)), status=status[8:9])
-        return self._forward_tail(lib, feat, edge_index, batch, k)
+        return self._forward_tail(lib, feat, edge_index, batch, k, query)
 
     def _encoder_input(self, x: torch.Tensor, what: str) -> torch.Tensor:
         """Images as the encoder takes them: uint8 frames through ``frame_transform``, dtype checked, viewed as [n, 3, H, W]."""
@@ -671,7 +738,7 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
         for st in streams:
             cur.wait_stream(st)
 
-    def _forward_streams(self, lib, features, n_total, dev, edge_index, parts, batch=None):
+    def _forward_streams(self, lib, features, n_total, dev, edge_index, parts, batch=None, query=None, per_graph=None):
         """use_AP / no extra attention / no explicit k, on ``len(parts)`` concurrent streams.  ``features(n0, n1, wkey)`` makes the
         node features [n1 - n0, d] of nodes n0..n1 on the current (slot) stream: the encoder over those images for ``forward``,
         the queries' encoder + node assembly from a feature map for ``forward_map``.  With ``knn > 0`` (the reference's
@@ -679,27 +746,33 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
         (posenet.py:1047-1048; graphs are independent, so the per-slot edge lists concatenate to the whole-batch list) and the
         host learns each slot's edge count behind an event on that slot's stream -- the other slots' encoders keep the GPU
         busy meanwhile -- before it enqueues the slot's GNN.  With ``droprate > 0`` the always-on dropout and the heads
-        (posenet.py:1073-1086) run per slot on the slot's stream."""
+        (posenet.py:1073-1086) run per slot on the slot's stream.  ``query`` (forward_map's query-only mode; ``per_graph`` =
+        (nodes, selected columns) of every graph): the outputs cover the query nodes and the selected columns, and every slot
+        computes the rows of its own graphs."""
         knn = int(self.knn) if self.knn > 0 else 0
         drop = self.droprate > 0
-        abs_pose = torch.empty((n_total, 6), dtype=torch.float32, device=dev)
+        abs_pose = torch.empty((n_total if query is None else query[1].numel(), 6), dtype=torch.float32, device=dev)
         status = self._counters.counters
         cur, streams = self._fork(1 + max(p[4] for p in parts), dev)
         d = self.feature_extractor.fc.out_features
 
-        def heads(feat, n0, n1, ei_ptrs, node_off, e, rel_out, slot, wkey):
-            node_f = torch.empty((n1 - n0, d), dtype=torch.float32, device=dev) if drop else None
-            edge_f = torch.empty((e, d), dtype=torch.float32, device=dev) if drop else None
-            self._gnn_call(lib, feat, ei_ptrs[0], ei_ptrs[1], node_off, n1 - n0, e, abs_pose[n0:n1], rel_out, node_f, edge_f,
-                           status[slot:slot + 1], wkey)
+        def heads(feat, n0, n1, ei_ptrs, node_off, e, rel_out, slot, wkey, q_slot=None):
+            abs_out, n_out, e_out = abs_pose[n0:n1], n1 - n0, e
+            if q_slot is not None:                # (first graph, selected columns, query nodes) of this slot
+                n_out, e_out = q_slot[2].numel(), q_slot[1].numel()
+                abs_out = abs_pose[q_slot[0]:q_slot[0] + n_out]
+            node_f = torch.empty((n_out, d), dtype=torch.float32, device=dev) if drop else None
+            edge_f = torch.empty((e_out, d), dtype=torch.float32, device=dev) if drop else None
+            self._gnn_call(lib, feat, ei_ptrs[0], ei_ptrs[1], node_off, n1 - n0, e, abs_out, rel_out, node_f, edge_f,
+                           status[slot:slot + 1], wkey, None if q_slot is None else q_slot[1:])
             if drop:
-                self._drop_heads(node_f, edge_f, abs_pose[n0:n1], rel_out)
+                self._drop_heads(node_f, edge_f, abs_out, rel_out)
                 for buf in (node_f, edge_f):
                     buf.record_stream(torch.cuda.current_stream())
 
         if not knn:
             e_total = edge_index.size(1)
-            rel_pose = torch.empty((e_total, 6), dtype=torch.float32, device=dev)
+            rel_pose = torch.empty((e_total if query is None else query[0].numel(), 6), dtype=torch.float32, device=dev)
             base = edge_index.data_ptr()
             for gi, (n0, n1, e0, e1, slot) in enumerate(parts):
                 st = streams[slot]
@@ -708,11 +781,19 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
                     # but a different shape would re-allocate every call
                     wkey = (slot, gi)
                     feat = features(n0, n1, wkey)
-                    heads(feat, n0, n1, (base + 8 * e0, base + 8 * (e_total + e0)), n0, e1 - e0, rel_pose[e0:e1], slot, wkey)
+                    rel_out, q_slot = rel_pose[e0:e1], None
+                    if query is not None:
+                        # the slot's graphs g0 .. g1: their query nodes (ids of the whole batch, like the slot's edges) and, the
+                        # list being one pattern per graph, the first (g1 - g0) K entries of the selection as its local columns
+                        n_per, k_sel = per_graph
+                        g0, g1 = n0 // n_per, n1 // n_per
+                        q_slot = (g0, query[0][:(g1 - g0) * k_sel], query[1][g0:g1])
+                        rel_out = rel_pose[g0 * k_sel:g1 * k_sel]
+                    heads(feat, n0, n1, (base + 8 * e0, base + 8 * (e_total + e0)), n0, e1 - e0, rel_out, slot, wkey, q_slot)
                     feat.record_stream(st)
             self._join(cur, streams)
             self.publish_status()
-            return abs_pose, rel_pose, edge_index
+            return abs_pose, rel_pose, (edge_index if query is None else query[2].clone())
 
         # ---- knn > 0: phase 1 = encoder + kNN build per slot (no host wait), phase 2 = GNN per slot once its edge count is in
         pend = []
