@@ -1430,9 +1430,6 @@ __global__ __launch_bounds__(NT) void global_avgpool_bf16_kernel(const uint4* __
     }
 }
 
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-inline int conv_out(int x, int k, int s, int p) { return (x + 2 * p - k) / s + 1; }
-
 }  // namespace
 
 namespace rpg {
@@ -1696,37 +1693,26 @@ extern "C" int rpg_conv2d_bn_act_nhwc_bf16(const void* x, const void* w_ohwi, co
                                  rpg::as_stream(stream));
 }
 
+typedef rpg::ResnetBuffers<unsigned short> ResnetBuffersBf16;      // NHWC8 input, no scratch: nothing here splits K
+
 extern "C" size_t rpg_resnet_bf16_workspace_bytes(int n, int h, int w, const int* planes) {
     if (n <= 0 || h <= 0 || w <= 0 || !planes) return 0;
-    const int h1 = conv_out(h, 7, 2, 3), w1 = conv_out(w, 7, 2, 3), h2 = conv_out(h1, 3, 2, 1), w2 = conv_out(w1, 3, 2, 1);
-    size_t blk = 0;
-    int hh = h2, ww = w2;
-    for (int l = 0; l < 4; ++l) {
-        if (l > 0) { hh = conv_out(hh, 3, 2, 1); ww = conv_out(ww, 3, 2, 1); }
-        const size_t sz = (size_t)n * hh * ww * planes[l];
-        if (sz > blk) blk = sz;
-    }
-    return align_up((size_t)n * h * w * 8 * 2, 256) + align_up((size_t)n * h1 * w1 * planes[0] * 2, 256) +
-           4 * align_up(blk * 2, 256) + align_up((size_t)n * planes[3] * 2, 256) + 7 * rpg::kWorkspaceSkew;
+    return rpg::planned_bytes<ResnetBuffersBf16>(n, h, w, planes, 8, (size_t)0);
 }
 
 // tensors: per conv {w_ohwi bf16, scale f32, shift f32} (stem Cin padded to 8), then fc weight bf16 [feat][512], bias f32.
 static int resnet_forward_bf16_impl(const void* const* tensors, int n_tensors, const int* blocks, const int* planes, int feat_dim,
                                    const void* x_nchw_any, int x_is_bf16, int n, int h, int w, float* feat, void* workspace,
                                    size_t workspace_bytes, void* stream) {
+    using rpg::ResnetWalk;
     const float* x_nchw = reinterpret_cast<const float*>(x_nchw_any);       // (only read as fp32 when !x_is_bf16)
     if (!tensors || !blocks || !planes || !x_nchw || !feat || !workspace || n <= 0 || h <= 0 || w <= 0 || feat_dim <= 0 ||
         (feat_dim & 3))
         return RPG_ERR_BAD_ARG;
-    int expect = 3 + 2, cin = planes[0];
-    for (int l = 0; l < 4; ++l) {
+    for (int l = 0; l < 4; ++l)
         if (planes[l] & 7) return RPG_ERR_BAD_ARG;
-        for (int b = 0; b < blocks[l]; ++b) {
-            const int stride = (l > 0 && b == 0) ? 2 : 1;
-            expect += 6 + ((stride != 1 || cin != planes[l]) ? 3 : 0);
-            cin = planes[l];
-        }
-    }
+    int expect = 3 + 2;
+    for (ResnetWalk b(blocks, planes, 1, 1); !b.done(); b.next()) expect += b.ds ? 9 : 6;      // (whatever the extent)
     // optional last tensor: the operands of the fused stem kernel (stem_bf16.hip; 64-channel stems)
     if (n_tensors != expect && n_tensors != expect + 1) return RPG_ERR_BAD_ARG;
     const void* stem_pack = n_tensors == expect + 1 ? tensors[expect] : nullptr;
@@ -1734,28 +1720,10 @@ static int resnet_forward_bf16_impl(const void* const* tensors, int n_tensors, c
         if (!tensors[i]) return RPG_ERR_BAD_ARG;
     if (workspace_bytes < rpg_resnet_bf16_workspace_bytes(n, h, w, planes)) return RPG_ERR_WORKSPACE;
     hipStream_t s = rpg::as_stream(stream);
-    const int h1 = conv_out(h, 7, 2, 3), w1 = conv_out(w, 7, 2, 3), h2 = conv_out(h1, 3, 2, 1), w2 = conv_out(w1, 3, 2, 1);
-    size_t blk = 0;
-    {
-        int hh = h2, ww = w2;
-        for (int l = 0; l < 4; ++l) {
-            if (l > 0) { hh = conv_out(hh, 3, 2, 1); ww = conv_out(ww, 3, 2, 1); }
-            const size_t sz = (size_t)n * hh * ww * planes[l];
-            if (sz > blk) blk = sz;
-        }
-    }
-    char* base = reinterpret_cast<char*>(workspace);
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char* p = base + off;
-        off += align_up(bytes, 256) + rpg::kWorkspaceSkew;      // see rpg_common.h: de-aliases the HBM channels
-        return reinterpret_cast<void*>(p);
-    };
-    void* in8 = take((size_t)n * h * w * 8 * 2);
-    void* stem = take((size_t)n * h1 * w1 * planes[0] * 2);
-    void* buf[4];
-    for (int i = 0; i < 4; ++i) buf[i] = take(blk * 2);
-    void* pool = take((size_t)n * planes[3] * 2);
+    rpg::Carver cv{reinterpret_cast<char*>(workspace), 0};
+    ResnetBuffersBf16 B;
+    B.carve(cv, n, h, w, planes, 8, 0);
+    unsigned short* const* buf = B.buf;
 
     int rc, ti = 0;
     if (stem_pack && g_bf16_fused_stem && rpg::stem_pool_bf16_supported(n, h, w, planes[0])) {
@@ -1769,111 +1737,104 @@ static int resnet_forward_bf16_impl(const void* const* tensors, int n_tensors, c
         const long npix = (long)n * h * w;
         if (x_is_bf16)
             hipLaunchKernelGGL(nchw3_to_nhwc8_bf16_kernel<__bf16>, dim3(capped_grid(npix)), dim3(NT), 0, s,
-                               reinterpret_cast<const __bf16*>(x_nchw_any), reinterpret_cast<uint4*>(in8), npix, h * w);
+                               reinterpret_cast<const __bf16*>(x_nchw_any), reinterpret_cast<uint4*>(B.in), npix, h * w);
         else
             hipLaunchKernelGGL(nchw3_to_nhwc8_bf16_kernel<float>, dim3(capped_grid(npix)), dim3(NT), 0, s, x_nchw,
-                               reinterpret_cast<uint4*>(in8), npix, h * w);
-        if ((rc = rpg::launch_conv_bf16(in8, tensors[0], (const float*)tensors[1], (const float*)tensors[2], nullptr, stem, n, h,
+                               reinterpret_cast<uint4*>(B.in), npix, h * w);
+        if ((rc = rpg::launch_conv_bf16(B.in, tensors[0], (const float*)tensors[1], (const float*)tensors[2], nullptr, B.stem, n, h,
                                         w, 8, planes[0], 7, 7, 2, 3, 1, 0, s)) != RPG_OK)
             return rc;
         const int c8 = planes[0] / 8;
-        const long total = (long)n * h2 * w2 * c8;
+        const long total = (long)n * B.h2 * B.w2 * c8;
         hipLaunchKernelGGL(maxpool3x3s2_bf16_kernel, dim3(capped_grid(total)), dim3(NT), 0, s,
-                           reinterpret_cast<const uint4*>(stem), reinterpret_cast<uint4*>(buf[0]), h1, w1, c8, h2, w2, total);
+                           reinterpret_cast<const uint4*>(B.stem), reinterpret_cast<uint4*>(buf[0]), B.h1, B.w1, c8, B.h2, B.w2, total);
     }
     ti += 3;
-    int cur = 0, hh = h2, ww = w2;
-    cin = planes[0];
-    for (int l = 0; l < 4; ++l) {
-        for (int b = 0; b < blocks[l]; ++b) {
-            const int stride = (l > 0 && b == 0) ? 2 : 1;
-            const int c = planes[l];
-            const bool ds = (stride != 1 || cin != c);
-            const int ho = conv_out(hh, 3, stride, 1), wo = conv_out(ww, 3, stride, 1);
-            // Depth-first over image groups (round 4, RPG_TUNE_BF16_CHUNK): a run of identity blocks (stride 1, no downsample)
-            // on LARGE activation tensors is walked group of images by group of images -- conv1, conv2 of every block of the
-            // run on `g_bf16_chunk` images, then the next group -- so that a group's intermediate tensors (and the residual) are
-            // re-read from the 256-MB Infinity Cache instead of HBM.  Images are independent: same kernels, same arithmetic,
-            // only the pointers and the image count of a launch change.
-            const size_t act_bytes = (size_t)n * hh * ww * c * 2;
-            if (!ds && g_bf16_chunk > 0 && n > g_bf16_chunk && act_bytes >= ((size_t)g_bf16_chunk_mb << 20)) {
-                int run = 1;                                   // identity blocks b .. b + run - 1 (all that follow in this layer)
-                while (b + run < blocks[l]) ++run;
-                const size_t img = (size_t)hh * ww * c * 2;    // bytes per image of every tensor in the run
-                for (int i0 = 0; i0 < n; i0 += g_bf16_chunk) {
-                    const int ni = n - i0 < g_bf16_chunk ? n - i0 : g_bf16_chunk;
-                    int cc = cur, tj = ti;
-                    for (int r = 0; r < run; ++r) {
-                        char* X = static_cast<char*>(buf[cc]) + i0 * img;
-                        char* T = static_cast<char*>(buf[(cc + 1) & 3]) + i0 * img;
-                        char* Y = static_cast<char*>(buf[(cc + 2) & 3]) + i0 * img;
-                        if ((rc = rpg::launch_conv_bf16(X, tensors[tj], (const float*)tensors[tj + 1], (const float*)tensors[tj + 2],
-                                                        nullptr, T, ni, hh, ww, c, c, 3, 3, 1, 1, 1, 0, s)) != RPG_OK)
-                            return rc;
-                        if ((rc = rpg::launch_conv_bf16(T, tensors[tj + 3], (const float*)tensors[tj + 4], (const float*)tensors[tj + 5],
-                                                        X, Y, ni, hh, ww, c, c, 3, 3, 1, 1, 1, 0, s)) != RPG_OK)
-                            return rc;
-                        tj += 6;
-                        cc = (cc + 2) & 3;
-                    }
+    int cur = 0;
+    ResnetWalk b(blocks, planes, B.h2, B.w2);
+    for (; !b.done(); b.next()) {
+        // Depth-first over image groups (round 4, RPG_TUNE_BF16_CHUNK): a run of identity blocks (stride 1, no downsample)
+        // on LARGE activation tensors is walked group of images by group of images -- conv1, conv2 of every block of the
+        // run on `g_bf16_chunk` images, then the next group -- so that a group's intermediate tensors (and the residual) are
+        // re-read from the 256-MB Infinity Cache instead of HBM.  Images are independent: same kernels, same arithmetic,
+        // only the pointers and the image count of a launch change.
+        const size_t act_bytes = (size_t)n * b.h * b.w * b.c * 2;
+        if (!b.ds && g_bf16_chunk > 0 && n > g_bf16_chunk && act_bytes >= ((size_t)g_bf16_chunk_mb << 20)) {
+            const int run = blocks[b.layer] - b.index;      // identity blocks: this one and all that follow in this layer
+            const size_t img = (size_t)b.h * b.w * b.c;         // elements per image of every tensor in the run
+            for (int i0 = 0; i0 < n; i0 += g_bf16_chunk) {
+                const int ni = n - i0 < g_bf16_chunk ? n - i0 : g_bf16_chunk;
+                int cc = cur, tj = ti;
+                ResnetWalk r = b;                           // a copy walks the run once per group
+                for (int j = 0; j < run; ++j, r.next()) {
+                    unsigned short* X = buf[cc] + i0 * img;
+                    unsigned short* T = buf[(cc + 1) & 3] + i0 * img;
+                    unsigned short* Y = buf[(cc + 2) & 3] + i0 * img;
+                    if ((rc = rpg::launch_conv_bf16(X, tensors[tj], (const float*)tensors[tj + 1], (const float*)tensors[tj + 2],
+                                                    nullptr, T, ni, r.h, r.w, r.c, r.c, 3, 3, 1, 1, 1, 0, s)) != RPG_OK)
+                        return rc;
+                    if ((rc = rpg::launch_conv_bf16(T, tensors[tj + 3], (const float*)tensors[tj + 4], (const float*)tensors[tj + 5],
+                                                    X, Y, ni, r.h, r.w, r.c, r.c, 3, 3, 1, 1, 1, 0, s)) != RPG_OK)
+                        return rc;
+                    tj += 6;
+                    cc = (cc + 2) & 3;
                 }
-                ti += 6 * run;
-                cur = (cur + 2 * run) & 3;
-                b += run - 1;
-                cin = c;
+            }
+            ti += 6 * run;
+            cur = (cur + 2 * run) & 3;
+            for (int j = 1; j < run; ++j) b.next();         // the loop's own next() steps past the last block of the run
+            continue;
+        }
+        void* X = buf[cur];
+        void* T = buf[(cur + 1) & 3];
+        void* Y = buf[(cur + 2) & 3];
+        void* D = buf[(cur + 3) & 3];
+        // 64-channel identity block (layer 1): conv1 + BN + ReLU + conv2 + BN + identity + ReLU in one kernel, the intermediate
+        // on chip (block_bf16.inc; bit-identical to the two launches below)
+        if (!b.ds && b.c == 64 && g_bf16_fuse_block && (long)n * b.h * b.w >= 8192) {
+            const int slot = rpg::timing_begin(RPG_TIMER_CONV, s);
+            if (launch_block64_fused(X, tensors[ti], (const float*)tensors[ti + 1], (const float*)tensors[ti + 2], tensors[ti + 3],
+                                     (const float*)tensors[ti + 4], (const float*)tensors[ti + 5], Y, n, b.h, b.w, s)) {
+                rpg::timing_end(slot, 2.0 * 2.0 * (double)n * b.h * b.w * 64.0 * 9.0 * 64.0, s);
+                RPG_CHECK_LAUNCH("basicblock64_bf16");
+                ti += 6;
+                cur = (cur + 2) & 3;
                 continue;
             }
-            void* X = buf[cur];
-            void* T = buf[(cur + 1) & 3];
-            void* Y = buf[(cur + 2) & 3];
-            void* D = buf[(cur + 3) & 3];
-            // 64-channel identity block (layer 1): conv1 + BN + ReLU + conv2 + BN + identity + ReLU in one kernel, the intermediate
-            // on chip (block_bf16.inc; bit-identical to the two launches below)
-            if (!ds && c == 64 && g_bf16_fuse_block && (long)n * hh * ww >= 8192) {
-                const int slot = rpg::timing_begin(RPG_TIMER_CONV, s);
-                if (launch_block64_fused(X, tensors[ti], (const float*)tensors[ti + 1], (const float*)tensors[ti + 2], tensors[ti + 3],
-                                         (const float*)tensors[ti + 4], (const float*)tensors[ti + 5], Y, n, hh, ww, s)) {
-                    rpg::timing_end(slot, 2.0 * 2.0 * (double)n * hh * ww * 64.0 * 9.0 * 64.0, s);
-                    RPG_CHECK_LAUNCH("basicblock64_bf16");
-                    ti += 6;
-                    cur = (cur + 2) & 3;
-                    continue;
-                }
-                rpg::timing_end(slot, 0.0, s);
-            }
-            const void* identity = X;
-            bool paired = false;
-            if (ds && stride == 2)
-                paired = rpg::launch_conv_pair_bf16(X, tensors[ti], (const float*)tensors[ti + 1], (const float*)tensors[ti + 2], T, tensors[ti + 6],
-                                                    (const float*)tensors[ti + 7], (const float*)tensors[ti + 8], D, n, hh, ww, cin, c, 3, stride, 1, s);
-            if (paired) {
-                identity = D;
-            } else if ((rc = rpg::launch_conv_bf16(X, tensors[ti], (const float*)tensors[ti + 1], (const float*)tensors[ti + 2],
-                                                   nullptr, T, n, hh, ww, cin, c, 3, 3, stride, 1, 1, 0, s)) != RPG_OK) {
-                return rc;
-            }
-            if (ds && !paired) {
-                if ((rc = rpg::launch_conv_bf16(X, tensors[ti + 6], (const float*)tensors[ti + 7], (const float*)tensors[ti + 8],
-                                                nullptr, D, n, hh, ww, cin, c, 1, 1, stride, 0, 0, 0, s)) != RPG_OK)
-                    return rc;
-                identity = D;
-            }
-            if ((rc = rpg::launch_conv_bf16(T, tensors[ti + 3], (const float*)tensors[ti + 4], (const float*)tensors[ti + 5],
-                                            identity, Y, n, ho, wo, c, c, 3, 3, 1, 1, 1, 0, s)) != RPG_OK)
-                return rc;
-            ti += ds ? 9 : 6;
-            cur = (cur + 2) & 3;
-            hh = ho; ww = wo; cin = c;
+            rpg::timing_end(slot, 0.0, s);
         }
+        const void* identity = X;
+        bool paired = false;
+        if (b.ds && b.stride == 2)
+            paired = rpg::launch_conv_pair_bf16(X, tensors[ti], (const float*)tensors[ti + 1], (const float*)tensors[ti + 2], T, tensors[ti + 6],
+                                                (const float*)tensors[ti + 7], (const float*)tensors[ti + 8], D, n, b.h, b.w, b.cin, b.c, 3, b.stride, 1, s);
+        if (paired) {
+            identity = D;
+        } else if ((rc = rpg::launch_conv_bf16(X, tensors[ti], (const float*)tensors[ti + 1], (const float*)tensors[ti + 2],
+                                               nullptr, T, n, b.h, b.w, b.cin, b.c, 3, 3, b.stride, 1, 1, 0, s)) != RPG_OK) {
+            return rc;
+        }
+        if (b.ds && !paired) {
+            if ((rc = rpg::launch_conv_bf16(X, tensors[ti + 6], (const float*)tensors[ti + 7], (const float*)tensors[ti + 8],
+                                            nullptr, D, n, b.h, b.w, b.cin, b.c, 1, 1, b.stride, 0, 0, 0, s)) != RPG_OK)
+                return rc;
+            identity = D;
+        }
+        if ((rc = rpg::launch_conv_bf16(T, tensors[ti + 3], (const float*)tensors[ti + 4], (const float*)tensors[ti + 5],
+                                        identity, Y, n, b.ho, b.wo, b.c, b.c, 3, 3, 1, 1, 1, 0, s)) != RPG_OK)
+            return rc;
+        ti += b.ds ? 9 : 6;
+        cur = (cur + 2) & 3;
     }
+    // the walk has ended: b.cin x b.h x b.w is the last activation tensor
     {
-        const int c8 = cin / 8;
+        const int c8 = b.cin / 8;
         const long total = (long)n * c8;
         hipLaunchKernelGGL(global_avgpool_bf16_kernel, dim3(capped_grid(total)), dim3(NT), 0, s,
-                           reinterpret_cast<const uint4*>(buf[cur]), reinterpret_cast<uint4*>(pool), hh * ww, c8, total);
+                           reinterpret_cast<const uint4*>(buf[cur]), reinterpret_cast<uint4*>(B.pool), b.h * b.w, c8, total);
     }
     // fc as a 1x1 convolution on a 1x1 image: [n][1][1][cin] x [feat][1][1][cin], bias in `shift`, fp32 output
-    return rpg::launch_conv_bf16(pool, tensors[ti], nullptr, (const float*)tensors[ti + 1], nullptr, feat, n, 1, 1, cin,
+    return rpg::launch_conv_bf16(B.pool, tensors[ti], nullptr, (const float*)tensors[ti + 1], nullptr, feat, n, 1, 1, b.cin,
                                  feat_dim, 1, 1, 1, 0, 0, 1, s);
 }
 

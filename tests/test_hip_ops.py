@@ -566,6 +566,93 @@ def test_composite_abi_error_codes(dev):
         _lib.check(_lib.RPG_ERR_WORKSPACE, "x")
 
 
+@pytest.fixture(scope="module")
+def composite_model(dev):
+    """The smallest model that reaches every workspace buffer: planes (64, 128, 256, 512) (the bf16 encoder's fused stem and fused
+    64-channel block take 64-channel stems only), one block per layer, D = 64, two recursions."""
+    from relpose_gnn_amd.posenet import PoseNetX_R2
+    from relpose_gnn_amd.resnet import ResNet
+    torch.manual_seed(1234)
+    m = PoseNetX_R2(ResNet((1, 1, 1, 1), (64, 128, 256, 512)), droprate=0.0, pretrained=False, feat_dim=64, edge_feat_dim=64, node_dim=64,
+                    input_img_height=64, use_gnn=True, knn=-1, use_AP=True, gnn_recursion=2)
+    return m.to(dev).eval()
+
+
+@pytest.mark.parametrize("entry", ["resnet_f32", "resnet_bf16", "gnn_f32", "gnn_bf16", "gnn_query_f32", "gnn_query_bf16"])
+def test_composites_run_in_exactly_their_workspace(dev, composite_model, entry):
+    """Every composite entry point runs in exactly the bytes its size function names: in a workspace of `need` bytes between two
+    4096-byte guards (all inside one allocation of this test, filled with 0xA5) it returns RPG_OK, leaves both guards intact and
+    gives bit for bit what the same call gives through the model's own pooled workspace; with need - 1 bytes it returns
+    RPG_ERR_WORKSPACE and writes no output.  Encoder: 2 images of 64 x 64.  GNN: three ragged fully-connected graphs of 8, 5 and 8
+    nodes; the query-only mode selects the columns into each graph's first node."""
+    from relpose_gnn_amd import _lib
+    from relpose_gnn_amd.graph import fc_edge_index, query_edge_columns
+    lib, m = _lib.lib(), composite_model
+    stream = torch.cuda.current_stream().cuda_stream
+    bf16 = entry.endswith("bf16")
+    if entry.startswith("resnet"):
+        m.encoder_dtype = "bf16" if bf16 else "f32"
+        x = _rand(2, 3, 64, 64, seed=77).to(dev)
+        pooled = [m._enc.run(m.feature_extractor.state_dict, "", x)]
+        tensors, blocks, planes = m._enc._packed
+        planes_c = _lib.int_array(planes)
+        need = int((lib.rpg_resnet_bf16_workspace_bytes if bf16 else lib.rpg_resnet_workspace_bytes)(2, 64, 64, planes_c))
+        fwd = lib.rpg_resnet_forward_bf16 if bf16 else lib.rpg_resnet_forward_f32
+        shapes, status = [(2, 64)], None
+
+        def call(ws_ptr, ws_bytes, outs):
+            return fwd(m._enc._ptrs, len(tensors), _lib.int_array(blocks), planes_c, 64, x.data_ptr(), 2, 64, 64, outs[0].data_ptr(),
+                       ws_ptr, ws_bytes, stream)
+    else:
+        sizes = (8, 5, 8)
+        offs = [sum(sizes[:i]) for i in range(len(sizes))]
+        ei = torch.cat([fc_edge_index(k) + o for k, o in zip(sizes, offs)], 1).contiguous().to(dev)
+        n, e, d = sum(sizes), int(ei.shape[1]), 64
+        feat = _rand(n, d, seed=78).to(dev)
+        m.gnn_dtype = "bf16" if bf16 else "f32"
+        m._pack_gnn()
+        weights = (m._gnn_ptrs, len(m._gnn_packed)) + ((m._gnn_bf16_ptrs, len(m._gnn_bf16)) if bf16 else ())
+        status = torch.zeros(16, dtype=torch.int32, device=dev)
+        query, sel_args = None, ()
+        rows_n, rows_e = n, e
+        if "query" in entry:
+            qn = torch.tensor(offs, dtype=torch.int64, device=dev)
+            sel = query_edge_columns(ei, offs).to(dev)
+            assert sel.numel() == sum(k - 1 for k in sizes)
+            query, sel_args = (sel, qn), (sel.data_ptr(), sel.numel(), qn.data_ptr(), qn.numel())
+            rows_n, rows_e = qn.numel(), sel.numel()
+            need = int(lib.rpg_gnn_query_workspace_bytes(n, e, d, rows_e, rows_n))
+            fwd = lib.rpg_gnn_forward_query_bf16 if bf16 else lib.rpg_gnn_forward_query_f32
+        else:
+            need = int(lib.rpg_gnn_workspace_bytes(n, e, d))
+            fwd = lib.rpg_gnn_forward_bf16 if bf16 else lib.rpg_gnn_forward_f32
+        shapes = [(rows_n, 6), (rows_e, 6), (rows_n, d), (rows_e, d)]          # abs_pose, rel_pose, node_out, edge_out
+        pooled = [torch.empty(s, device=dev) for s in shapes]
+        m._gnn_call(lib, feat, ei[0].data_ptr(), ei[1].data_ptr(), 0, n, e, *pooled, status, 0, query=query)
+
+        def call(ws_ptr, ws_bytes, outs):
+            return fwd(*weights, feat.data_ptr(), ei[0].data_ptr(), ei[1].data_ptr(), 0, n, e, d, 2, *sel_args, *(o.data_ptr() for o in outs),
+                       status.data_ptr(), ws_ptr, ws_bytes, stream)
+    assert need > 0
+    guard, fill = 4096, -7.0
+    raw = torch.full((need + 2 * guard,), 0xA5, dtype=torch.uint8, device=dev)
+    outs = [torch.full(s, fill, device=dev) for s in shapes]
+    rc = call(raw.data_ptr() + guard, need, outs)
+    torch.cuda.synchronize()
+    assert rc == _lib.RPG_OK, (rc, lib.rpg_last_error())
+    assert bool((raw[:guard] == 0xA5).all()), "the guard in front of the workspace was written"
+    assert bool((raw[guard + need:] == 0xA5).all()), "the guard behind the workspace was written"
+    for o, p in zip(outs, pooled):
+        assert bool(torch.isfinite(p).all()) and torch.equal(o, p)
+    outs = [torch.full(s, fill, device=dev) for s in shapes]
+    rc = call(raw.data_ptr() + guard, need - 1, outs)
+    torch.cuda.synchronize()
+    assert rc == _lib.RPG_ERR_WORKSPACE
+    assert all(bool((o == fill).all()) for o in outs), "a refused call wrote an output"
+    if status is not None:
+        assert int(status.sum()) == 0                                           # no edge and no selection was counted as bad
+
+
 # ---- in-kernel combine of split-K / stream-K partial tiles (round 4) ------------------------------------------------------
 def _with_fixup_mode(mode, fn):
     from relpose_gnn_amd import ops

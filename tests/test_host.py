@@ -287,3 +287,64 @@ def test_host_f32_to_bf16_is_round_to_nearest_even():
             ran += 1
     assert ran >= 7
     assert lib.rpg_host_f32_to_bf16_isa(both.data_ptr(), want.data_ptr(), 4, 9) == _lib.RPG_ERR_BAD_ARG
+
+
+# ---- the composite forwards' workspace plan (csrc/composite_plan.h) ---------------------------------------------------------------
+# Bytes every size function returned BEFORE the layouts moved into composite_plan.h, recorded from a build of that commit (256 CUs:
+# the count the library assumes without a GPU, and the MI355X's).  Every buffer keeps its place, so the sizes keep their value.
+_RESNET34, _TINY, _STEEP = (64, 128, 256, 512), (8, 16, 32, 64), (8, 64, 512, 4096)      # _STEEP: the LAST layer owns the largest block buffer
+ENCODER_BYTES = [    # (planes, (n, h, w), fp32, bf16)
+    (_RESNET34, (1, 224, 224), 110069760, 5907456),
+    (_RESNET34, (8, 256, 341), 203948032, 58032128),
+    (_RESNET34, (256, 224, 224), 1953054720, 1029758976),
+    (_RESNET34, (3, 33, 47), 103568128, 2292480),
+    (_TINY, (2, 32, 40), 102924800, 1954048),
+    (_STEEP, (2, 64, 64), 103596032, 2334720),
+]
+GNN_BYTES = [        # ((n, e, d), bytes); (3, 1, 32) and (2000, 100, 64): e < 2n
+    ((8, 56, 2048), 109488640), ((256, 1792, 2048), 223323392), ((8, 56, 64), 105933312), ((3, 1, 32), 105822976),
+    ((2000, 100, 64), 110098944), ((1, 1, 32), 105820928),
+]
+QUERY_BYTES = [      # ((n, e, d, e_sel, q), bytes)
+    ((8, 56, 64, 7, 1), 107559168), ((256, 1792, 2048, 224, 32), 228229120), ((8, 56, 64, 56, 8), 107582976),
+]
+
+
+def test_workspace_size_functions_return_what_they_always_did():
+    from relpose_gnn_amd import _lib
+    lib = _lib.lib()
+    for planes, (n, h, w), f32, bf16 in ENCODER_BYTES:
+        p = _lib.int_array(list(planes))
+        assert lib.rpg_resnet_workspace_bytes(n, h, w, p) == f32, (planes, n, h, w)
+        assert lib.rpg_resnet_bf16_workspace_bytes(n, h, w, p) == bf16, (planes, n, h, w)
+    for shape, nbytes in GNN_BYTES:
+        assert lib.rpg_gnn_workspace_bytes(*shape) == nbytes, shape
+    for shape, nbytes in QUERY_BYTES:
+        assert lib.rpg_gnn_query_workspace_bytes(*shape) == nbytes, shape
+    # refused shapes: 0
+    p = _lib.int_array(list(_RESNET34))
+    for fn in (lib.rpg_resnet_workspace_bytes, lib.rpg_resnet_bf16_workspace_bytes):
+        for bad in ((0, 224, 224), (1, 0, 224), (1, 224, 0), (-1, 224, 224)):
+            assert fn(*bad, p) == 0, bad
+        assert fn(1, 224, 224, None) == 0
+    for bad in ((0, 56, 64), (8, 0, 64), (8, 56, 0), (8, 56, 100), (-8, 56, 64)):          # n = 0, e = 0, d = 0, d % 32 != 0
+        assert lib.rpg_gnn_workspace_bytes(*bad) == 0, bad
+    for bad in ((8, 56, 64, 0, 1), (8, 56, 64, 57, 1), (8, 56, 64, 7, 0), (8, 56, 64, 7, 9), (8, 56, 100, 7, 1),      # e_sel = 0, e_sel > e, q = 0, q > n
+                (0, 56, 64, 7, 1), (8, 0, 64, 7, 1), (8, 56, 0, 7, 1)):
+        assert lib.rpg_gnn_query_workspace_bytes(*bad) == 0, bad
+
+
+def test_composite_plan_header_stands_alone(tmp_path):
+    """tests/composite_plan_check.cpp includes nothing of the project but csrc/composite_plan.h: the host compiler alone builds it
+    (the header needs no HIP).  It carves every buffer set into a host buffer of exactly the dry run's size, tags every buffer over
+    its full extent, re-reads the tags (overlap), checks alignment and bounds, and walks ResnetWalk against plain nested loops."""
+    import shutil
+    import subprocess
+    cxx = os.environ.get("CXX") or shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
+    assert cxx, "no host C++ compiler"
+    exe = str(tmp_path / "composite_plan_check")
+    subprocess.run([cxx, "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-o", exe,
+                    os.path.join(ROOT, "tests", "composite_plan_check.cpp")], check=True)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "composite_plan: ok" in r.stdout
