@@ -460,8 +460,9 @@ def test_knn_graph(dev, sizes, k, d):
 ])
 @pytest.mark.parametrize("kernel", [2, 3], ids=["wave4", "wave8"])
 def test_conv3x3_winograd(dev, n, h, w, cin, cout, res, relu, kernel):
-    """1-D Winograd F(4,3) convolution vs F.conv2d; tolerance 2e-5 (the transforms cost ~2.5x the rounding error of
-    the direct kernel per layer: measured in tools, still 5x below the per-op bar used elsewhere x 2)."""
+    """1-D Winograd F(4,3) convolution vs F.conv2d at the max-norm tolerance 2e-5.  The bound the kernels are actually held to is
+    the per-element one of tests/test_hip_encoder_sweep.py (c_hip <= M c_ref against float64, every launch route); this one is a
+    coarse guard on the layer shapes."""
     from relpose_gnn_amd import ops
     x = _rand(n, cin, h, w, seed=1)
     wt = _rand(cout, cin, 3, 3, seed=2, scale=(2.0 / (cin * 9)) ** 0.5)
