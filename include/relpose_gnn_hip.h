@@ -319,6 +319,22 @@ int rpg_linear_gather_ex_f32(int n_src, const float* const* a, const int64_t* co
                              const int64_t* res2_idx, int ldr, float* out, float* out_relu, int m, int n_out, int relu,
                              void* stream);
 
+/* HOST: what the launcher did with the last fp32 GEMM of the calling thread (rpg_linear_gather_f32 / _ex_f32,
+ * rpg_conv2d_bn_act_nhwc_f32 and the composite forwards' Linears and direct convolutions; the Winograd and bf16 kernels
+ * do not record).  Writes the first min(n, 15) of these ints to out and returns 15 (RPG_ERR_BAD_ARG: out NULL or n < 0):
+ *    0 kernel    0 nothing launched yet | 1 tile engine | 2 linear112 (4 waves) | 3 linear112k2 (8 waves)
+ *    1 BM, 2 BN, 3 BK   the workgroup tile and its K step
+ *    4 waves     4 | 8 per workgroup
+ *    5 loader    A operand: 0 general (64-bit row pointers, any K) | 1 buffer loads (32-bit row offsets) | 2 one tap per slot
+ *    6 epi_lds   1: the epilogue transposes through LDS (16-byte accesses) | 0: direct, one float per lane
+ *    7 occ       resident workgroups per CU the launcher planned with
+ *    8 tiles, 9 t_dp    output tiles, and how many of them whole workgroups ran over all of K
+ *   10 g_sk, 11 rem, 12 its_per   stream-K: workgroups that share the rem = tiles - t_dp other tiles, K steps each (0 0 0: none)
+ *   13 combine   of the split tiles: 0 none | 1 the fix-up launch | 2 the last-arriving workgroup (RPG_TUNE_INKERNEL_FIXUP bit 0)
+ *   14 fold_k    two-level accumulation period in force for this launch (0: one sequential chain; RPG_TUNE_FOLD_K)
+ * A diagnostic for tests and tools: a few integer stores per launch, no effect on any launch.                           */
+int rpg_gemm_last_route(int* out, int n);
+
 /* AttentionBlock core (att.py:20-31) on rows: gtp [r][3c] = [g | theta | phi] projections,
  * y[r][i] = sum_j softmax_j(phi_i * theta_j) * g_j.                                            */
 int rpg_attention_rows_f32(const float* gtp, int r, int c, float* y, void* stream);

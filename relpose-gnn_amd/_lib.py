@@ -32,7 +32,7 @@ SYMBOLS = (
     "rpg_frames_u8_to_bf16", "rpg_gather_graph_nodes_f32", "rpg_linear_bf16_ex", "rpg_conv_pair_bf16",
     "rpg_retrieve_workspace_bytes", "rpg_retrieve_max_rank", "rpg_row_inv_norms_f32", "rpg_retrieve_cosine_f32",
     "rpg_query_pose_f64", "rpg_query_pose_fused_f64", "rpg_gather_add2_relu_f32",
-    "rpg_gnn_query_workspace_bytes", "rpg_gnn_forward_query_f32", "rpg_gnn_forward_query_bf16",
+    "rpg_gnn_query_workspace_bytes", "rpg_gnn_forward_query_f32", "rpg_gnn_forward_query_bf16", "rpg_gemm_last_route",
 )
 
 
@@ -66,6 +66,7 @@ def _declare(lib: C.CDLL) -> None:
                                           _vp, _vp, _i, _i, _i, _vp]
     lib.rpg_linear_gather_ex_f32.argtypes = [_i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i), C.POINTER(_i), C.POINTER(C.c_long),
                                              _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp]
+    lib.rpg_gemm_last_route.argtypes = [C.POINTER(_i), _i]
     lib.rpg_attention_rows_f32.argtypes = [_vp, _i, _i, _vp, _vp]
     lib.rpg_scatter_mean_f32.argtypes = [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]
     lib.rpg_attention_aggregate_f32.argtypes = [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]

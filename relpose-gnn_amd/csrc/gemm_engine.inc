@@ -860,6 +860,16 @@ int launch_one(const Args& args, const float* Wt, int ldw, int M, int N, int K, 
             if (partial) t_dp = tiles - rem;
         }
     }
+    // the route record (rpg_gemm_last_route); the loader kind was noted by launch_tiles
+    int fold = 0;
+    if constexpr (std::is_same<Args, GatherArgs>::value)
+        if (t_route.loader == ROUTE_LOADER_BUFFER && T::FM * T::FN == 1 && args.fold_k >= 2 * BK) fold = args.fold_k;
+    t_route = RouteRecord{ROUTE_TILE, BM, BN, BK, NTHREADS / 64, t_route.loader, EPI ? 1 : 0, occ, tiles, t_dp, t_dp == tiles ? 0 : g_sk,
+                          tiles - t_dp, t_dp == tiles ? 0 : its_per,
+                          t_dp == tiles ? ROUTE_COMBINE_NONE
+                                        : (((g_inkernel_fixup & 1) && arrive && tiles - t_dp <= (int)(kCounterBytes / sizeof(unsigned)))
+                                               ? ROUTE_COMBINE_INKERNEL : ROUTE_COMBINE_FIXUP),
+                          fold};
     if (t_dp == tiles) {
         hipLaunchKernelGGL(kern, dim3(t_dp), dim3(NTHREADS), lds, s, args, Wt, ldw, M, N, K, ep, tn);
     } else {

@@ -231,6 +231,18 @@ inline TileShape pick_tile(int M, int N, int K) {
 
 thread_local double t_executed = 0.0;      // FLOP the matrix pipe issues for the last launch_one (whole padded tiles)
 
+// What the launcher did with the last GEMM of this thread (rpg_gemm_last_route; host side only: a few integer stores per launch,
+// nothing a kernel or a launch depends on).  Which route a shape takes rests on the device (CU count, the occupancy the runtime
+// reports), so the tests that pin a route read it here and do not restate the rule.
+enum RouteKernel { ROUTE_NONE = 0, ROUTE_TILE = 1, ROUTE_LIN112 = 2, ROUTE_LIN112K2 = 3 };
+enum RouteLoader { ROUTE_LOADER_GENERAL = 0, ROUTE_LOADER_BUFFER = 1, ROUTE_LOADER_TAP = 2 };
+enum RouteCombine { ROUTE_COMBINE_NONE = 0, ROUTE_COMBINE_FIXUP = 1, ROUTE_COMBINE_INKERNEL = 2 };
+struct RouteRecord {
+    int kernel, bm, bn, bk, waves, loader, epi_lds, occ, tiles, t_dp, g_sk, rem, its_per, combine, fold_k;
+};
+constexpr int kRouteFields = (int)(sizeof(RouteRecord) / sizeof(int));
+thread_local RouteRecord t_route{};
+
 #define RPG_ENGINE_NS eng4
 #define RPG_ENGINE_NT 256
 #include "gemm_engine.inc"
@@ -533,8 +545,11 @@ bool launch_linear112(const float* A, int lda, const float* Wt, int ldw, int M, 
                         rpg::aligned16(Wt) && (lda % 4 == 0) && (ldw % 4 == 0);
     if (!vec_ok) return false;
     t_executed = 2.0 * (double)M * N * (double)K;
+    const bool k2 = (g_lin112 & 2) && 2 * tiles < 3L * cu_count();
+    t_route = RouteRecord{k2 ? ROUTE_LIN112K2 : ROUTE_LIN112, L112_BM, L112_BN, L112_BK, k2 ? 8 : 4, ROUTE_LOADER_BUFFER, 1, k2 ? 1 : 2,
+                          (int)tiles, (int)tiles, 0, 0, 0, ROUTE_COMBINE_NONE, g_fold_k >= 2 * L112_BK ? g_fold_k : 0};
     // about one tile per CU: eight waves per tile (two per SIMD); from two tiles per CU on: four waves, two workgroups per CU
-    if ((g_lin112 & 2) && 2 * tiles < 3L * cu_count())
+    if (k2)
         hipLaunchKernelGGL(linear112k2_kernel, dim3((unsigned)tiles), dim3(L112_NT2), L112_LDS_BYTES, s, A, lda, Wt, ldw, M, N, K, ep, tn, g_fold_k);
     else
         hipLaunchKernelGGL(linear112_kernel, dim3((unsigned)tiles), dim3(L112_NT), L112_LDS_BYTES, s, A, lda, Wt, ldw, M, N, K, ep, tn, g_fold_k);
@@ -596,7 +611,9 @@ int launch_tiles(const Args& args, const float* Wt, int ldw, int M, int N, int K
     const bool epi = g_epi_lds && vec_ok;
     const bool fast = g_fast && epi && seg_align > 0 && seg_align % bk == 0 && K % bk == 0 &&
                       (long)N * ldw * 4 < (1L << 31);
-    if (g_fast && epi && seg_align == -1 && (long)N * ldw * 4 < (1L << 31)) {
+    const bool tap = g_fast && epi && seg_align == -1 && (long)N * ldw * 4 < (1L << 31);
+    t_route.loader = tap ? ROUTE_LOADER_TAP : (fast ? ROUTE_LOADER_BUFFER : ROUTE_LOADER_GENERAL);     // launch_one fills in the rest
+    if (tap) {
         if (bk == 32) launch_shape<32, true, Kind::template T4, Args>(t, args, Wt, ldw, M, N, K, ep, vec_ok, s);
         else launch_shape<16, true, Kind::template T4, Args>(t, args, Wt, ldw, M, N, K, ep, vec_ok, s);
         return 0;
@@ -751,6 +768,13 @@ extern "C" int rpg_linear_gather_ex_f32(int n_src, const float* const* a, const 
                : rpg::launch_linear(src, weight, bias, residual, out, m, n_out, relu, rpg::as_stream(stream), nullptr, out_relu);
     rpg::GatherRes gr{residual, res_idx, residual2, res2_idx, ldr};
     return rpg::launch_linear(src, weight, bias, nullptr, out, m, n_out, relu, rpg::as_stream(stream), &gr, out_relu);
+}
+
+extern "C" int rpg_gemm_last_route(int* out, int n) {
+    if (!out || n < 0) return RPG_ERR_BAD_ARG;
+    const int* f = reinterpret_cast<const int*>(&t_route);
+    for (int i = 0; i < n && i < kRouteFields; ++i) out[i] = f[i];
+    return kRouteFields;
 }
 
 extern "C" int rpg_release_scratch(void) {

@@ -781,6 +781,26 @@ def linear_gather_ex(sources: Sequence[Tuple[torch.Tensor, Optional[torch.Tensor
     return (out, out_relu) if want_relu_copy else out
 
 
+ROUTE_FIELDS = ("kernel", "BM", "BN", "BK", "waves", "loader", "epi_lds", "occ", "tiles", "t_dp", "g_sk", "rem", "its_per", "combine",
+                "fold_k")
+ROUTE_KERNELS = ("none", "tile", "linear112", "linear112k2")
+ROUTE_LOADERS = ("general", "buffer", "tap")
+ROUTE_COMBINES = ("none", "fixup", "inkernel")
+
+
+def gemm_last_route() -> Dict[str, object]:
+    """What the launcher did with this thread's last fp32 GEMM (rpg_gemm_last_route): kernel "tile" | "linear112" | "linear112k2"
+    ("none" before the first launch), BM / BN / BK, waves, loader "general" | "buffer" | "tap", epi_lds, occ, tiles, t_dp, g_sk,
+    rem, its_per, combine "none" | "fixup" | "inkernel", fold_k."""
+    raw = (C.c_int * len(ROUTE_FIELDS))()
+    n = L.lib().rpg_gemm_last_route(raw, len(ROUTE_FIELDS))
+    if n != len(ROUTE_FIELDS):
+        raise L.RpgError(f"gemm_last_route: the library records {n} fields, this binding knows {len(ROUTE_FIELDS)}")
+    rec: Dict[str, object] = dict(zip(ROUTE_FIELDS, (int(v) for v in raw)))
+    rec["kernel"], rec["loader"], rec["combine"] = ROUTE_KERNELS[raw[0]], ROUTE_LOADERS[raw[5]], ROUTE_COMBINES[raw[13]]
+    return rec
+
+
 def attention_rows(gtp: torch.Tensor) -> torch.Tensor:
     gtp = _req(gtp, "gtp")
     r, c3 = gtp.shape

@@ -340,8 +340,9 @@ def test_tile_engine_variants(dev, bk, epi, tile, streamk):
 def test_tile_engine_eight_wave_workgroups(dev, tile, streamk):
     """The 8-wave instantiation of the tile engine (two waves per SIMD; 128x128 and 128x64 tiles, K step 32, buffer loaders)
     against torch and against the 4-wave one (RPG_TUNE_WAVES8 = 0): a strided 3x3 convolution with residual whose tile count
-    leaves a stream-K remainder, a 1x1/2 convolution, and the gathered Linears of the GNN (two gathered residual rows in the
-    epilogue, K = 2048 and K = 256) at M = 1792 / 256 rows."""
+    leaves a stream-K remainder, a 1x1/2 convolution, and Linears at the GNN's sizes through ops.linear_gather -- one to three
+    PLAIN (ungathered) sources, K = 2048, 256, 4096 and 64 + 32 + 160, M = 1792 / 256 / 300 rows, bias, a plain residual and
+    ReLU.  Gathered sources on the buffer loader and gathered residual rows in the epilogue are tests/test_hip_linear_sweep.py's."""
     from relpose_gnn_amd import ops
     try:
         ops.set_tuning(ops.TUNE_TILE, tile)
