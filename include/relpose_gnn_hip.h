@@ -584,7 +584,12 @@ int rpg_host_f32_to_bf16_isa(const float* src, void* dst_bf16, size_t count, int
                                      streams they are dispatched ahead of the other stream's queued convolution workgroups */
 #define RPG_TUNE_BF16_PAIR 31        /* bf16 encoder: 1 (default) = the 3x3 / stride-2 convolution and the 1x1 / stride-2 shortcut of a down-sampling BasicBlock
                                      run as ONE launch of the LDS-DMA kernel (their tiles side by side in the grid; same arithmetic) | 0 = two launches */
+/* RPG_ERR_BAD_ARG for an unknown key or a value the key does not accept (nothing changes then).  Process-wide; set keys between
+ * launches, from the thread that launches. */
 int rpg_set_tuning(int key, int value);
+/* Read-back: *value = the value last accepted for `key`, exactly as it was passed to rpg_set_tuning (the default before any set);
+ * *default_value = the key's default.  Either pointer may be NULL.  RPG_ERR_BAD_ARG for an unknown key. */
+int rpg_get_tuning(int key, int* value, int* default_value);
 
 /* ------------------------------------------------------------------------------------------- */
 /* Input transform (replaces the reference's CPU transform of every node image,                 */

@@ -32,7 +32,7 @@ SYMBOLS = (
     "rpg_frames_u8_to_bf16", "rpg_gather_graph_nodes_f32", "rpg_linear_bf16_ex", "rpg_conv_pair_bf16",
     "rpg_retrieve_workspace_bytes", "rpg_retrieve_max_rank", "rpg_row_inv_norms_f32", "rpg_retrieve_cosine_f32",
     "rpg_query_pose_f64", "rpg_query_pose_fused_f64", "rpg_gather_add2_relu_f32",
-    "rpg_gnn_query_workspace_bytes", "rpg_gnn_forward_query_f32", "rpg_gnn_forward_query_bf16", "rpg_gemm_last_route",
+    "rpg_gnn_query_workspace_bytes", "rpg_gnn_forward_query_f32", "rpg_gnn_forward_query_bf16", "rpg_gemm_last_route", "rpg_get_tuning",
 )
 
 
@@ -89,6 +89,7 @@ def _declare(lib: C.CDLL) -> None:
     lib.rpg_conv_pair_bf16.argtypes = [_vp] * 9 + [_i] * 8 + [_vp]
     lib.rpg_timing_enable.argtypes = [_i]
     lib.rpg_set_tuning.argtypes = [_i, _i]
+    lib.rpg_get_tuning.argtypes = [_i, C.POINTER(_i), C.POINTER(_i)]
     lib.rpg_conv2d_bn_act_nhwc_bf16.argtypes = [_vp] * 6 + [_i] * 11 + [_vp]
     lib.rpg_basicblock64_bf16.argtypes = [_vp] * 8 + [_i] * 3 + [_vp]
     lib.rpg_resnet_bf16_workspace_bytes.argtypes = [_i, _i, _i, C.POINTER(_i)]

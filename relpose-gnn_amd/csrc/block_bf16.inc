@@ -565,8 +565,6 @@ __global__ __launch_bounds__(512) void block64_bf16_fused_kernel(BlockArgs a, co
 #undef RPG_PP_SYNC
 }
 
-int g_bf16_fuse_block = 3;       // RPG_TUNE_BF16_FUSE_BLOCK: 64-channel identity BasicBlocks of the bf16 encoder as one kernel (bit 1: the persistent form)
-
 // x [n][h][w][64] -> y [n][h][w][64] = relu(bn2(conv2(relu(bn1(conv1(x))))) + x); false if the shape is not eligible (the caller
 // then launches the two convolutions)
 bool launch_block64_fused(const void* x, const void* w1, const float* scale1, const float* shift1, const void* w2, const float* scale2,
@@ -623,7 +621,7 @@ bool launch_block64_fused(const void* x, const void* w1, const float* scale1, co
         once[dev] = true;
     }
     // two-group schedule (RPG_TUNE_BF16_FUSE_BLOCK bit 2, experiment): one tile per workgroup, five weight stages
-    if ((g_bf16_fuse_block & 4) && lds + C * 64 <= 160 * 1024) {
+    if ((rpg::tuning().bf16.fuse_block & 4) && lds + C * 64 <= 160 * 1024) {
         static bool once_pp[64] = {};
         if (!once_pp[dev]) {
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(block64_bf16_fused_kernel<BM2, 5, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -636,7 +634,7 @@ bool launch_block64_fused(const void* x, const void* w1, const float* scale1, co
     // persistent form (RPG_TUNE_BF16_FUSE_BLOCK bit 1): more than one round of tiles, a grid of whole octets of CUs (the XCD-wise tile
     // order needs blockIdx & 7 to be the XCD of every tile a workgroup walks); the epilogue slabs must fit buffer 1
     const int pgrid = rpg::num_cus() & ~7;
-    if ((g_bf16_fuse_block & 2) && pgrid >= 8 && a.n_tiles > pgrid && a.patch_bytes >= slab_bytes) {
+    if ((rpg::tuning().bf16.fuse_block & 2) && pgrid >= 8 && a.n_tiles > pgrid && a.patch_bytes >= slab_bytes) {
         hipLaunchKernelGGL((block64_bf16_fused_kernel<BM2, NS, true>), dim3(pgrid), dim3(512), lds, s, a, reinterpret_cast<const __bf16*>(w1),
                            reinterpret_cast<const __bf16*>(w2), ep);
         return true;

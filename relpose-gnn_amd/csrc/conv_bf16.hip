@@ -1153,15 +1153,8 @@ __global__ __launch_bounds__(64 * WM * WN) void conv3x3_bf16_patch_kernel(PatchA
 #endif
 }
 
-int g_bf16_lean_epi = 1;     // RPG_TUNE_BF16_LEAN_EPI: the branch-free epilogue for plain convolutions (0: the general one, rounds 1-3)
-int g_bf16_fused_stem = 1;   // RPG_TUNE_FUSED_STEM also selects the bf16 encoder's fused stem (stem_bf16.hip)
-int g_bf16_chunk = 0;        // RPG_TUNE_BF16_CHUNK: images per depth-first group of the bf16 encoder's identity-block runs (0 = off)
-int g_bf16_chunk_mb = 64;    // ... for activation tensors of at least this many MB
-int g_bf16_linear_dma = 0;   // RPG_TUNE_BF16_LINEAR_DMA: 0 = the interleaved buffer-load kernel | 10 + i: LDS-DMA configuration i
-int g_bf16_dma = 1;      // RPG_TUNE_BF16_DMA: 0 off | 1 by shape | 10 + i: configuration i of launch_dma_config wherever it is eligible
-int g_bf16_tile = -1;    // RPG_TUNE_BF16_TILE: -1 auto | 0: 64x64 | 1: 128x128 | 2: 256x64 | 3: 128x64 (interleaved kernel only)
-int g_bf16_fast = 1;     // RPG_TUNE_BF16_FAST: the interleaved buffer-load kernel where eligible
-int g_bf16_bk = 32;      // measured on MI355X at 64 graphs: K step 32 -> 9.97 ms/step, 64 -> 12.5 (the 72-KB LDS image halves occupancy)
+// The tuning knobs of this unit are rpg::tuning().bf16 (tuning.h).  bk: measured on MI355X at 64 graphs: K step 32 -> 9.97 ms/step,
+// 64 -> 12.5 (the 72-KB LDS image halves occupancy)
 
 template <int BM, int BN, int WM, int WN, int BK>
 void launch_tile(const ConvArgsB& a, const __bf16* w, int M, int N, int K, const EpiB& ep, hipStream_t s) {
@@ -1225,18 +1218,14 @@ void launch_dma_pair(const DmaOne& c1in, const DmaOne& c2in, hipStream_t s) {
     const int t1 = ((c1.M + BM - 1) / BM) * c1.tiles_n, t2 = ((c2.M + BM - 1) / BM) * c2.tiles_n;
     hipLaunchKernelGGL(kern, dim3(t1 + t2), dim3(64 * WM * WN), lds, s, c1, c2, t1);
 }
-int g_bf16_pair = 1;     // RPG_TUNE_BF16_PAIR: the strided 3x3 + 1x1 shortcut pair of a down-sampling block in one launch
 
-int g_bf16_stages = 4;   // weight stages of the patch kernel (experiments: 3 = never the prefetching form); RPG_TUNE_BF16_PATCH + 10
 // RPG_TUNE_BF16_PERSIST: the persistent form of the patch kernel (cross-tile prefetch) on the 64-channel layer.  OFF by default: the kernel
 // itself is 10 % (in the model) to 15 % (stand-alone) faster, but 256 resident workgroups hold every CU for the whole launch, and the
 // default two-stream schedule lives on the other stream's workgroups slipping into this launch's gaps: configs[2] 13.53-13.60 k graphs/s
 // without it, 13.26-13.39 k with it (same box, alternating runs; one-stream kernel sums equal).
-int g_bf16_persist = 0;
-int g_bf16_tail = 1;     // RPG_TUNE_BF16_TAIL: bit 0 (default): 512 x 128 launches hand the rows beyond the last full round to 256 x 128 tiles (layer 2 at 512
-                         // images: -4..5 %); bit 1: 256 x 256 launches likewise to 160 x 256 tiles (layer 3: measured no gain -- the partly empty
-                         // second round of the single launch already runs 1.46x faster per tile: the kernels are bound chip-wide, not per CU)
-int g_bf16_patch = 1;    // RPG_TUNE_BF16_PATCH: the patch kernel for 3x3 / stride-1 convolutions: 0 off | 1 by shape | 2 wherever eligible
+// RPG_TUNE_BF16_TAIL: bit 0 (default): 512 x 128 launches hand the rows beyond the last full round to 256 x 128 tiles (layer 2 at 512
+// images: -4..5 %); bit 1: 256 x 256 launches likewise to 160 x 256 tiles (layer 3: measured no gain -- the partly empty second round of
+// the single launch already runs 1.46x faster per tile: the kernels are bound chip-wide, not per CU)
 
 // The patch kernel, if the shape is eligible (3x3, stride 1, pad 1, Cin % 64 == 0, patch <= 64 pieces, 32-bit offsets, LDS fits)
 // m_begin / m_end: the launch covers the output rows [m_begin, m_end) only (m_end = 0: to M); the tiles start at m_begin
@@ -1434,24 +1423,6 @@ __global__ __launch_bounds__(NT) void global_avgpool_bf16_kernel(const uint4* __
 
 namespace rpg {
 
-void bf16_set_bk(int bk) { g_bf16_bk = bk; }
-void bf16_set_fast(int on) { g_bf16_fast = on; }
-void bf16_set_tile(int t) { g_bf16_tile = t; }
-void bf16_set_dma(int v) { g_bf16_dma = v; }
-void bf16_set_patch(int v) { g_bf16_stages = v >= 10 ? 3 : 4; g_bf16_patch = v % 10; }
-void bf16_set_fused_stem(int on) { g_bf16_fused_stem = on; }
-void bf16_set_lean_epi(int on) { g_bf16_lean_epi = on; }
-void bf16_set_persist(int v) { g_bf16_persist = v; }
-void bf16_set_fuse_block(int v) { g_bf16_fuse_block = v; }
-void bf16_set_tail(int v) { g_bf16_tail = v & 7; }
-void bf16_set_linear_dma(int v) { g_bf16_linear_dma = v; }
-void bf16_set_chunk(int images, int min_mb) { g_bf16_chunk = images; g_bf16_chunk_mb = min_mb; }
-#ifdef RPG_PROBE_WS64
-int bf16_set_ws64(int v) { g_bf16_ws64 = v; return RPG_OK; }
-#else
-int bf16_set_ws64(int v) { return v == 0 ? RPG_OK : RPG_ERR_BAD_ARG; }      // the probe kernel is not in this build
-#endif
-
 // fp32 [rows][ld_src] (first `cols` columns) -> bf16 dst[rows][ld_dst] at column offset col_off (cols % 8 == 0)
 __global__ __launch_bounds__(NT) void f32_to_bf16_kernel(const float* __restrict__ src, int ld_src, __bf16* __restrict__ dst,
                                                          int ld_dst, int col_off, long total8, int cols8) {
@@ -1504,12 +1475,12 @@ int launch_linear_bf16_ex(const void* a, int lda, const void* w, const float* bi
     ep.out2 = reinterpret_cast<__bf16*>(o.out2); ep.ld2 = o.ld2; ep.relu2 = o.relu2;
     const __bf16* wp = reinterpret_cast<const __bf16*>(w);
     const int slot = timing_begin(RPG_TIMER_LINEAR, s);
-    const bool fast = g_bf16_fast && k % 64 == 0 && 258L * lda * 2 < (1L << 31) && (long)n_out * k * 2 < (1L << 31);
+    const bool fast = rpg::tuning().bf16.fast && k % 64 == 0 && 258L * lda * 2 < (1L << 31) && (long)n_out * k * 2 < (1L << 31);
     const long t128 = (long)((m + 127) / 128) * ((n_out + 127) / 128);
     // RPG_TUNE_BF16_LINEAR_DMA = 10 + i: configuration i of the LDS-DMA kernel for the edge-row Linears (a 1 x 1 convolution over an
     // m-pixel image; the general epilogue carries the gathers and the second output)
     const bool dma_ok = 1026L * lda * 2 < (1L << 31) && (long)n_out * k * 2 < (1L << 31);
-    if (g_bf16_linear_dma >= 10 && dma_ok && t128 >= 192 && launch_dma_config(g_bf16_linear_dma - 10, ca, wp, m, n_out, k, ep, s)) {
+    if (rpg::tuning().bf16.linear_dma >= 10 && dma_ok && t128 >= 192 && launch_dma_config(rpg::tuning().bf16.linear_dma - 10, ca, wp, m, n_out, k, ep, s)) {
     } else if (fast) {
         if (t128 >= 192) launch_fast<128, 128, 2, 2>(ca, wp, m, n_out, k, ep, s);
         else launch_fast<64, 64, 2, 2>(ca, wp, m, n_out, k, ep, s);
@@ -1522,13 +1493,11 @@ int launch_linear_bf16_ex(const void* a, int lda, const void* w, const float* bi
     return RPG_OK;
 }
 
-void bf16_set_pair(int v) { g_bf16_pair = v; }
-
 // conv A (kh x kw / stride / pad) and conv B (1 x 1 / same stride, pad 0) of the same input x [n][h][w][cin] -> ya, yb (both
 // [n][ho][wo][cout], bf16, BN folded, ReLU on A only per `relu_a`); false: not eligible (the caller launches them one by one)
 bool launch_conv_pair_bf16(const void* x, const void* wa, const float* sa, const float* ha, void* ya, const void* wb_, const float* sb,
                            const float* hb, void* yb, int n, int h, int wd, int cin, int cout, int k, int stride, int pad, hipStream_t s) {
-    if (!g_bf16_pair || g_bf16_dma != 1 || !x || !wa || !wb_ || !ya || !yb || n <= 0 || (cin & 31) || (cout & 3)) return false;
+    if (!rpg::tuning().bf16.pair || rpg::tuning().bf16.dma != 1 || !x || !wa || !wb_ || !ya || !yb || n <= 0 || (cin & 31) || (cout & 3)) return false;
     const int ho = conv_out(h, k, stride, pad), wo = conv_out(wd, k, stride, pad);
     if (ho <= 0 || wo <= 0 || ho != conv_out(h, 1, stride, 0) || wo != conv_out(wd, 1, stride, 0)) return false;
     const long M = (long)n * ho * wo, Ka = (long)k * k * cin, Kb = cin;
@@ -1543,7 +1512,7 @@ bool launch_conv_pair_bf16(const void* x, const void* wa, const float* sa, const
     c1.M = c2.M = (int)M; c1.N = c2.N = cout; c1.K = (int)Ka; c2.K = (int)Kb;
     c1.ep = EpiB{sa, ha, nullptr, ya, cout, 1, 0};
     c2.ep = EpiB{sb, hb, nullptr, yb, cout, 0, 0};
-    const bool lean = g_bf16_lean_epi && 1024L * cout * 2 < (1L << 31);
+    const bool lean = rpg::tuning().bf16.lean_epi && 1024L * cout * 2 < (1L << 31);
     c1.ep.lean = lean; c2.ep.lean = lean;
     const int slot = timing_begin(RPG_TIMER_CONV, s);
     // the tile template of launch_conv_bf16's choice for the 3x3 (configuration 7 up to 128 channels, 0 above where 256 x 256 tiles
@@ -1569,14 +1538,14 @@ int launch_conv_bf16(const void* x, const void* w, const float* scale, const flo
     ConvArgsB a{reinterpret_cast<const __bf16*>(x), h, wd, cin, kh, kw, stride, pad, ho, wo};
     EpiB ep{scale, shift, reinterpret_cast<const __bf16*>(residual), y, cout, relu, out_f32};
     // plain convolution: the lean epilogue (RPG_TUNE_BF16_LEAN_EPI); a workgroup's <= 1024 rows within 32-bit byte offsets
-    ep.lean = g_bf16_lean_epi && !out_f32 && (cout & 3) == 0 && 1024L * cout * 2 < (1L << 31);
+    ep.lean = rpg::tuning().bf16.lean_epi && !out_f32 && (cout & 3) == 0 && 1024L * cout * 2 < (1L << 31);
     const __bf16* wp = reinterpret_cast<const __bf16*>(w);
     const int slot = timing_begin(RPG_TIMER_CONV, s);
-    const bool big_k = g_bf16_bk == 64 && K >= 128;
+    const bool big_k = rpg::tuning().bf16.bk == 64 && K >= 128;
     // the interleaved buffer-load kernel: whole 64-element K steps per kernel tap, 32-bit offsets relative to the
     // first image of a tile (whose <= 256 rows span at most 256 / (ho*wo) + 2 images)
     const long span = 256 / ((long)ho * wo) + 2;
-    const bool fast = g_bf16_fast && cin % 64 == 0 && span * h * wd * cin * 2 < (1L << 31) && (long)cout * K * 2 < (1L << 31);
+    const bool fast = rpg::tuning().bf16.fast && cin % 64 == 0 && span * h * wd * cin * 2 < (1L << 31) && (long)cout * K * 2 < (1L << 31);
     const long span1k = 1024 / ((long)ho * wo) + 2;          // the widest DMA tile has 1024 rows
     const bool dma_ok = span1k * h * wd * cin * 2 < (1L << 31) && (long)cout * K * 2 < (1L << 31);
     // RPG_TUNE_BF16_DMA = 1: the LDS-DMA kernel by shape (measured at 256 / 512 images, tools/conv_bench.py --dma-sweep,
@@ -1584,21 +1553,21 @@ int launch_conv_bf16(const void* x, const void* w, const float* scale, const flo
     // fill from L2 bounds it, N is too small to amortise the A tile), 256 x 128 / K step 32 / two workgroups per CU up to 128
     // channels and wherever 256 x 256 tiles would leave a quarter of the CUs idle, 256 x 256 (wave tile 128 x 64) otherwise
     int dma_cfg = -1;
-    if (dma_ok && g_bf16_dma == 1 && M >= 8192 && cin % 32 == 0) {
+    if (dma_ok && rpg::tuning().bf16.dma == 1 && M >= 8192 && cin % 32 == 0) {
         const long t256 = ((M + 255) / 256) * ((cout + 255) / 256);
         if (cout <= 64) dma_cfg = cin % 64 == 0 ? 5 : -1;
         else if (cout <= 128 || 4 * t256 < 3L * num_cus() || cin % 64) dma_cfg = 7;
         else dma_cfg = 0;
-    } else if (dma_ok && g_bf16_dma >= 10) {
-        dma_cfg = g_bf16_dma - 10;                    // forced configuration (experiments)
+    } else if (dma_ok && rpg::tuning().bf16.dma >= 10) {
+        dma_cfg = rpg::tuning().bf16.dma - 10;                    // forced configuration (experiments)
     }
     // 3x3 / stride 1: the patch kernel (input pixels fetched once per 32-channel chunk instead of once per tap)
     bool done = false;
 #ifdef RPG_PROBE_WS64
-    if (g_bf16_ws64 && cin == 64 && cout == 64 && M >= 8192)
-        done = g_bf16_ws64 == 2 ? launch_ws64<2>(a, wp, n, (int)M, cout, ep, s) : launch_ws64<3>(a, wp, n, (int)M, cout, ep, s);
+    if (rpg::tuning().bf16.ws64 && cin == 64 && cout == 64 && M >= 8192)
+        done = rpg::tuning().bf16.ws64 == 2 ? launch_ws64<2>(a, wp, n, (int)M, cout, ep, s) : launch_ws64<3>(a, wp, n, (int)M, cout, ep, s);
 #endif
-    if (!done && g_bf16_patch && kh == 3 && kw == 3 && stride == 1 && pad == 1 && (g_bf16_patch >= 2 || M >= 8192)) {
+    if (!done && rpg::tuning().bf16.patch && kh == 3 && kw == 3 && stride == 1 && pad == 1 && (rpg::tuning().bf16.patch >= 2 || M >= 8192)) {
         // measured (tools/conv_bench.py --dma-sweep, r3): from 256 output channels up the patch kernel beats the im2col DMA kernel
         // by 5-10 %; 256 x 256 tiles where they occupy at least three quarters of the CUs, else 256 x 128 (layer 4 at 256 images:
         // 98 vs 196 tiles, 98 vs 68 us); at 128 channels the DMA kernel's 256 x 128 / K-step-32 configuration is faster
@@ -1607,7 +1576,7 @@ int launch_conv_bf16(const void* x, const void* w, const float* scale, const flo
         // that fills three quarters of the CUs, else 256 x 128; 512 x 128 for 128 channels, 512 x 64 for 64 -- the narrow layers
         // need the tall tile to put 8-16 MFMAs per wave between two barriers.  Four weight stages (next step's weight fragments
         // read before the barrier) where the LDS allows and it measured faster, else three.
-        const bool big = M >= 65536 || g_bf16_patch >= 2;
+        const bool big = M >= 65536 || rpg::tuning().bf16.patch >= 2;
         // Tail re-tiling (round 5, RPG_TUNE_BF16_TAIL): M = 49 * 2^k pixels puts 49 * 2^j tiles on 256 CUs -- 3.06 rounds on layer 2,
         // 1.53 on layer 3 at 512 images -- and the last, mostly empty round costs a whole tile time.  Splitting the tail tiles along
         // K (what the fp32 Winograd kernel does) would move fp32 partial slabs of 256 KB per part through HBM: more than the round it
@@ -1615,23 +1584,23 @@ int launch_conv_bf16(const void* x, const void* w, const float* scale, const flo
         // (160 x 256 on 8 x 1 waves / 256 x 128): one short round instead of a full one, no partial sums, same arithmetic per output.
         const int cus = num_cus();
         auto tail_split = [&](int bm, int bm_tail) -> int {        // rows of the main launch, or 0: do not split
-            if (!g_bf16_tail || cout > 256 || M >= (1L << 30)) return 0;
+            if (!rpg::tuning().bf16.tail || cout > 256 || M >= (1L << 30)) return 0;
             const long tiles = (M + bm - 1) / bm;
             const long main_tiles = tiles / cus * cus, rem = tiles - main_tiles;
             if (main_tiles == 0 || rem == 0) return 0;
             const long tail_rows = M - main_tiles * bm;
             return (tail_rows + bm_tail - 1) / bm_tail <= cus ? (int)(main_tiles * bm) : 0;
         };
-        if (g_bf16_patch == 3) {
+        if (rpg::tuning().bf16.patch == 3) {
             done = launch_patch<256, 128, 4, 2, 3>(a, wp, n, (int)M, cout, ep, s);
-        } else if (g_bf16_patch == 4 && cout > 128) {
+        } else if (rpg::tuning().bf16.patch == 4 && cout > 128) {
             // round-6 experiment (RPG_TUNE_BF16_PATCH = 4): 512 x 128 tiles on the 256- / 512-channel layers too -- 15 instead of 21 bytes of
             // L2 -> LDS fill per output.  Measured at 512 images: layer 3 124-127 us against 127-130, layer 4 126-137 against 119-123: the
             // fill volume is not what bounds these layers either
             done = launch_patch<512, 128, 4, 2, 4>(a, wp, n, (int)M, cout, ep, s) || launch_patch<512, 128, 4, 2, 3>(a, wp, n, (int)M, cout, ep, s);
         } else if (cout > 128 && 4 * t256 >= 3L * num_cus()) {
-            const int m_main = (g_bf16_tail & 2) && cout <= 256 ? tail_split(256, 160) : 0;
-            done = (g_bf16_stages != 3 && launch_patch<256, 256, 2, 4, 4>(a, wp, n, (int)M, cout, ep, s, 0, m_main)) ||
+            const int m_main = (rpg::tuning().bf16.tail & 2) && cout <= 256 ? tail_split(256, 160) : 0;
+            done = (rpg::tuning().bf16.stages != 3 && launch_patch<256, 256, 2, 4, 4>(a, wp, n, (int)M, cout, ep, s, 0, m_main)) ||
                    launch_patch<256, 256, 2, 4, 3>(a, wp, n, (int)M, cout, ep, s, 0, m_main);
             if (done && m_main && !launch_patch<160, 256, 1, 8, 3>(a, wp, n, (int)M, cout, ep, s, m_main, 0))
                 done = launch_patch<256, 256, 2, 4, 3>(a, wp, n, (int)M, cout, ep, s, m_main, 0);
@@ -1641,29 +1610,29 @@ int launch_conv_bf16(const void* x, const void* w, const float* scale, const flo
             // (the persistent form of this tile was built and measured slower -- 141 -> 179 us: at 256 VGPRs the next tile's piece
             // addresses, computed in front of the last chunk with the accumulators live, spill 65-113 registers)
             // (bit 2, round-6 experiment: the tail on 128 x 128 tiles -- twice the workgroups, half the rows each)
-            const int m_main = (g_bf16_tail & 1) ? tail_split(512, (g_bf16_tail & 4) ? 128 : 256) : 0;
-            done = (g_bf16_stages != 3 && launch_patch<512, 128, 4, 2, 4>(a, wp, n, (int)M, cout, ep, s, 0, m_main)) ||
+            const int m_main = (rpg::tuning().bf16.tail & 1) ? tail_split(512, (rpg::tuning().bf16.tail & 4) ? 128 : 256) : 0;
+            done = (rpg::tuning().bf16.stages != 3 && launch_patch<512, 128, 4, 2, 4>(a, wp, n, (int)M, cout, ep, s, 0, m_main)) ||
                    launch_patch<512, 128, 4, 2, 3>(a, wp, n, (int)M, cout, ep, s, 0, m_main);
-            if (done && m_main && (g_bf16_tail & 4) && launch_patch<128, 128, 4, 2, 3>(a, wp, n, (int)M, cout, ep, s, m_main, 0)) {
+            if (done && m_main && (rpg::tuning().bf16.tail & 4) && launch_patch<128, 128, 4, 2, 3>(a, wp, n, (int)M, cout, ep, s, m_main, 0)) {
             } else if (done && m_main && !launch_patch<256, 128, 4, 2, 3>(a, wp, n, (int)M, cout, ep, s, m_main, 0))
                 done = launch_patch<512, 128, 4, 2, 3>(a, wp, n, (int)M, cout, ep, s, m_main, 0);
-        } else if (g_bf16_patch >= 2 || big) {
+        } else if (rpg::tuning().bf16.patch >= 2 || big) {
             // 64 output channels (layer 1).  Round 3 measured 232-245 us at 512 images against 205-222 us for the im2col DMA kernel
             // with two 80-KB workgroups per CU (configuration 5: they hide each other's epilogue) and kept this tile for tests only.
             // With the lean epilogue of round 4 the order flipped where it matters: 216-223 / 229-239 us (without / with residual)
             // against 214-215 / 246-248, and the whole configs[2] step gains 2.4 % (12.79 -> 13.10 k graphs/s, two streams:
             // profiles/r4_bf16_epilogue_experiments.txt) -- a quarter of the L2 -> LDS traffic leaves more of the chip to the other stream.
-            done = (g_bf16_persist && g_bf16_stages != 3 && launch_patch<512, 64, 8, 1, 4, true>(a, wp, n, (int)M, cout, ep, s)) ||
-                   (g_bf16_stages != 3 && launch_patch<512, 64, 8, 1, 4>(a, wp, n, (int)M, cout, ep, s)) ||
+            done = (rpg::tuning().bf16.persist && rpg::tuning().bf16.stages != 3 && launch_patch<512, 64, 8, 1, 4, true>(a, wp, n, (int)M, cout, ep, s)) ||
+                   (rpg::tuning().bf16.stages != 3 && launch_patch<512, 64, 8, 1, 4>(a, wp, n, (int)M, cout, ep, s)) ||
                    launch_patch<512, 64, 8, 1, 3>(a, wp, n, (int)M, cout, ep, s);
         }
     }
     if (done) {
     } else if (dma_cfg >= 0 && launch_dma_config(dma_cfg, a, wp, (int)M, cout, (int)K, ep, s)) {
-    } else if (fast && g_bf16_tile >= 0) {       // RPG_TUNE_BF16_TILE: forced tile of the interleaved kernel (experiments)
-        if (g_bf16_tile == 0) launch_fast<64, 64, 2, 2>(a, wp, (int)M, cout, (int)K, ep, s);
-        else if (g_bf16_tile == 1) launch_fast<128, 128, 2, 2>(a, wp, (int)M, cout, (int)K, ep, s);
-        else if (g_bf16_tile == 3) launch_fast<128, 64, 4, 1>(a, wp, (int)M, cout, (int)K, ep, s);
+    } else if (fast && rpg::tuning().bf16.tile >= 0) {       // RPG_TUNE_BF16_TILE: forced tile of the interleaved kernel (experiments)
+        if (rpg::tuning().bf16.tile == 0) launch_fast<64, 64, 2, 2>(a, wp, (int)M, cout, (int)K, ep, s);
+        else if (rpg::tuning().bf16.tile == 1) launch_fast<128, 128, 2, 2>(a, wp, (int)M, cout, (int)K, ep, s);
+        else if (rpg::tuning().bf16.tile == 3) launch_fast<128, 64, 4, 1>(a, wp, (int)M, cout, (int)K, ep, s);
         else launch_fast<256, 64, 4, 1>(a, wp, (int)M, cout, (int)K, ep, s);
     } else if (fast) {
         // Cout = 64 on many rows (layer 1): 128 x 64 (three workgroups per CU; 238 vs 251 us with 256 x 64 at 512 images)
@@ -1726,7 +1695,7 @@ static int resnet_forward_bf16_impl(const void* const* tensors, int n_tensors, c
     unsigned short* const* buf = B.buf;
 
     int rc, ti = 0;
-    if (stem_pack && g_bf16_fused_stem && rpg::stem_pool_bf16_supported(n, h, w, planes[0])) {
+    if (stem_pack && rpg::tuning().bf16.fused_stem && rpg::stem_pool_bf16_supported(n, h, w, planes[0])) {
         // fp32 NCHW -> conv7x7/2 + BN + ReLU + maxpool3x3/2 -> pooled bf16 NHWC, one kernel
         if ((rc = rpg::launch_stem_pool_bf16(x_nchw_any, x_is_bf16, stem_pack, (const float*)tensors[1], (const float*)tensors[2], buf[0],
                                              n, h, w, s)) != RPG_OK)
@@ -1755,15 +1724,15 @@ static int resnet_forward_bf16_impl(const void* const* tensors, int n_tensors, c
     for (; !b.done(); b.next()) {
         // Depth-first over image groups (round 4, RPG_TUNE_BF16_CHUNK): a run of identity blocks (stride 1, no downsample)
         // on LARGE activation tensors is walked group of images by group of images -- conv1, conv2 of every block of the
-        // run on `g_bf16_chunk` images, then the next group -- so that a group's intermediate tensors (and the residual) are
+        // run on `rpg::tuning().bf16.chunk` images, then the next group -- so that a group's intermediate tensors (and the residual) are
         // re-read from the 256-MB Infinity Cache instead of HBM.  Images are independent: same kernels, same arithmetic,
         // only the pointers and the image count of a launch change.
         const size_t act_bytes = (size_t)n * b.h * b.w * b.c * 2;
-        if (!b.ds && g_bf16_chunk > 0 && n > g_bf16_chunk && act_bytes >= ((size_t)g_bf16_chunk_mb << 20)) {
+        if (!b.ds && rpg::tuning().bf16.chunk > 0 && n > rpg::tuning().bf16.chunk && act_bytes >= ((size_t)rpg::tuning().bf16.chunk_mb << 20)) {
             const int run = blocks[b.layer] - b.index;      // identity blocks: this one and all that follow in this layer
             const size_t img = (size_t)b.h * b.w * b.c;         // elements per image of every tensor in the run
-            for (int i0 = 0; i0 < n; i0 += g_bf16_chunk) {
-                const int ni = n - i0 < g_bf16_chunk ? n - i0 : g_bf16_chunk;
+            for (int i0 = 0; i0 < n; i0 += rpg::tuning().bf16.chunk) {
+                const int ni = n - i0 < rpg::tuning().bf16.chunk ? n - i0 : rpg::tuning().bf16.chunk;
                 int cc = cur, tj = ti;
                 ResnetWalk r = b;                           // a copy walks the run once per group
                 for (int j = 0; j < run; ++j, r.next()) {
@@ -1791,7 +1760,7 @@ static int resnet_forward_bf16_impl(const void* const* tensors, int n_tensors, c
         void* D = buf[(cur + 3) & 3];
         // 64-channel identity block (layer 1): conv1 + BN + ReLU + conv2 + BN + identity + ReLU in one kernel, the intermediate
         // on chip (block_bf16.inc; bit-identical to the two launches below)
-        if (!b.ds && b.c == 64 && g_bf16_fuse_block && (long)n * b.h * b.w >= 8192) {
+        if (!b.ds && b.c == 64 && rpg::tuning().bf16.fuse_block && (long)n * b.h * b.w >= 8192) {
             const int slot = rpg::timing_begin(RPG_TIMER_CONV, s);
             if (launch_block64_fused(X, tensors[ti], (const float*)tensors[ti + 1], (const float*)tensors[ti + 2], tensors[ti + 3],
                                      (const float*)tensors[ti + 4], (const float*)tensors[ti + 5], Y, n, b.h, b.w, s)) {

@@ -183,7 +183,7 @@ int prepare(GnnCall& k, const float* const* tensors, int n_tensors, const void* 
     if (workspace_bytes < cv.off) return RPG_ERR_WORKSPACE;      // before any pointer of k.g / k.q is used
     k.tensors = tensors; k.wb = wb;
     k.n = n; k.e = e; k.d = d; k.c = d / 8; k.recursion = gnn_recursion;
-    k.split = (n_tensors == T_COUNT_SPLIT) && (wb || rpg::gnn_split_enabled());
+    k.split = (n_tensors == T_COUNT_SPLIT) && (wb || rpg::tuning().gnn.split != 0);
     if (wb && !k.split) return RPG_ERR_BAD_ARG;            // the bf16 Linears exist for the split formulation only
     k.qs = qs; k.es = qs ? qs->e_sel : 0; k.nq = qs ? qs->q : 0;
     k.s = rpg::as_stream(stream);
@@ -381,7 +381,7 @@ int layers_general(GnnCall& k) {
     const rpg::GnnBuffers& g = k.g;
     const rpg::GnnQueryBuffers& q = k.q;
     const int e = k.e, d = k.d, c = k.c;
-    const bool split = k.split, fuse_agg = rpg::gnn_fuse_agg_enabled();
+    const bool split = k.split, fuse_agg = rpg::tuning().gnn.fuse_agg != 0;
     int rc;
     // edge_feat = relu(proj_edge(cat[x[min], x[max]]))                                   posenet.py:1053-1055
     const float* x = k.x;
@@ -488,7 +488,7 @@ int gnn_forward_impl(const float* const* tensors, int n_tensors, const void* con
     if (rc != RPG_OK) return rc;
     rpg::ScratchScope scratch(k.g.scratch, scratch_bytes, k.s);      // stream-K partial tiles; its memset precedes every launch
     if ((rc = prepare_graph(k, esrc, edst, node_offset, status)) != RPG_OK) return rc;
-    rc = (wb && rpg::gnn_fuse_agg_enabled()) ? layers_bf16_chained(k) : layers_general(k);
+    rc = (wb && rpg::tuning().gnn.fuse_agg != 0) ? layers_bf16_chained(k) : layers_general(k);
     if (rc != RPG_OK) return rc;
     return finish(k, abs_pose, rel_pose, node_out, edge_out);
 }

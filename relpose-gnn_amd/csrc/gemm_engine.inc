@@ -849,11 +849,11 @@ int launch_one(const Args& args, const float* Wt, int ldw, int M, int N, int K, 
     int t_dp = tiles, its_per = 0, g_sk = 0;
     float* partial = nullptr;
     unsigned* arrive = nullptr;            // arrival counters of the scratch block (in-kernel combine of the split tiles)
-    if (g_streamk && nk >= SK_MIN_NK && tiles % slots != 0) {
+    if (rpg::tuning().gemm.streamk && nk >= SK_MIN_NK && tiles % slots != 0) {
         const int rem = tiles % slots;
         const long total = (long)rem * nk;
         its_per = (int)((total + slots - 1) / slots);
-        if (its_per < SK_MIN_ITS) its_per = SK_MIN_ITS;
+        if (its_per < rpg::tuning().gemm.sk_min_its) its_per = rpg::tuning().gemm.sk_min_its;
         g_sk = (int)((total + its_per - 1) / its_per);
         if (g_sk > rem) {             // stream-K spreads the remainder over more workgroups than tiles: worth it
             partial = get_scratch(s, (size_t)(g_sk + rem) * BM * BN * sizeof(float), &arrive);
@@ -867,7 +867,7 @@ int launch_one(const Args& args, const float* Wt, int ldw, int M, int N, int K, 
     t_route = RouteRecord{ROUTE_TILE, BM, BN, BK, NTHREADS / 64, t_route.loader, EPI ? 1 : 0, occ, tiles, t_dp, t_dp == tiles ? 0 : g_sk,
                           tiles - t_dp, t_dp == tiles ? 0 : its_per,
                           t_dp == tiles ? ROUTE_COMBINE_NONE
-                                        : (((g_inkernel_fixup & 1) && arrive && tiles - t_dp <= (int)(kCounterBytes / sizeof(unsigned)))
+                                        : (((rpg::tuning().gemm.inkernel_fixup & 1) && arrive && tiles - t_dp <= (int)(kCounterBytes / sizeof(unsigned)))
                                                ? ROUTE_COMBINE_INKERNEL : ROUTE_COMBINE_FIXUP),
                           fold};
     if (t_dp == tiles) {
@@ -876,7 +876,7 @@ int launch_one(const Args& args, const float* Wt, int ldw, int M, int N, int K, 
         // stream-K blocks and (if any) the whole tiles in ONE launch, then the fix-up of the split tiles
         const int rem = tiles - t_dp;
         // the split tiles are finished by a fix-up launch (default) or by their last-arriving workgroup (RPG_TUNE_INKERNEL_FIXUP bit 0)
-        if (!(g_inkernel_fixup & 1) || rem > (int)(kCounterBytes / sizeof(unsigned))) arrive = nullptr;
+        if (!(rpg::tuning().gemm.inkernel_fixup & 1) || rem > (int)(kCounterBytes / sizeof(unsigned))) arrive = nullptr;
         hipLaunchKernelGGL(kern_sk, dim3(g_sk + t_dp), dim3(NTHREADS), lds, s, args, Wt, ldw, M, N, K, ep, tn, t_dp, rem * nk, nk,
                            its_per, partial, g_sk, arrive, vec_ok ? 1 : 0);
         if (!arrive) {

@@ -99,16 +99,8 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const float* p) {
 
 enum TileShape { TILE_128x128 = 0, TILE_256x64 = 1, TILE_64x64 = 2, TILE_128x64 = 3 };
 
-// Tuning knobs (rpg_set_tuning): -1 = automatic.
-int g_force_tile = -1;
+// The tuning knobs of this unit (rpg_set_tuning) are rpg::tuning().gemm (tuning.h).
 int g_tile_128x64 = 1;                // prefer 128x64 over 128x128 tiles for problems smaller than 1.5 big tiles per CU
-int g_bk = 0;                        // 0 = automatic: 32 for the 128x128 tile (2 workgroups/CU), else 16
-int g_epi_lds = 1;
-int g_streamk = 1;
-int g_gnn_split = 1;
-int g_gnn_fuse_agg = 1;
-int g_fold_k = 256;                  // RPG_TUNE_FOLD_K: two-level accumulation of the Linears (gemm_engine.inc), 0 = one sequential chain
-int SK_MIN_ITS = 8;                  // at least this many k-steps per stream-K workgroup (RPG_TUNE_SK_MIN_ITS)
 constexpr int SK_MIN_NK = 32;        // tiles with fewer k-steps are not worth splitting (fix-up traffic dominates)
 
 // Library-owned scratch pool of the fine-grained entry points (see rpg_common.h): one block per (device, stream) that
@@ -159,11 +151,10 @@ float* get_scratch(hipStream_t s, size_t bytes, unsigned** counters = nullptr) {
 // a 6-us fix-up is dispatched ahead of the other stream's queued convolution workgroups instead of behind them (measured r5:
 // 22 us per Winograd fix-up under two streams against 6 alone).  One companion (stream + two events) per (device, stream), created
 // on first use outside of any capture; never freed (streams are few and live as long as the process).
-int g_fixup_prio = 0;
 struct Companion { hipStream_t hi = nullptr; hipEvent_t there = nullptr, back = nullptr; };
 std::map<std::pair<int, hipStream_t>, Companion> g_companion;
 hipStream_t fixup_hop_begin_impl(hipStream_t s) {
-    if (!g_fixup_prio) return s;
+    if (!rpg::tuning().gemm.fixup_prio) return s;
     int dev = 0;
     (void)hipGetDevice(&dev);
     Companion* c;
@@ -197,8 +188,6 @@ void fixup_hop_end_impl(hipStream_t s, hipStream_t used) {
     (void)hipEventRecord(c.back, used);
     (void)hipStreamWaitEvent(s, c.back, 0);
 }
-int g_inkernel_fixup = 0;            // RPG_TUNE_INKERNEL_FIXUP (bit 0: stream-K, bit 1: Winograd): partial tiles combined by the last-arriving
-                                     // workgroup instead of a fix-up launch.  OFF by default: measured slower
 
 constexpr int MAX_DEV = 64;
 int cu_count() {
@@ -214,7 +203,7 @@ int cu_count() {
 }
 
 inline TileShape pick_tile(int M, int N, int K) {
-    if (g_force_tile >= 0 && g_force_tile <= 3) return (TileShape)g_force_tile;
+    if (rpg::tuning().gemm.force_tile >= 0 && rpg::tuning().gemm.force_tile <= 3) return (TileShape)rpg::tuning().gemm.force_tile;
     if (N <= 64) return (M >= 256 * 256) ? TILE_256x64 : TILE_64x64;
     const long t128 = (long)((M + 127) / 128) * ((N + 127) / 128);
     // a K loop of <= 16 steps is all prologue and epilogue: small tiles, several workgroups per CU hiding each other's (the 1x1 / stride 2
@@ -225,7 +214,7 @@ inline TileShape pick_tile(int M, int N, int K) {
     // fewer big tiles than CUs can balance: fine with stream-K when K is long enough to split, else go small
     // (128x64 halves the tile so that twice as many workgroups share the work before stream-K has to split K: measured
     // on the GNN Linears, M = 1792: N = 768 85 -> 68 us, N = 2048 142 -> 136 us; M = 256, N = 2048 63 -> 57 us)
-    if (g_streamk && K >= 32 * SK_MIN_NK && (long)M * N >= 128L * 128 * 8) return g_tile_128x64 ? TILE_128x64 : TILE_128x128;
+    if (rpg::tuning().gemm.streamk && K >= 32 * SK_MIN_NK && (long)M * N >= 128L * 128 * 8) return g_tile_128x64 ? TILE_128x64 : TILE_128x128;
     return TILE_64x64;
 }
 
@@ -275,7 +264,6 @@ constexpr int L112_BM = 112, L112_BN = 64, L112_BK = 32, L112_LD = L112_BK + 4, 
 constexpr int L112_STAGE = (L112_BM + L112_BN) * L112_LD;                 // floats per LDS image
 constexpr int L112_SLAB = L112_BM * (L112_BN + 4);                        // floats of the epilogue slab
 constexpr int L112_LDS_BYTES = (2 * L112_STAGE > L112_SLAB ? 2 * L112_STAGE : L112_SLAB) * 4;
-int g_lin112 = 3;                    // RPG_TUNE_LIN112: bit 0 the exact-fit kernel, bit 1 its eight-wave form for launches of about one tile per CU
 
 __global__ __launch_bounds__(L112_NT, 2) void linear112_kernel(const float* __restrict__ A, int lda, const float* __restrict__ Wt, int ldw,
                                                                int M, int N, int K, Epilogue ep, int tiles_n, int fold_k) {
@@ -532,7 +520,7 @@ __global__ __launch_bounds__(L112_NT2, 1) void linear112k2_kernel(const float* _
 
 // true if launched (shape eligible)
 bool launch_linear112(const float* A, int lda, const float* Wt, int ldw, int M, int N, int K, const Epilogue& ep, hipStream_t s) {
-    if (!(g_lin112 & 1) || M % L112_BM || N % L112_BN || K % L112_BK || K < 2 * L112_BK) return false;
+    if (!(rpg::tuning().gemm.lin112 & 1) || M % L112_BM || N % L112_BN || K % L112_BK || K < 2 * L112_BK) return false;
     const int tm = M / L112_BM, tn = N / L112_BN;
     const long tiles = (long)tm * tn;
     // worth it where the tiles fill the machine: >= 1 per CU (N = 2048: M = 896 -> 256 tiles, M = 1792 -> 512).  Measured below that:
@@ -545,14 +533,14 @@ bool launch_linear112(const float* A, int lda, const float* Wt, int ldw, int M, 
                         rpg::aligned16(Wt) && (lda % 4 == 0) && (ldw % 4 == 0);
     if (!vec_ok) return false;
     t_executed = 2.0 * (double)M * N * (double)K;
-    const bool k2 = (g_lin112 & 2) && 2 * tiles < 3L * cu_count();
+    const bool k2 = (rpg::tuning().gemm.lin112 & 2) && 2 * tiles < 3L * cu_count();
     t_route = RouteRecord{k2 ? ROUTE_LIN112K2 : ROUTE_LIN112, L112_BM, L112_BN, L112_BK, k2 ? 8 : 4, ROUTE_LOADER_BUFFER, 1, k2 ? 1 : 2,
-                          (int)tiles, (int)tiles, 0, 0, 0, ROUTE_COMBINE_NONE, g_fold_k >= 2 * L112_BK ? g_fold_k : 0};
+                          (int)tiles, (int)tiles, 0, 0, 0, ROUTE_COMBINE_NONE, rpg::tuning().gemm.fold_k >= 2 * L112_BK ? rpg::tuning().gemm.fold_k : 0};
     // about one tile per CU: eight waves per tile (two per SIMD); from two tiles per CU on: four waves, two workgroups per CU
     if (k2)
-        hipLaunchKernelGGL(linear112k2_kernel, dim3((unsigned)tiles), dim3(L112_NT2), L112_LDS_BYTES, s, A, lda, Wt, ldw, M, N, K, ep, tn, g_fold_k);
+        hipLaunchKernelGGL(linear112k2_kernel, dim3((unsigned)tiles), dim3(L112_NT2), L112_LDS_BYTES, s, A, lda, Wt, ldw, M, N, K, ep, tn, rpg::tuning().gemm.fold_k);
     else
-        hipLaunchKernelGGL(linear112_kernel, dim3((unsigned)tiles), dim3(L112_NT), L112_LDS_BYTES, s, A, lda, Wt, ldw, M, N, K, ep, tn, g_fold_k);
+        hipLaunchKernelGGL(linear112_kernel, dim3((unsigned)tiles), dim3(L112_NT), L112_LDS_BYTES, s, A, lda, Wt, ldw, M, N, K, ep, tn, rpg::tuning().gemm.fold_k);
     return true;
 }
 
@@ -576,9 +564,6 @@ void launch_shape8(TileShape t, const Args& args, const float* Wt, int ldw, int 
     else eng8::launch_one<128, 64, 4, 2, 32, true, Loader8, Args>(args, Wt, ldw, M, N, K, ep, true, s);
 }
 
-int g_fast = 1;                      // RPG_TUNE_FAST_LOADER: buffer-load loaders + interleaved main loop where eligible
-int g_waves8 = 1;                    // RPG_TUNE_WAVES8: 8-wave workgroups for the 128-row tiles where the fast path applies
-
 // The loaders of the two A-operand kinds, per engine (alias templates: template-template arguments of the launchers).
 struct ConvKind {
     template <int R, int BK> using L4 = eng4::ConvLoader<R, BK>;
@@ -601,24 +586,24 @@ int launch_tiles(const Args& args, const float* Wt, int ldw, int M, int N, int K
                  int seg_align) {
     TileShape t = pick_tile(M, N, K);
     // two-level accumulation lives in the 32x32 wave tiles (128x64 on 8 waves): a Linear long enough to need it does not take the 128x128 tile
-    if (std::is_same<Kind, GatherKind>::value && g_fold_k > 0 && g_force_tile < 0 && t == TILE_128x128 && K >= 2 * g_fold_k) t = TILE_128x64;
-    const int bk = g_bk ? g_bk : (((t == TILE_128x128 || t == TILE_128x64) && K >= 256) ? 32 : 16);
+    if (std::is_same<Kind, GatherKind>::value && rpg::tuning().gemm.fold_k > 0 && rpg::tuning().gemm.force_tile < 0 && t == TILE_128x128 && K >= 2 * rpg::tuning().gemm.fold_k) t = TILE_128x64;
+    const int bk = rpg::tuning().gemm.bk ? rpg::tuning().gemm.bk : (((t == TILE_128x128 || t == TILE_128x64) && K >= 256) ? 32 : 16);
     // 16-byte epilogue accesses need 4-column groups: N % 4 == 0 and 16-byte aligned rows
     const bool vec_ok = (N % 4 == 0) && (ep.ldc % 4 == 0) && rpg::aligned16(ep.out) &&
                         (!ep.residual || rpg::aligned16(ep.residual)) && (!ep.residual2 || rpg::aligned16(ep.residual2)) &&
                         (ep.ldr % 4 == 0) && (!ep.scale || rpg::aligned16(ep.scale)) &&
                         (!ep.shift || rpg::aligned16(ep.shift));
-    const bool epi = g_epi_lds && vec_ok;
-    const bool fast = g_fast && epi && seg_align > 0 && seg_align % bk == 0 && K % bk == 0 &&
+    const bool epi = rpg::tuning().gemm.epi_lds && vec_ok;
+    const bool fast = rpg::tuning().gemm.fast && epi && seg_align > 0 && seg_align % bk == 0 && K % bk == 0 &&
                       (long)N * ldw * 4 < (1L << 31);
-    const bool tap = g_fast && epi && seg_align == -1 && (long)N * ldw * 4 < (1L << 31);
+    const bool tap = rpg::tuning().gemm.fast && epi && seg_align == -1 && (long)N * ldw * 4 < (1L << 31);
     t_route.loader = tap ? ROUTE_LOADER_TAP : (fast ? ROUTE_LOADER_BUFFER : ROUTE_LOADER_GENERAL);     // launch_one fills in the rest
     if (tap) {
         if (bk == 32) launch_shape<32, true, Kind::template T4, Args>(t, args, Wt, ldw, M, N, K, ep, vec_ok, s);
         else launch_shape<16, true, Kind::template T4, Args>(t, args, Wt, ldw, M, N, K, ep, vec_ok, s);
         return 0;
     }
-    if (fast && bk == 32 && g_waves8 && (t == TILE_128x128 || t == TILE_128x64)) {
+    if (fast && bk == 32 && rpg::tuning().gemm.waves8 && (t == TILE_128x128 || t == TILE_128x64)) {
         launch_shape8<Kind::template B8, Args>(t, args, Wt, ldw, M, N, K, ep, s);
         return 0;
     }
@@ -638,12 +623,9 @@ int launch_tiles(const Args& args, const float* Wt, int ldw, int M, int N, int K
 
 namespace rpg {
 
-bool gnn_split_enabled() { return g_gnn_split != 0; }
-bool gnn_fuse_agg_enabled() { return g_gnn_fuse_agg != 0; }
 float* stream_scratch(hipStream_t s, size_t bytes, unsigned** counters) { return get_scratch(s, bytes, counters); }
 hipStream_t fixup_hop_begin(hipStream_t s) { return fixup_hop_begin_impl(s); }
 void fixup_hop_end(hipStream_t s, hipStream_t used) { fixup_hop_end_impl(s, used); }
-bool inkernel_fixup_enabled() { return (g_inkernel_fixup & 2) != 0; }      // (the Winograd launcher asks)
 ScratchScope::ScratchScope(void* p, size_t bytes, hipStream_t s) {
     // the arrival counters at the head of the slice must be zero when the first split launch of this call starts: the
     // slice is a piece of a workspace that other calls use for other things in between
@@ -700,7 +682,7 @@ int launch_linear(const GatherSrc& src, const float* weight, const float* bias, 
     a.w0 = src.width[0];
     a.w01 = src.n >= 2 ? src.width[0] + src.width[1] : K;
     a.K = K;
-    a.fold_k = g_fold_k;
+    a.fold_k = rpg::tuning().gemm.fold_k;
     Epilogue ep{nullptr, bias, residual, out, n_out, relu};
     ep.out_relu = out_relu;
     if (out_relu && !aligned16(out_relu)) return RPG_ERR_BAD_ARG;
@@ -791,50 +773,6 @@ extern "C" int rpg_release_scratch(void) {
     return RPG_OK;
 }
 
-extern "C" int rpg_set_tuning(int key, int value) {
-    switch (key) {
-        case RPG_TUNE_FIXUP_PRIO: g_fixup_prio = value != 0; return RPG_OK;
-        case RPG_TUNE_BF16_PAIR: rpg::bf16_set_pair(value != 0); return RPG_OK;
-        case RPG_TUNE_TILE: g_force_tile = value; return RPG_OK;
-        case RPG_TUNE_BK: if (value != 0 && value != 16 && value != 32) return RPG_ERR_BAD_ARG; g_bk = value; return RPG_OK;
-        case RPG_TUNE_EPILOGUE: g_epi_lds = value != 0; return RPG_OK;
-        case RPG_TUNE_STREAMK: g_streamk = value != 0; return RPG_OK;
-        case RPG_TUNE_BF16_BK: if (value != 32 && value != 64) return RPG_ERR_BAD_ARG; rpg::bf16_set_bk(value); return RPG_OK;
-        case RPG_TUNE_INKERNEL_FIXUP:      // bit 0: stream-K tiles of the GEMM engine, bit 1: Winograd tail tiles (<= 8 parts); + 4: <= 32 parts
-            if (value < 0 || value > 7) return RPG_ERR_BAD_ARG;
-            g_inkernel_fixup = value & 3;
-            rpg::wino_combine_max_set((value & 4) ? 32 : 8);
-            return RPG_OK;
-        case RPG_TUNE_GNN_SPLIT: g_gnn_split = value != 0; return RPG_OK;
-        case RPG_TUNE_GNN_FUSE_AGG: g_gnn_fuse_agg = value != 0; return RPG_OK;
-        case RPG_TUNE_LIN112: if (value < 0 || value > 3) return RPG_ERR_BAD_ARG; g_lin112 = value; return RPG_OK;
-        case RPG_TUNE_FOLD_K: if (value < 0 || (value % 64)) return RPG_ERR_BAD_ARG; g_fold_k = value; return RPG_OK;
-        case RPG_TUNE_FAST_LOADER: g_fast = value != 0; return RPG_OK;
-        case RPG_TUNE_WAVES8: g_waves8 = value != 0; return RPG_OK;
-        case RPG_TUNE_WINO_SPLIT: if (value < 0 || value > 96) return RPG_ERR_BAD_ARG; rpg::wino_split_set(value); return RPG_OK;
-        case RPG_TUNE_BF16_TILE: if (value < -1 || value > 3) return RPG_ERR_BAD_ARG; rpg::bf16_set_tile(value); return RPG_OK;
-        case RPG_TUNE_BF16_FAST: rpg::bf16_set_fast(value != 0); return RPG_OK;
-        case RPG_TUNE_BF16_LEAN_EPI: rpg::bf16_set_lean_epi(value != 0); return RPG_OK;
-        case RPG_TUNE_BF16_PERSIST: rpg::bf16_set_persist(value != 0); return RPG_OK;
-        case RPG_TUNE_BF16_FUSE_BLOCK: rpg::bf16_set_fuse_block((int)(value & 7)); return RPG_OK;
-        case RPG_TUNE_BF16_TAIL: if (value < 0 || value > 7) return RPG_ERR_BAD_ARG; rpg::bf16_set_tail(value); return RPG_OK;
-        case RPG_TUNE_BF16_LINEAR_DMA: if (value != 0 && (value < 10 || value > 19)) return RPG_ERR_BAD_ARG; rpg::bf16_set_linear_dma(value); return RPG_OK;
-        case RPG_TUNE_WINO2D:              // probe builds only (tools/probes/winograd2d.hip); the product accepts 0
-            if (value < 0 || value > 2 || (value != 0 && rpg_wino43_weights_floats(1, 1) != 42)) return RPG_ERR_BAD_ARG;
-            rpg::wino2d_set(value);
-            return RPG_OK;
-        case RPG_TUNE_BF16_CHUNK:          // images per depth-first group (0 = off) + 4096 * (least activation-tensor size in MB; 0 = 64)
-            if (value < 0) return RPG_ERR_BAD_ARG;
-            rpg::bf16_set_chunk(value & 4095, (value >> 12) ? (value >> 12) : 64);
-            return RPG_OK;
-        case RPG_TUNE_BF16_PATCH: if (value < 0 || value % 10 > 4 || value > 14) return RPG_ERR_BAD_ARG; rpg::bf16_set_patch(value); return RPG_OK;
-        case RPG_TUNE_BF16_DMA: if (value < 0 || value > 40) return RPG_ERR_BAD_ARG; rpg::bf16_set_dma(value); return RPG_OK;
-        case RPG_TUNE_SK_MIN_ITS: if (value < 1 || value > 4096) return RPG_ERR_BAD_ARG; SK_MIN_ITS = value; return RPG_OK;
-        case RPG_TUNE_BF16_WS64: if (value < 0 || value > 2) return RPG_ERR_BAD_ARG; return rpg::bf16_set_ws64(value);
-        case RPG_TUNE_FUSED_STEM: rpg::stem_pool_set((value & 1) != 0); rpg::stem_pool_set_strip((value & 128) != 0, value >> 8); rpg::bf16_set_fused_stem((value & 1) != 0); rpg::bf16_set_stem_strip((value & 2) ? 0 : ((value & 32) ? 1 : 9), value >> 8); return RPG_OK;
-        case RPG_TUNE_WINOGRAD: if (value < 0 || (value > 3 && value < 16)) return RPG_ERR_BAD_ARG; rpg::wino_set(value); return RPG_OK;
-        case RPG_TUNE_WINO_PERSIST: if (value < 0 || value > 2) return RPG_ERR_BAD_ARG; rpg::wino_persist_set(value); return RPG_OK;
-        case RPG_TUNE_WINO_SHORT: if (value < 0) return RPG_ERR_BAD_ARG; rpg::wino_short_set(value); return RPG_OK;
-        default: return RPG_ERR_BAD_ARG;
-    }
-}
+extern "C" int rpg_set_tuning(int key, int value) { return rpg::set_tuning(key, value); }
+
+extern "C" int rpg_get_tuning(int key, int* value, int* default_value) { return rpg::get_tuning(key, value, default_value); }

@@ -6,6 +6,7 @@
 
 #include "../../include/relpose_gnn_hip.h"
 
+#include "tuning.h"            // the tuning keys' table and the state the launchers read, rpg::tuning() (host-only)
 #include "composite_plan.h"    // kWorkspaceSkew, align_up / conv_out, the workspace layouts and the block walk of the composite forwards (host-only)
 #include "rpg_coherent.h"      // agent-scope partial-slab accesses + arrival ticket (device code of winograd.hip / gemm_engine.inc)
 
@@ -78,7 +79,6 @@ float* stream_scratch(hipStream_t s, size_t bytes, unsigned** counters = nullptr
 // already waiting for what s has enqueued) and the hand-back (s waits for the companion)
 hipStream_t fixup_hop_begin(hipStream_t s);
 void fixup_hop_end(hipStream_t s, hipStream_t used);
-bool inkernel_fixup_enabled();            // RPG_TUNE_INKERNEL_FIXUP bit 1 (Winograd tail tiles); OFF by default (measured slower)
 struct ScratchScope {
     ScratchScope(void* p, size_t bytes, hipStream_t s);       // zeroes the slice's counter header on s (one memset node per call)
     ~ScratchScope();
@@ -89,38 +89,15 @@ struct ScratchScope {
 // <= 3 workgroups per CU; Winograd split-K tail: <= one 128-KB partial tile per CU)
 size_t split_scratch_bytes();
 int num_cus();
-bool wino_enabled();
 // true if the composite forward should route this 3x3/stride-1 convolution to launch_conv_wino (enabled, shape
 // addressable, and large enough that the un-split K loop is not latency-bound)
 bool wino_pays(int n, int h, int w, int cin, int cout);
-void wino_set(int on);
-// nested 2-D Winograd F(4x2, 3x3) (csrc/winograd2d.hip)
-void wino2d_set(int v);
+// nested 2-D Winograd F(4x2, 3x3) (tools/probes/winograd2d.hip, probe builds)
 size_t wino_weight_floats(int cout, int cin);
 int launch_wino2d_weights(const float* w_ohwi, float* u2, int cout, int cin, hipStream_t s);
 bool wino2d_takes(int n, int h, int w, int cin, int cout);
 int launch_conv_wino2d(const float* x, const float* u2, const float* scale, const float* shift, const float* residual, float* y,
                        int n, int h, int w, int cin, int cout, int relu, hipStream_t s);
-void stem_pool_set(int on);
-void stem_pool_set_strip(int on, int band_rows);      // stem.hip: fp32 strip-march kernel (round 6) | tile kernel (rounds 2-5)
-void wino_split_set(int on);
-void wino_short_set(int cin);
-void wino_persist_set(int on);
-void wino_combine_max_set(int v);
-void bf16_set_fast(int on);
-void bf16_set_tile(int t);
-void bf16_set_dma(int v);
-void bf16_set_patch(int v);
-void bf16_set_fused_stem(int on);
-void bf16_set_stem_strip(int on, int band_rows);   // stem_bf16.hip: strip-march kernel (round 6) | tile kernel (rounds 3-5)
-void bf16_set_chunk(int images, int min_mb);
-void bf16_set_lean_epi(int on);
-void bf16_set_persist(int v);
-void bf16_set_fuse_block(int v);
-void bf16_set_tail(int v);
-void bf16_set_pair(int v);
-void bf16_set_linear_dma(int v);
-int bf16_set_ws64(int v);      // RPG_OK, or RPG_ERR_BAD_ARG for v != 0 in a build without the probe kernel (tools/probes/conv3x3_bf16_ws64.inc)
 bool stem_pool_bf16_supported(int n, int h, int w, int cout);      // incl. the ranges the kernel's magic divisions are exact for
 int launch_stem_pool_bf16(const void* x_nchw, int x_is_bf16, const void* wpack, const float* scale, const float* shift, void* out, int n, int h,
                           int w, hipStream_t s);
@@ -160,8 +137,5 @@ int launch_query_select(const int64_t* esrc, const int64_t* edst, int64_t node_o
                         hipStream_t s);
 int launch_gather_rows16(const void* in, int ld_in_bytes, const int32_t* idx, void* out, int ld_out_bytes, int row_bytes, long rows,
                          hipStream_t s);
-bool gnn_split_enabled();
-bool gnn_fuse_agg_enabled();
-void bf16_set_bk(int bk);
 
 }  // namespace rpg

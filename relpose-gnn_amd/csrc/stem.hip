@@ -506,14 +506,10 @@ __global__ __launch_bounds__(SF_NT) __attribute__((amdgpu_waves_per_eu(2, 2))) v
 
 namespace rpg {
 
-static int g_fused_stem = 1;                     // RPG_TUNE_FUSED_STEM
-void stem_pool_set(int on) { g_fused_stem = on; }
-bool stem_pool_supported(int h, int w, int cout) { return g_fused_stem && cout == 64 && h >= 1 && w >= 1; }
+bool stem_pool_supported(int h, int w, int cout) { return tuning().stem.fused && cout == 64 && h >= 1 && w >= 1; }
 
-static int g_stem_f32_strip = 0;                 // RPG_TUNE_FUSED_STEM bit 7 sets it: the strip-march kernel of round 6 (measured -6..-12 % on the kernel, +0.3..0.5 % on
-                                                 // the step; off by default: see the comment at its head)
-static int g_stem_f32_bh = 0;                    // pooled rows per band (0: by the launch's size)
-void stem_pool_set_strip(int on, int bh) { g_stem_f32_strip = on; g_stem_f32_bh = bh > 0 ? bh : 0; }
+// tuning().stem.strip (RPG_TUNE_FUSED_STEM bit 7): the strip-march kernel of round 6 (measured -6..-12 % on the kernel, +0.3..0.5 % on
+// the step; off by default: see the comment at its head)
 
 // Pooled rows per band of a strip-march launch: a band costs one extra convolution row and three warm-up row loads (~1.5 rows), so
 // long bands are cheap -- but the launch should fill whole rounds of the resident workgroup slots (`slots` = CUs x workgroups per CU;
@@ -538,7 +534,7 @@ static int strip_band_rows(long items_per_band, int hp, long slots) {
 int launch_stem_pool(const float* x_nchw, const float* wpack, const float* shift, float* out, int n, int h, int w,
                      hipStream_t s) {
     if (!x_nchw || !wpack || !shift || !out || n <= 0 || h <= 0 || w <= 0 || !aligned16(out)) return RPG_ERR_BAD_ARG;
-    if (g_stem_f32_strip && (long)3 * h * w * 4 < (1L << 31)) {
+    if (tuning().stem.strip && (long)3 * h * w * 4 < (1L << 31)) {
         StemSFArgs sa{};
         sa.x = x_nchw; sa.wpack = wpack + KP * NF * 64; sa.shift = shift; sa.out = out;      // second part of params.pack_stem_pairs
         sa.N = n; sa.H = h; sa.W = w;
@@ -546,8 +542,8 @@ int launch_stem_pool(const float* x_nchw, const float* wpack, const float* shift
         sa.Hp = (sa.Hc + 2 - 3) / 2 + 1; sa.Wp = (sa.Wc + 2 - 3) / 2 + 1;
         sa.tiles_x = (sa.Wp + SF_TP - 1) / SF_TP;
         sa.TP = (sa.Wp + sa.tiles_x - 1) / sa.tiles_x;
-        if (g_stem_f32_bh > 0) {
-            sa.BH = g_stem_f32_bh < sa.Hp ? g_stem_f32_bh : sa.Hp;
+        if (tuning().stem.strip_bh > 0) {
+            sa.BH = tuning().stem.strip_bh < sa.Hp ? tuning().stem.strip_bh : sa.Hp;
         } else {
             sa.BH = strip_band_rows((long)n * sa.tiles_x * 2, sa.Hp, 2L * num_cus());
         }

@@ -527,12 +527,9 @@ static bool stem_pool_bf16_geometry(int n, int h, int w, StemBArgs& a, int& grid
     return (long)((long)n / a.nxcd + 1 + grid) * a.tiles_y * a.tiles_x * a.tiles_y * a.tiles_x < (1L << 32);
 }
 
-int g_stem_strip = 9;          // 0: the tile kernel (rounds 3-5) | bit 0: the strip-march kernel of round 6, + bit 3 (default): both 32-channel halves in
-                               // one wave (measured at 512 images, profiles/r6_stem_bf16_variants.txt: 227 us against 255-265 with one half per wave
-                               // and three waves per SIMD -- the texture addresser was 72 % busy with every input window loaded by two waves --,
-                               // 375 for the tile kernel)
-int g_stem_strip_bh = 0;       // pooled rows per band (RPG_TUNE_FUSED_STEM value >> 4, experiments); 0 = by the launch's size
-void bf16_set_stem_strip(int mode, int bh) { g_stem_strip = mode; g_stem_strip_bh = bh > 0 ? bh : 0; }
+// tuning().bf16.stem_strip: 0: the tile kernel (rounds 3-5) | bit 0: the strip-march kernel of round 6, + bit 3 (default): both 32-channel
+// halves in one wave (measured at 512 images, profiles/r6_stem_bf16_variants.txt: 227 us against 255-265 with one half per wave and three
+// waves per SIMD -- the texture addresser was 72 % busy with every input window loaded by two waves --, 375 for the tile kernel)
 
 // Pooled rows per band of a strip-march launch: a band costs one extra convolution row and three warm-up row loads (~1.5 rows), so
 // long bands are cheap -- but the launch should fill whole rounds of the resident workgroup slots (`slots` = CUs x workgroups per CU;
@@ -561,13 +558,13 @@ static bool stem_strip_geometry(int n, int h, int w, int esz, StemSArgs& a, int&
     a.Hp = (a.Hc + 2 - 3) / 2 + 1; a.Wp = (a.Wc + 2 - 3) / 2 + 1;
     a.tiles_x = (a.Wp + SS_TP - 1) / SS_TP;
     a.TP = (a.Wp + a.tiles_x - 1) / a.tiles_x;
-    if (g_stem_strip_bh > 0) {
-        a.BH = g_stem_strip_bh < a.Hp ? g_stem_strip_bh : a.Hp;
+    if (tuning().bf16.stem_strip_bh > 0) {
+        a.BH = tuning().bf16.stem_strip_bh < a.Hp ? tuning().bf16.stem_strip_bh : a.Hp;
     } else {
-        a.BH = strip_band_rows((long)n * a.tiles_x * (g_stem_strip & 8 ? 1 : 2), a.Hp, (g_stem_strip & 8 ? 2L : 3L) * num_cus());
+        a.BH = strip_band_rows((long)n * a.tiles_x * (tuning().bf16.stem_strip & 8 ? 1 : 2), a.Hp, (tuning().bf16.stem_strip & 8 ? 2L : 3L) * num_cus());
     }
     a.bands = (a.Hp + a.BH - 1) / a.BH;
-    const long items = (long)n * a.bands * a.tiles_x * (g_stem_strip & 8 ? 1 : 2);        // bit 3: both channel halves in one wave
+    const long items = (long)n * a.bands * a.tiles_x * (tuning().bf16.stem_strip & 8 ? 1 : 2);        // bit 3: both channel halves in one wave
     // 32-bit byte offsets inside an image (incl. the rows read past its ends), 32-bit item index
     if ((long)3 * h * w * esz + (long)16 * w * esz >= (1L << 31) || items + 64 >= (1L << 32)) return false;
     a.items = (unsigned)items;
@@ -586,14 +583,14 @@ int launch_stem_pool_bf16(const void* x_nchw, int x_is_bf16, const void* wpack, 
                           int n, int h, int w, hipStream_t s) {
     if (!x_nchw || !wpack || !scale || !shift || !out || n <= 0 || h <= 0 || w <= 0 || !aligned16(out) || !aligned16(wpack))
         return RPG_ERR_BAD_ARG;
-    if (g_stem_strip) {
+    if (tuning().bf16.stem_strip) {
         StemSArgs sa{};
         int sgrid = 0;
         if (stem_strip_geometry(n, h, w, x_is_bf16 ? 2 : 4, sa, sgrid)) {
             sa.x = x_nchw; sa.scale = scale; sa.shift = shift; sa.out = reinterpret_cast<__bf16*>(out);
             sa.wpack = reinterpret_cast<const uint4*>(wpack) + KS * NF * 64;       // second part of params.pack_stem_bf16
             const int slot = timing_begin(RPG_TIMER_CONV, s);
-            if (g_stem_strip & 8) {
+            if (tuning().bf16.stem_strip & 8) {
                 if (x_is_bf16) hipLaunchKernelGGL((stem_strip_bf16_kernel<__bf16, 2>), dim3(sgrid), dim3(SS_NT), 0, s, sa);
                 else hipLaunchKernelGGL((stem_strip_bf16_kernel<float, 2>), dim3(sgrid), dim3(SS_NT), 0, s, sa);
             } else {

@@ -1148,15 +1148,10 @@ __global__ __launch_bounds__(NT) void wino43_weights_kernel(const float* __restr
     for (int xi = 0; xi < 6; ++xi) U[xi * plane + i] = (float)u[xi];
 }
 
-int g_wino_split = 1;                    // RPG_TUNE_WINO_SPLIT: split-K tail of the 8-wave kernel
-int g_wino_split_steps = 3;              // ... and the least number of K steps a part of a tile gets in the one-workgroup-per-tile form (values >= 2 of the same key;
-                                         // one 8-node graph, r3: 4 -> 1.63 ms per forward, 3 or 2 -> 1.50; 6 -> 1.61; the benched 32-graph launches do not get here:
-                                         // their part count is bound by CUs / tail tiles)
-int g_wino = 1;                          // RPG_TUNE_WINOGRAD: 0 off | 1 auto | 2 / 3: always the 4-wave / 8-wave kernel
-int g_wino_min_blocks = 16;              // ... | n >= 16: auto, Winograd from n blocks of 64 tiles x 64 channels up (default 16; round 6: the per-layer rule of small batches)
-int g_wino_persist = 1;                  // RPG_TUNE_WINO_PERSIST: the persistent 8-wave kernel when a launch has more tiles than CUs
-int g_wino_combine_max = 8;              // most parts of a tail tile that its last-arriving workgroup adds up itself (one CU reads parts x 128 KB:
-                                         // beyond this the 32-blocks-per-tile fix-up launch is the faster way); RPG_TUNE_INKERNEL_FIXUP >= 2 sets it
+// The tuning knobs of this unit are rpg::tuning().wino (tuning.h).  Measured: split_steps (the least K steps a part of a tile gets in the
+// one-workgroup-per-tile form), one 8-node graph, r3: 4 -> 1.63 ms per forward, 3 or 2 -> 1.50; 6 -> 1.61; the benched 32-graph launches do
+// not get there: their part count is bound by CUs / tail tiles.  combine_max: one CU reads parts x 128 KB, beyond 8 parts the
+// 32-blocks-per-tile fix-up launch is the faster way.
 
 }  // namespace
 
@@ -1166,26 +1161,16 @@ int g_wino_combine_max = 8;              // most parts of a tail tile that its l
 
 namespace rpg {
 
-#ifndef RPG_PROBE_WINO2D
-void wino2d_set(int) {}                           // RPG_TUNE_WINO2D is accepted (0) and ignored in a build without the probe kernel
-#endif
-bool wino_enabled() { return g_wino != 0; }
-void wino_set(int on) { if (on >= 16) { g_wino = 1; g_wino_min_blocks = on; } else { g_wino = on; g_wino_min_blocks = 16; } }
-void wino_split_set(int v) { g_wino_split = v != 0; g_wino_split_steps = v >= 2 ? v : 3; }
-void wino_short_set(int) {}              // RPG_TUNE_WINO_SHORT: retired with the short-K kernel (accepted, ignored)
-void wino_persist_set(int on) { g_wino_persist = on; }      // 2: also for launches of at most one tile per CU
-void wino_combine_max_set(int v) { g_wino_combine_max = v; }
-
 // Winograd needs (a) 32-bit buffer offsets (checked again by the launcher) and (b) enough work to occupy the chip.  Since
 // the 8-wave kernel cuts a grid that does not fill the CUs along K (split-K tail), that is little: from 16 units of 64
 // tiles x 64 channels on it beats the direct kernel + stream-K (measured on the whole forward: 2 graphs 1068 -> 1198
 // graphs/s, 4: 1400 -> 1525, 8: 1891 -> 2149; 1 graph: equal).
 bool wino_pays(int n, int h, int w, int cin, int cout) {
-    if (!g_wino || (cin & 3) || (cout & 3)) return false;
+    if (!tuning().wino.on || (cin & 3) || (cout & 3)) return false;
     const long tiles = (long)n * h * ((w + 3) / 4);
     const long blocks = ((tiles + BMT - 1) / BMT) * ((cout + BN - 1) / BN);
     const int tw = (w + 3) / 4;
-    return blocks >= g_wino_min_blocks && (long)h * w * cin * 4 * 67 < (1L << 31) && 6L * cout * 3 * cin * 4 < (1L << 31) &&
+    return blocks >= tuning().wino.min_blocks && (long)h * w * cin * 4 * 67 < (1L << 31) && 6L * cout * 3 * cin * 4 < (1L << 31) &&
            (32L / tw + 3) * w * cout * 4 < (1L << 31);
 }
 
@@ -1223,10 +1208,10 @@ int launch_conv_wino(const float* x, const float* u, const float* scale, const f
     double executed = 0.0;                 // matrix-pipe FLOP: workgroups x K steps x 48 MFMAs x waves x 4096
     const long tm8 = (M + BMT8 - 1) / BMT8;
     const bool fits8 = (long)h * w * cin * 4 * 131 < (1L << 31);     // a workgroup's 128 tiles span at most 129 images
-    if (fits8 && (g_wino == 3 || (g_wino == 1 && tm8 * tn >= 8))) {
+    if (fits8 && (tuning().wino.on == 3 || (tuning().wino.on == 1 && tm8 * tn >= 8))) {
         // large problems (or RPG_TUNE_WINOGRAD = 3): 8 waves on 128 tiles, double-buffered, one workgroup per CU.
         // The tiles beyond the last full round of CUs would cost a whole extra round (784 tiles on 256 CUs: a 4th
-        // round for 2 % of the work): they are cut along K into floor(CUs / tail) parts (>= g_wino_split_steps K steps each) whose partial
+        // round for 2 % of the work): they are cut along K into floor(CUs / tail) parts (>= wino.split_steps K steps each) whose partial
         // tiles a small fix-up kernel adds in k order.
         static bool attr8[64] = {};
         if (!attr8[dev]) {
@@ -1240,7 +1225,7 @@ int launch_conv_wino(const float* x, const float* u, const float* scale, const f
         long t_main = T;
         Split sp{0, 1, 0, nullptr, nullptr};
         const long tail = T % S;
-        if (g_wino_persist && cin % BK == 0 && (T > S || g_wino_persist == 2) && h >= 2) {
+        if (tuning().wino.persist && cin % BK == 0 && (T > S || tuning().wino.persist == 2) && h >= 2) {
             // more tiles than CUs: the persistent kernel, S workgroups walking items b, b + S, ...; the tail tiles are cut
             // into parts of whole channel blocks (3 K steps) handed to the first workgroups
             static bool attr8p[64] = {};
@@ -1249,7 +1234,7 @@ int launch_conv_wino(const float* x, const float* u, const float* scale, const f
                                           hipFuncAttributeMaxDynamicSharedMemorySize, LDS8_BYTES);
                 attr8p[dev] = true;
             }
-            if (g_wino_split && tail > 0) {
+            if (tuning().wino.split && tail > 0) {
                 int parts = (int)(S / tail);
                 if (parts > kpr) parts = kpr;
                 if (parts >= 2) {
@@ -1270,15 +1255,15 @@ int launch_conv_wino(const float* x, const float* u, const float* scale, const f
             RPG_CHECK_LAUNCH("conv3x3_wino43");
             return RPG_OK;
         }
-        if (g_wino_split && tail > 0) {
+        if (tuning().wino.split && tail > 0) {
             int parts = (int)(S / tail);
             if (parts > kpr) parts = kpr;               // a part is at least one channel block (3 K steps)
-            if (parts > nk / g_wino_split_steps && nk / g_wino_split_steps >= 2) parts = nk / g_wino_split_steps;
+            if (parts > nk / tuning().wino.split_steps && nk / tuning().wino.split_steps >= 2) parts = nk / tuning().wino.split_steps;
             if (parts >= 2) {
                 unsigned* counters = nullptr;
                 sp.partial = stream_scratch(s, (size_t)tail * parts * (BMT8 * 4 * BN) * sizeof(float), &counters);
                 if (sp.partial) { sp.parts = parts; t_main = T - tail; sp.tile_base = (int)t_main; sp.n_split = (int)(tail * parts); }
-                if (sp.partial && inkernel_fixup_enabled() && parts <= g_wino_combine_max) sp.arrive = counters;
+                if (sp.partial && (tuning().gemm.inkernel_fixup & 2) && parts <= tuning().wino.combine_max) sp.arrive = counters;
             }
         }
         // one launch: the split workgroups first, then the whole tiles

@@ -6,6 +6,7 @@ tensors, allocates its output with ``torch.empty`` and launches the HIP kernel o
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import numbers
 from typing import Dict, Optional, Sequence, Tuple
@@ -914,8 +915,55 @@ def release_scratch() -> None:
     L.check(L.lib().rpg_release_scratch(), "release_scratch")
 
 
-TUNE_TILE, TUNE_BK, TUNE_EPILOGUE, TUNE_STREAMK, TUNE_WINOGRAD, TUNE_GNN_SPLIT, TUNE_BF16_BK, TUNE_FAST_LOADER, TUNE_WINO_SPLIT, TUNE_BF16_FAST, TUNE_FUSED_STEM, TUNE_WAVES8, TUNE_WINO_SHORT, TUNE_GNN_FUSE_AGG, TUNE_WINO_PERSIST, TUNE_BF16_TILE, TUNE_BF16_DMA, TUNE_BF16_PATCH, TUNE_BF16_WS64, TUNE_SK_MIN_ITS, TUNE_INKERNEL_FIXUP, TUNE_BF16_CHUNK, TUNE_WINO2D, TUNE_BF16_LEAN_EPI, TUNE_BF16_LINEAR_DMA, TUNE_BF16_PERSIST, TUNE_FOLD_K, TUNE_BF16_FUSE_BLOCK, TUNE_BF16_TAIL, TUNE_LIN112, TUNE_FIXUP_PRIO, TUNE_BF16_PAIR = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 29, 30, 31
+# The tuning keys in key order: TUNE_<name> = the header's RPG_TUNE_<name> (tests/test_host.py checks them against it).  The header
+# documents each key's values; csrc/tuning.h holds their defaults, accepted values and decoding.
+TUNING_KEYS = (
+    "TILE", "BK", "EPILOGUE", "STREAMK", "WINOGRAD", "GNN_SPLIT", "BF16_BK", "FAST_LOADER", "WINO_SPLIT", "BF16_FAST", "FUSED_STEM",
+    "WAVES8", "WINO_SHORT", "GNN_FUSE_AGG", "WINO_PERSIST", "BF16_TILE", "BF16_DMA", "BF16_PATCH", "BF16_WS64", "SK_MIN_ITS",
+    "INKERNEL_FIXUP", "BF16_CHUNK", "WINO2D", "BF16_LEAN_EPI", "BF16_LINEAR_DMA", "BF16_PERSIST", "FOLD_K", "BF16_FUSE_BLOCK",
+    "BF16_TAIL", "LIN112", "FIXUP_PRIO", "BF16_PAIR",
+)
+globals().update({"TUNE_" + _name: _key for _key, _name in enumerate(TUNING_KEYS)})
+
+
+def _tuning_key(key) -> int:
+    """A key given as its number, its name ("FOLD_K") or its constant's name ("TUNE_FOLD_K")."""
+    if isinstance(key, str):
+        return TUNING_KEYS.index(key[5:] if key.startswith("TUNE_") else key)
+    return int(key)
 
 
 def set_tuning(key: int, value: int) -> None:
     L.check(L.lib().rpg_set_tuning(key, value), "set_tuning")
+
+
+def get_tuning(key) -> int:
+    """The value last accepted for the key, as it was passed in (its default before any set)."""
+    value = C.c_int()
+    L.check(L.lib().rpg_get_tuning(_tuning_key(key), C.byref(value), None), "get_tuning")
+    return value.value
+
+
+def tuning_default(key) -> int:
+    value = C.c_int()
+    L.check(L.lib().rpg_get_tuning(_tuning_key(key), None, C.byref(value)), "tuning_default")
+    return value.value
+
+
+def reset_tuning() -> None:
+    """Every key back to its default."""
+    for key in range(len(TUNING_KEYS)):
+        set_tuning(key, tuning_default(key))
+
+
+@contextlib.contextmanager
+def tuned(keys):
+    """with tuned({key or name: value, ...}): the keys set for the block, EVERY key back at its default afterwards -- also when a
+    set is refused half-way or the block raises.  Blocks do not nest (the inner one's exit resets the outer one's keys): name
+    every key of a launch in one block."""
+    try:
+        for key, value in keys.items():
+            set_tuning(_tuning_key(key), value)
+        yield
+    finally:
+        reset_tuning()

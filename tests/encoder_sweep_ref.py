@@ -347,7 +347,7 @@ def harness_findings(inputs: Sequence[Moated], out: Moated) -> List[str]:
 # launch_conv_wino's route rule, restated
 # ----------------------------------------------------------------------------------------------------------------------
 ROUTES: Dict[str, Dict[str, int]] = {
-    # route              RPG_TUNE_ keys (csrc/winograd.hip launch_conv_wino); everything is restored to DEFAULT_KEYS afterwards
+    # route              RPG_TUNE_ keys (csrc/winograd.hip launch_conv_wino); ops.tuned puts every key back afterwards
     "wave4":            {"WINOGRAD": 2},
     "wave8_whole":      {"WINOGRAD": 3, "WINO_SPLIT": 0, "WINO_PERSIST": 0},
     "split_launch":     {"WINOGRAD": 3, "WINO_SPLIT": 1, "WINO_PERSIST": 0, "INKERNEL_FIXUP": 0},
@@ -356,14 +356,16 @@ ROUTES: Dict[str, Dict[str, int]] = {
     "persist_whole":    {"WINOGRAD": 3, "WINO_SPLIT": 0, "WINO_PERSIST": 2},
     "persist_split":    {"WINOGRAD": 3, "WINO_SPLIT": 1, "WINO_PERSIST": 2},
 }
-DEFAULT_KEYS = {"WINOGRAD": 1, "WINO_SPLIT": 1, "WINO_PERSIST": 1, "INKERNEL_FIXUP": 0}
+# The model's constants: the defaults of the four keys wino_taken restates the launcher's rule over (this module needs no library;
+# tests/test_encoder_sweep_cpu.py holds each to ops.tuning_default).  Nothing is restored from them.
+WINO_MODEL_DEFAULTS = {"WINOGRAD": 1, "WINO_SPLIT": 1, "WINO_PERSIST": 1, "INKERNEL_FIXUP": 0}
 
 
 def wino_taken(keys: Dict[str, int], n: int, h: int, w: int, cin: int, cout: int, cus: int) -> str:
     """What launch_conv_wino does with this shape under these keys on a device of ``cus`` compute units: "wave4" | "wave8_whole" |
     "wave8_split_launch:P" | "wave8_split_inkernel:P" | "persist_whole" | "persist_split:P" (P parts per tail tile).  The persistent
     kernel combines its parts by the fix-up launch.  Shapes of this sweep are far below the 32-bit offset limits."""
-    k = {**DEFAULT_KEYS, **keys}
+    k = {**WINO_MODEL_DEFAULTS, **keys}
     tw = (w + 3) // 4
     m = n * h * tw
     if k["WINOGRAD"] == 2:

@@ -359,10 +359,6 @@ class Spec:
         return sum(s[1] for s in self.srcs)
 
 
-# the Linear-side tuning keys of a sweep case and the values every test leaves behind
-DEFAULT_KEYS = {"TILE": -1, "BK": 0, "WAVES8": 1, "STREAMK": 1, "INKERNEL_FIXUP": 0, "FOLD_K": 256, "LIN112": 3, "EPILOGUE": 1,
-                "FAST_LOADER": 1}
-
 TILES = {0: (128, 128), 1: (256, 64), 2: (64, 64), 3: (128, 64)}
 
 # route -> (keys, expected record fields, width tuples; the LAST tuple has three segments and serves the mixed arrangement)

@@ -181,6 +181,13 @@ def test_relu_clamps_at_most_60_percent_direct_and_stem():
         assert float((pooled <= 0).double().mean()) <= R.CLAMP_CAP, (h, w)
 
 
+def test_the_route_models_constants_are_the_librarys_defaults():
+    """wino_taken's four constants (encoder_sweep_ref.WINO_MODEL_DEFAULTS) against the library's own defaults (no GPU needed)."""
+    from relpose_gnn_amd import ops
+    for name, value in R.WINO_MODEL_DEFAULTS.items():
+        assert ops.tuning_default(name) == value, name
+
+
 def test_composite_plan_mixes_the_routes():
     """33 x 47, n = 48, by the rule: layers 1, 2 and 4 take Winograd (21, 16, 16 units), layer 3 does not (12); one image never does."""
     assert R.layer_extents(33, 47) == [(9, 12), (5, 6), (3, 3), (2, 2)]

@@ -115,13 +115,8 @@ def test_winograd_at_bench_grids(dev, n, h, c):
     errs = {}
     for persist in (2, 1, 0):            # the persistent kernel always / where there are more tiles than CUs (default) / never
         for split in (1, 0):
-            ops.set_tuning(ops.TUNE_WINO_SPLIT, split)
-            ops.set_tuning(ops.TUNE_WINO_PERSIST, persist)
-            try:
+            with ops.tuned({ops.TUNE_WINO_SPLIT: split, ops.TUNE_WINO_PERSIST: persist}):
                 y = ops.conv3x3_wino43_bn_act_nhwc(xd, u, scale.to(dev), shift.to(dev), rd, relu=True)
-            finally:
-                ops.set_tuning(ops.TUNE_WINO_SPLIT, 1)
-                ops.set_tuning(ops.TUNE_WINO_PERSIST, 1)
             errs[(persist, split)] = rel_err(y.cpu().permute(0, 3, 1, 2), ref)
     _report({"case": f"wino43_stage_{h}x{h}x{c}_n{n}", "workgroups": tiles, "rel_err_split": errs[(1, 1)],
              "rel_err_nosplit": errs[(1, 0)], "rel_err_one_workgroup_per_tile": errs[(0, 1)],
@@ -206,15 +201,8 @@ def test_fuzz_winograd_vs_conv2d(dev, block):
         u = ops.wino43_transform_weights(nh(wt))
         for kern in (2, 3, 5):           # 5 = the 8-wave kernel without its persistent form
             for split in (0, 1):
-                ops.set_tuning(ops.TUNE_WINOGRAD, min(kern, 3))
-                ops.set_tuning(ops.TUNE_WINO_SPLIT, split)
-                ops.set_tuning(ops.TUNE_WINO_PERSIST, int(kern != 5))
-                try:
+                with ops.tuned({ops.TUNE_WINOGRAD: min(kern, 3), ops.TUNE_WINO_SPLIT: split, ops.TUNE_WINO_PERSIST: int(kern != 5)}):
                     y = ops.conv3x3_wino43_bn_act_nhwc(nh(x), u, sc.to(dev), sh.to(dev), nh(r), relu=relu)
-                finally:
-                    ops.set_tuning(ops.TUNE_WINOGRAD, 1)
-                    ops.set_tuning(ops.TUNE_WINO_SPLIT, 1)
-                    ops.set_tuning(ops.TUNE_WINO_PERSIST, 1)
                 e = rel_err(y.cpu().permute(0, 3, 1, 2), ref)
                 if not e < 2e-5:
                     bad.append((case, kern, split, tuple(x.shape), wt.shape[0], e))
@@ -232,13 +220,8 @@ def test_fuzz_tile_engine_vs_conv2d(dev, block):
         x, wt, sc, sh, r, relu, stride, pad, ref = _conv_case(rng, case, False)
         nh = lambda t: None if t is None else t.permute(0, 2, 3, 1).contiguous().to(dev)
         tile, bk, sk, fast = rng.choice([-1, 0, 1, 2, 3]), rng.choice([0, 16, 32]), rng.choice([0, 1]), rng.choice([0, 1])
-        for k, v in ((ops.TUNE_TILE, tile), (ops.TUNE_BK, bk), (ops.TUNE_STREAMK, sk), (ops.TUNE_FAST_LOADER, fast)):
-            ops.set_tuning(k, v)
-        try:
+        with ops.tuned({ops.TUNE_TILE: tile, ops.TUNE_BK: bk, ops.TUNE_STREAMK: sk, ops.TUNE_FAST_LOADER: fast}):
             y = ops.conv2d_bn_act_nhwc(nh(x), nh(wt), sc.to(dev), sh.to(dev), nh(r), stride=stride, pad=pad, relu=relu)
-        finally:
-            for k, v in ((ops.TUNE_TILE, -1), (ops.TUNE_BK, 0), (ops.TUNE_STREAMK, 1), (ops.TUNE_FAST_LOADER, 1)):
-                ops.set_tuning(k, v)
         e = rel_err(y.cpu().permute(0, 3, 1, 2), ref)
         if not e < 1e-5:
             bad.append((case, tuple(x.shape), tuple(wt.shape), stride, pad, tile, bk, sk, fast, e))

@@ -44,7 +44,6 @@ def test_conv_bf16(dev, n, h, w, cin, cout, k, stride, pad, res, relu, f32out, f
     """Both bf16 convolution kernels (RPG_TUNE_BF16_FAST: the interleaved buffer-load kernel serves Cin % 64 == 0, the
     general one everything else, so fast=1 exercises the dispatch and fast=0 forces the general kernel)."""
     from relpose_gnn_amd import ops
-    ops.set_tuning(ops.TUNE_BF16_FAST, fast)
     x = _rand(n, cin, h, w, seed=1).bfloat16()
     wt = _rand(cout, cin, k, k, seed=2, scale=(2.0 / (cin * k * k)) ** 0.5).bfloat16()
     scale = torch.rand(cout, generator=torch.Generator().manual_seed(3)) + 0.5
@@ -56,10 +55,10 @@ def test_conv_bf16(dev, n, h, w, cin, cout, k, stride, pad, res, relu, f32out, f
         ref = ref + r.float()
     if relu:
         ref = F.relu(ref)
-    y = ops.conv2d_bn_act_nhwc_bf16(x.permute(0, 2, 3, 1).contiguous().to(dev), wt.permute(0, 2, 3, 1).contiguous().to(dev),
-                                    scale.to(dev), shift.to(dev), None if r is None else r.permute(0, 2, 3, 1).contiguous().to(dev),
-                                    stride=stride, pad=pad, relu=relu, out_f32=f32out)
-    ops.set_tuning(ops.TUNE_BF16_FAST, 1)
+    with ops.tuned({ops.TUNE_BF16_FAST: fast}):
+        y = ops.conv2d_bn_act_nhwc_bf16(x.permute(0, 2, 3, 1).contiguous().to(dev), wt.permute(0, 2, 3, 1).contiguous().to(dev),
+                                        scale.to(dev), shift.to(dev), None if r is None else r.permute(0, 2, 3, 1).contiguous().to(dev),
+                                        stride=stride, pad=pad, relu=relu, out_f32=f32out)
     assert y.dtype == (torch.float32 if f32out else torch.bfloat16)
     err = rel_err(y.float().cpu().permute(0, 3, 1, 2), ref)
     assert err < (1e-5 if f32out else 1e-2), err
@@ -77,13 +76,10 @@ def test_conv_bf16_interleaved_tiles(dev, tile):
     shift = _rand(cout, seed=24, scale=0.1)
     r = _rand(n, cout, h, w, seed=25).bfloat16()
     ref = F.relu(F.conv2d(x.float(), wt.float(), None, padding=1) * scale.view(1, -1, 1, 1) + shift.view(1, -1, 1, 1) + r.float())
-    ops.set_tuning(ops.TUNE_BF16_TILE, tile)
-    try:
+    with ops.tuned({ops.TUNE_BF16_TILE: tile}):
         y = ops.conv2d_bn_act_nhwc_bf16(x.permute(0, 2, 3, 1).contiguous().to(dev), wt.permute(0, 2, 3, 1).contiguous().to(dev),
                                         scale.to(dev), shift.to(dev), r.permute(0, 2, 3, 1).contiguous().to(dev), stride=1, pad=1,
                                         relu=True)
-    finally:
-        ops.set_tuning(ops.TUNE_BF16_TILE, -1)
     err = rel_err(y.float().cpu().permute(0, 3, 1, 2), ref)
     assert err < 1e-2, err
 
@@ -139,11 +135,8 @@ def test_bf16_forward_with_persistent_layer1_is_bit_identical(dev):
     m.encoder_dtype = "bf16"
     d = fc_batch(S.synth_images(48, 224, 224, seed=9), 8).to(dev)
     a0, r0, _ = m(d)
-    ops.set_tuning(ops.TUNE_BF16_PERSIST, 1)
-    try:
+    with ops.tuned({ops.TUNE_BF16_PERSIST: 1}):
         a1, r1, _ = m(d)
-    finally:
-        ops.set_tuning(ops.TUNE_BF16_PERSIST, 0)
     assert torch.equal(a0, a1) and torch.equal(r0, r1)
     assert bool(torch.isfinite(a1).all()) and float(a1.abs().max()) > 0
 
@@ -217,11 +210,8 @@ def test_linear_bf16_on_dma_configs(dev, cfg, m, k, n_out, gather):
     args = (ops, ab, w.bfloat16().to(dev), bias.to(dev), tdev, None if idx is None else idx.to(dev), r2dev,
             None if idx2 is None else idx2.to(dev), 3 * n_out if gather else n_out, m, k, n_out)
     base = _linear_bf16_raw(*args)
-    ops.set_tuning(ops.TUNE_BF16_LINEAR_DMA, 10 + cfg)
-    try:
+    with ops.tuned({ops.TUNE_BF16_LINEAR_DMA: 10 + cfg}):
         out = _linear_bf16_raw(*args)
-    finally:
-        ops.set_tuning(ops.TUNE_BF16_LINEAR_DMA, 0)
     assert rel_err(out.cpu(), ref) < 2e-5 and rel_err(base.cpu(), ref) < 2e-5
 
 
@@ -253,13 +243,10 @@ def test_conv_bf16_dma_configs(dev, cfg, n, h, w, cin, cout, k, stride, pad, res
         ref = ref + r.float()
     if relu:
         ref = F.relu(ref)
-    ops.set_tuning(ops.TUNE_BF16_DMA, 10 + cfg)
-    try:
+    with ops.tuned({ops.TUNE_BF16_DMA: 10 + cfg}):
         y = ops.conv2d_bn_act_nhwc_bf16(x.permute(0, 2, 3, 1).contiguous().to(dev), wt.permute(0, 2, 3, 1).contiguous().to(dev),
                                         scale.to(dev), shift.to(dev), None if r is None else r.permute(0, 2, 3, 1).contiguous().to(dev),
                                         stride=stride, pad=pad, relu=relu, out_f32=f32out)
-    finally:
-        ops.set_tuning(ops.TUNE_BF16_DMA, 1)
     assert rel_err(y.float().cpu().permute(0, 3, 1, 2), ref) < (1e-4 if f32out else 1e-2)
 
 
@@ -312,20 +299,15 @@ def _patch_kernel_case(dev, mode, persist, n, h, w, cin, cout, res, relu):
         ref = ref + r.float()
     if relu:
         ref = F.relu(ref)
-    ops.set_tuning(ops.TUNE_BF16_PATCH, mode)
     args = (x.permute(0, 2, 3, 1).contiguous().to(dev), wt.permute(0, 2, 3, 1).contiguous().to(dev), scale.to(dev), shift.to(dev),
             None if r is None else r.permute(0, 2, 3, 1).contiguous().to(dev))
-    try:
-        ops.set_tuning(ops.TUNE_BF16_PERSIST, 0)
+    with ops.tuned({ops.TUNE_BF16_PATCH: mode, ops.TUNE_BF16_PERSIST: 0}):
         y = ops.conv2d_bn_act_nhwc_bf16(*args, stride=1, pad=1, relu=relu)
-        if persist:
-            ops.set_tuning(ops.TUNE_BF16_PERSIST, 1)
+    if persist:
+        with ops.tuned({ops.TUNE_BF16_PATCH: mode, ops.TUNE_BF16_PERSIST: 1}):
             y1 = ops.conv2d_bn_act_nhwc_bf16(*args, stride=1, pad=1, relu=relu)
-            assert torch.equal(y1, y)
-            y = y1
-    finally:
-        ops.set_tuning(ops.TUNE_BF16_PATCH, 1)
-        ops.set_tuning(ops.TUNE_BF16_PERSIST, 0)
+        assert torch.equal(y1, y)
+        y = y1
     got = y.float().cpu().permute(0, 3, 1, 2)
     assert rel_err(got, ref) < 1e-2
     assert float((got - ref).abs().mean() / ref.abs().mean().clamp(min=1e-30)) < 3e-3     # bf16 output rounding only
@@ -360,12 +342,9 @@ def test_conv_bf16_lean_epilogue_equals_general(dev, n, h, w, cin, cout, k, stri
     xd, wd = x.permute(0, 2, 3, 1).contiguous().to(dev), wt.permute(0, 2, 3, 1).contiguous().to(dev)
     rd = None if r is None else r.permute(0, 2, 3, 1).contiguous().to(dev)
     outs = {}
-    try:
-        for lean in (1, 0):
-            ops.set_tuning(ops.TUNE_BF16_LEAN_EPI, lean)
+    for lean in (1, 0):
+        with ops.tuned({ops.TUNE_BF16_LEAN_EPI: lean}):
             outs[lean] = ops.conv2d_bn_act_nhwc_bf16(xd, wd, scale.to(dev), shift.to(dev), rd, stride=stride, pad=pad, relu=True)
-    finally:
-        ops.set_tuning(ops.TUNE_BF16_LEAN_EPI, 1)
     assert torch.equal(outs[1], outs[0])
     got = outs[1].float().cpu().permute(0, 3, 1, 2)
     assert rel_err(got, ref) < 1e-2
@@ -388,11 +367,8 @@ def test_fused_stem_bf16(dev, n, h, w, kernel):
     an even convolution row), images narrower than a strip) and the tile kernel of rounds 3-5 behind RPG_TUNE_FUSED_STEM = 3."""
     from relpose_gnn_amd import ops
     from relpose_gnn_amd.params import pack_stem_bf16
-    ops.set_tuning(ops.TUNE_FUSED_STEM, kernel)
-    try:
+    with ops.tuned({ops.TUNE_FUSED_STEM: kernel}):
         _fused_stem_bf16_case(dev, n, h, w)
-    finally:
-        ops.set_tuning(ops.TUNE_FUSED_STEM, 1)
 
 
 def _fused_stem_bf16_case(dev, n, h, w):
@@ -499,8 +475,7 @@ def test_fused_basicblock64_equals_two_convolutions(dev, shape):
         t = ops.conv2d_bn_act_nhwc_bf16(xx, w1, s1, b1, None, stride=1, pad=1, relu=True)
         return ops.conv2d_bn_act_nhwc_bf16(t, w2, s2, b2, xx, stride=1, pad=1, relu=True)
 
-    ops.set_tuning(ops.TUNE_BF16_PATCH, 2)
-    try:
+    with ops.tuned({ops.TUNE_BF16_PATCH: 2}):
         if w <= 62:
             want = two_launches(x)
         else:
@@ -514,8 +489,6 @@ def test_fused_basicblock64_equals_two_convolutions(dev, shape):
             y1 = two_launches(x[:, :, w - wv:, :].contiguous())
             want = torch.cat([y0[:, :, :ws, :], y1[:, :, ws - (w - wv):, :]], dim=2)
             whole = two_launches(x)                       # what the encoder runs with the fusion off: equal up to summation order
-    finally:
-        ops.set_tuning(ops.TUNE_BF16_PATCH, 1)
     got = ops.basicblock64_bf16(x, w1, s1, b1, w2, s2, b2)
     torch.cuda.synchronize()
     assert got.shape == want.shape and bool(torch.isfinite(got.float()).all())
@@ -549,22 +522,19 @@ def test_fused_basicblock64_large_batches_and_persistent_form(dev, shape):
     w2 = (torch.randn((64, 3, 3, 64), generator=g) * (2.0 / 576) ** 0.5).bfloat16().to(dev)
     s1, b1 = (torch.rand(64, generator=g) + 0.5).to(dev), (torch.randn(64, generator=g) * 0.2).to(dev)
     s2, b2 = (torch.rand(64, generator=g) + 0.5).to(dev), (torch.randn(64, generator=g) * 0.2).to(dev)
-    try:
-        ops.set_tuning(ops.TUNE_BF16_FUSE_BLOCK, 1)
+    with ops.tuned({ops.TUNE_BF16_FUSE_BLOCK: 1}):
         parts = torch.cat([ops.basicblock64_bf16(x[i:i + 12].contiguous(), w1, s1, b1, w2, s2, b2) for i in range(0, n, 12)])
         # fill the allocator's free blocks of this size with NaN patterns: a dropped store then shows
         junk = torch.full_like(x, float("nan"))
         del junk
         one = ops.basicblock64_bf16(x, w1, s1, b1, w2, s2, b2)
-        ops.set_tuning(ops.TUNE_BF16_FUSE_BLOCK, 3)
+    with ops.tuned({ops.TUNE_BF16_FUSE_BLOCK: 3}):
         junk = torch.full_like(x, float("nan"))
         del junk
         per = ops.basicblock64_bf16(x, w1, s1, b1, w2, s2, b2)
-        ops.set_tuning(ops.TUNE_BF16_FUSE_BLOCK, 5)      # (iii) the two-group schedule (experiment, off by default): same MFMA order per accumulator
+    with ops.tuned({ops.TUNE_BF16_FUSE_BLOCK: 5}):      # (iii) the two-group schedule (experiment, off by default): same MFMA order per accumulator
         two_group = ops.basicblock64_bf16(x, w1, s1, b1, w2, s2, b2)
         torch.cuda.synchronize()
-    finally:
-        ops.set_tuning(ops.TUNE_BF16_FUSE_BLOCK, 3)
     assert bool(torch.isfinite(one.float()).all()) and bool(torch.isfinite(per.float()).all())
     for name, got in (("one tile per workgroup", one), ("persistent", per), ("two-group schedule", two_group)):
         bad = (got != parts).nonzero()
@@ -598,13 +568,10 @@ def test_bf16_encoder_with_and_without_block_fusion_is_bit_identical(dev):
     m.encoder_dtype = "bf16"
     d = fc_batch(S.synth_images(48, 224, 224, seed=9), 8).to(dev)
     outs = []
-    try:
-        for fuse in (3, 0, 1, 5):                         # persistent (default) | two launches | one tile per workgroup | two-group schedule
-            ops.set_tuning(ops.TUNE_BF16_FUSE_BLOCK, fuse)
+    for fuse in (3, 0, 1, 5):                         # persistent (default) | two launches | one tile per workgroup | two-group schedule
+        with ops.tuned({ops.TUNE_BF16_FUSE_BLOCK: fuse}):
             a, r, _ = m(d)
             outs.append((a.clone(), r.clone()))
-    finally:
-        ops.set_tuning(ops.TUNE_BF16_FUSE_BLOCK, 3)
     for k in (1, 2, 3):
         assert torch.equal(outs[0][0], outs[k][0]) and torch.equal(outs[0][1], outs[k][1]), k
     assert bool(torch.isfinite(outs[0][0]).all()) and float(outs[0][0].abs().max()) > 0
@@ -629,13 +596,10 @@ def test_bf16_encoder_paired_downsample_launch_is_bit_identical(dev):
         m.encoder_dtype = "bf16"
         d = fc_batch(S.synth_images(nimg, hh, ww, seed=19), 8).to(dev)
         outs = []
-        try:
-            for pair in (1, 0):
-                ops.set_tuning(ops.TUNE_BF16_PAIR, pair)
+        for pair in (1, 0):
+            with ops.tuned({ops.TUNE_BF16_PAIR: pair}):
                 a, r, _ = m(d)
                 outs.append((a.clone(), r.clone()))
-        finally:
-            ops.set_tuning(ops.TUNE_BF16_PAIR, 1)
         assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1]), (hh, ww)
         assert bool(torch.isfinite(outs[0][0]).all()) and float(outs[0][0].abs().max()) > 0
 
@@ -651,12 +615,9 @@ def test_conv_bf16_lean_epilogue_without_relu_keeps_nan(dev):
     scale, shift = torch.rand(128, generator=torch.Generator().manual_seed(73)) + 0.5, _rand(128, seed=74, scale=0.1)
     xd, wd = x.permute(0, 2, 3, 1).contiguous().to(dev), wt.permute(0, 2, 3, 1).contiguous().to(dev)
     outs = {}
-    try:
-        for lean in (1, 0):
-            ops.set_tuning(ops.TUNE_BF16_LEAN_EPI, lean)
+    for lean in (1, 0):
+        with ops.tuned({ops.TUNE_BF16_LEAN_EPI: lean}):
             outs[lean] = ops.conv2d_bn_act_nhwc_bf16(xd, wd, scale.to(dev), shift.to(dev), None, stride=2, pad=0, relu=False)
-    finally:
-        ops.set_tuning(ops.TUNE_BF16_LEAN_EPI, 1)
     a, b = outs[1].float().cpu(), outs[0].float().cpu()
     assert torch.equal(torch.isnan(a), torch.isnan(b)) and int(torch.isnan(a).sum()) == 128          # output pixel (3, 4) of image 3, all channels
     assert torch.equal(torch.nan_to_num(a, nan=0.0), torch.nan_to_num(b, nan=0.0))
@@ -676,12 +637,9 @@ def test_patch_kernel_tail_retiling_is_bit_identical(dev, n, h, w, c, res):
     sc, sh = (torch.rand(c, generator=g) + 0.5).to(dev), (torch.randn(c, generator=g) * 0.1).to(dev)
     r = torch.randn((n, h, w, c), generator=g).bfloat16().to(dev) if res else None
     outs = {}
-    try:
-        for tail in (3, 0):                                   # both re-tilings on (layer-2 and layer-3 style) / one launch
-            ops.set_tuning(ops.TUNE_BF16_TAIL, tail)
+    for tail in (3, 0):                                   # both re-tilings on (layer-2 and layer-3 style) / one launch
+        with ops.tuned({ops.TUNE_BF16_TAIL: tail}):
             outs[tail] = ops.conv2d_bn_act_nhwc_bf16(x, wt, sc, sh, r, stride=1, pad=1, relu=True)
-    finally:
-        ops.set_tuning(ops.TUNE_BF16_TAIL, 1)
     assert torch.equal(outs[3], outs[0])
     for i in (0, n // 2, n - 1):                               # first image, one in the middle, the last (tail launch)
         ref = F.conv2d(x[i:i + 1].float().permute(0, 3, 1, 2).cpu(), wt.float().permute(0, 3, 1, 2).cpu(), padding=1)

@@ -51,29 +51,6 @@ def _record(case: str, rep: dict) -> None:
     _report({"case": case, **{k: v for k, v in rep.items() if k != "first"}})
 
 
-def _defaults(ops):
-    return {ops.TUNE_BF16_FAST: 1, ops.TUNE_BF16_TILE: -1, ops.TUNE_BF16_DMA: 1, ops.TUNE_BF16_BK: 32, ops.TUNE_BF16_PATCH: 1,
-            ops.TUNE_BF16_PERSIST: 0, ops.TUNE_BF16_LEAN_EPI: 1, ops.TUNE_BF16_TAIL: 1, ops.TUNE_BF16_PAIR: 1,
-            ops.TUNE_BF16_LINEAR_DMA: 0, ops.TUNE_FUSED_STEM: 1}
-
-
-class _tuned:
-    """with _tuned(ops, {key: value}): ... -- the keys go back to the library's defaults on the way out."""
-
-    def __init__(self, ops, keys):
-        self.ops, self.keys = ops, keys
-
-    def __enter__(self):
-        for k, v in self.keys.items():
-            self.ops.set_tuning(k, v)
-
-    def __exit__(self, *exc):
-        d = _defaults(self.ops)
-        for k in self.keys:
-            self.ops.set_tuning(k, d[k])
-        return False
-
-
 # n, h, w, cin, cout, k, stride, pad
 SHAPES = {
     "tiny_cin8": (2, 9, 11, 8, 16, 3, 1, 1),            # ragged M, K = 72 (K tail), general kernel only
@@ -124,7 +101,7 @@ def _conv_check(dev, name, dist, res, relu, tuning, out_f32=False, what=""):
     from relpose_gnn_amd import ops
     x, wt, scale, shift, r, ref, memo = _conv_case(name, dist, res)
     stride, pad = SHAPES[name][6], SHAPES[name][7]
-    with _tuned(ops, tuning):
+    with ops.tuned(tuning):
         y = ops.conv2d_bn_act_nhwc_bf16(_nhwc(x, dev), _nhwc(wt, dev), scale.to(dev), shift.to(dev), _nhwc(r, dev), stride=stride,
                                         pad=pad, relu=relu, out_f32=out_f32)
         torch.cuda.synchronize()
@@ -263,7 +240,7 @@ def test_conv_paired_downsample_launch(dev, n, h, w, cin, cout, dist):
     ra = R.check(ya, R.conv_ref(x, wa, sa, ha, None, 2, 1), True, what="pair: 3x3 / 2")
     rb = R.check(yb, R.conv_ref(x, wb, sb, hb, None, 2, 0), False, what="pair: 1x1 / 2 shortcut")
     assert ra["bad"] == 0 and rb["bad"] == 0 and max(ra["ambiguous"], rb["ambiguous"]) <= R.AMBIGUOUS_CAP
-    with _tuned(ops, {ops.TUNE_BF16_PAIR: 0}):                # switched off, the entry point refuses (the caller launches one by one)
+    with ops.tuned({ops.TUNE_BF16_PAIR: 0}):                # switched off, the entry point refuses (the caller launches one by one)
         with pytest.raises(ValueError):
             ops.conv_pair_bf16(_nhwc(x, dev), _nhwc(wa, dev), sa.to(dev), ha.to(dev), _nhwc(wb, dev), sb.to(dev), hb.to(dev))
 
@@ -338,7 +315,7 @@ def test_linear_bf16_outputs(dev, shape, cfg, dist):
     case = _linear_case(m, k, n_out, gather, dist)
     ref = case[-1]
     tag = f"linear {m}x{k}->{n_out} gather={gather} {dist} cfg={cfg}"
-    with _tuned(ops, {ops.TUNE_BF16_LINEAR_DMA: 0 if cfg is None else 10 + cfg}):
+    with ops.tuned({ops.TUNE_BF16_LINEAR_DMA: 0 if cfg is None else 10 + cfg}):
         y32, none2 = _linear_run(ops, dev, case, gather, n_out, relu=True)
         plain = ops.linear_bf16(case[0].to(dev), case[1].to(dev), case[2].to(dev), relu=False) if gather == 0 else None
         y16, _ = _linear_run(ops, dev, case, gather, n_out, relu=False, out_dtype=torch.bfloat16)
@@ -399,7 +376,7 @@ def test_stem_bf16(dev, n, h, w, dist, kernel, xdtype):
     from relpose_gnn_amd import ops
     from relpose_gnn_amd.params import pack_stem_bf16
     x, wt, scale, shift, ref, c_ref = _stem_case(n, h, w, dist)
-    with _tuned(ops, {ops.TUNE_FUSED_STEM: kernel}):
+    with ops.tuned({ops.TUNE_FUSED_STEM: kernel}):
         y = ops.stem_conv_bn_relu_maxpool_bf16(x.to(xdtype).to(dev), pack_stem_bf16(wt).to(dev), scale.to(dev), shift.to(dev))
         torch.cuda.synchronize()
     rep = R.check(y, ref, True, post=_pool_nhwc, c_ref=c_ref, what=f"stem {n}x{h}x{w} {dist} kernel={kernel} {xdtype}")
@@ -423,7 +400,7 @@ def test_basicblock_reference_pair(dev, shape, cols):
     w2 = (torch.randn((64, 3, 3, 64), generator=g) * (2.0 / 576) ** 0.5).bfloat16()
     (s1, b1), (s2, b2) = R.wide_scales(64, 41, 0.2), R.unit_scales(64, 42, 0.2)
     xd = x.to(dev)
-    with _tuned(ops, {ops.TUNE_BF16_PATCH: 2}):
+    with ops.tuned({ops.TUNE_BF16_PATCH: 2}):
         t = ops.conv2d_bn_act_nhwc_bf16(xd, w1.to(dev), s1.to(dev), b1.to(dev), None, stride=1, pad=1, relu=True)
         y = ops.conv2d_bn_act_nhwc_bf16(t, w2.to(dev), s2.to(dev), b2.to(dev), xd, stride=1, pad=1, relu=True)
         torch.cuda.synchronize()

@@ -50,6 +50,7 @@ import torch.nn.functional as F
 
 import encoder_sweep_ref as R
 from conftest import rel_err
+from relpose_gnn_amd import ops
 from test_hip_graph_sweep import _record
 
 pytestmark = pytest.mark.gpu
@@ -73,28 +74,6 @@ def lib():
 
 def _stream():
     return torch.cuda.current_stream().cuda_stream
-
-
-class _keys:
-    """Tuning keys for the length of a with block; the defaults of encoder_sweep_ref.DEFAULT_KEYS (and any others named) afterwards."""
-
-    def __init__(self, keys, defaults=None):
-        self.keys, self.defaults = keys, {**R.DEFAULT_KEYS, **(defaults or {})}
-
-    def _set(self, keys):
-        from relpose_gnn_amd import ops
-        for k, v in keys.items():
-            ops.set_tuning(getattr(ops, "TUNE_" + k), v)
-
-    def __enter__(self):
-        try:
-            self._set(self.keys)
-        except BaseException:
-            self._set(self.defaults)
-            raise
-
-    def __exit__(self, *exc):
-        self._set(self.defaults)
 
 
 def _ratio(section, case, c_ref, c_hip, margin):
@@ -170,14 +149,14 @@ def test_winograd_route(dev, lib, route, shape):
     def launch(relu):
         return lambda y: lib.rpg_conv3x3_wino43_bn_act_nhwc_f32(buf.x.ptr(), buf.w.ptr(), buf.scale.ptr(), buf.shift.ptr(), _opt(buf.res),
                                                                y.ptr(), n, h, w, cin, cout, relu, _stream())
-    with _keys(R.ROUTES[route]):
+    with ops.tuned(R.ROUTES[route]):
         y_relu, y_lin = buf.run(launch(1), dev), buf.run(launch(0), dev)
     assert rel_err(y_relu, torch.relu(y32)) < 2e-5 and rel_err(y_lin, y32) < 2e-5
     c_relu, c_lin = R.c_of(y_relu, ref.z, ref.S, relu=True), R.c_of(y_lin, ref.z, ref.S)
     assert c_relu <= M_KERNEL * ref.c_ref, (taken, ref.c_ref, c_relu)
     _ratio("winograd", f"{route}-{R.wino_shape_id(shape)}->{taken}", ref.c_ref, c_lin, M_KERNEL)
     if taken == "persist_whole":
-        with _keys(R.ROUTES["wave8_whole"]):
+        with ops.tuned(R.ROUTES["wave8_whole"]):
             y_whole = buf.run(launch(0), dev)
         assert rel_err(y_lin, y_whole) < 1e-6
 
@@ -201,7 +180,7 @@ def test_direct_convolution(dev, lib, kind, extent, streamk):
     def launch(act):
         return lambda y: lib.rpg_conv2d_bn_act_nhwc_f32(buf.x.ptr(), buf.w.ptr(), buf.scale.ptr(), buf.shift.ptr(), None, y.ptr(), n, h, w,
                                                        cin, cout, k, k, stride, pad, act, _stream())
-    with _keys({"STREAMK": streamk}, {"STREAMK": 1}):
+    with ops.tuned({"STREAMK": streamk}):
         y_lin = buf.run(launch(0), dev)
         y_relu = buf.run(launch(1), dev) if relu else None
     assert rel_err(y_lin, y32) < 1e-5
@@ -242,7 +221,7 @@ def test_stem(dev, lib, h, w, kernel):
     wpb = R.Moated(wp.shape, dev, wp)
     hp, wpool = ((h - 1) // 2 + 1 - 1) // 2 + 1, ((w - 1) // 2 + 1 - 1) // 2 + 1
     y = R.Moated((n, hp, wpool, 64), dev)
-    with _keys({"FUSED_STEM": kernel}, {"FUSED_STEM": 1}):
+    with ops.tuned({"FUSED_STEM": kernel}):
         rc = lib.rpg_stem_conv7x7s2_bn_relu_maxpool_f32(xb.ptr(), wpb.ptr(), sh.ptr(), y.ptr(), n, h, w, _stream())
         torch.cuda.synchronize()
     assert rc == 0

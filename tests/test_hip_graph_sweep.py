@@ -375,14 +375,9 @@ def test_forward_irregular_batch_all_formulations(dev, fwd, split, fuse_agg):
     from relpose_gnn_amd import ops
     m = fwd["m"]
     m.hip_streams = 1
-    ops.set_tuning(ops.TUNE_GNN_SPLIT, split)
-    ops.set_tuning(ops.TUNE_GNN_FUSE_AGG, fuse_agg)
-    try:
+    with ops.tuned({ops.TUNE_GNN_SPLIT: split, ops.TUNE_GNN_FUSE_AGG: fuse_agg}):
         a, r, ei = m(fwd["grouped"])
         got = (a.cpu(), r.cpu())
-    finally:
-        ops.set_tuning(ops.TUNE_GNN_SPLIT, 1)
-        ops.set_tuning(ops.TUNE_GNN_FUSE_AGG, 1)
     m.check_edge_index()
     assert torch.equal(ei.cpu(), fwd["ei"]) and bool(torch.isfinite(got[0]).all()) and bool(torch.isfinite(got[1]).all())
     _against_float64(f"split={split} fuse_agg={fuse_agg}", got, fwd["o32"], fwd["o64"])

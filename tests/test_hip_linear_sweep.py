@@ -54,7 +54,7 @@ import torch
 
 import linear_sweep_ref as R
 from conftest import rel_err
-from test_hip_encoder_sweep import _keys
+from relpose_gnn_amd import ops
 from test_hip_graph_sweep import _record
 
 pytestmark = pytest.mark.gpu
@@ -83,11 +83,6 @@ def cus(dev):
 
 def _stream():
     return torch.cuda.current_stream().cuda_stream
-
-
-def _tuned(keys):
-    """The spec's tuning keys for the length of a with block; linear_sweep_ref.DEFAULT_KEYS afterwards (in ``finally``)."""
-    return _keys(dict(keys), R.DEFAULT_KEYS)
 
 
 def _opt(buf):
@@ -165,7 +160,7 @@ def _ref(spec):
 
 def _margin(spec):
     """M_LINEAR for a case that runs K as one sequential chain (RPG_TUNE_FOLD_K = 0), the tighter M_FOLDED for every other."""
-    return M_LINEAR if dict(spec.keys).get("FOLD_K", R.DEFAULT_KEYS["FOLD_K"]) == 0 else M_FOLDED
+    return M_LINEAR if dict(spec.keys).get("FOLD_K", ops.tuning_default("FOLD_K")) == 0 else M_FOLDED
 
 
 def _run(spec, lib, dev, section, repeats=1, assert_bar=True):
@@ -174,7 +169,7 @@ def _run(spec, lib, dev, section, repeats=1, assert_bar=True):
     the caller compares them (after it has recorded a second launch)."""
     case, ref, y32 = _ref(spec)
     ops_ = _Operands(case, dev)
-    with _tuned(spec.keys):
+    with ops.tuned(dict(spec.keys)):
         out, out_relu, route = ops_.launch(lib, dev, 0, spec.entry)
         _assert_route(spec, route)
         for _ in range(repeats - 1):
@@ -290,7 +285,7 @@ def test_offset_guard_at_2_31_bytes(dev, lib, rows, loader):
     big[named.to(dev)] = src.a.to(dev)
     idx = named[pick].to(dev)
     w, bias, out = R.Moated(case.weight.shape, dev, case.weight), R.Moated(case.bias.shape, dev, case.bias), R.Moated((m, n_out), dev)
-    with _tuned({"TILE": 2}):
+    with ops.tuned({"TILE": 2}):
         rc = lib.rpg_linear_gather_ex_f32(1, _lib.ptr_array([big.data_ptr()]), _lib.ptr_array([idx.data_ptr()]), _lib.int_array([ld]),
                                           _lib.int_array([width]), (C.c_long * 1)(rows), w.ptr(), bias.ptr(), None, None, None, None, 0,
                                           out.ptr(), None, m, n_out, 0, _stream())

@@ -487,15 +487,12 @@ def test_bf16_encoder_takes_host_rounded_bf16_images(dev):
     # RPG_TUNE_FUSED_STEM = 0: the three-kernel stem takes the host-rounded bf16 images too -- a tuning knob must
     # not turn a working evaluation loop into an error -- and agrees with its own fp32-input run bit for bit
     from relpose_gnn_amd import ops
-    ops.set_tuning(ops.TUNE_FUSED_STEM, 0)
-    try:
+    with ops.tuned({ops.TUNE_FUSED_STEM: 0}):
         assert m.accepts_bf16_input
         a16u, r16u, _ = m(b)
         b.x = b.x.float()
         a32u, r32u, _ = m(b)
         unfused = E.evaluate_stream(m, graphs, dev, micro_batch=3).pred_poses
-    finally:
-        ops.set_tuning(ops.TUNE_FUSED_STEM, 1)
     assert torch.equal(a16u, a32u) and torch.equal(r16u, r32u)
     assert rel_err(a16u, a32) < 2e-2 and np.isfinite(unfused).all()           # fused vs three-kernel stem: one extra bf16 rounding
     b.x = b.x.bfloat16()
@@ -580,14 +577,11 @@ def test_gnn_node_split_equals_reference_formulation(dev, golden_dir):
     big, _ = _build(2048, 64, (64, 128, 256, 512), (3, 4, 6, 3), dev)
     db = _data(S.synth_images(8 * 6, 64, 64, seed=21), 8, dev)
     outs = {}
-    try:
-        for split in (1, 0):
-            ops.set_tuning(ops.TUNE_GNN_SPLIT, split)
+    for split in (1, 0):
+        with ops.tuned({ops.TUNE_GNN_SPLIT: split}):
             a, r, _ = m(d)
             assert rel_err(a.cpu(), g["abs"]) < TOL and rel_err(r.cpu(), g["rel"]) < TOL
             outs[split] = tuple(t.cpu() for t in big(db)[:2])
-    finally:
-        ops.set_tuning(ops.TUNE_GNN_SPLIT, 1)
     ea, er = rel_err(outs[1][0], outs[0][0]), rel_err(outs[1][1], outs[0][1])
     _report("gnn_node_split_vs_reference_formulation_R3_64px", ea, er)
     assert ea < TOL and er < TOL
@@ -605,11 +599,8 @@ def test_gnn_fused_aggregation_equals_reference_order(dev):
     b = Batch.from_data_list(graphs).to(dev)
     m.hip_streams = 1
     a1, r1, _ = m(b)
-    ops.set_tuning(ops.TUNE_GNN_FUSE_AGG, 0)
-    try:
+    with ops.tuned({ops.TUNE_GNN_FUSE_AGG: 0}):
         a0, r0, _ = m(b)
-    finally:
-        ops.set_tuning(ops.TUNE_GNN_FUSE_AGG, 1)
     ea, er = rel_err(a1, a0), rel_err(r1, r0)
     _report("gnn_fused_aggregation_vs_reference_order_R3_64px", ea, er)
     assert ea < TOL and er < TOL, (ea, er)
@@ -619,10 +610,9 @@ def test_gnn_fused_aggregation_equals_reference_order(dev):
     m.gnn_dtype = "bf16"
     try:
         ab1, rb1, _ = m(b)
-        ops.set_tuning(ops.TUNE_GNN_FUSE_AGG, 0)
-        ab0, rb0, _ = m(b)
+        with ops.tuned({ops.TUNE_GNN_FUSE_AGG: 0}):
+            ab0, rb0, _ = m(b)
     finally:
-        ops.set_tuning(ops.TUNE_GNN_FUSE_AGG, 1)
         m.gnn_dtype = "f32"
     eab, erb = rel_err(ab1, ab0), rel_err(rb1, rb0)
     _report("gnn_bf16_epilogue_emitted_vs_convert_per_linear_R3_64px", eab, erb)

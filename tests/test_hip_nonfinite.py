@@ -11,21 +11,18 @@ launch, and the result is compared with the same launch on clean input and with 
       zero-weight taps next to the 7 x 7 window, so those are held to a stated superset inside the poisoned image.
 Model level: every abs row of the poisoned graph and every rel row of its edges is non-finite, every other graph bit-identical
 to the forward of the clean batch (same shapes, so the same launch geometry)."""
-import contextlib
 
 import pytest
 import torch
 import torch.nn.functional as F
+
+from relpose_gnn_amd import ops
 
 pytestmark = pytest.mark.gpu
 
 NEG_NAN = torch.tensor([0xFFC00000 - 2 ** 32], dtype=torch.int32).view(torch.float32).item()      # 0xFFC00000: a quiet NaN, sign bit set
 BAD = {"nan": float("nan"), "-nan": NEG_NAN, "inf": float("inf"), "-inf": float("-inf")}
 BITS32 = {"nan": 0x7FC00000, "-nan": 0xFFC00000, "inf": 0x7F800000, "-inf": 0xFF800000}
-# library defaults of the tuning keys the variant cases set (what every other test file restores in its `finally`)
-TUNE_DEFAULTS = {"TILE": -1, "STREAMK": 1, "BK": 0, "EPILOGUE": 1, "FAST_LOADER": 1, "WAVES8": 1, "WINOGRAD": 1, "WINO_PERSIST": 1,
-                 "WINO_SPLIT": 1, "BF16_FAST": 1, "BF16_DMA": 1, "BF16_PATCH": 1, "BF16_PERSIST": 0, "BF16_LEAN_EPI": 1,
-                 "BF16_FUSE_BLOCK": 3, "BF16_LINEAR_DMA": 0, "FUSED_STEM": 1, "GNN_SPLIT": 1, "GNN_FUSE_AGG": 1}
 
 
 def _put(t, idx, kind):
@@ -41,18 +38,6 @@ def _put(t, idx, kind):
     else:
         assert t.dtype == torch.float32
         t.view(torch.int32)[idx] = b - (1 << 32) if b >= 1 << 31 else b
-
-
-@contextlib.contextmanager
-def _tuned(**keys):
-    from relpose_gnn_amd import ops
-    try:
-        for k, v in keys.items():
-            ops.set_tuning(getattr(ops, "TUNE_" + k), v)
-        yield
-    finally:
-        for k in keys:
-            ops.set_tuning(getattr(ops, "TUNE_" + k), TUNE_DEFAULTS[k])
 
 
 def _vid(v):
@@ -221,8 +206,7 @@ def test_fused_stem_f32(dev, kind, kernel):
     wt = _rand(64, 3, 7, 7, seed=2, scale=(2.0 / 147) ** 0.5)
     sc, sh = torch.rand(64, generator=torch.Generator().manual_seed(3)) + 0.5, _rand(64, seed=4, scale=0.3)
     wp = pack_stem_pairs(wt, sc).to(dev)
-    ops.set_tuning(ops.TUNE_FUSED_STEM, kernel)
-    try:
+    with ops.tuned({ops.TUNE_FUSED_STEM: kernel}):
         clean = ops.stem_conv_bn_relu_maxpool(x.to(dev), wp, sh.to(dev))
         for (c, y, xx) in ((0, 0, 0), (1, 20, 27), (2, h - 1, w - 1)):
             xb = x.clone()
@@ -232,8 +216,6 @@ def test_fused_stem_f32(dev, kind, kernel):
             if kind == "-inf" and not bool((~torch.isfinite(ref[1])).any()):
                 continue                                             # -inf after a ReLU and a max-pool is often gone
             _check(got, clean, ref, 1, exact=False, within=_stem_bound(h, w, y, xx, STEM_READS[("f32", kernel)]))
-    finally:
-        ops.set_tuning(ops.TUNE_FUSED_STEM, 1)
 
 
 @pytest.mark.parametrize("kind", list(BAD))
@@ -250,8 +232,7 @@ def test_fused_stem_bf16(dev, kind, kernel, in_bf16):
     sc, sh = torch.rand(64, generator=torch.Generator().manual_seed(3)) + 0.5, _rand(64, seed=4, scale=0.3)
     wp = pack_stem_bf16(wt).to(dev)
     xin = x.bfloat16() if in_bf16 else x
-    ops.set_tuning(ops.TUNE_FUSED_STEM, kernel)
-    try:
+    with ops.tuned({ops.TUNE_FUSED_STEM: kernel}):
         clean = ops.stem_conv_bn_relu_maxpool_bf16(xin.to(dev), wp, sc.to(dev), sh.to(dev))
         for (c, y, xx) in ((0, 0, 0), (1, 20, 27), (2, h - 1, w - 1)):
             xb = xin.clone()
@@ -261,8 +242,6 @@ def test_fused_stem_bf16(dev, kind, kernel, in_bf16):
             if kind == "-inf" and not bool((~torch.isfinite(ref[1])).any()):
                 continue
             _check(got.float(), clean.float(), ref, 1, exact=False, within=_stem_bound(h, w, y, xx, STEM_READS[("bf16", kernel)]))
-    finally:
-        ops.set_tuning(ops.TUNE_FUSED_STEM, 1)
 
 
 @pytest.mark.parametrize("kind", list(BAD) + ["3e38"])
@@ -275,8 +254,7 @@ def test_conv_bf16(dev, kind, fast, k, stride, pad, relu):
     wt = _rand(cout, k, k, cin, seed=16, scale=(2.0 / (cin * k * k)) ** 0.5).bfloat16()
     sc, sh = torch.rand(cout, generator=torch.Generator().manual_seed(17)) + 0.5, _rand(cout, seed=18, scale=0.1)
     v = 3e38 if kind == "3e38" else kind
-    ops.set_tuning(ops.TUNE_BF16_FAST, fast)
-    try:
+    with ops.tuned({ops.TUNE_BF16_FAST: fast}):
         run = lambda t: ops.conv2d_bn_act_nhwc_bf16(t.to(dev), wt.to(dev), sc.to(dev), sh.to(dev), None, stride=stride, pad=pad, relu=relu)
         clean = run(x)
         for (y, xx) in ((0, 0), (6, 8), (h - 1, w - 1)):
@@ -293,8 +271,6 @@ def test_conv_bf16(dev, kind, fast, k, stride, pad, relu):
             if not bool((~torch.isfinite(ref[1])).any()):
                 continue
             _check(got.float(), clean.float(), ref, 1, exact=kind != "3e38")
-    finally:
-        ops.set_tuning(ops.TUNE_BF16_FAST, 1)
 
 
 # --------------------------------------------------------------------------------------------------------------------- model level
@@ -450,7 +426,7 @@ def test_conv_f32_variants(dev, variant, shape, kind):
     r = _rand(n, ho, wo, cout, seed=45) if res else None
     img = n // 2
     args = (wt.to(dev), sc.to(dev), sh.to(dev), None if r is None else r.to(dev))
-    with _tuned(**variant):
+    with ops.tuned(variant):
         clean = ops.conv2d_bn_act_nhwc(x.to(dev), *args, stride=st, pad=pad, relu=relu)
         for (y, xx) in _positions(h, w):
             xb = x.clone()
@@ -490,7 +466,7 @@ def test_wino43_variants(dev, variant, shape, relu, kind):
     r = _rand(n, h, w, cout, seed=55) if res else None
     u = ops.wino43_transform_weights(wt.to(dev))
     args = (u, sc.to(dev), sh.to(dev), None if r is None else r.to(dev))
-    with _tuned(**variant):
+    with ops.tuned(variant):
         clean = ops.conv3x3_wino43_bn_act_nhwc(x.to(dev), *args, relu=relu)
         for img in (1, n - 2):
             for (y, xx) in ((0, 0), (h // 2 + 1, w // 2 - 3), (h - 1, w - 1)):
@@ -529,7 +505,7 @@ def test_conv_bf16_variants(dev, variant, shape, kind):
     r = _rand(n, ho, wo, cout, seed=65).bfloat16() if res else None
     img = n // 2
     args = (wt.to(dev), sc.to(dev), sh.to(dev), None if r is None else r.to(dev))
-    with _tuned(**variant):
+    with ops.tuned(variant):
         clean = ops.conv2d_bn_act_nhwc_bf16(x.to(dev), *args, stride=st, pad=pad, relu=relu)
         for (y, xx) in _positions(h, w):
             xb = x.clone()
@@ -558,7 +534,7 @@ def test_basicblock64_bf16(dev, fuse, shape, kind):
     s2, b2 = torch.rand(64, generator=g) + 0.5, torch.randn(64, generator=g) * 0.2
     wd = [t.to(dev) for t in (w1, s1, b1, w2, s2, b2)]
     img = n // 2
-    with _tuned(BF16_FUSE_BLOCK=fuse):
+    with ops.tuned({"BF16_FUSE_BLOCK": fuse}):
         clean = ops.basicblock64_bf16(x.to(dev), *wd)
         for (y, xx) in ((0, 0), (h // 2, (w + 1) // 2), (h - 1, w - 1)):
             xb = x.clone()
@@ -581,7 +557,7 @@ def test_linear_bf16(dev, m, k, n_out, cfg, relu, kind):
     a = _rand(m, k, seed=81).bfloat16()
     w, b = _rand(n_out, k, seed=82, scale=k ** -0.5).bfloat16(), _rand(n_out, seed=83)
     res = _rand(m, n_out, seed=84)
-    with _tuned(BF16_LINEAR_DMA=cfg):
+    with ops.tuned({"BF16_LINEAR_DMA": cfg}):
         run = lambda t: ops.linear_bf16(t.to(dev), w.to(dev), b.to(dev), res.to(dev), relu=relu)
         clean = run(a)
         for row in (0, m // 2, m - 1):
@@ -746,7 +722,7 @@ def test_model_variants_bad_pixel(dev, variant, kind):
     if "FUSED_STEM" in variant:
         m.encoder_dtype = "bf16"
     x = S.synth_images(4 * 8, 32, 40, seed=24)
-    with _tuned(**variant):
+    with ops.tuned(variant):
         a0, r0, ei = [t.clone() for t in m(fc_batch(x, 8).to(dev))]
         a, r, _ = m(fc_batch(_poison(x, 13, 32, 40, "mid", kind), 8).to(dev))
     _graph_check(a, r, a0, r0, ei, 1)

@@ -86,11 +86,8 @@ def test_fused_stem_conv_bn_relu_maxpool(dev, n, h, w, kernel):
     pooled rows, odd convolution heights and widths, images narrower than a strip)."""
     from relpose_gnn_amd import ops
     from relpose_gnn_amd.params import pack_stem_pairs
-    ops.set_tuning(ops.TUNE_FUSED_STEM, kernel)
-    try:
+    with ops.tuned({ops.TUNE_FUSED_STEM: kernel}):
         _fused_stem_f32_case(dev, n, h, w)
-    finally:
-        ops.set_tuning(ops.TUNE_FUSED_STEM, 1)
 
 
 def _fused_stem_f32_case(dev, n, h, w):
@@ -299,11 +296,7 @@ def test_tile_engine_variants(dev, bk, epi, tile, streamk):
     """Every (K-step, epilogue, workgroup-tile) variant of the MFMA tile engine on a conv with ragged M, K tail,
     residual + ReLU, and on a 3-source gathered Linear whose N is not a tile multiple."""
     from relpose_gnn_amd import ops
-    try:
-        ops.set_tuning(ops.TUNE_BK, bk)
-        ops.set_tuning(ops.TUNE_EPILOGUE, epi)
-        ops.set_tuning(ops.TUNE_TILE, tile)
-        ops.set_tuning(ops.TUNE_STREAMK, streamk)
+    with ops.tuned({ops.TUNE_BK: bk, ops.TUNE_EPILOGUE: epi, ops.TUNE_TILE: tile, ops.TUNE_STREAMK: streamk}):
         n, h, w, cin, cout = 3, 13, 17, 24, 72            # M = 663, K = 216 (not a multiple of 16/32), N = 72
         x = _rand(n, cin, h, w, seed=1)
         wt = _rand(cout, cin, 3, 3, seed=2, scale=(2.0 / (cin * 9)) ** 0.5)
@@ -328,11 +321,6 @@ def test_tile_engine_variants(dev, bk, epi, tile, streamk):
         ref = F.linear(torch.cat(cat, 1), wl, bias) + res
         out = ops.linear_gather(srcs, wl.to(dev), bias.to(dev), m, res.to(dev), False)
         assert rel_err(out.cpu(), ref) < TOL
-    finally:
-        ops.set_tuning(ops.TUNE_BK, 0)
-        ops.set_tuning(ops.TUNE_EPILOGUE, 1)
-        ops.set_tuning(ops.TUNE_TILE, -1)
-        ops.set_tuning(ops.TUNE_STREAMK, 1)
 
 
 @pytest.mark.parametrize("tile", [0, 3])
@@ -344,43 +332,37 @@ def test_tile_engine_eight_wave_workgroups(dev, tile, streamk):
     PLAIN (ungathered) sources, K = 2048, 256, 4096 and 64 + 32 + 160, M = 1792 / 256 / 300 rows, bias, a plain residual and
     ReLU.  Gathered sources on the buffer loader and gathered residual rows in the epilogue are tests/test_hip_linear_sweep.py's."""
     from relpose_gnn_amd import ops
-    try:
-        ops.set_tuning(ops.TUNE_TILE, tile)
-        ops.set_tuning(ops.TUNE_STREAMK, streamk)
-        for ci, (n, h, w, cin, cout, k, st, pad, res) in enumerate([(9, 28, 28, 128, 256, 3, 2, 1, True), (7, 30, 22, 64, 160, 1, 2, 0, False)]):
-            x = _rand(n, cin, h, w, seed=140 + ci)
-            wt = _rand(cout, cin, k, k, seed=150 + ci, scale=(2.0 / (cin * k * k)) ** 0.5)
-            scale = torch.rand(cout, generator=torch.Generator().manual_seed(160 + ci)) + 0.5
-            shift = _rand(cout, seed=170 + ci, scale=0.1)
-            ref = F.conv2d(x, wt, None, stride=st, padding=pad) * scale.view(1, -1, 1, 1) + shift.view(1, -1, 1, 1)
-            r = _rand(*ref.shape, seed=180 + ci) if res else None
-            ref = F.relu(ref + r if res else ref)
-            args = (x.permute(0, 2, 3, 1).contiguous().to(dev), wt.permute(0, 2, 3, 1).contiguous().to(dev), scale.to(dev),
-                    shift.to(dev), None if r is None else r.permute(0, 2, 3, 1).contiguous().to(dev))
+    keys = {ops.TUNE_TILE: tile, ops.TUNE_STREAMK: streamk}
+    for ci, (n, h, w, cin, cout, k, st, pad, res) in enumerate([(9, 28, 28, 128, 256, 3, 2, 1, True), (7, 30, 22, 64, 160, 1, 2, 0, False)]):
+        x = _rand(n, cin, h, w, seed=140 + ci)
+        wt = _rand(cout, cin, k, k, seed=150 + ci, scale=(2.0 / (cin * k * k)) ** 0.5)
+        scale = torch.rand(cout, generator=torch.Generator().manual_seed(160 + ci)) + 0.5
+        shift = _rand(cout, seed=170 + ci, scale=0.1)
+        ref = F.conv2d(x, wt, None, stride=st, padding=pad) * scale.view(1, -1, 1, 1) + shift.view(1, -1, 1, 1)
+        r = _rand(*ref.shape, seed=180 + ci) if res else None
+        ref = F.relu(ref + r if res else ref)
+        args = (x.permute(0, 2, 3, 1).contiguous().to(dev), wt.permute(0, 2, 3, 1).contiguous().to(dev), scale.to(dev),
+                shift.to(dev), None if r is None else r.permute(0, 2, 3, 1).contiguous().to(dev))
+        with ops.tuned(keys):
             y8 = ops.conv2d_bn_act_nhwc(*args, stride=st, pad=pad, relu=True)
-            ops.set_tuning(ops.TUNE_WAVES8, 0)
+        with ops.tuned({**keys, ops.TUNE_WAVES8: 0}):
             y4 = ops.conv2d_bn_act_nhwc(*args, stride=st, pad=pad, relu=True)
-            ops.set_tuning(ops.TUNE_WAVES8, 1)
-            assert rel_err(y8.cpu().permute(0, 3, 1, 2), ref) < TOL and rel_err(y8, y4) < TOL, ci
-        g0 = torch.Generator().manual_seed(9)
-        for m, widths, n_out in [(1792, (2048,), 768), (1792, (256,), 2048), (256, (2048, 2048), 512), (300, (64, 32, 160), 132)]:
-            srcs, cat = [], []
-            for i, wd in enumerate(widths):
-                a = _rand(m, wd, seed=110 + i)
-                srcs.append((a.to(dev), None))
-                cat.append(a)
-            kk = sum(widths)
-            wl, bias, res = _rand(n_out, kk, seed=120, scale=kk ** -0.5), _rand(n_out, seed=121), _rand(m, n_out, seed=122)
-            ref = F.relu(F.linear(torch.cat(cat, 1), wl, bias) + res)
+        assert rel_err(y8.cpu().permute(0, 3, 1, 2), ref) < TOL and rel_err(y8, y4) < TOL, ci
+    g0 = torch.Generator().manual_seed(9)
+    for m, widths, n_out in [(1792, (2048,), 768), (1792, (256,), 2048), (256, (2048, 2048), 512), (300, (64, 32, 160), 132)]:
+        srcs, cat = [], []
+        for i, wd in enumerate(widths):
+            a = _rand(m, wd, seed=110 + i)
+            srcs.append((a.to(dev), None))
+            cat.append(a)
+        kk = sum(widths)
+        wl, bias, res = _rand(n_out, kk, seed=120, scale=kk ** -0.5), _rand(n_out, seed=121), _rand(m, n_out, seed=122)
+        ref = F.relu(F.linear(torch.cat(cat, 1), wl, bias) + res)
+        with ops.tuned(keys):
             out8 = ops.linear_gather(srcs, wl.to(dev), bias.to(dev), m, res.to(dev), True)
-            ops.set_tuning(ops.TUNE_WAVES8, 0)
+        with ops.tuned({**keys, ops.TUNE_WAVES8: 0}):
             out4 = ops.linear_gather(srcs, wl.to(dev), bias.to(dev), m, res.to(dev), True)
-            ops.set_tuning(ops.TUNE_WAVES8, 1)
-            assert rel_err(out8.cpu(), ref) < TOL and rel_err(out8, out4) < TOL, (m, widths, n_out)
-    finally:
-        ops.set_tuning(ops.TUNE_WAVES8, 1)
-        ops.set_tuning(ops.TUNE_TILE, -1)
-        ops.set_tuning(ops.TUNE_STREAMK, 1)
+        assert rel_err(out8.cpu(), ref) < TOL and rel_err(out8, out4) < TOL, (m, widths, n_out)
 
 
 @pytest.mark.parametrize("bk", [16, 32])
@@ -397,40 +379,33 @@ def test_tile_engine_buffer_loaders(dev, bk, tile, streamk):
         (2, 37, 29, 4, 64, 7, 2, 3, False),
         (5, 9, 11, 32, 40, 1, 2, 0, False),
     ]
-    try:
-        ops.set_tuning(ops.TUNE_BK, bk)
-        ops.set_tuning(ops.TUNE_TILE, tile)
-        ops.set_tuning(ops.TUNE_STREAMK, streamk)
-        for ci, (n, h, w, cin, cout, k, st, pad, res) in enumerate(convs):
-            x = _rand(n, cin, h, w, seed=40 + ci)
-            wt = _rand(cout, cin, k, k, seed=50 + ci, scale=(2.0 / (cin * k * k)) ** 0.5)
-            scale = torch.rand(cout, generator=torch.Generator().manual_seed(60 + ci)) + 0.5
-            shift = _rand(cout, seed=70 + ci, scale=0.1)
-            ref = F.conv2d(x, wt, None, stride=st, padding=pad) * scale.view(1, -1, 1, 1) + shift.view(1, -1, 1, 1)
-            r = _rand(*ref.shape, seed=80 + ci) if res else None
-            if res:
-                ref = ref + r
-            ref = F.relu(ref)
-            args = (x.permute(0, 2, 3, 1).contiguous().to(dev), wt.permute(0, 2, 3, 1).contiguous().to(dev), scale.to(dev),
-                    shift.to(dev), None if r is None else r.permute(0, 2, 3, 1).contiguous().to(dev))
+    keys = {ops.TUNE_BK: bk, ops.TUNE_TILE: tile, ops.TUNE_STREAMK: streamk}
+    for ci, (n, h, w, cin, cout, k, st, pad, res) in enumerate(convs):
+        x = _rand(n, cin, h, w, seed=40 + ci)
+        wt = _rand(cout, cin, k, k, seed=50 + ci, scale=(2.0 / (cin * k * k)) ** 0.5)
+        scale = torch.rand(cout, generator=torch.Generator().manual_seed(60 + ci)) + 0.5
+        shift = _rand(cout, seed=70 + ci, scale=0.1)
+        ref = F.conv2d(x, wt, None, stride=st, padding=pad) * scale.view(1, -1, 1, 1) + shift.view(1, -1, 1, 1)
+        r = _rand(*ref.shape, seed=80 + ci) if res else None
+        if res:
+            ref = ref + r
+        ref = F.relu(ref)
+        args = (x.permute(0, 2, 3, 1).contiguous().to(dev), wt.permute(0, 2, 3, 1).contiguous().to(dev), scale.to(dev),
+                shift.to(dev), None if r is None else r.permute(0, 2, 3, 1).contiguous().to(dev))
+        with ops.tuned(keys):
             y = ops.conv2d_bn_act_nhwc(*args, stride=st, pad=pad, relu=True)
-            assert rel_err(y.cpu().permute(0, 3, 1, 2), ref) < TOL, (ci, "vs torch")
-            ops.set_tuning(ops.TUNE_FAST_LOADER, 0)
+        assert rel_err(y.cpu().permute(0, 3, 1, 2), ref) < TOL, (ci, "vs torch")
+        with ops.tuned({**keys, ops.TUNE_FAST_LOADER: 0}):
             y0 = ops.conv2d_bn_act_nhwc(*args, stride=st, pad=pad, relu=True)
-            ops.set_tuning(ops.TUNE_FAST_LOADER, 1)
-            assert rel_err(y.cpu(), y0.cpu()) < TOL, (ci, "vs general loader")
-        m, widths, n_out = 333, (64, 96), 100              # K = 160: segments are multiples of 32
-        srcs = [(_rand(m, wd, seed=90 + i).to(dev), None) for i, wd in enumerate(widths)]
-        k = sum(widths)
-        wl, bias, res = _rand(n_out, k, seed=95, scale=k ** -0.5), _rand(n_out, seed=96), _rand(m, n_out, seed=97)
-        ref = F.relu(F.linear(torch.cat([a.cpu() for a, _ in srcs], 1), wl, bias) + res)
+        assert rel_err(y.cpu(), y0.cpu()) < TOL, (ci, "vs general loader")
+    m, widths, n_out = 333, (64, 96), 100              # K = 160: segments are multiples of 32
+    srcs = [(_rand(m, wd, seed=90 + i).to(dev), None) for i, wd in enumerate(widths)]
+    k = sum(widths)
+    wl, bias, res = _rand(n_out, k, seed=95, scale=k ** -0.5), _rand(n_out, seed=96), _rand(m, n_out, seed=97)
+    ref = F.relu(F.linear(torch.cat([a.cpu() for a, _ in srcs], 1), wl, bias) + res)
+    with ops.tuned(keys):
         out = ops.linear_gather(srcs, wl.to(dev), bias.to(dev), m, res.to(dev), True)
-        assert rel_err(out.cpu(), ref) < TOL
-    finally:
-        ops.set_tuning(ops.TUNE_BK, 0)
-        ops.set_tuning(ops.TUNE_TILE, -1)
-        ops.set_tuning(ops.TUNE_STREAMK, 1)
-        ops.set_tuning(ops.TUNE_FAST_LOADER, 1)
+    assert rel_err(out.cpu(), ref) < TOL
 
 
 @pytest.mark.parametrize("sizes,k,d", [((8, 8, 8), 4, 2048), ((8, 9, 3, 1), 4, 64), ((40,), 7, 128)])
@@ -483,12 +458,9 @@ def test_conv3x3_winograd(dev, n, h, w, cin, cout, res, relu, kernel):
                       [1 / 24, -1 / 12, 1 / 6], [0, 0, 1]], dtype=torch.float64)
     u_ref = torch.einsum("xj,ohjc->xohc", G, wt.permute(0, 2, 3, 1).double()).float()
     assert torch.allclose(u.cpu(), u_ref, rtol=2e-7, atol=1e-9)
-    ops.set_tuning(ops.TUNE_WINOGRAD, kernel)          # 2: the 4-wave / 64-tile kernel, 3: the 8-wave / 128-tile one
-    try:
+    with ops.tuned({ops.TUNE_WINOGRAD: kernel}):          # 2: the 4-wave / 64-tile kernel, 3: the 8-wave / 128-tile one
         y = ops.conv3x3_wino43_bn_act_nhwc(x.permute(0, 2, 3, 1).contiguous().to(dev), u, scale.to(dev), shift.to(dev),
                                            None if r is None else r.permute(0, 2, 3, 1).contiguous().to(dev), relu=relu)
-    finally:
-        ops.set_tuning(ops.TUNE_WINOGRAD, 1)
     err = rel_err(y.cpu().permute(0, 3, 1, 2), ref)
     assert err < 2e-5, err
 
@@ -521,15 +493,8 @@ def test_conv3x3_winograd_persistent(dev, n, h, w, cin, cout, res):
     out = {}
     for persist in (1, 0):
         for split in (1, 0):
-            ops.set_tuning(ops.TUNE_WINOGRAD, 3)
-            ops.set_tuning(ops.TUNE_WINO_PERSIST, persist)
-            ops.set_tuning(ops.TUNE_WINO_SPLIT, split)
-            try:
+            with ops.tuned({ops.TUNE_WINOGRAD: 3, ops.TUNE_WINO_PERSIST: persist, ops.TUNE_WINO_SPLIT: split}):
                 out[(persist, split)] = ops.conv3x3_wino43_bn_act_nhwc(xd, u, scale.to(dev), shift.to(dev), rd, relu=True).cpu()
-            finally:
-                ops.set_tuning(ops.TUNE_WINOGRAD, 1)
-                ops.set_tuning(ops.TUNE_WINO_PERSIST, 1)
-                ops.set_tuning(ops.TUNE_WINO_SPLIT, 1)
     for k, y in out.items():
         e = rel_err(y.permute(0, 3, 1, 2), ref)
         assert e < 2e-5, (k, e)
@@ -656,13 +621,11 @@ def test_composites_run_in_exactly_their_workspace(dev, composite_model, entry):
 
 
 # ---- in-kernel combine of split-K / stream-K partial tiles (round 4) ------------------------------------------------------
-def _with_fixup_mode(mode, fn):
+def _with_fixup_mode(mode, fn, keys=None):
+    """fn() under RPG_TUNE_INKERNEL_FIXUP = mode and the other ``keys`` (ops.tuned blocks do not nest: one block names every key)."""
     from relpose_gnn_amd import ops
-    ops.set_tuning(ops.TUNE_INKERNEL_FIXUP, mode)
-    try:
+    with ops.tuned({**(keys or {}), ops.TUNE_INKERNEL_FIXUP: mode}):
         return fn()
-    finally:
-        ops.set_tuning(ops.TUNE_INKERNEL_FIXUP, 0)
 
 
 @pytest.mark.parametrize("n,h,c,res", [
@@ -689,13 +652,9 @@ def test_winograd_split_parts_combined_by_last_arriver(dev, n, h, c, res):
     nh = lambda t: None if t is None else t.permute(0, 2, 3, 1).contiguous().to(dev)
     u = ops.wino43_transform_weights(nh(wt))
     xd, rd, sc, sh = nh(x), nh(r), scale.to(dev), shift.to(dev)
-    ops.set_tuning(ops.TUNE_WINOGRAD, 3)
-    try:
-        run = lambda: ops.conv3x3_wino43_bn_act_nhwc(xd, u, sc, sh, rd, relu=True)
-        y_launch = _with_fixup_mode(0, run)
-        outs = {mode: [_with_fixup_mode(mode, run) for _ in range(6 if mode == 2 else 3)] for mode in (2, 6)}
-    finally:
-        ops.set_tuning(ops.TUNE_WINOGRAD, 1)
+    run, wave8 = lambda: ops.conv3x3_wino43_bn_act_nhwc(xd, u, sc, sh, rd, relu=True), {ops.TUNE_WINOGRAD: 3}
+    y_launch = _with_fixup_mode(0, run, wave8)
+    outs = {mode: [_with_fixup_mode(mode, run, wave8) for _ in range(6 if mode == 2 else 3)] for mode in (2, 6)}
     assert rel_err(y_launch.cpu().permute(0, 3, 1, 2), ref) < 2e-5
     for mode, ys in outs.items():
         assert all(torch.equal(y, ys[0]) for y in ys[1:]), f"mode {mode}: not deterministic"
@@ -759,12 +718,9 @@ def test_linear_exact_fit_112_row_tiles(dev, m, k, n_out, res, relu):
     if relu:
         ref = F.relu(ref)
     outs = {}
-    try:
-        for mode in (3, 1, 0):                               # eight-wave form where about one tile per CU / four-wave form only / engine
-            ops.set_tuning(ops.TUNE_LIN112, mode)
+    for mode in (3, 1, 0):                                   # eight-wave form where about one tile per CU / four-wave form only / engine
+        with ops.tuned({ops.TUNE_LIN112: mode}):
             outs[mode] = ops.linear_gather([(a.to(dev), None)], wt.to(dev), bias.to(dev), m, None if r is None else r.to(dev), relu).cpu()
-    finally:
-        ops.set_tuning(ops.TUNE_LIN112, 3)
     for mode in (3, 1, 0):
         assert rel_err(outs[mode], ref) < TOL, (mode, rel_err(outs[mode], ref))
     assert rel_err(outs[1], outs[0]) < TOL and rel_err(outs[3], outs[0]) < TOL
@@ -789,21 +745,44 @@ def test_linear_exact_fit_112_epilogue_and_strided_a(dev, m, nodes, k, pad_a, pa
     i2 = torch.randint(0, nodes, (m,), generator=g)
     pre = F.linear(a_wide[:, :k], wt, bias) + r1[i1, :n_out] + r2[i2, :n_out]
     outs = {}
-    try:
-        for mode in (3, 1, 0):
-            ops.set_tuning(ops.TUNE_LIN112, mode)
+    for mode in (3, 1, 0):
+        with ops.tuned({ops.TUNE_LIN112: mode}):
             for relu in (False, True):
                 o, o_relu = ops.linear_gather_ex([(a_wide.to(dev), None)], wt.to(dev), bias.to(dev), m, r1.to(dev), i1.to(dev), r2.to(dev),
                                                  i2.to(dev), relu=relu, want_relu_copy=True, widths=[k])
                 outs[(mode, relu)] = (o.cpu(), o_relu.cpu())
-    finally:
-        ops.set_tuning(ops.TUNE_LIN112, 3)
     for (mode, relu), (o, o_relu) in outs.items():
         want = F.relu(pre) if relu else pre
         assert rel_err(o, want) < TOL, (mode, relu, rel_err(o, want))
         assert torch.equal(o_relu, F.relu(o)) or rel_err(o_relu, F.relu(pre)) < TOL, (mode, relu)
-    # plain (un-gathered) residual through the same entry point == rpg_linear_gather_f32
-    ops.set_tuning(ops.TUNE_LIN112, 3)
+    # plain (un-gathered) residual through the same entry point == rpg_linear_gather_f32 (at the default tuning)
     res = _rand(m, n_out, seed=47)
     o = ops.linear_gather_ex([(a_wide.to(dev), None)], wt.to(dev), bias.to(dev), m, res.to(dev), relu=True, widths=[k]).cpu()
     assert rel_err(o, F.relu(F.linear(a_wide[:, :k], wt, bias) + res)) < TOL
+
+
+def test_tuned_block_sets_its_keys_and_leaves_every_default(dev):
+    """ops.tuned on the 64 x 72 -> 40 Linear: inside the block the launcher records the forced 64 x 64 tile and no split; a ValueError
+    raised inside it still leaves every key at its default (read back through rpg_get_tuning); the same launch afterwards records
+    the automatic route it recorded before the block."""
+    from relpose_gnn_amd import ops
+    m, k, n_out = 64, 72, 40
+    a, wt, bias = _rand(m, k, seed=61).to(dev), _rand(n_out, k, seed=62, scale=k ** -0.5).to(dev), _rand(n_out, seed=63).to(dev)
+
+    def launch():
+        out = ops.linear_gather([(a, None)], wt, bias, m, None, False)
+        return out, ops.gemm_last_route()
+    ref = F.linear(a.cpu(), wt.cpu(), bias.cpu())
+    out0, auto = launch()
+    with pytest.raises(ValueError, match="stop"):
+        with ops.tuned({"TILE": 2, "STREAMK": 0}):
+            assert ops.get_tuning("TILE") == 2 and ops.get_tuning(ops.TUNE_STREAMK) == 0
+            out1, forced = launch()
+            raise ValueError("stop")
+    assert (forced["kernel"], forced["BM"], forced["BN"]) == ("tile", 64, 64), forced
+    assert (forced["g_sk"], forced["rem"], forced["combine"]) == (0, 0, "none") and forced["t_dp"] == forced["tiles"], forced
+    for key, name in enumerate(ops.TUNING_KEYS):
+        assert ops.get_tuning(key) == ops.tuning_default(key), name
+    out2, after = launch()
+    assert after == auto, (after, auto)
+    assert rel_err(out0.cpu(), ref) < TOL and rel_err(out1.cpu(), ref) < TOL and torch.equal(out2, out0)

@@ -129,24 +129,18 @@ def test_query_forward_irregular(dev, irr, qset, recursion):
 def test_query_forward_irregular_other_formulations(dev, irr, split, fuse_agg):
     """The 22-tensor formulation and the unfused aggregation, as tests/test_hip_graph_sweep.py switches them."""
     from relpose_gnn_amd import ops
-    ops.set_tuning(ops.TUNE_GNN_SPLIT, split)
-    ops.set_tuning(ops.TUNE_GNN_FUSE_AGG, fuse_agg)
-    try:
+    with ops.tuned({ops.TUNE_GNN_SPLIT: split, ops.TUNE_GNN_FUSE_AGG: fuse_agg}):
         for qset in ("first", "largest"):
             got = _run_query(dev, irr, qset, 2)
             torch.cuda.synchronize()
             _against_oracles(f"{qset} R=2 split={split} fuse_agg={fuse_agg}", irr, qset, 2, got)
-    finally:
-        ops.set_tuning(ops.TUNE_GNN_SPLIT, 1)
-        ops.set_tuning(ops.TUNE_GNN_FUSE_AGG, 1)
 
 
 @pytest.mark.parametrize("fuse_agg", [1, 0])
 @pytest.mark.parametrize("recursion", [1, 2])
 def test_query_forward_irregular_bf16_linears(dev, irr, recursion, fuse_agg):
     from relpose_gnn_amd import ops
-    ops.set_tuning(ops.TUNE_GNN_FUSE_AGG, fuse_agg)
-    try:
+    with ops.tuned({ops.TUNE_GNN_FUSE_AGG: fuse_agg}):
         for qset in ("first", "largest", "all"):
             got = _run_query(dev, irr, qset, recursion, bf16=True)
             torch.cuda.synchronize()
@@ -155,8 +149,6 @@ def test_query_forward_irregular_bf16_linears(dev, irr, recursion, fuse_agg):
             er = rel_err(got[1].cpu(), r32[irr["sel"][qset]])
             _record("query_forward_bf16", f"{qset} R={recursion} fuse_agg={fuse_agg}", {"abs": ea, "rel": er})
             assert ea < TOL_BF16 and er < TOL_BF16, (qset, ea, er)
-    finally:
-        ops.set_tuning(ops.TUNE_GNN_FUSE_AGG, 1)
 
 
 def test_query_rows_are_the_full_forwards_rows(dev, irr):

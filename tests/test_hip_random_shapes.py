@@ -128,12 +128,9 @@ def test_random_conv_winograd(dev, case, kernel):
     if relu:
         ref = F.relu(ref)
     u = ops.wino43_transform_weights(wt.permute(0, 2, 3, 1).contiguous().to(dev))
-    ops.set_tuning(ops.TUNE_WINOGRAD, kernel)          # both Winograd kernels on every shape (1 = choose by size)
-    try:
+    with ops.tuned({ops.TUNE_WINOGRAD: kernel}):          # both Winograd kernels on every shape (1 = choose by size)
         y = ops.conv3x3_wino43_bn_act_nhwc(x.permute(0, 2, 3, 1).contiguous().to(dev), u, scale.to(dev), shift.to(dev),
                                            None if r is None else r.permute(0, 2, 3, 1).contiguous().to(dev), relu=relu)
-    finally:
-        ops.set_tuning(ops.TUNE_WINOGRAD, 1)
     assert rel_err(y.cpu().permute(0, 3, 1, 2), ref) < 2e-5, (cin, cout, n, h, w)
 
 
@@ -214,13 +211,10 @@ def test_random_stem_bf16_strips(dev, case):
     shift = _rand(64, seed=case + 3, scale=0.3)
     conv = F.conv2d(x.bfloat16().float(), wt.bfloat16().float(), None, stride=2, padding=3)
     ref = F.max_pool2d(F.relu(conv * scale.view(1, -1, 1, 1) + shift.view(1, -1, 1, 1)), 3, 2, 1).bfloat16().float()
-    ops.set_tuning(ops.TUNE_FUSED_STEM, variant)
-    try:
+    with ops.tuned({ops.TUNE_FUSED_STEM: variant}):
         wp = pack_stem_bf16(wt).to(dev)
         y = ops.stem_conv_bn_relu_maxpool_bf16(x.to(dev), wp, scale.to(dev), shift.to(dev))
         y16 = ops.stem_conv_bn_relu_maxpool_bf16(x.bfloat16().to(dev), wp, scale.to(dev), shift.to(dev))
-    finally:
-        ops.set_tuning(ops.TUNE_FUSED_STEM, 1)
     got = y.float().cpu().permute(0, 3, 1, 2)
     assert got.shape == ref.shape and torch.equal(y, y16), (n, h, w, variant)
     assert rel_err(got, ref) < 1e-2, (n, h, w, variant)

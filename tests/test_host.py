@@ -33,7 +33,9 @@ def test_library_exports_every_declared_symbol():
 
 def test_tuning_and_timer_constants_match_the_header():
     """ops.TUNE_* and the timer classes are the header's #defines (they are passed across the ABI as plain ints), and
-    rpg_set_tuning validates keys / values on the host side (no GPU involved)."""
+    rpg_set_tuning validates keys / values on the host side (no GPU involved).  rpg_get_tuning reads every key back: its default
+    before any set, the value as passed after a set, the default again after ops.reset_tuning(); the test ends in the default state
+    (the defaults themselves are pinned by tests/tuning_check.cpp)."""
     from relpose_gnn_amd import _lib, ops
     hdr = open(os.path.join(ROOT, "include", "relpose_gnn_hip.h")).read()
     defs = {k: int(v) for k, v in re.findall(r"#define\s+(RPG_[A-Z0-9_]+)\s+(-?\d+)\b", hdr)}
@@ -43,12 +45,38 @@ def test_tuning_and_timer_constants_match_the_header():
         assert getattr(ops, "TUNE_" + name) == key, name
     assert {k for k in dir(ops) if k.startswith("TUNE_")} == {"TUNE_" + k for k in tune}
     lib = _lib.lib()
+    accepts_any = {"TILE", "EPILOGUE", "STREAMK", "GNN_SPLIT", "FAST_LOADER", "BF16_FAST", "FUSED_STEM", "WAVES8", "GNN_FUSE_AGG",
+                   "BF16_LEAN_EPI", "BF16_PERSIST", "BF16_FUSE_BLOCK", "FIXUP_PRIO", "BF16_PAIR"}      # flags and masked keys: no value is refused
     assert lib.rpg_set_tuning(12345, 0) == _lib.RPG_ERR_BAD_ARG       # unknown key
     assert lib.rpg_set_tuning(defs["RPG_TUNE_BK"], 24) == _lib.RPG_ERR_BAD_ARG
     assert lib.rpg_set_tuning(defs["RPG_TUNE_WINOGRAD"], 7) == _lib.RPG_ERR_BAD_ARG
-    for name, key in tune.items():                                    # defaults are accepted and restore the defaults
-        default = {"TILE": -1, "BK": 0, "BF16_BK": 32, "WINO_SHORT": 0, "BF16_TILE": -1, "BF16_WS64": 0, "SK_MIN_ITS": 8, "INKERNEL_FIXUP": 0, "BF16_CHUNK": 0, "WINO2D": 0, "BF16_LINEAR_DMA": 0, "BF16_PERSIST": 0, "FOLD_K": 256, "LIN112": 3}.get(name, 1)
-        assert lib.rpg_set_tuning(key, default) == 0, name
+    # read-back: the default before any set, the value as passed after a set, the default again after ops.reset_tuning()
+    ops.reset_tuning()
+    probe = {"BK": 16, "BF16_BK": 64, "WINOGRAD": 40, "WINO_SPLIT": 96, "FUSED_STEM": 129 | (5 << 8), "BF16_PATCH": 14, "SK_MIN_ITS": 4096,
+             "BF16_CHUNK": 8 | (128 << 12), "BF16_LINEAR_DMA": 12, "FOLD_K": 64, "BF16_FUSE_BLOCK": 11, "BF16_WS64": 0, "WINO2D": 0}
+    assert list(ops.TUNING_KEYS) == [name for name, _ in sorted(tune.items(), key=lambda kv: kv[1])]
+    for name, key in tune.items():
+        default = ops.tuning_default(key)
+        assert ops.get_tuning(key) == default == ops.tuning_default(name) == ops.get_tuning("TUNE_" + name), name
+        value = probe.get(name, 0 if default else 1)
+        ops.set_tuning(key, value)
+        assert ops.get_tuning(key) == value, name
+        assert lib.rpg_set_tuning(key, -7) == (0 if name in accepts_any else _lib.RPG_ERR_BAD_ARG), name
+        assert ops.get_tuning(key) == (-7 if name in accepts_any else value), name            # a refused value changes nothing
+    ops.reset_tuning()
+    for name, key in tune.items():
+        assert ops.get_tuning(key) == ops.tuning_default(key), name
+    assert lib.rpg_get_tuning(12345, None, None) == lib.rpg_get_tuning(-1, None, None) == _lib.RPG_ERR_BAD_ARG
+    assert lib.rpg_get_tuning(0, None, None) == _lib.RPG_OK
+    # ops.tuned: the keys hold inside the block; afterwards EVERY key is at its default, also when a set is refused half-way
+    with ops.tuned({"FIXUP_PRIO": 1, ops.TUNE_BF16_FUSE_BLOCK: 1}):
+        assert ops.get_tuning("FIXUP_PRIO") == 1 and ops.get_tuning("BF16_FUSE_BLOCK") == 1
+        ops.set_tuning(ops.TUNE_TILE, 2)
+    with pytest.raises(ValueError):
+        with ops.tuned({"STREAMK": 0, "BK": 24}):
+            raise AssertionError("entered with a refused key")
+    for name, key in tune.items():
+        assert ops.get_tuning(key) == ops.tuning_default(key), name
     # the weights-stationary probe kernel is not part of the product library (tools/probes/conv3x3_bf16_ws64.inc)
     assert lib.rpg_set_tuning(defs["RPG_TUNE_BF16_WS64"], 1) == _lib.RPG_ERR_BAD_ARG
     # ... and neither is the nested 2-D Winograd kernel (tools/probes/winograd2d.hip)
@@ -334,17 +362,47 @@ def test_workspace_size_functions_return_what_they_always_did():
         assert lib.rpg_gnn_query_workspace_bytes(*bad) == 0, bad
 
 
-def test_composite_plan_header_stands_alone(tmp_path):
-    """tests/composite_plan_check.cpp includes nothing of the project but csrc/composite_plan.h: the host compiler alone builds it
-    (the header needs no HIP).  It carves every buffer set into a host buffer of exactly the dry run's size, tags every buffer over
-    its full extent, re-reads the tags (overlap), checks alignment and bounds, and walks ResnetWalk against plain nested loops."""
+def test_set_tuning_accepts_what_it_always_did():
+    """tests/tuning_accepted.json: for every key, the values among -3 .. 4100, (64 << 12) | 8, 1 << 20, INT_MAX and INT_MIN that
+    rpg_set_tuning accepted BEFORE the keys moved into csrc/tuning.h, recorded from a build of that commit as closed intervals.
+    The table's predicates must give the same answer for every key and value."""
+    import json
+    from relpose_gnn_amd import _lib, ops
+    lib = _lib.lib()
+    accepted = json.load(open(os.path.join(ROOT, "tests", "tuning_accepted.json")))
+    assert list(accepted) == list(ops.TUNING_KEYS)
+    values = list(range(-3, 4101)) + [1 << 12, (64 << 12) | 8, 1 << 20, 2 ** 31 - 1, -2 ** 31]
+    try:
+        for name, intervals in accepted.items():
+            key = getattr(ops, "TUNE_" + name)
+            for v in values:
+                want = any(lo <= v <= hi for lo, hi in intervals)
+                assert (lib.rpg_set_tuning(key, v) == _lib.RPG_OK) == want, (name, v)
+    finally:
+        ops.reset_tuning()
+
+
+def _build_and_run_host_check(tmp_path, name):
     import shutil
     import subprocess
     cxx = os.environ.get("CXX") or shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
     assert cxx, "no host C++ compiler"
-    exe = str(tmp_path / "composite_plan_check")
+    exe = str(tmp_path / name)
     subprocess.run([cxx, "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-o", exe,
-                    os.path.join(ROOT, "tests", "composite_plan_check.cpp")], check=True)
+                    os.path.join(ROOT, "tests", name + ".cpp")], check=True)
     r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stdout + r.stderr
-    assert "composite_plan: ok" in r.stdout
+    return r.stdout
+
+
+def test_tuning_header_stands_alone(tmp_path):
+    """tests/tuning_check.cpp includes nothing of the project but csrc/tuning.h (which needs the C header and no HIP): every key's
+    raw default against a list of its own, the decoded default state field by field, and the packed keys' decoding at chosen values."""
+    assert "tuning: ok (32 keys)" in _build_and_run_host_check(tmp_path, "tuning_check")
+
+
+def test_composite_plan_header_stands_alone(tmp_path):
+    """tests/composite_plan_check.cpp includes nothing of the project but csrc/composite_plan.h: the host compiler alone builds it
+    (the header needs no HIP).  It carves every buffer set into a host buffer of exactly the dry run's size, tags every buffer over
+    its full extent, re-reads the tags (overlap), checks alignment and bounds, and walks ResnetWalk against plain nested loops."""
+    assert "composite_plan: ok" in _build_and_run_host_check(tmp_path, "composite_plan_check")

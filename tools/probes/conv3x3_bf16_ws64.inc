@@ -266,7 +266,7 @@ __global__ __launch_bounds__(256) void conv3x3_bf16_ws64_kernel(Ws64Args a, cons
 }
 
 
-int g_bf16_ws64 = 0;     // RPG_TUNE_BF16_WS64: the weights-stationary kernel for 64 -> 64 channel 3x3 convolutions: 0 off (default: not faster, see the kernel) | 1: 384-pixel tiles | 2: 256
+// rpg::tuning().bf16.ws64 (RPG_TUNE_BF16_WS64): the weights-stationary kernel for 64 -> 64 channel 3x3 convolutions: 0 off (default: not faster, see the kernel) | 1: 384-pixel tiles | 2: 256
 
 // The weights-stationary kernel, if the shape is eligible (3x3, stride 1, pad 1, 64 -> 64 channels, plain bf16 epilogue)
 template <int FM>

@@ -360,13 +360,9 @@ __global__ __launch_bounds__(256) void wino2d_weights_kernel(const float* __rest
     }
 }
 
-int g_wino2d = 0;                          // RPG_TUNE_WINO2D: 0 off (default: measured slower) | 1 by shape | 2 wherever eligible
-
 }  // namespace w2d
 
 namespace rpg {
-
-void wino2d_set(int v) { w2d::g_wino2d = v; }
 
 // floats of the transformed-weight buffer of one convolution: the 1-D image [6][Cout][3][Cin] followed by the nested one
 // [24][Cout][Cin] (both are written by rpg_wino43_transform_weights_f32; the launcher picks per shape)
@@ -381,14 +377,15 @@ int launch_wino2d_weights(const float* w_ohwi, float* u2, int cout, int cin, hip
 
 // true if the nested kernel takes this convolution (eligible, enabled, and measured faster for the shape class)
 bool wino2d_takes(int n, int h, int w, int cin, int cout) {
-    if (!w2d::g_wino2d || (cin % w2d::KS) || (cout % w2d::TC)) return false;
+    // tuning().wino.wino2d (RPG_TUNE_WINO2D): 0 off (default: measured slower) | 1 by shape | 2 wherever eligible
+    if (!tuning().wino.wino2d || (cin % w2d::KS) || (cout % w2d::TC)) return false;
     const int h2 = (h + 1) / 2, tw = (w + 3) / 4;
     const long M = (long)n * h2 * tw;
     // 32-bit buffer offsets: a workgroup's 64 tiles span at most 64 / (h2 tw) + 2 images; U2 is addressed from its base
     if (M >= (1L << 31) || (64L / ((long)h2 * tw) + 2) * h * w * (cin > cout ? cin : cout) * 4 >= (1L << 31) ||
         24L * cout * cin * 4 >= (1L << 31))
         return false;
-    if (w2d::g_wino2d >= 2) return true;
+    if (tuning().wino.wino2d >= 2) return true;
     const long tiles = ((M + w2d::TT - 1) / w2d::TT) * (cout / w2d::TC);
     return tiles >= 2L * num_cus() && h >= 8;   // enough workgroups to fill the chip twice; 7 x 7 maps pad 64 / 49
 }
