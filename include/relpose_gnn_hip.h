@@ -356,6 +356,17 @@ int rpg_scatter_mean_f32(const float* msg, const int32_t* rowptr, const int32_t*
 int rpg_attention_aggregate_f32(const float* gtp, const float* msg, const int32_t* rowptr, const int32_t* perm,
                                 const float* bias, int n, int e, int c, int d, float* ybar, float* mbar, void* stream);
 
+/* The same kernel for the mean-first formulation of rpg_gnn_forward_f32: `hid` [e][d] holds the message MLP's hidden rows
+ * relu(mlp.0(.)) instead of the messages, and the bias is kept apart so that the Linear behind it cannot put it on an isolated node:
+ *   ybar[v][i] = as above                                                                                    [n][c]
+ *   hbar[v][:] = mean_{e -> v} hid[e][:]         (bit-exact rpg_scatter_mean_f32 of hid: the same order)     [n][d]
+ *   res[v][:]  = bias[:] if the node has an incoming edge, else zeros      (bias [d], required)              [n][d]
+ * The composite forward then runs ONE n-row Linear, agg = [hbar ; ybar] cat(W_mlp2, W_att)^T + res, without a bias operand: a node
+ * without incoming edges has hbar = ybar = res = 0 and gets agg = 0 exactly.  Shapes and limits as rpg_attention_aggregate_f32.  */
+int rpg_attention_aggregate_hidden_f32(const float* gtp, const float* hid, const int32_t* rowptr, const int32_t* perm,
+                                       const float* bias, int n, int e, int c, int d, float* ybar, float* hbar, float* res,
+                                       void* stream);
+
 /* Two 3-output Linear heads on the same rows, concatenated: out[r][0:3] = x W1^T + b1,
  * out[r][3:6] = x W2^T + b2 (posenet.py:1077-1091).  w6 [6][d] = cat(W1, W2), b6 [6].           */
 int rpg_pose_heads_f32(const float* x, const float* w6, const float* b6, int r, int d, float* out, void* stream);
@@ -363,7 +374,18 @@ int rpg_pose_heads_f32(const float* x, const float* w6, const float* b6, int r, 
 /* Everything after the encoder for use_gnn=True, use_AP=True, knn<=0 (posenet.py:1052-1091).
  * `tensors` HOST array of device pointers, order in params.py: 22 tensors (reference formulation) or 26 (adds the
  * node/edge column blocks of proj_edge, edge_mlp.0 and mlp.0 as separate matrices, which lets the node terms be
- * computed once per node and gathered in the edge GEMM epilogues).
+ * computed once per node and gathered in the edge GEMM epilogues), or 30 (adds four more, which let the fp32 forward take the
+ * mean over a node's incoming edges BEFORE the message MLP's second Linear instead of after it; c = d / 8):
+ *   tensors[26] [3c][d]      W_gtp W_mlp2, the product evaluated in float64 and rounded once
+ *   tensors[27] [3c]         W_gtp b_mlp2 + b_gtp, likewise
+ *   tensors[28] [d][d + c]   cat(W_mlp2, W_att) along the input dimension
+ *   tensors[29] [d]          b_att + b_mlp2
+ * mlp.2 has no activation behind it and its output is read only by g|theta|phi (a Linear) and by the mean, so
+ *   gtp_k = (W_gtp W_mlp2) h_k + (W_gtp b_mlp2 + b_gtp),   agg_i = W_mlp2 hbar_i + W_att ybar_i + (b_att + b_mlp2)   (in-degree > 0)
+ * with h_k = relu(mlp.0(.)) of edge k and hbar_i / ybar_i the means over the edges into node i: the e-row Linear mlp.2 goes away and
+ * att.W becomes one n-row Linear over [hbar ; ybar] (rpg_attention_aggregate_hidden_f32).  Rounding changes, nothing else.  Used by
+ * the fp32 forwards (the query-only one too) with RPG_TUNE_GNN_FUSE_AGG = 1; the bf16 forwards accept the 30-tensor table and keep
+ * the 26-tensor formulation.
  * feat [n][d], edge rows src[e] / dst[e] with node_offset (see rpg_graph_prepare) -> abs_pose [n][6], rel_pose [e][6].
  * node_out [n][d] / edge_out [e][d]: optional (NULL to skip) copies of the final ReLU'd node and
  * edge features, i.e. the inputs of the heads; the host mirror uses them to apply the reference's
@@ -495,7 +517,9 @@ int rpg_probe_mfma_bf16(const void* operands, long iters, int workgroups, float*
 #define RPG_TUNE_BF16_BK 6        /* K step of the bf16 convolution kernel: 32 (default) | 64 */
 #define RPG_TUNE_BF16_FAST 9      /* 1: interleaved buffer-load bf16 conv kernel where Cin % 64 == 0 (default) | 0: general kernel */
 #define RPG_TUNE_GNN_FUSE_AGG 13  /* 1: attention rows + mean aggregation in one kernel, att.W on node rows (default) | 0: per-edge
-                                     attention rows, att.W on edge rows, separate scatter-mean (the reference's order) */
+                                     attention rows, att.W on edge rows, separate scatter-mean (the reference's order).  With the 30-tensor
+                                     table the fp32 forward also takes the mean BEFORE mlp.2 (see rpg_gnn_forward_f32): 2 = as 1, but
+                                     mlp.2 stays on the edge rows (the 26-tensor formulation, for A/B in one binary).  Any other value: 1. */
 #define RPG_TUNE_WAVES8 11        /* 1: 8-wave workgroups (two waves per SIMD) for the 128x128 / 128x64 tiles of the f32 tile engine where
                                      the buffer-load path applies (default) | 0: always 4-wave workgroups */
 #define RPG_TUNE_FUSED_STEM 10    /* bit 0: one-kernel stem (conv7x7 + BN + ReLU + max-pool) where its operands are given (default 1) | 0: three kernels.

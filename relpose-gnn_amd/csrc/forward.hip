@@ -115,7 +115,13 @@ enum GnnTensor {
     T_NODE3_W,             // [3D][D]  = rows cat(edge_mlp.0.W[:, :D], edge_mlp.0.W[:, D:2D], mlp.0.W[:, :D])
     T_EDGE0E_W,            // [D][D]   = edge_mlp.0.W[:, 2D:]
     T_MSG0E_W,             // [D][D]   = mlp.0.W[:, D:]
-    T_COUNT_SPLIT
+    T_COUNT_SPLIT,
+    // optional products / concatenations around mlp.2 (enable the mean-first message path of layers_general; c = D / 8):
+    T_GTPM_W = T_COUNT_SPLIT,   // [3c][D]     = att.gtp.W mlp.2.W (float64 product, rounded once); T_GTPM_B follows it as a bias does
+    T_GTPM_B,                   // [3c]        = att.gtp.W mlp.2.b + att.gtp.b
+    T_MSG2ATT_W,                // [D][D + c]  = cat(mlp.2.W, att.W.W) along the input dimension
+    T_MSG2ATT_B,                // [D]         = att.W.b + mlp.2.b: the residual row of nodes with incoming edges, never a bias operand
+    T_COUNT_MEAN
 };
 
 // The query-only output mode (rpg_gnn_forward_query_*): the selection.  The pruned last recursion reuses the buffers of
@@ -157,6 +163,7 @@ struct GnnCall {
     const void* const* wb;
     int n, e, d, c, recursion;           // c = d / 8, the width of the attention vector
     bool split;                          // the concatenated-input Linears run in their node / edge split form
+    bool mean_first;                     // fp32, fused aggregation: mlp.2 runs behind the mean (needs T_COUNT_MEAN tensors)
     const QuerySel* qs;                  // null: full outputs
     int es, nq;                          // qs ? its e_sel, q : 0
     hipStream_t s;
@@ -171,7 +178,7 @@ struct GnnCall {
 int prepare(GnnCall& k, const float* const* tensors, int n_tensors, const void* const* wb, const float* feat, const int64_t* esrc,
             const int64_t* edst, int n, int e, int d, int gnn_recursion, const float* abs_pose, const float* rel_pose, const int32_t* status,
             void* workspace, size_t workspace_bytes, size_t scratch_bytes, void* stream, const QuerySel* qs) {
-    if (!tensors || (n_tensors != T_COUNT && n_tensors != T_COUNT_SPLIT) || !feat || !esrc || !edst || !abs_pose || !rel_pose || !status || !workspace ||
+    if (!tensors || (n_tensors != T_COUNT && n_tensors != T_COUNT_SPLIT && n_tensors != T_COUNT_MEAN) || !feat || !esrc || !edst || !abs_pose || !rel_pose || !status || !workspace ||
         n <= 0 || e <= 0 || d <= 0 || (d & 31) || gnn_recursion < 0)
         return RPG_ERR_BAD_ARG;
     for (int i = 0; i < n_tensors; ++i)
@@ -183,7 +190,8 @@ int prepare(GnnCall& k, const float* const* tensors, int n_tensors, const void* 
     if (workspace_bytes < cv.off) return RPG_ERR_WORKSPACE;      // before any pointer of k.g / k.q is used
     k.tensors = tensors; k.wb = wb;
     k.n = n; k.e = e; k.d = d; k.c = d / 8; k.recursion = gnn_recursion;
-    k.split = (n_tensors == T_COUNT_SPLIT) && (wb || rpg::tuning().gnn.split != 0);
+    k.split = (n_tensors >= T_COUNT_SPLIT) && (wb || rpg::tuning().gnn.split != 0);
+    k.mean_first = (n_tensors == T_COUNT_MEAN) && !wb && rpg::tuning().gnn.mean_first != 0;      // implies fuse_agg
     if (wb && !k.split) return RPG_ERR_BAD_ARG;            // the bf16 Linears exist for the split formulation only
     k.qs = qs; k.es = qs ? qs->e_sel : 0; k.nq = qs ? qs->q : 0;
     k.s = rpg::as_stream(stream);
@@ -375,8 +383,8 @@ int layers_bf16_chained(GnnCall& k) {
     return RPG_OK;
 }
 
-// Every other form: fp32 split / unsplit (RPG_TUNE_GNN_SPLIT), fused / unfused aggregation (RPG_TUNE_GNN_FUSE_AGG), and the bf16
-// Linears that convert their input per Linear (bf16 with unfused aggregation).
+// Every other form: fp32 split / unsplit (RPG_TUNE_GNN_SPLIT), fused / unfused aggregation and, with the T_COUNT_MEAN table, the mean
+// before or after mlp.2 (RPG_TUNE_GNN_FUSE_AGG), and the bf16 Linears that convert their input per Linear (bf16 with unfused aggregation).
 int layers_general(GnnCall& k) {
     const rpg::GnnBuffers& g = k.g;
     const rpg::GnnQueryBuffers& q = k.q;
@@ -420,15 +428,34 @@ int layers_general(GnnCall& k) {
         } else if ((rc = linear(k, {{x, rw.src, d}, {enew, nullptr, d}}, T_MSG0_W, nullptr, g.hid, me, d, 1)) != RPG_OK) {
             return rc;
         }
-        if ((rc = linear(k, {{g.hid, nullptr, d}}, T_MSG2_W, nullptr, g.msg, me, d, 0)) != RPG_OK) return rc;
-        if ((rc = linear(k, {{g.msg, nullptr, d}}, T_GTP_W, nullptr, g.gtp, me, 3 * c, 0)) != RPG_OK) return rc;
-        if (fuse_agg) {
+        if (k.mean_first) {
+            // mlp.2 has no activation behind it and feeds a Linear (g|theta|phi) and the mean, so it moves behind the mean:
+            // g|theta|phi reads the hidden rows through the product weight, the aggregate kernel averages the hidden rows and ONE
+            // node-row Linear applies cat(mlp.2.W, att.W) to [hbar ; ybar].  The biases b_att + b_mlp2 come in as the residual
+            // row, which the kernel leaves zero for a node without incoming edges.  g.msg stays unused.  The three node-row
+            // tensors live in NODE-sized buffers that are free here (an [e][d] buffer is too small for them where n > e): hbar
+            // in nhid (written next by mlp_updating.0, which reads agg), the residual rows and ybar in node3 (its three
+            // per-node terms were consumed by the two edge GEMMs above).
+            float* hbar = g.nhid;
+            float* res = g.node3;
+            float* ybar = g.node3 + (size_t)k.n * d;
+            if ((rc = linear(k, {{g.hid, nullptr, d}}, T_GTPM_W, nullptr, g.gtp, me, 3 * c, 0)) != RPG_OK) return rc;
+            if ((rc = rpg_attention_aggregate_hidden_f32(g.gtp, g.hid, rw.rowptr, rw.perm, k.tensors[T_MSG2ATT_B], mn, me, c, d, ybar, hbar,
+                                                         res, k.s)) != RPG_OK)
+                return rc;
+            if ((rc = linear(k, {{hbar, nullptr, d}, {ybar, nullptr, c}}, T_MSG2ATT_W, res, g.agg, mn, d, 0, nullptr, false)) != RPG_OK)
+                return rc;
+        } else if (fuse_agg) {
+            if ((rc = linear(k, {{g.hid, nullptr, d}}, T_MSG2_W, nullptr, g.msg, me, d, 0)) != RPG_OK) return rc;
+            if ((rc = linear(k, {{g.msg, nullptr, d}}, T_GTP_W, nullptr, g.gtp, me, 3 * c, 0)) != RPG_OK) return rc;
             // aggregate FIRST (att = W y + b + msg is linear in (y, msg): mean(att) = W mean(y) + b + mean(msg)), in the
             // attention kernel itself, then att.W on the n node rows                    my_gnn_layer.py:301,304-307; att.py:32-33
             if ((rc = rpg_attention_aggregate_f32(g.gtp, g.msg, rw.rowptr, rw.perm, k.tensors[T_ATTW_B], mn, me, c, d, g.yat, g.att, k.s)) != RPG_OK)
                 return rc;
             if ((rc = linear(k, {{g.yat, nullptr, c}}, T_ATTW_W, g.att, g.agg, mn, d, 0, nullptr, false)) != RPG_OK) return rc;
         } else {
+            if ((rc = linear(k, {{g.hid, nullptr, d}}, T_MSG2_W, nullptr, g.msg, me, d, 0)) != RPG_OK) return rc;
+            if ((rc = linear(k, {{g.msg, nullptr, d}}, T_GTP_W, nullptr, g.gtp, me, 3 * c, 0)) != RPG_OK) return rc;
             if ((rc = rpg_attention_rows_f32(g.gtp, me, c, g.yat, k.s)) != RPG_OK) return rc;
             if ((rc = linear(k, {{g.yat, nullptr, c}}, T_ATTW_W, g.msg, g.att, me, d, 0)) != RPG_OK) return rc;
             // aggregate (mean over incoming edges)                                       my_gnn_layer.py:301

@@ -204,10 +204,15 @@ __global__ __launch_bounds__(NT) void attention_rows_kernel(const float* __restr
 // ------------------------------------------------------------------------------------------------
 constexpr int AA_NT = 512, AA_W = AA_NT / 64;
 
+// SPLIT_BIAS (the mean-first form, rpg_attention_aggregate_hidden_f32): `msg` holds the message MLP's HIDDEN rows, whose mean goes
+// out without the bias, and the bias goes to a row of its own, `res` = bias where cnt > 0, zeros otherwise: the node-level Linear
+// that follows (mlp.2 | att.W on [mbar ; ybar]) takes it as its residual operand, so an isolated node's aggregate stays exactly 0.
+template <bool SPLIT_BIAS>
 __global__ __launch_bounds__(AA_NT) void attention_aggregate_kernel(const float* __restrict__ gtp, const float4* __restrict__ msg,
                                                                     const int* __restrict__ rowptr, const int* __restrict__ perm,
                                                                     const float4* __restrict__ bias, int C, int d4,
-                                                                    float* __restrict__ ybar, float4* __restrict__ mbar) {
+                                                                    float* __restrict__ ybar, float4* __restrict__ mbar,
+                                                                    float4* __restrict__ res) {
     __shared__ float s_y[AA_W][64];
     const int v = blockIdx.x, s = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -275,7 +280,9 @@ __global__ __launch_bounds__(AA_NT) void attention_aggregate_kernel(const float*
     }
     if (m_ok) {
         float4 o = make_float4(macc.x / dv, macc.y / dv, macc.z / dv, macc.w / dv);
-        if (bias && cnt > 0) {
+        if constexpr (SPLIT_BIAS) {
+            res[(size_t)v * d4 + mc] = cnt > 0 ? bias[mc] : make_float4(0.f, 0.f, 0.f, 0.f);
+        } else if (bias && cnt > 0) {
             const float4 b = bias[mc];
             o.x += b.x; o.y += b.y; o.z += b.z; o.w += b.w;
         }
@@ -521,13 +528,33 @@ extern "C" int rpg_attention_aggregate_f32(const float* gtp, const float* msg, c
     const int quarters = (c + 63) / 64;                       // 64 output channels per workgroup
     if ((d / 4 + quarters - 1) / quarters > AA_NT) return RPG_ERR_BAD_ARG;   // one mbar column per thread
     const int slot = rpg::timing_begin(RPG_TIMER_ATT_AGG, s);
-    hipLaunchKernelGGL(attention_aggregate_kernel, dim3(n, quarters), dim3(AA_NT), 0, s, gtp,
+    hipLaunchKernelGGL(attention_aggregate_kernel<false>, dim3(n, quarters), dim3(AA_NT), 0, s, gtp,
                        reinterpret_cast<const float4*>(msg), rowptr, perm, reinterpret_cast<const float4*>(bias), c, d / 4, ybar,
-                       reinterpret_cast<float4*>(mbar));
+                       reinterpret_cast<float4*>(mbar), nullptr);
     // algorithmic bytes: the scatter-mean of SURVEY 8(a) A9 (messages E*D*4 + targets E*8 + output N*D*4) plus the attention
     // operands it now reads itself (E*3C*4) and the N*C*4 it writes
     rpg::timing_end(slot, (double)e * d * 4.0 + (double)e * 8.0 + (double)n * d * 4.0 + (double)e * 3.0 * c * 4.0 + (double)n * c * 4.0, s);
     RPG_CHECK_LAUNCH("attention_aggregate");
+    return RPG_OK;
+}
+
+extern "C" int rpg_attention_aggregate_hidden_f32(const float* gtp, const float* hid, const int32_t* rowptr, const int32_t* perm,
+                                                  const float* bias, int n, int e, int c, int d, float* ybar, float* hbar, float* res,
+                                                  void* stream) {
+    if (!gtp || !hid || !rowptr || !perm || !bias || !ybar || !hbar || !res || n <= 0 || e <= 0 || c <= 0 || d <= 0 || (c & 3) ||
+        (d & 3) || c > 4096 || !rpg::aligned16(gtp) || !rpg::aligned16(hid) || !rpg::aligned16(hbar) || !rpg::aligned16(res) ||
+        !rpg::aligned16(bias))
+        return RPG_ERR_BAD_ARG;
+    hipStream_t s = rpg::as_stream(stream);
+    const int quarters = (c + 63) / 64;
+    if ((d / 4 + quarters - 1) / quarters > AA_NT) return RPG_ERR_BAD_ARG;   // one hbar column per thread
+    const int slot = rpg::timing_begin(RPG_TIMER_ATT_AGG, s);
+    hipLaunchKernelGGL(attention_aggregate_kernel<true>, dim3(n, quarters), dim3(AA_NT), 0, s, gtp,
+                       reinterpret_cast<const float4*>(hid), rowptr, perm, reinterpret_cast<const float4*>(bias), c, d / 4, ybar,
+                       reinterpret_cast<float4*>(hbar), reinterpret_cast<float4*>(res));
+    // algorithmic bytes: as rpg_attention_aggregate_f32, plus the residual rows (N*D*4)
+    rpg::timing_end(slot, (double)e * d * 4.0 + (double)e * 8.0 + 2.0 * n * d * 4.0 + (double)e * 3.0 * c * 4.0 + (double)n * c * 4.0, s);
+    RPG_CHECK_LAUNCH("attention_aggregate_hidden");
     return RPG_OK;
 }
 

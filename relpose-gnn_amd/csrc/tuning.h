@@ -21,7 +21,10 @@ struct Tuning {
         int inkernel_fixup;    // bit 0: stream-K, bit 1: Winograd: partial tiles combined by the last-arriving workgroup
         int fixup_prio;        // fix-up launches on the high-priority companion stream
     } gemm;
-    struct Gnn { int split, fuse_agg; } gnn;      // forward.hip
+    struct Gnn {               // forward.hip
+        int split, fuse_agg;
+        int mean_first;        // fused aggregation only: mlp.2 runs on the node means of the hidden rows, not per edge
+    } gnn;
     struct Wino {              // winograd.hip
         int on;                // 0 off | 1 auto | 2 / 3: always the 4-wave / 8-wave kernel
         int min_blocks;        // auto: Winograd from this many blocks of 64 tiles x 64 channels up
@@ -80,7 +83,8 @@ inline constexpr TuningRow kTuningRows[kTuningKeys] = {
                    t.bf16.stem_strip_bh = (v >> 8) > 0 ? (v >> 8) : 0),
     RPG_TUNING_ROW(WAVES8, 1, true, t.gemm.waves8 = v != 0),
     RPG_TUNING_ROW(WINO_SHORT, 0, v >= 0, ),                       // retired with the short-K kernel: accepted, ignored
-    RPG_TUNING_ROW(GNN_FUSE_AGG, 1, true, t.gnn.fuse_agg = v != 0),
+    RPG_TUNING_ROW(GNN_FUSE_AGG, 1, true,                          // 2: fused, but mlp.2 still per edge (the form before mean-first)
+                   t.gnn.fuse_agg = v != 0; t.gnn.mean_first = v != 0 && v != 2),
     RPG_TUNING_ROW(WINO_PERSIST, 1, v >= 0 && v <= 2, t.wino.persist = v),
     RPG_TUNING_ROW(BF16_TILE, -1, v >= -1 && v <= 3, t.bf16.tile = v),
     RPG_TUNING_ROW(BF16_DMA, 1, v >= 0 && v <= 40, t.bf16.dma = v),

@@ -836,6 +836,25 @@ def attention_aggregate(gtp: torch.Tensor, msg: torch.Tensor, rowptr: torch.Tens
     return ybar, mbar
 
 
+def attention_aggregate_hidden(gtp: torch.Tensor, hid: torch.Tensor, rowptr: torch.Tensor, perm: torch.Tensor, n: int,
+                               bias: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(ybar [n, c], hbar [n, d], res [n, d]): attention_aggregate on the message MLP's hidden rows, with the bias kept apart as the
+    residual rows of the node-level Linear behind it (bias on nodes with incoming edges, zeros on the others); see
+    rpg_attention_aggregate_hidden_f32."""
+    gtp, hid, bias = _req(gtp, "gtp"), _req(hid, "hid"), _req(bias, "bias")
+    rowptr, perm = _req(rowptr, "rowptr", torch.int32), _req(perm, "perm", torch.int32)
+    e, c3 = gtp.shape
+    c, d = c3 // 3, hid.shape[1]
+    if bias.numel() != d or hid.shape[0] != e:
+        raise ValueError("attention_aggregate_hidden: gtp [e, 3c], hid [e, d], bias [d]")
+    ybar = torch.empty((n, c), dtype=torch.float32, device=gtp.device)
+    hbar = torch.empty((n, d), dtype=torch.float32, device=gtp.device)
+    res = torch.empty((n, d), dtype=torch.float32, device=gtp.device)
+    L.check(L.lib().rpg_attention_aggregate_hidden_f32(_p(gtp), _p(hid), _p(rowptr), _p(perm), _p(bias), n, e, c, d, _p(ybar), _p(hbar),
+                                                       _p(res), _stream()), "attention_aggregate_hidden")
+    return ybar, hbar, res
+
+
 def pose_heads(x: torch.Tensor, w6: torch.Tensor, b6: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     x, w6, b6 = _req(x, "x"), _req(w6, "w6"), _req(b6, "b6")
     r, d = x.shape
@@ -849,7 +868,7 @@ def gnn_forward_query(tensors: Sequence[torch.Tensor], feat: torch.Tensor, edge_
                       node_offset: int = 0, want_features: bool = False, status: Optional[torch.Tensor] = None,
                       workspace: Optional[torch.Tensor] = None):
     """The GNN and its heads in the query-only output mode (rpg_gnn_forward_query_f32, or _bf16 with ``weights_bf16`` from
-    params.pack_gnn_bf16): ``tensors`` from params.pack_gnn (22 or 26), feat [n, d], edge_index int64 [2, e], ``sel`` int64
+    params.pack_gnn_bf16): ``tensors`` from params.pack_gnn (22 or 26, or 30 with params.pack_gnn_mean_first's behind them), feat [n, d], edge_index int64 [2, e], ``sel`` int64
     [e_sel] -- ascending, exactly the valid columns whose target is in ``qnodes`` (graph.query_edge_columns) -- and ``qnodes``
     int64 [q], ascending node ids -> (abs_pose [q, 6] of qnodes, rel_pose [e_sel, 6] of the sel columns), and with
     ``want_features`` also (node_out [q, d], edge_out [e_sel, d]), the heads' inputs.  Every row is what the full forward gives

@@ -13,7 +13,8 @@ encoder (``rpg_resnet_forward_f32`` tensor order)
                                         (stem: wpack [74][2][64] of the fused stem kernel, see pack_stem_pairs)
     then fc.weight [feat][512], fc.bias [feat]
 
-GNN (``rpg_gnn_forward_f32`` tensor order, 22 tensors + 4 optional split matrices, see pack_gnn)
+GNN (``rpg_gnn_forward_f32`` tensor order, 22 tensors + 4 optional split matrices, see pack_gnn, + 4 optional mean-first
+tensors, see pack_gnn_mean_first)
     proj_edge.{weight,bias}; gnn1.edge_model.edge_mlp.{0,2}.{weight,bias}; gnn1.mlp.{0,2}.{weight,bias};
     att g|theta|phi weights concatenated to [3C][D] and biases to [3C]; gnn1.att.W.{weight,bias};
     gnn1.mlp_updating.{0,2}.{weight,bias}; node heads cat(fc_xyz, fc_wpqr) -> [6][D],[6];
@@ -220,10 +221,25 @@ def pack_gnn(sd: Dict[str, torch.Tensor], gnn: str = "gnn1.") -> List[torch.Tens
     return t
 
 
+def pack_gnn_mean_first(packed: List[torch.Tensor]) -> List[torch.Tensor]:
+    """The four tensors behind pack_gnn's 26 (slots 26..29 of rpg_gnn_forward_f32) that let the fp32 GNN take the mean over a node's
+    incoming edges BEFORE mlp.2: with h = relu(mlp.0(.)), msg = W2 h + b2 is read by g|theta|phi (a Linear) and by the mean only, so
+        gtp = (Wg W2) h + (Wg b2 + bg)         agg = [mean h ; mean y] cat(W2, Wa)^T + (ba + b2)    (nodes with incoming edges)
+    The products are evaluated in float64 and rounded to fp32 once.  Weights only: packed once per weight load, like the split."""
+    if len(packed) != 26:
+        raise ValueError("the mean-first tensors extend the 26-tensor (node/edge split) table")
+    w2, b2, wg, bg, wa, ba = (packed[i] for i in (8, 9, 10, 11, 12, 13))
+    w2d, b2d, wgd = w2.double(), b2.double(), wg.double()
+    return [(wgd @ w2d).float().contiguous(),                                             # [3c][D]
+            (wgd @ b2d + bg.double()).float().contiguous(),                               # [3c]
+            torch.cat([w2, wa], 1).contiguous(),                                          # [D][D + c]
+            (ba.double() + b2d).float().contiguous()]                                     # [D]
+
+
 def pack_gnn_bf16(packed: List[torch.Tensor]) -> List[torch.Tensor]:
     """bf16 images of the 10 GEMM weights of the split formulation, in the order rpg_gnn_forward_bf16 expects
-    (include/relpose_gnn_hip.h); `packed` is pack_gnn's 26-tensor table."""
-    if len(packed) != 26:
+    (include/relpose_gnn_hip.h); `packed` is pack_gnn's 26-tensor table, with or without pack_gnn_mean_first's four behind it."""
+    if len(packed) not in (26, 30):
         raise ValueError("the bf16 GNN needs the 26-tensor (node/edge split) table")
     order = (22, 23, 24, 4, 25, 8, 10, 12, 14, 16)
     return [packed[i].to(torch.bfloat16).contiguous() for i in order]

@@ -34,7 +34,7 @@ import torch.nn.functional as F
 
 from . import _lib as _L
 from . import ops
-from .params import pack_gnn, pack_gnn_bf16
+from .params import pack_gnn, pack_gnn_bf16, pack_gnn_mean_first
 from .resnet import EncoderRunner, WorkspacePool
 from .status import DeferredCounters
 
@@ -232,6 +232,8 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
                 self._extra["att_gtp_b"] = torch.cat([sd["att.g.bias"], sd["att.theta.bias"], sd["att.phi.bias"]], 0).float().contiguous()
                 self._extra["att_w"], self._extra["att_b"] = sd["att.W.weight"].float().contiguous(), sd["att.W.bias"].float().contiguous()
             self._gnn_packed = pack_gnn(sd)
+            if len(self._gnn_packed) == 26:            # the split table: the fp32 forward can take the mean before mlp.2
+                self._gnn_packed += pack_gnn_mean_first(self._gnn_packed)
             self._gnn_ptrs = _L.ptr_array([t.data_ptr() for t in self._gnn_packed])
         if self._gnn_dtype == "bf16" and self._gnn_bf16 is None:
             self._gnn_bf16 = pack_gnn_bf16(self._gnn_packed)
