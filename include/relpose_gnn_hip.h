@@ -273,6 +273,32 @@ int rpg_query_pose_fused_f64(const float* rel_pose, const int64_t* edge_src, con
                              double pose_m0, double pose_m1, double pose_m2, double pose_s0, double pose_s1, double pose_s2,
                              int fuse, int max_edges, double* out, double* cand, int32_t* count, int32_t* status, void* stream);
 
+/* A query's reference edges fused by consensus, with the inlier count: the third mode of the kernel behind
+ * rpg_query_pose_fused_f64 (whose `fuse` stays 0 or 1).  Candidates (used, C, t_c, q_c), the graphs' two forms, arithmetic, row
+ * layout, cand, count, bad graphs and status are those of rpg_query_pose_fused_f64.  With the thresholds inlier_t (in the unit of
+ * the un-normalised translation, i.e. compared after `* pose_s + pose_m`) and inlier_deg (degrees), for graph i:
+ *   a candidate with a non-finite component supports nothing and is supported by nothing (support 0); a finite one supports itself
+ *   finite c != d support each other when sqrt((dx dx + dy dy) + dz dz) <= inlier_t, d* = t_c - t_d, AND the angular error of
+ *                    rpg_query_pose_f64 between q_c and q_d <= inlier_deg -- symmetric bit for bit
+ *   support_c        the number of candidates that support c;  c* = the lowest c among those of largest support
+ *   I                the candidates that support c*, in column order
+ *   pred             fuse 0 (mean) over the candidates of I alone, in column order, sign-aligned to the first of them; one inlier
+ *                    as it is; the errors are those of that pose against targ
+ *   every used candidate non-finite: pred[7] and both errors NaN (targ as always), 0 inliers; not a bad graph.  A non-finite
+ *                    candidate next to finite ones is an outlier and voids nothing, and there is no separate C = 1 case
+ *   inliers [g][2] int32 or NULL   (|I|, min(count, max_edges)) per graph; (0, that minimum) for a bad graph
+ * inliers 8-byte aligned, inlier_t finite and >= 0, 0 <= inlier_deg <= 360, 1 <= max_edges <= 64 (RPG_ERR_BAD_ARG otherwise).
+ * Lane c counts its support as an integer over the slots in order, a butterfly of cross-lane moves takes the lexicographic maximum
+ * of (support, lowest c), one ballot of every lane's test against c* is the inlier mask and its popcount |I|, lane 0 runs the
+ * mean's sequential sums over the masked slots; no floating-point atomics.  One launch, no allocation, no synchronisation
+ * (graph-capturable).                                                                                                    */
+int rpg_query_pose_consensus_f64(const float* rel_pose, const int64_t* edge_src, const int64_t* edge_dst, int64_t e,
+                                 const int64_t* node_first, const int64_t* edge_first, int g, const float* node_targets, int64_t n,
+                                 const float* map_poses, int64_t m, const int64_t* neighbours, int k, const float* query_targets,
+                                 double pose_m0, double pose_m1, double pose_m2, double pose_s0, double pose_s1, double pose_s2,
+                                 int max_edges, double inlier_t, double inlier_deg, double* out, double* cand, int32_t* count,
+                                 int32_t* inliers, int32_t* status, void* stream);
+
 /* torch_cluster.knn_graph(x, k, batch, loop=False, flow='source_to_target') (posenet.py:1043-1050): for every node
  * the k nearest OTHER nodes of its graph by squared Euclidean distance (k+1 nearest including itself by
  * (distance, index), self match dropped).  x [n][d]; batch [n] int64 graph id per node, nodes of a graph contiguous,

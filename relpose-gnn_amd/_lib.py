@@ -33,7 +33,7 @@ SYMBOLS = (
     "rpg_retrieve_workspace_bytes", "rpg_retrieve_max_rank", "rpg_row_inv_norms_f32", "rpg_retrieve_cosine_f32",
     "rpg_query_pose_f64", "rpg_query_pose_fused_f64", "rpg_gather_add2_relu_f32",
     "rpg_gnn_query_workspace_bytes", "rpg_gnn_forward_query_f32", "rpg_gnn_forward_query_bf16", "rpg_gemm_last_route", "rpg_get_tuning",
-    "rpg_attention_aggregate_hidden_f32",
+    "rpg_attention_aggregate_hidden_f32", "rpg_query_pose_consensus_f64",
 )
 
 
@@ -131,6 +131,8 @@ def _declare(lib: C.CDLL) -> None:
         _i, _vp, _vp, _vp]
     lib.rpg_query_pose_fused_f64.argtypes = [_vp, _vp, _vp, C.c_int64, _vp, _vp, _i, _vp, C.c_int64, _vp, C.c_int64, _vp, _i, _vp] + [
         C.c_double] * 6 + [_i, _i, _vp, _vp, _vp, _vp, _vp]
+    lib.rpg_query_pose_consensus_f64.argtypes = [_vp, _vp, _vp, C.c_int64, _vp, _vp, _i, _vp, C.c_int64, _vp, C.c_int64, _vp, _i, _vp] + [
+        C.c_double] * 6 + [_i, C.c_double, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp]
     for name in SYMBOLS:
         getattr(lib, name)         # AttributeError here = the library does not export a declared symbol
 

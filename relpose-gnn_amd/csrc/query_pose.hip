@@ -163,7 +163,13 @@ __global__ __launch_bounds__(QP_NT) void query_pose_kernel(const QpArgs a) {
 // lane ranks its own value (smaller values, ties by slot) and the lane(s) of the middle rank(s) are read with a cross-lane move;
 // for the medoid lane c adds up its own row of angles in slot order and a butterfly of cross-lane moves takes the lexicographic
 // minimum of (sum, c).  No floating-point atomics; the only atomic is the integer count of bad graphs.
-constexpr int QF_MEAN = 0, QF_MEDIAN = 1;
+//
+// `consensus` (rpg_query_pose_consensus_f64) is the third mode: the candidates vote.  Lane c walks the slots in order over LDS and
+// counts, as an integer, the finite candidates within `inlier_t` and `inlier_deg` of its own (itself included, by c == d and not by
+// an angle test); the same kind of butterfly takes the lexicographic maximum of (support, lowest c); every lane then tests itself
+// against that winner, one ballot is the inlier mask in slot order and its popcount the inlier count; lane 0 runs the mean's
+// sequential sums over the masked slots.  A non-finite candidate is an outlier here, it does not void the pose.
+constexpr int QF_MEAN = 0, QF_MEDIAN = 1, QF_CONSENSUS = 2;
 constexpr int QF_MAX = 64;            // candidates per graph: one per lane
 
 struct QfArgs {
@@ -171,6 +177,8 @@ struct QfArgs {
     int fuse, max_edges;
     double* cand;                     // [g][max_edges][16] | null
     int32_t* count;                   // [g] | null
+    double inlier_t, inlier_deg;      // consensus: the two thresholds
+    int32_t* inliers;                 // consensus: [g][2] = (inliers, used) | null
 };
 
 // 2 acos(|<p, q>|) in degrees (pose_utils.py:420-431) with Python's min(1.0, max(-1.0, d)), as in the kernel above
@@ -205,6 +213,13 @@ __device__ __forceinline__ void store_nan_row(double* row) {
     const double nan = __builtin_nan("");
     double2* orow = reinterpret_cast<double2*>(row);
     for (int i = 0; i < 8; ++i) orow[i] = make_double2(nan, nan);
+}
+
+// whether two FINITE candidates (t[3], q[4]) support each other: symmetric bit for bit -- the squares and the products of the dot
+// are the same numbers either way round
+__device__ __forceinline__ bool cons_support(const double* c, const double* d, double inlier_t, double inlier_deg) {
+#pragma clang fp contract(off)
+    return trans_dist(c, d) <= inlier_t && quat_angle(c + 3, d + 3) <= inlier_deg;
 }
 
 __global__ __launch_bounds__(QP_NT) void query_pose_fused_kernel(const QfArgs f) {
@@ -250,6 +265,7 @@ __global__ __launch_bounds__(QP_NT) void query_pose_fused_kernel(const QfArgs f)
     const int cn = (int)(found < f.max_edges ? found : f.max_edges);      // C, the candidates used
     const bool mine = active && lane < cn;
     bool bad = false, void_row = false;
+    unsigned long long finite = 0ull;                     // the used candidates without a non-finite component, by slot
     double pt[3], pq[4], tt[3], tq[4], t_err = 0.0, q_err = 0.0;
     for (int i = 0; i < 3; ++i) pt[i] = tt[i] = 0.0;
     for (int i = 0; i < 4; ++i) pq[i] = tq[i] = 0.0;
@@ -298,7 +314,9 @@ __global__ __launch_bounds__(QP_NT) void query_pose_fused_kernel(const QfArgs f)
                     nf_lane = nf_lane || !isfinite(pq[i]);
                 }
             }
-            void_row = cn > 1 && __ballot(nf_lane) != 0ull;       // a non-finite candidate voids the fused pose (not C = 1)
+            const unsigned long long nf = __ballot(nf_lane);
+            finite = __ballot(mine) & ~nf;
+            void_row = cn > 1 && nf != 0ull;              // a non-finite candidate voids the fused pose (not C = 1)
         }
         if (f.cand && lane < f.max_edges) {
             double* crow = f.cand + (gi * f.max_edges + lane) * 16;
@@ -316,7 +334,63 @@ __global__ __launch_bounds__(QP_NT) void query_pose_fused_kernel(const QfArgs f)
         if (lane == 0) {
             atomicAdd(a.status, 1);
             store_nan_row(a.out + gi * 16);
+            if (f.inliers) *reinterpret_cast<int2*>(f.inliers + gi * 2) = make_int2(0, cn);
         }
+        return;
+    }
+    if (f.fuse == QF_CONSENSUS) {
+        // ---- the candidates vote (the whole wave is here) ------------------------------------------------------------------------
+        const bool fin = ((finite >> lane) & 1ull) != 0ull;
+        double me[7];
+        for (int i = 0; i < 3; ++i) me[i] = pt[i];
+        for (int i = 0; i < 4; ++i) me[3 + i] = pq[i];
+        int support = 0, best = lane;
+        if (fin) {
+            for (int d = 0; d < cn; ++d) {
+                if (d == lane) {
+                    ++support;
+                } else if ((finite >> d) & 1ull) {
+                    support += cons_support(me, s_cand[w][d], f.inlier_t, f.inlier_deg) ? 1 : 0;
+                }
+            }
+        }
+        for (int off = 32; off > 0; off >>= 1) {          // the lexicographic maximum of (support, lowest c)
+            const int so = __shfl_xor(support, off);
+            const int bo = __shfl_xor(best, off);
+            if (so > support || (so == support && bo < best)) {
+                support = so;
+                best = bo;
+            }
+        }
+        // (support == 0: no finite candidate at all, and `best` is lane 0 -- nobody is an inlier)
+        const bool inl = fin && support > 0 && (lane == best || cons_support(me, s_cand[w][best], f.inlier_t, f.inlier_deg));
+        const unsigned long long mask = __ballot(inl);
+        if (lane != 0) return;
+        const int ni = __popcll(mask);
+        if (f.inliers) *reinterpret_cast<int2*>(f.inliers + gi * 2) = make_int2(ni, cn);
+        const double nan = __builtin_nan("");
+        double ft[3] = {nan, nan, nan}, fq[4] = {nan, nan, nan, nan};
+        if (ni == 0) {
+            store_row(a.out + gi * 16, ft, fq, tt, tq, nan, nan);
+            return;
+        }
+        const double* c0 = s_cand[w][__ffsll((long long)mask) - 1];      // the first inlier: the mean's q_0
+        if (ni == 1) {                                    // one inlier as it is
+            for (int i = 0; i < 3; ++i) ft[i] = c0[i];
+            for (int i = 0; i < 4; ++i) fq[i] = c0[3 + i];
+        } else {
+            double st[3] = {0.0, 0.0, 0.0}, sq[4] = {0.0, 0.0, 0.0, 0.0};
+            for (unsigned long long rest = mask; rest != 0ull; rest &= rest - 1ull) {
+                const double* cd = s_cand[w][__ffsll((long long)rest) - 1];
+                for (int i = 0; i < 3; ++i) st[i] = st[i] + cd[i];
+                const double dot = cd[3] * c0[3] + cd[4] * c0[4] + cd[5] * c0[5] + cd[6] * c0[6];
+                for (int i = 0; i < 4; ++i) sq[i] = dot >= 0.0 ? sq[i] + cd[3 + i] : sq[i] - cd[3 + i];
+            }
+            for (int i = 0; i < 3; ++i) ft[i] = st[i] / (double)ni;
+            const double norm = sqrt(sq[0] * sq[0] + sq[1] * sq[1] + sq[2] * sq[2] + sq[3] * sq[3]);
+            for (int i = 0; i < 4; ++i) fq[i] = norm == 0.0 ? c0[3 + i] : sq[i] / norm;
+        }
+        store_row(a.out + gi * 16, ft, fq, tt, tq, trans_dist(ft, tt), quat_angle(fq, tq));
         return;
     }
     if (cn == 1) {                                        // the candidate as it is: the single-edge rule's row
@@ -429,14 +503,15 @@ extern "C" int rpg_query_pose_f64(const float* rel_pose, const int64_t* edge_src
     return RPG_OK;
 }
 
-extern "C" int rpg_query_pose_fused_f64(const float* rel_pose, const int64_t* edge_src, const int64_t* edge_dst, int64_t e,
-                                        const int64_t* node_first, const int64_t* edge_first, int g, const float* node_targets,
-                                        int64_t n, const float* map_poses, int64_t m, const int64_t* neighbours, int k,
-                                        const float* query_targets, double pose_m0, double pose_m1, double pose_m2,
-                                        double pose_s0, double pose_s1, double pose_s2, int fuse, int max_edges, double* out,
-                                        double* cand, int32_t* count, int32_t* status, void* stream) {
+namespace {
+
+int launch_fused(const float* rel_pose, const int64_t* edge_src, const int64_t* edge_dst, int64_t e, const int64_t* node_first,
+                 const int64_t* edge_first, int g, const float* node_targets, int64_t n, const float* map_poses, int64_t m,
+                 const int64_t* neighbours, int k, const float* query_targets, const double* pose_m, const double* pose_s, int fuse,
+                 int max_edges, double inlier_t, double inlier_deg, double* out, double* cand, int32_t* count, int32_t* inliers,
+                 int32_t* status, void* stream) {
     if (!rel_pose || !edge_src || !edge_dst || !out || !status || e < 1 || g < 1) return RPG_ERR_BAD_ARG;
-    if ((fuse != QF_MEAN && fuse != QF_MEDIAN) || max_edges < 1 || max_edges > QF_MAX) return RPG_ERR_BAD_ARG;
+    if (max_edges < 1 || max_edges > QF_MAX) return RPG_ERR_BAD_ARG;
     if ((node_targets == nullptr) == (map_poses == nullptr)) return RPG_ERR_BAD_ARG;      // one source of poses, not both
     if (node_targets) {
         if (!node_first || n < 1 || neighbours || query_targets) return RPG_ERR_BAD_ARG;
@@ -445,8 +520,8 @@ extern "C" int rpg_query_pose_fused_f64(const float* rel_pose, const int64_t* ed
     }
     if (misaligned(rel_pose, 3) || misaligned(node_targets, 3) || misaligned(map_poses, 3) || misaligned(query_targets, 3) ||
         misaligned(edge_src, 7) || misaligned(edge_dst, 7) || misaligned(node_first, 7) || misaligned(edge_first, 7) ||
-        misaligned(neighbours, 7) || misaligned(status, 3) || misaligned(count, 3) || !rpg::aligned16(out) ||
-        (cand && !rpg::aligned16(cand)))
+        misaligned(neighbours, 7) || misaligned(status, 3) || misaligned(count, 3) || misaligned(inliers, 7) ||
+        !rpg::aligned16(out) || (cand && !rpg::aligned16(cand)))
         return RPG_ERR_BAD_ARG;
     QfArgs f;
     QpArgs& a = f.q;
@@ -464,8 +539,7 @@ extern "C" int rpg_query_pose_fused_f64(const float* rel_pose, const int64_t* ed
     a.neighbours = neighbours;
     a.k = k;
     a.query_targets = query_targets;
-    a.pose_m[0] = pose_m0, a.pose_m[1] = pose_m1, a.pose_m[2] = pose_m2;
-    a.pose_s[0] = pose_s0, a.pose_s[1] = pose_s1, a.pose_s[2] = pose_s2;
+    for (int i = 0; i < 3; ++i) a.pose_m[i] = pose_m[i], a.pose_s[i] = pose_s[i];
     a.ref_node = 0;
     a.out = out;
     a.status = status;
@@ -473,8 +547,40 @@ extern "C" int rpg_query_pose_fused_f64(const float* rel_pose, const int64_t* ed
     f.max_edges = max_edges;
     f.cand = cand;
     f.count = count;
+    f.inlier_t = inlier_t;
+    f.inlier_deg = inlier_deg;
+    f.inliers = inliers;
     const unsigned grid = (unsigned)((g + QP_NT / 64 - 1) / (QP_NT / 64));
     hipLaunchKernelGGL(query_pose_fused_kernel, dim3(grid), dim3(QP_NT), 0, rpg::as_stream(stream), f);
     RPG_CHECK_LAUNCH("query_pose_fused");
     return RPG_OK;
+}
+
+}  // namespace
+
+extern "C" int rpg_query_pose_fused_f64(const float* rel_pose, const int64_t* edge_src, const int64_t* edge_dst, int64_t e,
+                                        const int64_t* node_first, const int64_t* edge_first, int g, const float* node_targets,
+                                        int64_t n, const float* map_poses, int64_t m, const int64_t* neighbours, int k,
+                                        const float* query_targets, double pose_m0, double pose_m1, double pose_m2,
+                                        double pose_s0, double pose_s1, double pose_s2, int fuse, int max_edges, double* out,
+                                        double* cand, int32_t* count, int32_t* status, void* stream) {
+    if (fuse != QF_MEAN && fuse != QF_MEDIAN) return RPG_ERR_BAD_ARG;
+    const double pm[3] = {pose_m0, pose_m1, pose_m2}, ps[3] = {pose_s0, pose_s1, pose_s2};
+    return launch_fused(rel_pose, edge_src, edge_dst, e, node_first, edge_first, g, node_targets, n, map_poses, m, neighbours, k,
+                        query_targets, pm, ps, fuse, max_edges, 0.0, 0.0, out, cand, count, nullptr, status, stream);
+}
+
+extern "C" int rpg_query_pose_consensus_f64(const float* rel_pose, const int64_t* edge_src, const int64_t* edge_dst, int64_t e,
+                                            const int64_t* node_first, const int64_t* edge_first, int g,
+                                            const float* node_targets, int64_t n, const float* map_poses, int64_t m,
+                                            const int64_t* neighbours, int k, const float* query_targets, double pose_m0,
+                                            double pose_m1, double pose_m2, double pose_s0, double pose_s1, double pose_s2,
+                                            int max_edges, double inlier_t, double inlier_deg, double* out, double* cand,
+                                            int32_t* count, int32_t* inliers, int32_t* status, void* stream) {
+    // (written so that a NaN threshold fails the test too)
+    if (!(inlier_t >= 0.0 && inlier_t < __builtin_inf()) || !(inlier_deg >= 0.0 && inlier_deg <= 360.0)) return RPG_ERR_BAD_ARG;
+    const double pm[3] = {pose_m0, pose_m1, pose_m2}, ps[3] = {pose_s0, pose_s1, pose_s2};
+    return launch_fused(rel_pose, edge_src, edge_dst, e, node_first, edge_first, g, node_targets, n, map_poses, m, neighbours, k,
+                        query_targets, pm, ps, QF_CONSENSUS, max_edges, inlier_t, inlier_deg, out, cand, count, inliers, status,
+                        stream);
 }

@@ -57,7 +57,10 @@ def query_pose(rel_pose: np.ndarray, target: np.ndarray, edges: np.ndarray, pose
     return pred, targ
 
 
-FUSE_MODES = ("mean", "median")
+FUSE_MODES = ("mean", "median", "consensus")
+# the consensus rule's thresholds: API defaults, not measured optima.  Both belong to the scene's scale; INLIER_T is in the unit of
+# the un-normalised translation (it is compared after `* pose_s + pose_m`), INLIER_DEG in degrees
+INLIER_T, INLIER_DEG = 0.25, 5.0
 _NO_EDGE = "graph has no edge into node 0: cannot derive the query pose"       # reference_edge's message
 
 
@@ -96,16 +99,75 @@ def medoid_angle_sums(q: np.ndarray) -> np.ndarray:
     return sums
 
 
-def fuse_poses(cands: np.ndarray, fuse: str) -> np.ndarray:
+def _check_thresholds(who: str, inlier_t, inlier_deg):
+    """The consensus rule's thresholds as floats: both finite, inlier_t >= 0, 0 <= inlier_deg <= 360 (ValueError otherwise)."""
+    for name, v in (("inlier_t", inlier_t), ("inlier_deg", inlier_deg)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise ValueError(f"{who}: {name} must be a finite number, got {v!r}")
+    t, deg = float(inlier_t), float(inlier_deg)
+    if not (t >= 0.0 and t != float("inf")):                # (written so that NaN fails too)
+        raise ValueError(f"{who}: inlier_t must be finite and >= 0, got {inlier_t!r}")
+    if not 0.0 <= deg <= 360.0:
+        raise ValueError(f"{who}: inlier_deg must be in 0..360 degrees, got {inlier_deg!r}")
+    return t, deg
+
+
+def consensus_support(cands: np.ndarray, inlier_t: float = INLIER_T, inlier_deg: float = INLIER_DEG) -> np.ndarray:
+    """bool [C, C]: whether candidates c and d of cands [C, 7] = (t, q) support each other.  A candidate with a non-finite
+    component supports nothing and is supported by nothing; a finite one supports itself (by c == d, not by an angle test); two
+    finite ones c != d support each other when ``sqrt((dx*dx + dy*dy) + dz*dz) <= inlier_t`` with d* = t_c - t_d, in that order
+    of operations, and ``quaternion_angular_error(q_c, q_d) <= inlier_deg``.  Symmetric bit for bit: the squares and the
+    products of the dot are the same numbers either way round."""
+    inlier_t, inlier_deg = _check_thresholds("consensus_support", inlier_t, inlier_deg)
+    cands = np.asarray(cands, dtype=np.float64)
+    c = cands.shape[0]
+    finite = np.isfinite(cands).all(axis=1)
+    sup = np.zeros((c, c), dtype=bool)
+    for i in range(c):
+        if not finite[i]:
+            continue
+        for d in range(c):
+            if d == i:
+                sup[i, d] = True
+            elif finite[d]:
+                with np.errstate(over="ignore", invalid="ignore"):       # (finite translations can still be 1e308 apart)
+                    dx, dy, dz = (float(v) for v in cands[i, :3] - cands[d, :3])
+                    dist = np.sqrt((dx * dx + dy * dy) + dz * dz)
+                sup[i, d] = bool(dist <= inlier_t) and quaternion_angular_error(cands[i, 3:], cands[d, 3:]) <= inlier_deg
+    return sup
+
+
+def consensus_inliers(cands: np.ndarray, inlier_t: float = INLIER_T, inlier_deg: float = INLIER_DEG):
+    """-> (I, support [C]): ``support[c]`` = how many candidates support c (``consensus_support``; 0 for a non-finite one), the
+    winner c* = the lowest c among those of largest support, and I = the slots of the candidates that support c*, ascending --
+    empty when every support is 0, i.e. when every candidate is non-finite."""
+    sup = consensus_support(cands, inlier_t, inlier_deg)
+    support = sup.sum(axis=1).astype(np.int64)
+    best = int(np.argmax(support))                          # argmax: the first of equals
+    if support[best] == 0:
+        return np.zeros(0, dtype=np.int64), support
+    return np.flatnonzero(sup[best]), support
+
+
+def fuse_poses(cands: np.ndarray, fuse: str, *, inlier_t: float = INLIER_T, inlier_deg: float = INLIER_DEG) -> np.ndarray:
     """cands [C, 7] = (t, q) -> the one pose [7] (float64; every sum in row order).
     ``"mean"``: t = (t_0 + .. + t_{C-1}) / C; q = S / |S| with S the sum of q_c where <q_c, q_0> >= 0 and of -q_c elsewhere (q and
     -q are one rotation), q_0 where |S| = 0.  ``"median"``: the component-wise median of t (``np.median``: the mean of the two
     middle values for even C) and the medoid q_c*, c* the lowest c that minimises ``medoid_angle_sums``.
     One candidate is returned as it is.  Two or more of which one has a non-finite component give NaN in every component, so
-    that neither mode depends on how NaN orders."""
+    that neither mode depends on how NaN orders.
+    ``"consensus"``: ``fuse_poses(cands[I], "mean")`` with I the inliers of ``consensus_inliers`` under the two thresholds
+    (``inlier_t`` in the unit of the un-normalised translation -- it is compared after ``* pose_s + pose_m`` --, ``inlier_deg`` in
+    degrees; the defaults 0.25 / 5.0 are API defaults that belong to the scene's scale, not measured optima).  Here a non-finite
+    candidate is an outlier and voids nothing, a lone candidate has no rule of its own, and NaN in every component means that
+    every candidate was non-finite.  The thresholds are checked for every mode and read by this one."""
     if fuse not in FUSE_MODES:
-        raise ValueError(f"fuse must be 'mean' or 'median', got {fuse!r}")
+        raise ValueError(f"fuse must be 'mean', 'median' or 'consensus', got {fuse!r}")
+    inlier_t, inlier_deg = _check_thresholds("fuse_poses", inlier_t, inlier_deg)
     cands = np.asarray(cands, dtype=np.float64)
+    if fuse == "consensus":
+        inl, _ = consensus_inliers(cands, inlier_t, inlier_deg)
+        return fuse_poses(cands[inl], "mean") if inl.size else np.full(7, np.nan)
     c = cands.shape[0]
     if c == 1:
         return cands[0].copy()
@@ -123,26 +185,42 @@ def fuse_poses(cands: np.ndarray, fuse: str) -> np.ndarray:
     return np.hstack((st / c, q[0] if norm == 0.0 else sq / norm))
 
 
-def fused_query_pose(rel_pose: np.ndarray, target: np.ndarray, edges: np.ndarray, pose_m, pose_s, fuse: str, max_edges: int = 64):
+def fused_query_pose(rel_pose: np.ndarray, target: np.ndarray, edges: np.ndarray, pose_m, pose_s, fuse: str, max_edges: int = 64, *,
+                     inlier_t: float = INLIER_T, inlier_deg: float = INLIER_DEG):
     """(pred[7], targ[7]) of the query node of ONE graph from ALL its usable reference edges (``pose_candidates``) combined by
     ``fuse_poses``: ``query_pose`` keeps one of these estimates, this is the rule that uses them all.  The host path of
-    ``fuse=`` in the two streams and the statement the device kernel (rpg_query_pose_fused_f64) is held to."""
+    ``fuse=`` in the two streams and the statement the device kernel (rpg_query_pose_fused_f64, and for ``"consensus"`` with
+    its thresholds rpg_query_pose_consensus_f64) is held to."""
     cands, targ, _ = pose_candidates(rel_pose, target, edges, pose_m, pose_s, max_edges)
-    return fuse_poses(cands, fuse), targ
+    return fuse_poses(cands, fuse, inlier_t=inlier_t, inlier_deg=inlier_deg), targ
 
 
-def fused_query_row(rel_pose, target, edges, pose_m, pose_s, fuse: str, max_edges: int = 64) -> np.ndarray:
+def fused_query_row(rel_pose, target, edges, pose_m, pose_s, fuse: str, max_edges: int = 64, *, inlier_t: float = INLIER_T,
+                    inlier_deg: float = INLIER_DEG) -> np.ndarray:
     """The device rule's row of 16 = pred[7], targ[7], translation error, rotation error for ONE graph.  The errors are
-    ``errors`` of the fused pose, except that a pose voided by a non-finite candidate (two or more candidates) has NaN for both
-    -- the rotation error of a NaN quaternion would be 360 by the reference's clamp."""
+    ``errors`` of the fused pose, except that a pose voided by a non-finite candidate (two or more candidates; with
+    ``"consensus"``: a pose without a single finite candidate behind it) has NaN for both -- the rotation error of a NaN
+    quaternion would be 360 by the reference's clamp."""
     cands, targ, _ = pose_candidates(rel_pose, target, edges, pose_m, pose_s, max_edges)
-    pred = fuse_poses(cands, fuse)
+    pred = fuse_poses(cands, fuse, inlier_t=inlier_t, inlier_deg=inlier_deg)
     with np.errstate(invalid="ignore"):
         r = errors(pred[None], targ[None])
     t_err, q_err = r.t_loss[0], r.q_loss[0]
-    if cands.shape[0] > 1 and np.isnan(pred).any():
+    if (cands.shape[0] > 1 or fuse == "consensus") and np.isnan(pred).any():
         t_err = q_err = np.nan
     return np.hstack((pred, targ, t_err, q_err))
+
+
+def consensus_query_row(rel_pose, target, edges, pose_m, pose_s, max_edges: int = 64, *, inlier_t: float = INLIER_T,
+                        inlier_deg: float = INLIER_DEG):
+    """``fused_query_row(..., fuse="consensus")`` with the two integers that say how far the pose can be believed: -> (row [16],
+    inliers, used).  ``used`` = min(usable edges, max_edges) candidates voted, ``inliers`` of them support the winner and are
+    averaged into the pose; ``inliers / used`` is the caller's confidence, ``inliers == 0`` a row whose pose and errors are NaN
+    because every used candidate was non-finite.  (A graph without a usable edge raises, as in ``pose_candidates``.)"""
+    cands, _, _ = pose_candidates(rel_pose, target, edges, pose_m, pose_s, max_edges)
+    inl, _ = consensus_inliers(cands, inlier_t, inlier_deg)
+    row = fused_query_row(rel_pose, target, edges, pose_m, pose_s, "consensus", max_edges, inlier_t=inlier_t, inlier_deg=inlier_deg)
+    return row, int(inl.size), int(cands.shape[0])
 
 
 @dataclass
@@ -151,6 +229,8 @@ class EvalResult:
     targ_poses: np.ndarray      # [G, 7]
     t_loss: np.ndarray          # [G] metres
     q_loss: np.ndarray          # [G] degrees
+    inliers: Optional[np.ndarray] = None     # [G] int, fuse="consensus" only: the candidates averaged into the pose
+    used: Optional[np.ndarray] = None        # [G] int, fuse="consensus" only: the candidates that voted; inliers / used = confidence
 
     @property
     def median_t(self) -> float:
@@ -174,18 +254,38 @@ def errors(pred_poses: np.ndarray, targ_poses: np.ndarray) -> EvalResult:
 class _PoseRows:
     """What a stream collects micro-batch by micro-batch, and the result made of it: the [G, 16] blocks of the device pose
     rule (``on_device``), or the (pred, targ) rows of the host rule of test.py:213-251.  With ``fuse`` the host rule is
-    ``fused_query_row`` and collects the same [G, 16] blocks as the device."""
+    ``fused_query_row`` and collects the same [G, 16] blocks as the device.  With ``fuse="consensus"`` every block comes with
+    its int [G, 2] block of (inliers, used) (``ints``), from the device or from ``consensus_query_row``."""
 
-    def __init__(self, pose_m, pose_s, ref_node: int, on_device: bool, fuse=None, max_edges: int = 64):
+    def __init__(self, pose_m, pose_s, ref_node: int, on_device: bool, fuse=None, max_edges: int = 64,
+                 inlier_t: float = INLIER_T, inlier_deg: float = INLIER_DEG):
         self.pose_m, self.pose_s = np.asarray(pose_m, dtype=np.float64), np.asarray(pose_s, dtype=np.float64)
         self.ref_node = ref_node
         self.fuse, self.max_edges = fuse, max_edges
+        self.inlier_t, self.inlier_deg = inlier_t, inlier_deg
+        self.ints: Optional[List[np.ndarray]] = [] if fuse == "consensus" else None
         self.rows: Optional[List[np.ndarray]] = [] if on_device or fuse is not None else None
         self.preds: List[np.ndarray] = []
         self.targs: List[np.ndarray] = []
 
+    def add_device(self, block: np.ndarray) -> None:
+        """One micro-batch as the device rule sent it: its [G, 16] block, or with ``fuse="consensus"`` the uint8 buffer of
+        ``query_pose.packed_rows`` -- that block and the int32 [G, 2] integers behind it, which came back in one copy."""
+        if self.ints is not None:
+            from .query_pose import unpack_rows
+            block, ints = unpack_rows(block)
+            self.ints.append(ints)
+        self.rows.append(block)
+
     def add(self, rel: np.ndarray, targets: Iterable, cut: Iterable) -> None:
         """The host rule over one micro-batch: per graph its targets [n, 6] and its (columns of ``rel``, local edge list)."""
+        if self.fuse == "consensus":
+            both = [consensus_query_row(rel[cols], target, edges, self.pose_m, self.pose_s, self.max_edges, inlier_t=self.inlier_t,
+                                        inlier_deg=self.inlier_deg) for target, (cols, edges) in zip(targets, cut)]
+            if both:
+                self.rows.append(np.stack([row for row, _, _ in both]))
+                self.ints.append(np.asarray([[inl, used] for _, inl, used in both], dtype=np.int64))
+            return
         if self.fuse is not None:
             rows = [fused_query_row(rel[cols], target, edges, self.pose_m, self.pose_s, self.fuse, self.max_edges)
                     for target, (cols, edges) in zip(targets, cut)]
@@ -198,8 +298,9 @@ class _PoseRows:
             self.targs.append(t)
 
     def result(self, gather=None, with_targets: bool = True):
-        """EvalResult of everything collected (``gather(pred, targ)``: all ranks' rows in place of this rank's); without
-        targets only the predicted poses [G, 7]."""
+        """EvalResult of everything collected (``gather(pred, targ, ints)``: all ranks' rows in place of this rank's); without
+        targets only the predicted poses [G, 7].  ``ints`` is None or, with ``fuse="consensus"``, the int64 [G, 2] block of
+        (inliers, used): it fills the result's two arrays, and without targets it is what ``self.integers()`` hands out."""
         all_rows = None
         if self.rows is not None:
             all_rows = np.concatenate(self.rows) if self.rows else np.zeros((0, 16))
@@ -209,16 +310,29 @@ class _PoseRows:
             targ = np.stack(self.targs) if self.targs else np.zeros((0, 7))
         if not with_targets:
             return np.ascontiguousarray(pred)
+        ints = self.integers()
         if gather is not None:
-            return errors(*gather(pred, targ))
-        return _result_from_rows(all_rows) if all_rows is not None else errors(pred, targ)
+            pred, targ, ints = gather(pred, targ, ints)
+            res = errors(pred, targ)
+        else:
+            res = _result_from_rows(all_rows) if all_rows is not None else errors(pred, targ)
+        if ints is not None:
+            res.inliers, res.used = ints[:, 0].copy(), ints[:, 1].copy()
+        return res
+
+    def integers(self) -> Optional[np.ndarray]:
+        """int64 [G, 2] = (inliers, used) of everything collected; None unless ``fuse="consensus"``."""
+        if self.ints is None:
+            return None
+        return np.concatenate(self.ints).astype(np.int64) if self.ints else np.zeros((0, 2), dtype=np.int64)
 
 
 @torch.no_grad()
 def evaluate_stream(model, graphs: Sequence[Data], device, micro_batch: int = 64, pose_m=(0.0, 0.0, 0.0),
                     pose_s=(1.0, 1.0, 1.0), ref_node: int = 0, rank: int = 0, world: int = 1,
                     stats: Optional[dict] = None, bf16_input: Optional[bool] = None, postprocess: str = "host",
-                    fuse: Optional[str] = None, max_edges: int = 64) -> EvalResult:
+                    fuse: Optional[str] = None, max_edges: int = 64, inlier_t: float = INLIER_T,
+                    inlier_deg: float = INLIER_DEG) -> EvalResult:
     """Run ``model`` over a stream of single-graph ``Data`` objects (x, edge_index, y) and post-process like test.py.
     With world > 1 every rank evaluates its contiguous block (shard_range) and the [G,7] rows are all-gathered.
 
@@ -248,10 +362,20 @@ def evaluate_stream(model, graphs: Sequence[Data], device, micro_batch: int = 64
     ``fuse``: None (default) derives the query's pose from the ``ref_node``-th edge into it, as the reference does.  ``"mean"``
     / ``"median"`` combine the estimates of ALL the edges into it (the first ``max_edges`` <= 64 in column order, self-edges
     skipped; ``fused_query_pose``): with ``postprocess="host"`` in numpy, with ``"device"`` in the fused kernel
-    (``QueryPose(fuse=...)``), still 16 doubles per graph back.  ``ref_node`` must stay 0 then."""
+    (``QueryPose(fuse=...)``), still 16 doubles per graph back.  ``ref_node`` must stay 0 then.
+
+    ``fuse="consensus"`` lets those estimates vote (``consensus_inliers``): two support each other when their translations lie
+    within ``inlier_t`` and their rotations within ``inlier_deg`` degrees, the best-supported one wins and the pose is the
+    ``"mean"`` of its supporters alone -- a wrong edge is outvoted instead of averaged in.  The result's ``inliers`` and ``used``
+    (int [G]; None for every other mode) say how many estimates were averaged and how many voted: ``inliers / used`` is the
+    accept / reject signal that goes with the pose.  On the device path the two integers travel with the rows, 8 more bytes per
+    graph (``stats["d2h_bytes"]`` counts them); under ``world > 1`` they are gathered in graph order like the poses.  The
+    defaults 0.25 / 5.0 are API defaults, not measured optima: both belong to the scene's scale, and ``inlier_t`` is compared
+    after ``* pose_s + pose_m``, i.e. in the unit of the un-normalised translation.  Both must be finite, ``inlier_t >= 0``
+    and ``0 <= inlier_deg <= 360`` (ValueError)."""
     from .shard import rank_host_slice
     _check_postprocess("evaluate_stream", postprocess, device)
-    _check_fuse("evaluate_stream", fuse, max_edges, ref_node)
+    _check_fuse("evaluate_stream", fuse, max_edges, ref_node, inlier_t, inlier_deg)
     if world > 1 and torch.device(device).type == "cuda":
         # one process per GPU on a shared host: this rank's staging threads and pinned buffers stay on its share of the
         # cores / its GPU's NUMA node for the duration of the call (shard.rank_host_slice puts the caller's mask back on
@@ -260,9 +384,9 @@ def evaluate_stream(model, graphs: Sequence[Data], device, micro_batch: int = 64
         local_world = int(os.environ.get("LOCAL_WORLD_SIZE", world))
         with rank_host_slice(int(os.environ.get("LOCAL_RANK", rank)), local_world, torch.device(device).index):
             return _evaluate_stream(model, graphs, device, micro_batch, pose_m, pose_s, ref_node, rank, world, stats, bf16_input, local_world,
-                                    postprocess, fuse, max_edges)
+                                    postprocess, fuse, max_edges, inlier_t, inlier_deg)
     return _evaluate_stream(model, graphs, device, micro_batch, pose_m, pose_s, ref_node, rank, world, stats, bf16_input, 1, postprocess,
-                            fuse, max_edges)
+                            fuse, max_edges, inlier_t, inlier_deg)
 
 
 def _check_postprocess(who: str, postprocess, device) -> None:
@@ -272,11 +396,12 @@ def _check_postprocess(who: str, postprocess, device) -> None:
         raise ValueError(f"{who}: postprocess='device' runs the pose rule on the GPU, the stream's device is {device}")
 
 
-def _check_fuse(who: str, fuse, max_edges, ref_node) -> None:
+def _check_fuse(who: str, fuse, max_edges, ref_node, inlier_t=INLIER_T, inlier_deg=INLIER_DEG) -> None:
+    _check_thresholds(who, inlier_t, inlier_deg)
     if fuse is None:
         return
     if fuse not in FUSE_MODES:
-        raise ValueError(f"{who}: fuse must be None, 'mean' or 'median', got {fuse!r}")
+        raise ValueError(f"{who}: fuse must be None, 'mean', 'median' or 'consensus', got {fuse!r}")
     if isinstance(max_edges, bool) or not isinstance(max_edges, (int, np.integer)) or not 1 <= max_edges <= 64:
         raise ValueError(f"{who}: max_edges must be an int in 1..64, got {max_edges!r}")
     if ref_node != 0:
@@ -290,20 +415,21 @@ def _result_from_rows(rows: np.ndarray) -> EvalResult:
 
 
 def _evaluate_stream(model, graphs, device, micro_batch, pose_m, pose_s, ref_node, rank, world, stats, bf16_input, local_world,
-                     postprocess="host", fuse=None, max_edges=64):
+                     postprocess="host", fuse=None, max_edges=64, inlier_t=INLIER_T, inlier_deg=INLIER_DEG):
     from .shard import gather_rows, shard_counts, shard_range
     qp = None
     if postprocess == "device":
         from .query_pose import QueryPose
-        qp = QueryPose(pose_m, pose_s, ref_node, fuse=fuse, max_edges=max_edges)
+        qp = QueryPose(pose_m, pose_s, ref_node, fuse=fuse, max_edges=max_edges, inlier_t=inlier_t, inlier_deg=inlier_deg)
     lo, hi = shard_range(len(graphs), rank, world)
-    acc = _PoseRows(pose_m, pose_s, ref_node, on_device=qp is not None, fuse=fuse, max_edges=max_edges)
+    acc = _PoseRows(pose_m, pose_s, ref_node, on_device=qp is not None, fuse=fuse, max_edges=max_edges, inlier_t=inlier_t,
+                    inlier_deg=inlier_deg)
     runner = _MicroBatchRunner(model, device, micro_batch, bf16_input, local_world, pose=qp)
 
     def finish(item):
         chunk, host = item.chunk, item.host
         if qp is not None:
-            return acc.rows.append(host["rel"].numpy())
+            return acc.add_device(host["rel"].numpy())
         ei = None if host["ei"] is None else host["ei"].numpy()              # a model-built (kNN) edge list
         acc.add(host["rel"].numpy(), (g.y.cpu().numpy() for g in chunk),
                 cut_per_graph([g.num_nodes for g in chunk], ei, (g.edge_index.cpu().numpy() for g in chunk)))
@@ -319,12 +445,14 @@ def _evaluate_stream(model, graphs, device, micro_batch, pose_m, pose_s, ref_nod
         # tensors of a device="cpu" run -- ADVICE r5; before round 5 world = 1 never reached a collective)
         grouped = torch.device(device).type == "cuda" or dist.get_backend() != "nccl"
 
-    def gather(pred, targ):
+    def gather(pred, targ, ints=None):
         # under a process group the collective runs at ANY world size, 1 included: a one-GPU box then executes the same RCCL
-        # all-gather the 4- / 8-GPU stream does (tools/eval_stream.py under torch.distributed.run)
-        both = torch.from_numpy(np.concatenate([pred, targ], 1)).to(device)
+        # all-gather the 4- / 8-GPU stream does (tools/eval_stream.py under torch.distributed.run).  The consensus rule's two
+        # integers ride in the same rows as two more float64 columns (small integers: exact), so they arrive in graph order too
+        parts = [pred, targ] if ints is None else [pred, targ, ints.astype(np.float64)]
+        both = torch.from_numpy(np.concatenate(parts, 1)).to(device)
         both = gather_rows(both, shard_counts(len(graphs), world), always=True).cpu().numpy()
-        return both[:, :7], both[:, 7:]
+        return both[:, :7], both[:, 7:14], None if ints is None else both[:, 14:].astype(np.int64)
     return acc.result(gather if world > 1 or grouped else None)
 
 
@@ -361,7 +489,7 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
                pose_s=(1.0, 1.0, 1.0), ref_node: int = 0, stats: Optional[dict] = None, targets=None,
                bf16_input: Optional[bool] = None, *, rule=None, query_descriptors=None, query_groups=None,
                postprocess: str = "host", fuse: Optional[str] = None, max_edges: int = 64, capture: bool = False,
-               outputs: str = "all"):
+               outputs: str = "all", inlier_t: float = INLIER_T, inlier_deg: float = INLIER_DEG):
     """The evaluation stream of the map path (``PoseNetX_R2.forward_map``): query g's graph is the query followed by the map
     rows ``neighbours[g]`` (its retrieved database images, dataset_7Scenes_multi.py:340-345).  Single process.
 
@@ -389,6 +517,12 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
 
     ``fuse`` (None, ``"mean"``, ``"median"``) and ``max_edges``: as in ``evaluate_stream`` -- one pose per query from the
     estimates of all its K database images instead of the ``ref_node``-th one, on the host or on the device.
+    ``fuse="consensus"`` with ``inlier_t`` / ``inlier_deg`` (as in ``evaluate_stream``, which see for their unit and defaults):
+    the K estimates vote, a database image that retrieval got wrong is outvoted, and every query gets ``inliers`` and ``used``
+    -- on the ``EvalResult`` when there are targets, else (the return value stays the poses [G, 7]) in ``stats["inliers"]`` /
+    ``stats["used"]``, int [G]; a caller accepts a pose when ``inliers / used`` is high enough for its use.  On the device path
+    the integers travel with the rows (8 more bytes per query in ``stats["d2h_bytes"]``); a captured step is keyed by the
+    thresholds too, so other thresholds capture a new step instead of replaying the old one.
 
     ``capture=True`` (GPU map only): a micro-batch's device step -- ``forward_map`` with its retrieval, and the device pose rule
     behind it -- is captured into a HIP graph once per shape (``graphed.GraphedForwardMap``: the full micro-batch and a ragged
@@ -429,7 +563,8 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
     if micro_batch < 1:
         raise ValueError("relocalize: micro_batch must be >= 1")
     _check_postprocess("relocalize", postprocess, device)
-    _check_fuse("relocalize", fuse, max_edges, ref_node)
+    _check_fuse("relocalize", fuse, max_edges, ref_node, inlier_t, inlier_deg)
+    inlier_t, inlier_deg = float(inlier_t), float(inlier_deg)
     if capture:
         if torch.device(device).type != "cuda":
             raise ValueError(f"relocalize: capture=True replays a HIP graph, the feature map is on {device}")
@@ -472,11 +607,12 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
     if postprocess == "device" and poses_h is not None:
         from .query_pose import QueryPose
         # a captured step counts its bad graphs in the status word of the rule it was captured with: that rule is kept with it
-        qp_key = ("pose", tuple(float(v) for v in pose_m), tuple(float(v) for v in pose_s), ref_node, fuse, max_edges)
+        qp_key = ("pose", tuple(float(v) for v in pose_m), tuple(float(v) for v in pose_s), ref_node, fuse, max_edges, inlier_t,
+                  inlier_deg)
         qp = captured.get(qp_key) if capture else None
         if qp is None:
             qp = QueryPose(np.asarray(pose_m, dtype=np.float64), np.asarray(pose_s, dtype=np.float64), ref_node, fuse=fuse,
-                           max_edges=max_edges)
+                           max_edges=max_edges, inlier_t=inlier_t, inlier_deg=inlier_deg)
             if capture:
                 captured[qp_key] = qp
         if targets is not None:
@@ -484,7 +620,11 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
             targ_dev = t32 if t32.is_cuda else (t32 if t32.is_pinned() else t32.pin_memory()).to(device, non_blocking=True)
         if model.knn <= 0:         # forward_map's own FC list: n (n - 1) columns per graph, graph after graph
             fc_first = torch.arange(min(micro_batch, g_all) + 1, dtype=torch.int64, device=device) * fc_edges.shape[1]
-    acc = _PoseRows(pose_m, pose_s, ref_node, on_device=qp is not None, fuse=fuse, max_edges=max_edges)
+    acc = _PoseRows(pose_m, pose_s, ref_node, on_device=qp is not None, fuse=fuse, max_edges=max_edges, inlier_t=inlier_t,
+                    inlier_deg=inlier_deg)
+    consensus = qp is not None and fuse == "consensus"        # the device rule also fills an int32 [G, 2] block per micro-batch
+    if consensus:
+        from .query_pose import packed_rows
     raw_abs, raw_rel = [], []
 
     def captured_step(x, qd, targ):
@@ -492,7 +632,7 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
         now with the micro-batch itself as the example."""
         nonlocal n_captured
         key = ("step", tuple(x.shape), x.dtype, kk, None if rule is None else (rule.sampling_period, rule.random), postprocess,
-               fuse, max_edges, qd is not None, targ is not None, outputs)
+               fuse, max_edges, qd is not None, targ is not None, outputs, inlier_t, inlier_deg)
         step = captured.get(key)
         if step is None or step.fmap is not fmap or step.pose is not qp or step.stale():
             if len(captured) >= 16:
@@ -506,12 +646,13 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
 
     def forward(chunk, x):
         """-> (abs, rel, edge list, the neighbours on the device, the retrieved ones on their way to the host | None, the pose
-        rule's rows when a captured step has already made them | None)"""
+        rule's rows when a captured step has already made them | None, the one buffer that holds them and the consensus rule's
+        integers | None)"""
         nonlocal n_replays
         b0, b1 = chunk[0].first, chunk[0].first + x.shape[0]
         if rule is None and not capture:
             ab, rel, ei = model.forward_map(x, nb_dev[b0:b1], fmap, **okw)
-            return ab, rel, ei, nb_dev[b0:b1], None, None
+            return ab, rel, ei, nb_dev[b0:b1], None, None, None
         qd = None
         if qd_all is not None:
             qd = qd_all[b0:b1]
@@ -534,19 +675,21 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
             # pinned memory (read_back here and in _MicroBatchRunner.launch, right after this returns) are enqueued on the stream
             # the replay ran on BEFORE the next launch() enqueues its replay there: stream order keeps micro-batch i's results.
             return (out.abs_pose, out.rel_pose, out.edge_index, out.neighbours,
-                    None if rule is None else runner.read_back(out.neighbours), out.rows)
+                    None if rule is None else runner.read_back(out.neighbours), out.rows, step.packed)
         ab, rel, ei, nb_mb = model.forward_map(x, None, fmap, rule=rule, query_descriptors=qd, query_groups=qg, **okw)
-        return ab, rel, ei, nb_mb, runner.read_back(nb_mb), None
+        return ab, rel, ei, nb_mb, runner.read_back(nb_mb), None, None
 
     def read_back_of(chunk, x, fwd):
-        ab, rel, ei, nb_mb, host_nb, rows = fwd
+        ab, rel, ei, nb_mb, host_nb, rows, packed = fwd
         if qp is None:
             return {"nb": host_nb, "abs": ab, "rel": rel, "ei": ei if model.knn > 0 else None}
         if rows is None:
             b0, n = chunk[0].first, x.shape[0]
+            # consensus: the integers travel back WITH the rows, in one buffer and one copy
+            packed, out, ints = packed_rows(n, rel.device) if consensus else (None, None, None)
             rows = qp.from_map(rel, ei, fmap, nb_mb, query_targets=None if targ_dev is None else targ_dev[b0:b0 + n],
-                               edge_first=None if fc_first is None else fc_first[:n + 1])
-        return {"nb": host_nb, "rel": rows}
+                               edge_first=None if fc_first is None else fc_first[:n + 1], out=out, inliers=ints)
+        return {"nb": host_nb, "rel": rows if packed is None else packed}
 
     def target_block(g):
         target = np.zeros((n_per, 6))
@@ -560,7 +703,7 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
         if host["nb"] is not None:
             nb_h[b0:b0 + host["nb"].shape[0]] = host["nb"].numpy()
         if qp is not None:
-            acc.rows.append(host["rel"].numpy())     # the [G, 16] block of the device pose rule
+            acc.add_device(host["rel"].numpy())      # the [G, 16] block of the device pose rule (+ the consensus integers)
         elif poses_h is None:
             raw_abs.append(host["abs"])
             raw_rel.append(host["rel"])
@@ -583,4 +726,7 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
     res = acc.result(with_targets=targ_h is not None)
     if targ_h is not None:
         res.neighbours = nb_h
+    elif stats is not None and acc.ints is not None:          # no EvalResult to carry them: the two arrays go to stats
+        ints = acc.integers()
+        stats["inliers"], stats["used"] = ints[:, 0].copy(), ints[:, 1].copy()
     return res

@@ -673,17 +673,33 @@ def _qp_on_one_gpu(who, rel, ei, by_name, outputs) -> None:
         by_name[name] = by_name[name].contiguous()
 
 
-FUSE_MODES = ("mean", "median")            # the C entry point's `fuse` is the index
+FUSE_MODES = ("mean", "median", "consensus")   # the first two: the C entry point's `fuse` is the index; the third has its own
+INLIER_T, INLIER_DEG = 0.25, 5.0               # consensus thresholds: API defaults, not measured optima (evaluate.py has the same)
 
 
 def _qp_fuse(fuse, max_edges, who: str = "query_pose_fused"):
     if fuse not in FUSE_MODES:
-        raise ValueError(f"{who}: fuse must be 'mean' or 'median', got {fuse!r}")
+        raise ValueError(f"{who}: fuse must be 'mean', 'median' or 'consensus', got {fuse!r}")
     if isinstance(max_edges, bool) or not isinstance(max_edges, numbers.Integral):
         raise TypeError(f"{who}: max_edges must be an int, got {type(max_edges).__name__}")
     if not 1 <= max_edges <= 64:
         raise ValueError(f"{who}: max_edges must be in 1..64 (one candidate per lane of a wave), got {max_edges}")
     return FUSE_MODES.index(fuse), int(max_edges)
+
+
+def _qp_thresholds(inlier_t, inlier_deg, who: str = "query_pose_fused") -> Tuple[float, float]:
+    """The consensus rule's two thresholds as floats: both finite, inlier_t >= 0, 0 <= inlier_deg <= 360 (ValueError otherwise)."""
+    out = []
+    for name, v in (("inlier_t", inlier_t), ("inlier_deg", inlier_deg)):
+        if isinstance(v, bool) or not isinstance(v, numbers.Real):
+            raise ValueError(f"{who}: {name} must be a finite number, got {v!r}")
+        out.append(float(v))
+    t, deg = out
+    if not (t >= 0.0 and t != float("inf")):                 # (written so that NaN fails too)
+        raise ValueError(f"{who}: inlier_t must be finite and >= 0, got {inlier_t!r}")
+    if not 0.0 <= deg <= 360.0:
+        raise ValueError(f"{who}: inlier_deg must be in 0..360 degrees, got {inlier_deg!r}")
+    return t, deg
 
 
 def query_pose_fused(rel_pose: torch.Tensor, edge_index: torch.Tensor, *, fuse: str, max_edges: int = 64,
@@ -692,12 +708,23 @@ def query_pose_fused(rel_pose: torch.Tensor, edge_index: torch.Tensor, *, fuse: 
                      query_targets: Optional[torch.Tensor] = None, edge_first: Optional[torch.Tensor] = None,
                      pose_m=(0.0, 0.0, 0.0), pose_s=(1.0, 1.0, 1.0), status: Optional[torch.Tensor] = None,
                      out: Optional[torch.Tensor] = None, candidates: Optional[torch.Tensor] = None,
-                     counts: Optional[torch.Tensor] = None) -> torch.Tensor:
+                     counts: Optional[torch.Tensor] = None, inlier_t: float = INLIER_T, inlier_deg: float = INLIER_DEG,
+                     inliers: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``query_pose`` over ALL the edges into every graph's query node (rpg_query_pose_fused_f64; evaluate.fused_query_pose on
     the device): each such edge whose source is not the query itself is one estimate of the query's pose, the first
     ``max_edges`` (1..64) of them in column order are combined by ``fuse`` -- ``"mean"`` (mean translation, sign-aligned
     normalised quaternion sum) or ``"median"`` (component-wise median translation, medoid quaternion) -- and the row's errors are
     those of the fused pose.  The graphs' two forms, ``edge_first``, ``status``, ``out`` and the row layout are ``query_pose``'s.
+
+    ``fuse="consensus"`` (rpg_query_pose_consensus_f64; ``evaluate.consensus_query_row`` in numpy): the candidates vote.  Two
+    finite candidates support each other when their translations lie within ``inlier_t`` AND their rotations within
+    ``inlier_deg`` degrees; the candidate of largest support wins (the lowest slot among equals) and the row holds the ``"mean"``
+    of its supporters alone.  A non-finite candidate is an outlier, it voids nothing; when every used candidate is non-finite the
+    pose and both errors are NaN (not a bad graph).  ``inliers`` int32 [G, 2] (optional output, this mode only): per graph
+    (supporters of the winner, candidates used) -- their ratio is the caller's confidence; (0, used) for a bad graph.  The
+    defaults 0.25 / 5.0 are API defaults, not measured optima: both belong to the scene's scale, and ``inlier_t`` is in the unit
+    of the UN-NORMALISED translation (compared after ``* pose_s + pose_m``).  Both must be finite, ``inlier_t >= 0`` and
+    ``0 <= inlier_deg <= 360`` (ValueError); with the other modes they are checked and not used.
 
     ``candidates`` float64 [G, max_edges, 16] (optional output): used candidate c as a full row, NaN past the graph's count;
     ``counts`` int32 [G] (optional output): the usable edges found before the cut at ``max_edges``.  A graph without a usable
@@ -707,22 +734,35 @@ def query_pose_fused(rel_pose: torch.Tensor, edge_index: torch.Tensor, *, fuse: 
         who, rel_pose, edge_index, node_first, node_targets, map_poses, neighbours, query_targets, edge_first, status, out)
     pm, ps = _qp_triple(pose_m, "pose_m"), _qp_triple(pose_s, "pose_s")
     mode, max_edges = _qp_fuse(fuse, max_edges)
+    inlier_t, inlier_deg = _qp_thresholds(inlier_t, inlier_deg)
+    consensus = fuse == "consensus"
+    if inliers is not None and not consensus:
+        raise ValueError(f"{who}: inliers is an output of fuse='consensus', got fuse={fuse!r}")
     if candidates is not None:
         _qp_tensor(candidates, "candidates", torch.float64, (g, max_edges, 16), who)
     if counts is not None:
         _qp_tensor(counts, "counts", torch.int32, (g,), who)
-    for name, t in (("candidates", candidates), ("counts", counts)):
+    if inliers is not None:
+        _qp_tensor(inliers, "inliers", torch.int32, (g, 2), who)
+    for name, t in (("candidates", candidates), ("counts", counts), ("inliers", inliers)):
         if t is not None and not t.is_contiguous():
             raise ValueError(f"{who}: {name} must be contiguous")
-    _qp_on_one_gpu(who, rel, ei, by_name, [("out", out), ("candidates", candidates), ("counts", counts)])
+    _qp_on_one_gpu(who, rel, ei, by_name, [("out", out), ("candidates", candidates), ("counts", counts), ("inliers", inliers)])
     rel, ei = rel.contiguous(), ei.contiguous()
     if out is None:
         out = torch.empty((g, 16), dtype=torch.float64, device=rel.device)
-    L.check(L.lib().rpg_query_pose_fused_f64(_p(rel), ei.data_ptr(), ei.data_ptr() + 8 * e, e, _p(by_name.get("node_first")),
-                                             _p(by_name.get("edge_first")), g, _p(by_name.get("node_targets")), n,
-                                             _p(by_name.get("map_poses")), m, _p(by_name.get("neighbours")), k,
-                                             _p(by_name.get("query_targets")), *pm, *ps, mode, max_edges, _p(out),
-                                             _p(candidates), _p(counts), status.data_ptr(), _stream()), who)
+    if consensus:
+        L.check(L.lib().rpg_query_pose_consensus_f64(
+            _p(rel), ei.data_ptr(), ei.data_ptr() + 8 * e, e, _p(by_name.get("node_first")), _p(by_name.get("edge_first")), g,
+            _p(by_name.get("node_targets")), n, _p(by_name.get("map_poses")), m, _p(by_name.get("neighbours")), k,
+            _p(by_name.get("query_targets")), *pm, *ps, max_edges, inlier_t, inlier_deg, _p(out), _p(candidates), _p(counts),
+            _p(inliers), status.data_ptr(), _stream()), who)
+    else:
+        L.check(L.lib().rpg_query_pose_fused_f64(_p(rel), ei.data_ptr(), ei.data_ptr() + 8 * e, e, _p(by_name.get("node_first")),
+                                                 _p(by_name.get("edge_first")), g, _p(by_name.get("node_targets")), n,
+                                                 _p(by_name.get("map_poses")), m, _p(by_name.get("neighbours")), k,
+                                                 _p(by_name.get("query_targets")), *pm, *ps, mode, max_edges, _p(out),
+                                                 _p(candidates), _p(counts), status.data_ptr(), _stream()), who)
     bad = _own_count(status, own)
     if bad:
         raise ValueError(f"graph has no edge into node 0: cannot derive the query pose ({bad} graph(s) of this call have no "

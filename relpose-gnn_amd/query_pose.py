@@ -16,6 +16,13 @@ call, so nothing blocks unless the caller asks it to.
 not the query) is an estimate of the query's pose, and the row holds their combination (``ops.query_pose_fused``,
 rpg_query_pose_fused_f64; ``evaluate.fused_query_pose`` is the rule in numpy).  Same row layout, same status word, same
 ``publish`` / ``check`` contract; a bad graph is then one without a usable edge or with a used edge from outside the graph.
+
+``QueryPose(fuse="consensus", inlier_t=..., inlier_deg=...)`` is the mode that says whether the pose can be believed: the
+candidates vote (two support each other when their translations lie within ``inlier_t`` and their rotations within
+``inlier_deg`` degrees), the best-supported one wins and the row is the mean of its supporters alone
+(rpg_query_pose_consensus_f64, the same kernel's third mode; ``evaluate.consensus_query_row`` is the rule in numpy).  With
+``inliers=`` (int32 [G, 2]) every graph also gets (supporters of the winner, candidates used): their ratio is the accept /
+reject signal that goes with the pose.  A non-finite candidate is an outlier there, it does not void the pose.
 """
 from __future__ import annotations
 
@@ -25,15 +32,39 @@ from . import ops
 from .status import DeferredCounters
 
 
+ROW_BYTES, INT_BYTES = 16 * 8, 2 * 4       # per graph: the row of 16 doubles, and the consensus rule's (inliers, used)
+
+
+def packed_rows(g: int, device):
+    """The consensus rule's two outputs of ``g`` graphs in ONE allocation, so that a stream brings both back with one copy: ->
+    (buf uint8 [g * 136], rows float64 [g, 16] = its first g * 128 bytes, inliers int32 [g, 2] = the rest).  ``unpack_rows`` cuts
+    the host copy of ``buf`` the same way."""
+    buf = torch.empty(g * (ROW_BYTES + INT_BYTES), dtype=torch.uint8, device=device)
+    return buf, buf[:g * ROW_BYTES].view(torch.float64).view(g, 16), buf[g * ROW_BYTES:].view(torch.int32).view(g, 2)
+
+
+def unpack_rows(buf):
+    """uint8 [g * 136] (a tensor or a numpy array, on the host) -> (rows float64 [g, 16], inliers int32 [g, 2]), views of it."""
+    g = buf.shape[0] // (ROW_BYTES + INT_BYTES)
+    if torch.is_tensor(buf):
+        return buf[:g * ROW_BYTES].view(torch.float64).view(g, 16), buf[g * ROW_BYTES:].view(torch.int32).view(g, 2)
+    return buf[:g * ROW_BYTES].view("<f8").reshape(g, 16), buf[g * ROW_BYTES:].view("<i4").reshape(g, 2)
+
+
 class QueryPose:
-    def __init__(self, pose_m=(0.0, 0.0, 0.0), pose_s=(1.0, 1.0, 1.0), ref_node: int = 0, fuse=None, max_edges: int = 64):
+    def __init__(self, pose_m=(0.0, 0.0, 0.0), pose_s=(1.0, 1.0, 1.0), ref_node: int = 0, fuse=None, max_edges: int = 64,
+                 inlier_t: float = ops.INLIER_T, inlier_deg: float = ops.INLIER_DEG):
         """``pose_m`` / ``pose_s``: translation mean / std (test.py:126-130, 248-251); ``ref_node``: which of the edges into the
-        query node is the reference edge (test.py:227-229).  ``fuse``: None (that one edge), or ``"mean"`` / ``"median"``: the
-        first ``max_edges`` (1..64) edges into the query node combined -- there is no reference edge then, so ``ref_node`` must
-        stay 0."""
+        query node is the reference edge (test.py:227-229).  ``fuse``: None (that one edge), or ``"mean"`` / ``"median"`` /
+        ``"consensus"``: the first ``max_edges`` (1..64) edges into the query node combined -- there is no reference edge then,
+        so ``ref_node`` must stay 0.  ``inlier_t`` / ``inlier_deg``: the thresholds of ``"consensus"`` (checked always, used by
+        that mode only).  Their defaults 0.25 / 5.0 are API defaults, not measured optima: they belong to the scene's scale, and
+        ``inlier_t`` is compared after ``* pose_s + pose_m``, i.e. in the unit of the un-normalised translation.  Both finite,
+        ``inlier_t >= 0``, ``0 <= inlier_deg <= 360`` (ValueError)."""
         self.pose_m, self.pose_s = ops._qp_triple(pose_m, "pose_m"), ops._qp_triple(pose_s, "pose_s")
         self.ref_node = ops._qp_ref_node(ref_node)
         self.fuse, self.max_edges = fuse, max_edges
+        self.inlier_t, self.inlier_deg = ops._qp_thresholds(inlier_t, inlier_deg, "QueryPose")
         if fuse is not None:
             ops._qp_fuse(fuse, max_edges, "QueryPose")
             if self.ref_node != 0:
@@ -43,29 +74,33 @@ class QueryPose:
 
     # ---- the two forms ---------------------------------------------------------------------------------------------------
     def from_targets(self, rel_pose, edge_index, node_first, node_targets, edge_first=None, out=None, candidates=None,
-                     counts=None) -> torch.Tensor:
+                     counts=None, inliers=None) -> torch.Tensor:
         """Graphs with collated targets (``evaluate_stream``): ``node_first`` int64 [G + 1], ``node_targets`` fp32 [N, 6] =
         the batch's ``data.y``.  -> float64 [G, 16] on the device.  With ``fuse``, optional outputs: ``candidates`` float64
-        [G, max_edges, 16] (every used candidate as a row) and ``counts`` int32 [G] (usable edges before the cut)."""
+        [G, max_edges, 16] (every used candidate as a row) and ``counts`` int32 [G] (usable edges before the cut); with
+        ``fuse="consensus"`` also ``inliers`` int32 [G, 2] = (supporters of the winning candidate, candidates used)."""
         return self._run(rel_pose, dict(edge_index=edge_index, node_first=node_first, node_targets=node_targets,
-                                        edge_first=edge_first, out=out), candidates, counts)
+                                        edge_first=edge_first, out=out), candidates, counts, inliers)
 
     def from_map(self, rel_pose, edge_index, fmap, neighbours, query_targets=None, edge_first=None, out=None, candidates=None,
-                 counts=None) -> torch.Tensor:
+                 counts=None, inliers=None) -> torch.Tensor:
         """Graphs of the map path (``forward_map`` / ``relocalize``): graph g is query g followed by the rows ``neighbours[g]``
         of ``fmap``, whose ``poses`` are the database images' targets; ``query_targets`` fp32 [G, 6] are the queries' own (None:
         zeros, the rows' ``targ`` part and errors then mean nothing).  -> float64 [G, 16] on the device.  ``candidates`` /
-        ``counts``: as in ``from_targets``."""
+        ``counts`` / ``inliers``: as in ``from_targets``."""
         poses = getattr(fmap, "poses", None)
         if poses is None:
             raise ValueError("QueryPose.from_map: the feature map holds no poses (build it with poses=...): a query's pose is "
                              "its database image's pose minus the predicted relative pose")
         return self._run(rel_pose, dict(edge_index=edge_index, map_poses=poses, neighbours=neighbours,
-                                        query_targets=query_targets, edge_first=edge_first, out=out), candidates, counts)
+                                        query_targets=query_targets, edge_first=edge_first, out=out), candidates, counts, inliers)
 
-    def _run(self, rel_pose, kw, candidates=None, counts=None) -> torch.Tensor:
+    def _run(self, rel_pose, kw, candidates=None, counts=None, inliers=None) -> torch.Tensor:
         if self.fuse is None and (candidates is not None or counts is not None):
-            raise ValueError("QueryPose: candidates / counts are outputs of the fused rule (fuse='mean' or 'median')")
+            raise ValueError("QueryPose: candidates / counts are outputs of the fused rule (fuse='mean', 'median' or "
+                             "'consensus')")
+        if self.fuse != "consensus" and inliers is not None:
+            raise ValueError(f"QueryPose: inliers is an output of fuse='consensus', this rule has fuse={self.fuse!r}")
         if torch.is_tensor(rel_pose) and rel_pose.is_cuda:      # (anything else is refused by ops.query_pose below)
             status = self._bad.tensor(rel_pose.device)
         else:
@@ -76,7 +111,8 @@ class QueryPose:
             rows = ops.query_pose(rel_pose, pose_m=self.pose_m, pose_s=self.pose_s, ref_node=self.ref_node, status=status, **kw)
         else:
             rows = ops.query_pose_fused(rel_pose, fuse=self.fuse, max_edges=self.max_edges, pose_m=self.pose_m, pose_s=self.pose_s,
-                                        status=status, candidates=candidates, counts=counts, **kw)
+                                        status=status, candidates=candidates, counts=counts, inlier_t=self.inlier_t,
+                                        inlier_deg=self.inlier_deg, inliers=inliers, **kw)
         self._bad.publish()                       # the counter's copy to pinned memory, behind this call's kernel
         return rows
 

@@ -19,9 +19,17 @@ against eager ``forward_map`` (here and in the baseline checkout).
 ``--only LEG`` runs one leg in one mode in a loop, for a profiler (``rocprofv3 --kernel-trace --stats -- python
 tools/postprocess_bench.py --only 256x341_bf16:device``), and prints the wall time of the timed loop to relate kernel time to.
 
+``--against MODE`` (with ``--baseline-root DIR`` and ONE mode in ``--modes``, both written as rows are named, e.g. ``--modes
+device+consensus --against device+median``) holds a new mode of this checkout against another mode of the baseline checkout:
+``--rounds`` times in turn a child process measures MODE there and a child process measures the mode here, so that both see the
+same box in the same minutes; reported are every round's rates, the median and spread over all of a side's timed calls, and
+whether this side is slower by more than the larger of 3 % and the observed spread.
+
 usage: tools/postprocess_bench.py [--reps 3] [--baseline-root DIR] [--out profiles/query_pose_bench.json]
        tools/postprocess_bench.py --fuse mean,median --baseline-root DIR --out profiles/query_pose_fused_bench.json
-       tools/postprocess_bench.py --capture --baseline-root DIR --out profiles/relocalize_capture_bench.json"""
+       tools/postprocess_bench.py --capture --baseline-root DIR --out profiles/relocalize_capture_bench.json
+       tools/postprocess_bench.py --modes device+consensus --against device+median --baseline-root DIR --legs 224x224_f32,224x224_bf16 \
+                                  --out profiles/consensus_pose_bench.json"""
 import argparse
 import json
 import os
@@ -77,6 +85,46 @@ def latency_ms(fn, calls=200):
     return {"median_ms": round(med, 4), "spread": round((ts[int(0.9 * len(ts))] - ts[int(0.1 * len(ts))]) / med, 4)}
 
 
+def alternate(args):
+    """``--against``: the baseline checkout's mode and this checkout's mode in alternating child processes."""
+    here_mode = args.modes
+    if not args.baseline_root or "," in here_mode or here_mode in ("host,device", ""):
+        raise SystemExit("--against needs --baseline-root and exactly one mode in --modes (e.g. --modes device+consensus)")
+    sides = {"baseline": (os.path.abspath(args.baseline_root), args.against), "here": (ROOT, here_mode)}
+    rounds, info = [], {}
+    for _ in range(args.rounds):
+        row = {}
+        for side, (root, mode) in sides.items():
+            cmd = [sys.executable, os.path.abspath(__file__), "--root", root, "--modes", mode, "--reps", str(args.reps), "--queries",
+                   str(args.queries), "--legs", args.legs or ",".join(f"{h}x{w}_{p}" for p in ("f32", "bf16") for h, w in GEOMS)]
+            res = subprocess.run(cmd, stdout=subprocess.PIPE, text=True, timeout=900)
+            if res.returncode != 0:
+                raise SystemExit(f"the {side} run failed with exit status {res.returncode}")
+            doc = json.loads(res.stdout.strip().splitlines()[-1])
+            info[side] = {"mode": mode, "library_digest": doc["library_digest"]}
+            info.update({k: doc[k] for k in ("K", "map_rows", "queries", "micro_batch", "reps", "device", "host", "cpus")})
+            row[side] = {key: leg[mode] for key, leg in doc["relocalize"].items()}
+            print(f"round {len(rounds)} {side} {mode}: " + ", ".join(f"{k} {v['median']}" for k, v in row[side].items()),
+                  file=sys.stderr, flush=True)
+        rounds.append(row)
+    out = {"metric": "query_pose_mode_against_baseline_mode", **info, "rounds": rounds, "legs": {}}
+    for key in rounds[0]["here"]:
+        leg = {}
+        for side in sides:
+            calls = [r for row in rounds for r in row[side][key]["graphs_per_s"]]
+            med = statistics.median(calls)
+            leg[side] = {"graphs_per_s": calls, "median": round(med, 1), "spread": round((max(calls) - min(calls)) / med, 4)}
+        spread = max(leg["baseline"]["spread"], leg["here"]["spread"])
+        ratio = leg["here"]["median"] / leg["baseline"]["median"]
+        leg.update(here_over_baseline=round(ratio, 4), spread=spread, allowed=round(max(0.03, spread), 4),
+                   slower_beyond_allowed=bool(ratio < 1.0 - max(0.03, spread)))
+        out["legs"][key] = leg
+    print(json.dumps(out), flush=True)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(json.dumps(out, indent=1) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=3)
@@ -93,7 +141,12 @@ def main():
     ap.add_argument("--legs", default=None, help="comma list of relocalize legs to keep, e.g. 256x341_bf16 (default: all four)")
     ap.add_argument("--only", default=None, help="LEG:MODE, e.g. 256x341_bf16:device -- that leg alone, for a profiler")
     ap.add_argument("--out", default=None, help="also write the JSON document to this file")
+    ap.add_argument("--against", default=None, help="a mode of the --baseline-root checkout (e.g. device+median) to hold the one "
+                    "mode of --modes against, in alternating child processes")
+    ap.add_argument("--rounds", type=int, default=3, help="--against: how often each side is run")
     args = ap.parse_args()
+    if args.against:
+        return alternate(args)
 
     import relpose_gnn_amd.synth as S
     from relpose_gnn_amd import build as B
