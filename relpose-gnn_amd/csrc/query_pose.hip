@@ -3,11 +3,18 @@
 // the first edge into the query node, `target[source] - rel_pose`, qexp, translation * std + mean, the two losses;
 // evaluate.query_pose / evaluate.errors restate it in numpy).  float64 arithmetic on the fp32 inputs, like the host code.
 //
-// One wave per graph.  The wave steps over the graph's columns 64 at a time: every lane tests one column's target against the
-// graph's first node, a ballot gathers the 64 answers in COLUMN order, popcounts are accumulated until the `ref_node`-th hit is
-// inside the current step, and the wave stops there.  Which column is chosen is a function of the column order only.  Lane 0
-// then does the few dozen double operations of one pose and stores the row of 16 doubles as eight 16-byte stores.  The only
-// atomic is the integer count of bad graphs.  One launch, no allocation, no synchronisation.
+// Three rules, two kernels, one set of pieces.  Shared by both kernels and stated once below: a graph's node span and clamped
+// column span (graph_span), the query's own target row and a source node's pose row in either graph form (target_row,
+// source_row), a row turned into (t, q) (pose_of), the two errors (trans_dist, quat_angle) and the row of 16 doubles written as
+// eight 16-byte stores (store_row, store_nan_row, store_void_row).  On the host one function checks the arguments the three
+// entry points share and fills QpArgs (qp_args); the fused launcher adds only what is its own.
+//
+// The single reference edge (query_pose_kernel): one wave per graph.  The wave steps over the graph's columns 64 at a time:
+// every lane tests one column's target against the graph's first node, a ballot gathers the 64 answers in COLUMN order,
+// popcounts are accumulated until the `ref_node`-th hit is inside the current step, and the wave stops there.  Which column is
+// chosen is a function of the column order only (a self-edge counts here; the fused rules skip it).  Lane 0 then does the few
+// dozen double operations of one pose and stores the row.  No LDS, no barrier.  The only atomic is the integer count of bad
+// graphs.  One launch, no allocation, no synchronisation.  The fused rules (query_pose_fused_kernel) are described above it.
 #include "rpg_common.h"
 
 #include <math.h>
@@ -51,137 +58,54 @@ __device__ __forceinline__ void qexp(const double* v, double* q) {
     q[3] = s * v[2];
 }
 
-__global__ __launch_bounds__(QP_NT) void query_pose_kernel(const QpArgs a) {
-#pragma clang fp contract(off)
-    const int lane = threadIdx.x & 63;
-    const int64_t gi = (int64_t)blockIdx.x * (QP_NT / 64) + (threadIdx.x >> 6);
-    if (gi >= a.g) return;                                // (the whole wave)
-    int64_t first, last;
-    if (a.node_first) {
-        first = a.node_first[gi];
-        last = a.node_first[gi + 1];
-    } else {
-        first = gi * (a.k + 1);
-        last = first + a.k + 1;
-    }
-    int64_t lo = 0, hi = a.e;
-    if (a.edge_first) {                                   // clamped: a wrong offset gives a wrong or bad row, never a read outside [0, e)
-        lo = clamp_i64(a.edge_first[gi], 0, a.e);
-        hi = clamp_i64(a.edge_first[gi + 1], 0, a.e);
-    }
-    // the ref_node-th column, in column order, whose target is the graph's first node (test.py:227-229)
-    int64_t ref = -1;
-    if (last > first) {                                   // (a graph without nodes owns no column)
-        int need = a.ref_node;
-        for (int64_t c0 = lo; c0 < hi; c0 += 64) {
-            const int64_t c = c0 + lane;
-            const bool hit = c < hi && a.edge_dst[c] == first;
-            unsigned long long mask = __ballot(hit);
-            const int cnt = __popcll(mask);
-            if (cnt > need) {
-                for (int i = 0; i < need; ++i) mask &= mask - 1;      // drop the hits before the wanted one
-                ref = c0 + (__ffsll((long long)mask) - 1);
-                break;
-            }
-            need -= cnt;
-        }
-    }
-    if (lane != 0) return;
-
-    double2* orow = reinterpret_cast<double2*>(a.out + gi * 16);
-    bool bad = ref < 0;
-    int64_t src = first;
-    if (!bad) {
-        src = a.edge_src[ref];
-        bad = src < first || src >= last;                 // the reference edge's source lies outside the graph
-    }
-    const float* trow = nullptr;                          // the query's own target row (null: zeros)
-    const float* srow = nullptr;                          // the target row of the reference edge's source node
-    if (a.node_targets) {
-        bad = bad || first < 0 || last > a.n;
-        if (!bad) {
-            trow = a.node_targets + first * 6;
-            srow = a.node_targets + src * 6;
-        }
-    } else if (!bad) {
-        trow = a.query_targets ? a.query_targets + gi * 6 : nullptr;
-        const int64_t s = src - first;                    // in [0, k]
-        if (s == 0) {
-            srow = trow;
-        } else {
-            // forward_map has counted a neighbour outside [0, m) already; here it is clamped like there
-            const int64_t idx = clamp_i64(a.neighbours[gi * a.k + (s - 1)], 0, a.m - 1);
-            srow = a.map_poses + idx * 6;
-        }
-    }
-    if (bad) {
-        atomicAdd(a.status, 1);
-        const double nan = __builtin_nan("");
-        for (int i = 0; i < 8; ++i) orow[i] = make_double2(nan, nan);
-        return;
-    }
-
-    const float* rrow = a.rel_pose + ref * 6;
-    double o[6], tg[6];
-    for (int i = 0; i < 6; ++i) {
-        o[i] = (srow ? (double)srow[i] : 0.0) - (double)rrow[i];      // test.py:231
-        tg[i] = trow ? (double)trow[i] : 0.0;
-    }
-    double pt[3], tt[3], pq[4], tq[4];
-    for (int i = 0; i < 3; ++i) {
-        pt[i] = o[i] * a.pose_s[i] + a.pose_m[i];                     // test.py:248-251
-        tt[i] = tg[i] * a.pose_s[i] + a.pose_m[i];
-    }
-    qexp(o + 3, pq);
-    qexp(tg + 3, tq);
-    const double dx = pt[0] - tt[0], dy = pt[1] - tt[1], dz = pt[2] - tt[2];
-    const double t_err = sqrt(dx * dx + dy * dy + dz * dz);
-    // 2 acos(|<q1, q2>|) in degrees (pose_utils.py:420-431); the clamp is Python's min(1.0, max(-1.0, d)): max keeps -1.0 unless
-    // d > -1.0, so a NaN dot becomes -1 and the error 360
-    double d = fabs(tq[0] * pq[0] + tq[1] * pq[1] + tq[2] * pq[2] + tq[3] * pq[3]);
-    d = d > -1.0 ? d : -1.0;
-    d = d < 1.0 ? d : 1.0;
-    const double q_err = 2.0 * acos(d) * 180.0 / M_PI;
-
-    orow[0] = make_double2(pt[0], pt[1]);
-    orow[1] = make_double2(pt[2], pq[0]);
-    orow[2] = make_double2(pq[1], pq[2]);
-    orow[3] = make_double2(pq[3], tt[0]);
-    orow[4] = make_double2(tt[1], tt[2]);
-    orow[5] = make_double2(tq[0], tq[1]);
-    orow[6] = make_double2(tq[2], tq[3]);
-    orow[7] = make_double2(t_err, q_err);
-}
-
-// ---- all of a query's reference edges fused into one pose ---------------------------------------------------------------------
-// Every column into the query node is one estimate of its pose (the single-edge rule above keeps one and drops the rest).  One
-// wave per graph again.  The wave steps over the graph's columns 64 at a time; a hit whose source is not the query itself takes
-// the next candidate slot (ballot + popcounts in column order) until `max_edges` slots are filled, and the scan goes on to the
-// end so that `count` tells what the limit cut.  Lane c then computes candidate c -- the sin / cos / sqrt of the candidates run
-// side by side -- and writes its 7 doubles to LDS (4 waves x 64 x 7 doubles = 14 KB, plus 2 KB of column indices).  Every
-// reduction is a function of the column order only: the sums of `mean` run sequentially over LDS in lane 0; for `median` every
-// lane ranks its own value (smaller values, ties by slot) and the lane(s) of the middle rank(s) are read with a cross-lane move;
-// for the medoid lane c adds up its own row of angles in slot order and a butterfly of cross-lane moves takes the lexicographic
-// minimum of (sum, c).  No floating-point atomics; the only atomic is the integer count of bad graphs.
-//
-// `consensus` (rpg_query_pose_consensus_f64) is the third mode: the candidates vote.  Lane c walks the slots in order over LDS and
-// counts, as an integer, the finite candidates within `inlier_t` and `inlier_deg` of its own (itself included, by c == d and not by
-// an angle test); the same kind of butterfly takes the lexicographic maximum of (support, lowest c); every lane then tests itself
-// against that winner, one ballot is the inlier mask in slot order and its popcount the inlier count; lane 0 runs the mean's
-// sequential sums over the masked slots.  A non-finite candidate is an outlier here, it does not void the pose.
-constexpr int QF_MEAN = 0, QF_MEDIAN = 1, QF_CONSENSUS = 2;
-constexpr int QF_MAX = 64;            // candidates per graph: one per lane
-
-struct QfArgs {
-    QpArgs q;                         // (ref_node unused)
-    int fuse, max_edges;
-    double* cand;                     // [g][max_edges][16] | null
-    int32_t* count;                   // [g] | null
-    double inlier_t, inlier_deg;      // consensus: the two thresholds
-    int32_t* inliers;                 // consensus: [g][2] = (inliers, used) | null
+// ---- what both kernels share ---------------------------------------------------------------------------------------------------
+struct QpSpan {
+    int64_t first, last;              // the graph's nodes [first, last); `first` is the query
+    int64_t lo, hi;                   // its columns [lo, hi), clamped: a wrong offset gives a wrong or bad row, never a read outside [0, e)
 };
 
-// 2 acos(|<p, q>|) in degrees (pose_utils.py:420-431) with Python's min(1.0, max(-1.0, d)), as in the kernel above
+__device__ __forceinline__ QpSpan graph_span(const QpArgs& a, int64_t gi) {
+    QpSpan s;
+    s.first = a.node_first ? a.node_first[gi] : gi * (a.k + 1);
+    s.last = a.node_first ? a.node_first[gi + 1] : s.first + a.k + 1;
+    s.lo = a.edge_first ? clamp_i64(a.edge_first[gi], 0, a.e) : 0;
+    s.hi = a.edge_first ? clamp_i64(a.edge_first[gi + 1], 0, a.e) : a.e;
+    return s;
+}
+
+// targets form: whether the graph's nodes lie outside node_targets (no row of such a graph is read)
+__device__ __forceinline__ bool outside_targets(const QpArgs& a, const QpSpan& s) {
+    return a.node_targets && (s.first < 0 || s.last > a.n);
+}
+
+// the query's own target row (null: zeros)
+__device__ __forceinline__ const float* target_row(const QpArgs& a, int64_t gi, const QpSpan& s) {
+    if (a.node_targets) return a.node_targets + s.first * 6;
+    return a.query_targets ? a.query_targets + gi * 6 : nullptr;
+}
+
+// the pose row of source node `src` in [first, last): its target, or in the map form the query's own row (`trow`) for src == first
+// and else the map row of its neighbour -- forward_map has counted a neighbour outside [0, m) already; here it is clamped like there
+__device__ __forceinline__ const float* source_row(const QpArgs& a, int64_t gi, const QpSpan& s, int64_t src, const float* trow) {
+    if (a.node_targets) return a.node_targets + src * 6;
+    if (src == s.first) return trow;
+    return a.map_poses + clamp_i64(a.neighbours[gi * a.k + (src - s.first - 1)], 0, a.m - 1) * 6;
+}
+
+// (t, q) of the normalised [t, log q] row `row` (null: zeros) minus, when given, the relative pose `rel`: test.py:231, 248-251
+__device__ __forceinline__ void pose_of(const QpArgs& a, const float* row, const float* rel, double* t, double* q) {
+#pragma clang fp contract(off)
+    double v[6];
+    for (int i = 0; i < 6; ++i) {
+        v[i] = row ? (double)row[i] : 0.0;
+        if (rel) v[i] = v[i] - (double)rel[i];
+    }
+    for (int i = 0; i < 3; ++i) t[i] = v[i] * a.pose_s[i] + a.pose_m[i];
+    qexp(v + 3, q);
+}
+
+// 2 acos(|<p, q>|) in degrees (pose_utils.py:420-431); the clamp is Python's min(1.0, max(-1.0, d)): max keeps -1.0 unless
+// d > -1.0, so a NaN dot becomes -1 and the error 360
 __device__ __forceinline__ double quat_angle(const double* p, const double* q) {
 #pragma clang fp contract(off)
     double d = fabs(q[0] * p[0] + q[1] * p[1] + q[2] * p[2] + q[3] * p[3]);
@@ -215,6 +139,104 @@ __device__ __forceinline__ void store_nan_row(double* row) {
     for (int i = 0; i < 8; ++i) orow[i] = make_double2(nan, nan);
 }
 
+// a row whose pose and errors are NaN behind a target that stands
+__device__ __forceinline__ void store_void_row(double* row, const double* tt, const double* tq) {
+    const double nan = __builtin_nan("");
+    const double nt[3] = {nan, nan, nan}, nq[4] = {nan, nan, nan, nan};
+    store_row(row, nt, nq, tt, tq, nan, nan);
+}
+
+// ---- the single reference edge --------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(QP_NT) void query_pose_kernel(const QpArgs a) {
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x & 63;
+    const int64_t gi = (int64_t)blockIdx.x * (QP_NT / 64) + (threadIdx.x >> 6);
+    if (gi >= a.g) return;                                // (the whole wave)
+    const QpSpan s = graph_span(a, gi);
+    // the ref_node-th column, in column order, whose target is the graph's first node (test.py:227-229); a self-edge counts
+    int64_t ref = -1;
+    if (s.last > s.first) {                               // (a graph without nodes owns no column)
+        int need = a.ref_node;
+        for (int64_t c0 = s.lo; c0 < s.hi; c0 += 64) {
+            const int64_t c = c0 + lane;
+            const bool hit = c < s.hi && a.edge_dst[c] == s.first;
+            unsigned long long mask = __ballot(hit);
+            const int cnt = __popcll(mask);
+            if (cnt > need) {
+                for (int i = 0; i < need; ++i) mask &= mask - 1;      // drop the hits before the wanted one
+                ref = c0 + (__ffsll((long long)mask) - 1);
+                break;
+            }
+            need -= cnt;
+        }
+    }
+    if (lane != 0) return;
+
+    bool bad = ref < 0;
+    int64_t src = s.first;
+    if (!bad) {
+        src = a.edge_src[ref];
+        bad = src < s.first || src >= s.last;             // the reference edge's source lies outside the graph
+    }
+    if (bad || outside_targets(a, s)) {
+        atomicAdd(a.status, 1);
+        store_nan_row(a.out + gi * 16);
+        return;
+    }
+    const float* trow = target_row(a, gi, s);
+    double pt[3], pq[4], tt[3], tq[4];
+    pose_of(a, source_row(a, gi, s, src, trow), a.rel_pose + ref * 6, pt, pq);
+    pose_of(a, trow, nullptr, tt, tq);
+    store_row(a.out + gi * 16, pt, pq, tt, tq, trans_dist(pt, tt), quat_angle(pq, tq));
+}
+
+// ---- all of a query's reference edges fused into one pose ---------------------------------------------------------------------
+// Every column into the query node is one estimate of its pose (the single-edge rule above keeps one and drops the rest).  One
+// wave per graph again.  The wave steps over the graph's columns 64 at a time; a hit whose source is not the query itself takes
+// the next candidate slot (ballot + popcounts in column order) until `max_edges` slots are filled, and the scan goes on to the
+// end so that `count` tells what the limit cut.  Lane c then computes candidate c -- the sin / cos / sqrt of the candidates run
+// side by side -- and writes its 7 doubles to LDS (4 waves x 64 x 7 doubles = 14 KB, plus 2 KB of column indices).  Every
+// reduction is a function of the column order only: the sums of `mean` run sequentially over LDS in lane 0 (mean_of, over a
+// slot mask: the low C bits here, the inlier mask for `consensus`); for `median` every
+// lane ranks its own value (smaller values, ties by slot) and the lane(s) of the middle rank(s) are read with a cross-lane move;
+// for the medoid lane c adds up its own row of angles in slot order and a butterfly of cross-lane moves takes the lexicographic
+// minimum of (sum, c).  No floating-point atomics; the only atomic is the integer count of bad graphs.
+//
+// `consensus` (rpg_query_pose_consensus_f64) is the third mode: the candidates vote.  Lane c walks the slots in order over LDS and
+// counts, as an integer, the finite candidates within `inlier_t` and `inlier_deg` of its own (itself included, by c == d and not by
+// an angle test); the same kind of butterfly takes the lexicographic maximum of (support, lowest c); every lane then tests itself
+// against that winner, one ballot is the inlier mask in slot order and its popcount the inlier count; lane 0 runs the mean's
+// sequential sums over the masked slots.  A non-finite candidate is an outlier here, it does not void the pose.
+constexpr int QF_MEAN = 0, QF_MEDIAN = 1, QF_CONSENSUS = 2;
+constexpr int QF_MAX = 64;            // candidates per graph: one per lane
+
+struct QfArgs {
+    QpArgs q;                         // (ref_node unused)
+    int fuse, max_edges;
+    double* cand;                     // [g][max_edges][16] | null
+    int32_t* count;                   // [g] | null
+    double inlier_t, inlier_deg;      // consensus: the two thresholds
+    int32_t* inliers;                 // consensus: [g][2] = (inliers, used) | null
+};
+
+// The `mean` of the candidates (t[3], q[4]) whose slot is set in `mask` (never empty), every sum sequential in slot order:
+// t = the sum / n; q = S / |S| with S the sum of q_c where <q_c, q_0> >= 0 and of -q_c elsewhere, q_0 = the first set slot, and
+// q_0 itself where |S| = 0.
+__device__ __forceinline__ void mean_of(const double (*cand)[7], unsigned long long mask, double* ft, double* fq) {
+#pragma clang fp contract(off)
+    const double* c0 = cand[__ffsll((long long)mask) - 1];
+    double st[3] = {0.0, 0.0, 0.0}, sq[4] = {0.0, 0.0, 0.0, 0.0};
+    for (unsigned long long rest = mask; rest != 0ull; rest &= rest - 1ull) {
+        const double* cd = cand[__ffsll((long long)rest) - 1];
+        for (int i = 0; i < 3; ++i) st[i] = st[i] + cd[i];
+        const double dot = cd[3] * c0[3] + cd[4] * c0[4] + cd[5] * c0[5] + cd[6] * c0[6];
+        for (int i = 0; i < 4; ++i) sq[i] = dot >= 0.0 ? sq[i] + cd[3 + i] : sq[i] - cd[3 + i];
+    }
+    for (int i = 0; i < 3; ++i) ft[i] = st[i] / (double)__popcll(mask);
+    const double norm = sqrt(sq[0] * sq[0] + sq[1] * sq[1] + sq[2] * sq[2] + sq[3] * sq[3]);
+    for (int i = 0; i < 4; ++i) fq[i] = norm == 0.0 ? c0[3 + i] : sq[i] / norm;
+}
+
 // whether two FINITE candidates (t[3], q[4]) support each other: symmetric bit for bit -- the squares and the products of the dot
 // are the same numbers either way round
 __device__ __forceinline__ bool cons_support(const double* c, const double* d, double inlier_t, double inlier_deg) {
@@ -232,24 +254,14 @@ __global__ __launch_bounds__(QP_NT) void query_pose_fused_kernel(const QfArgs f)
     const bool active = gi < a.g;                         // (wave-uniform; no wave leaves before the last barrier)
 
     // ---- the usable columns, in column order: target = the graph's first node, source != that node -------------------------------
-    int64_t first = 0, last = 0, found = 0;
+    QpSpan s = {0, 0, 0, 0};
+    int64_t found = 0;
     if (active) {
-        if (a.node_first) {
-            first = a.node_first[gi];
-            last = a.node_first[gi + 1];
-        } else {
-            first = gi * (a.k + 1);
-            last = first + a.k + 1;
-        }
-        int64_t lo = 0, hi = a.e;
-        if (a.edge_first) {                               // clamped, as above
-            lo = clamp_i64(a.edge_first[gi], 0, a.e);
-            hi = clamp_i64(a.edge_first[gi + 1], 0, a.e);
-        }
-        if (last > first) {
-            for (int64_t c0 = lo; c0 < hi; c0 += 64) {
+        s = graph_span(a, gi);
+        if (s.last > s.first) {
+            for (int64_t c0 = s.lo; c0 < s.hi; c0 += 64) {
                 const int64_t c = c0 + lane;
-                const bool hit = c < hi && a.edge_dst[c] == first && a.edge_src[c] != first;
+                const bool hit = c < s.hi && a.edge_dst[c] == s.first && a.edge_src[c] != s.first;
                 const unsigned long long mask = __ballot(hit);
                 if (hit) {
                     const int64_t slot = found + __popcll(mask & ((1ull << lane) - 1ull));
@@ -270,39 +282,20 @@ __global__ __launch_bounds__(QP_NT) void query_pose_fused_kernel(const QfArgs f)
     for (int i = 0; i < 3; ++i) pt[i] = tt[i] = 0.0;
     for (int i = 0; i < 4; ++i) pq[i] = tq[i] = 0.0;
     if (active) {
-        int64_t col = 0, src = first;
+        int64_t col = 0, src = s.first;
         bool bad_lane = false;
         if (mine) {
             col = s_col[w][lane];
             src = a.edge_src[col];
-            bad_lane = src < first || src >= last;        // a used edge's source lies outside the graph
+            bad_lane = src < s.first || src >= s.last;    // a used edge's source lies outside the graph
         }
-        bad = cn == 0 || __ballot(bad_lane) != 0ull;
-        if (a.node_targets) bad = bad || first < 0 || last > a.n;
+        bad = cn == 0 || __ballot(bad_lane) != 0ull || outside_targets(a, s);
         if (!bad) {
-            const float* trow;                            // the query's own target row (null: zeros)
-            const float* srow = nullptr;                  // the target row of this candidate's source node
-            if (a.node_targets) {
-                trow = a.node_targets + first * 6;
-                if (mine) srow = a.node_targets + src * 6;
-            } else {
-                trow = a.query_targets ? a.query_targets + gi * 6 : nullptr;
-                if (mine) {                               // src - first in [1, k]: the query's own node is never a source here
-                    const int64_t idx = clamp_i64(a.neighbours[gi * a.k + (src - first - 1)], 0, a.m - 1);
-                    srow = a.map_poses + idx * 6;
-                }
-            }
-            double tg[6];
-            for (int i = 0; i < 6; ++i) tg[i] = trow ? (double)trow[i] : 0.0;
-            for (int i = 0; i < 3; ++i) tt[i] = tg[i] * a.pose_s[i] + a.pose_m[i];
-            qexp(tg + 3, tq);
+            const float* trow = target_row(a, gi, s);
+            pose_of(a, trow, nullptr, tt, tq);
             bool nf_lane = false;
-            if (mine) {
-                const float* rrow = a.rel_pose + col * 6;
-                double o[6];
-                for (int i = 0; i < 6; ++i) o[i] = (double)srow[i] - (double)rrow[i];
-                for (int i = 0; i < 3; ++i) pt[i] = o[i] * a.pose_s[i] + a.pose_m[i];
-                qexp(o + 3, pq);
+            if (mine) {                                   // (the query's own node is never a source here)
+                pose_of(a, source_row(a, gi, s, src, trow), a.rel_pose + col * 6, pt, pq);
                 t_err = trans_dist(pt, tt);
                 q_err = quat_angle(pq, tq);
                 for (int i = 0; i < 3; ++i) {
@@ -338,8 +331,9 @@ __global__ __launch_bounds__(QP_NT) void query_pose_fused_kernel(const QfArgs f)
         }
         return;
     }
-    if (f.fuse == QF_CONSENSUS) {
-        // ---- the candidates vote (the whole wave is here) ------------------------------------------------------------------------
+    // ---- the fused pose (the whole wave is here: cross-lane moves below; lane 0 stores it) -----------------------------------------
+    double ft[3], fq[4];
+    if (f.fuse == QF_CONSENSUS) {                         // the candidates vote
         const bool fin = ((finite >> lane) & 1ull) != 0ull;
         double me[7];
         for (int i = 0; i < 3; ++i) me[i] = pt[i];
@@ -368,58 +362,26 @@ __global__ __launch_bounds__(QP_NT) void query_pose_fused_kernel(const QfArgs f)
         if (lane != 0) return;
         const int ni = __popcll(mask);
         if (f.inliers) *reinterpret_cast<int2*>(f.inliers + gi * 2) = make_int2(ni, cn);
-        const double nan = __builtin_nan("");
-        double ft[3] = {nan, nan, nan}, fq[4] = {nan, nan, nan, nan};
-        if (ni == 0) {
-            store_row(a.out + gi * 16, ft, fq, tt, tq, nan, nan);
+        if (ni == 0) {                                    // every candidate is non-finite
+            store_void_row(a.out + gi * 16, tt, tq);
             return;
         }
-        const double* c0 = s_cand[w][__ffsll((long long)mask) - 1];      // the first inlier: the mean's q_0
         if (ni == 1) {                                    // one inlier as it is
+            const double* c0 = s_cand[w][__ffsll((long long)mask) - 1];
             for (int i = 0; i < 3; ++i) ft[i] = c0[i];
             for (int i = 0; i < 4; ++i) fq[i] = c0[3 + i];
         } else {
-            double st[3] = {0.0, 0.0, 0.0}, sq[4] = {0.0, 0.0, 0.0, 0.0};
-            for (unsigned long long rest = mask; rest != 0ull; rest &= rest - 1ull) {
-                const double* cd = s_cand[w][__ffsll((long long)rest) - 1];
-                for (int i = 0; i < 3; ++i) st[i] = st[i] + cd[i];
-                const double dot = cd[3] * c0[3] + cd[4] * c0[4] + cd[5] * c0[5] + cd[6] * c0[6];
-                for (int i = 0; i < 4; ++i) sq[i] = dot >= 0.0 ? sq[i] + cd[3 + i] : sq[i] - cd[3 + i];
-            }
-            for (int i = 0; i < 3; ++i) ft[i] = st[i] / (double)ni;
-            const double norm = sqrt(sq[0] * sq[0] + sq[1] * sq[1] + sq[2] * sq[2] + sq[3] * sq[3]);
-            for (int i = 0; i < 4; ++i) fq[i] = norm == 0.0 ? c0[3 + i] : sq[i] / norm;
+            mean_of(s_cand[w], mask, ft, fq);
         }
-        store_row(a.out + gi * 16, ft, fq, tt, tq, trans_dist(ft, tt), quat_angle(fq, tq));
-        return;
-    }
-    if (cn == 1) {                                        // the candidate as it is: the single-edge rule's row
+    } else if (cn == 1) {                                 // the candidate as it is: the single-edge rule's row
         if (lane == 0) store_row(a.out + gi * 16, pt, pq, tt, tq, t_err, q_err);
         return;
-    }
-    if (void_row) {
-        if (lane == 0) {
-            const double nan = __builtin_nan("");
-            const double nt[3] = {nan, nan, nan}, nq[4] = {nan, nan, nan, nan};
-            store_row(a.out + gi * 16, nt, nq, tt, tq, nan, nan);
-        }
+    } else if (void_row) {
+        if (lane == 0) store_void_row(a.out + gi * 16, tt, tq);
         return;
-    }
-
-    // ---- the fused pose (the whole wave is here: cross-lane moves below) ----------------------------------------------------------
-    double ft[3], fq[4];
-    if (f.fuse == QF_MEAN) {
+    } else if (f.fuse == QF_MEAN) {
         if (lane != 0) return;
-        double st[3] = {0.0, 0.0, 0.0}, sq[4] = {0.0, 0.0, 0.0, 0.0};
-        for (int d = 0; d < cn; ++d) {
-            const double* cd = s_cand[w][d];
-            for (int i = 0; i < 3; ++i) st[i] = st[i] + cd[i];
-            const double dot = cd[3] * pq[0] + cd[4] * pq[1] + cd[5] * pq[2] + cd[6] * pq[3];    // <q_d, q_0>
-            for (int i = 0; i < 4; ++i) sq[i] = dot >= 0.0 ? sq[i] + cd[3 + i] : sq[i] - cd[3 + i];
-        }
-        for (int i = 0; i < 3; ++i) ft[i] = st[i] / (double)cn;
-        const double norm = sqrt(sq[0] * sq[0] + sq[1] * sq[1] + sq[2] * sq[2] + sq[3] * sq[3]);
-        for (int i = 0; i < 4; ++i) fq[i] = norm == 0.0 ? pq[i] : sq[i] / norm;
+        mean_of(s_cand[w], ~0ull >> (64 - cn), ft, fq);    // slots 0 .. cn - 1 (cn can be 64: no 1ull << cn)
     } else {
         // component-wise median of t: every lane ranks its own value, ties by slot, and the middle rank(s) are read
         for (int j = 0; j < 3; ++j) {
@@ -459,90 +421,41 @@ __global__ __launch_bounds__(QP_NT) void query_pose_fused_kernel(const QfArgs f)
 
 inline bool misaligned(const void* p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
 
-}  // namespace
+// what the three entry points share, as they declare it and as they hand it on
+#define QP_SHARED_PARAMS                                                                                                        \
+    const float *rel_pose, const int64_t *edge_src, const int64_t *edge_dst, int64_t e, const int64_t *node_first,             \
+        const int64_t *edge_first, int g, const float *node_targets, int64_t n, const float *map_poses, int64_t m,              \
+        const int64_t *neighbours, int k, const float *query_targets, double pose_m0, double pose_m1, double pose_m2,           \
+        double pose_s0, double pose_s1, double pose_s2
+#define QP_SHARED                                                                                                               \
+    rel_pose, edge_src, edge_dst, e, node_first, edge_first, g, node_targets, n, map_poses, m, neighbours, k, query_targets,   \
+        pose_m0, pose_m1, pose_m2, pose_s0, pose_s1, pose_s2
 
-extern "C" int rpg_query_pose_f64(const float* rel_pose, const int64_t* edge_src, const int64_t* edge_dst, int64_t e,
-                                  const int64_t* node_first, const int64_t* edge_first, int g, const float* node_targets,
-                                  int64_t n, const float* map_poses, int64_t m, const int64_t* neighbours, int k,
-                                  const float* query_targets, double pose_m0, double pose_m1, double pose_m2, double pose_s0,
-                                  double pose_s1, double pose_s2, int ref_node, double* out, int32_t* status, void* stream) {
-    if (!rel_pose || !edge_src || !edge_dst || !out || !status || e < 1 || g < 1 || ref_node < 0) return RPG_ERR_BAD_ARG;
-    if ((node_targets == nullptr) == (map_poses == nullptr)) return RPG_ERR_BAD_ARG;      // one source of poses, not both
+// The shared arguments checked (null, range, the two forms, alignment) and `a` filled from them; false: RPG_ERR_BAD_ARG.
+bool qp_args(QpArgs& a, QP_SHARED_PARAMS, int ref_node, double* out, int32_t* status) {
+    if (!rel_pose || !edge_src || !edge_dst || !out || !status || e < 1 || g < 1 || ref_node < 0) return false;
+    if ((node_targets == nullptr) == (map_poses == nullptr)) return false;                // one source of poses, not both
     if (node_targets) {
-        if (!node_first || n < 1 || neighbours || query_targets) return RPG_ERR_BAD_ARG;
+        if (!node_first || n < 1 || neighbours || query_targets) return false;
     } else {
-        if (node_first || !neighbours || m < 1 || k < 1) return RPG_ERR_BAD_ARG;
+        if (node_first || !neighbours || m < 1 || k < 1) return false;
     }
     if (misaligned(rel_pose, 3) || misaligned(node_targets, 3) || misaligned(map_poses, 3) || misaligned(query_targets, 3) ||
         misaligned(edge_src, 7) || misaligned(edge_dst, 7) || misaligned(node_first, 7) || misaligned(edge_first, 7) ||
         misaligned(neighbours, 7) || misaligned(status, 3) || !rpg::aligned16(out))
-        return RPG_ERR_BAD_ARG;
-    QpArgs a;
-    a.rel_pose = rel_pose;
-    a.edge_src = edge_src;
-    a.edge_dst = edge_dst;
-    a.e = e;
-    a.node_first = node_first;
-    a.edge_first = edge_first;
-    a.g = g;
-    a.node_targets = node_targets;
-    a.n = n;
-    a.map_poses = map_poses;
-    a.m = m;
-    a.neighbours = neighbours;
-    a.k = k;
-    a.query_targets = query_targets;
-    a.pose_m[0] = pose_m0, a.pose_m[1] = pose_m1, a.pose_m[2] = pose_m2;
-    a.pose_s[0] = pose_s0, a.pose_s[1] = pose_s1, a.pose_s[2] = pose_s2;
-    a.ref_node = ref_node;
-    a.out = out;
-    a.status = status;
-    const unsigned grid = (unsigned)((g + QP_NT / 64 - 1) / (QP_NT / 64));
-    hipLaunchKernelGGL(query_pose_kernel, dim3(grid), dim3(QP_NT), 0, rpg::as_stream(stream), a);
-    RPG_CHECK_LAUNCH("query_pose");
-    return RPG_OK;
+        return false;
+    a = QpArgs{rel_pose, edge_src, edge_dst, e, node_first, edge_first, g, node_targets, n, map_poses, m, neighbours, k,
+               query_targets, {pose_m0, pose_m1, pose_m2}, {pose_s0, pose_s1, pose_s2}, ref_node, out, status};
+    return true;
 }
 
-namespace {
+inline unsigned qp_grid(int g) { return (unsigned)((g + QP_NT / 64 - 1) / (QP_NT / 64)); }
 
-int launch_fused(const float* rel_pose, const int64_t* edge_src, const int64_t* edge_dst, int64_t e, const int64_t* node_first,
-                 const int64_t* edge_first, int g, const float* node_targets, int64_t n, const float* map_poses, int64_t m,
-                 const int64_t* neighbours, int k, const float* query_targets, const double* pose_m, const double* pose_s, int fuse,
-                 int max_edges, double inlier_t, double inlier_deg, double* out, double* cand, int32_t* count, int32_t* inliers,
-                 int32_t* status, void* stream) {
-    if (!rel_pose || !edge_src || !edge_dst || !out || !status || e < 1 || g < 1) return RPG_ERR_BAD_ARG;
+// the fused kernel over `f`, whose `q` qp_args has filled: what is the fused rule's own is checked and set here
+int launch_fused(QfArgs& f, int fuse, int max_edges, double inlier_t, double inlier_deg, double* cand, int32_t* count,
+                 int32_t* inliers, void* stream) {
     if (max_edges < 1 || max_edges > QF_MAX) return RPG_ERR_BAD_ARG;
-    if ((node_targets == nullptr) == (map_poses == nullptr)) return RPG_ERR_BAD_ARG;      // one source of poses, not both
-    if (node_targets) {
-        if (!node_first || n < 1 || neighbours || query_targets) return RPG_ERR_BAD_ARG;
-    } else {
-        if (node_first || !neighbours || m < 1 || k < 1) return RPG_ERR_BAD_ARG;
-    }
-    if (misaligned(rel_pose, 3) || misaligned(node_targets, 3) || misaligned(map_poses, 3) || misaligned(query_targets, 3) ||
-        misaligned(edge_src, 7) || misaligned(edge_dst, 7) || misaligned(node_first, 7) || misaligned(edge_first, 7) ||
-        misaligned(neighbours, 7) || misaligned(status, 3) || misaligned(count, 3) || misaligned(inliers, 7) ||
-        !rpg::aligned16(out) || (cand && !rpg::aligned16(cand)))
-        return RPG_ERR_BAD_ARG;
-    QfArgs f;
-    QpArgs& a = f.q;
-    a.rel_pose = rel_pose;
-    a.edge_src = edge_src;
-    a.edge_dst = edge_dst;
-    a.e = e;
-    a.node_first = node_first;
-    a.edge_first = edge_first;
-    a.g = g;
-    a.node_targets = node_targets;
-    a.n = n;
-    a.map_poses = map_poses;
-    a.m = m;
-    a.neighbours = neighbours;
-    a.k = k;
-    a.query_targets = query_targets;
-    for (int i = 0; i < 3; ++i) a.pose_m[i] = pose_m[i], a.pose_s[i] = pose_s[i];
-    a.ref_node = 0;
-    a.out = out;
-    a.status = status;
+    if (misaligned(count, 3) || misaligned(inliers, 7) || (cand && !rpg::aligned16(cand))) return RPG_ERR_BAD_ARG;
     f.fuse = fuse;
     f.max_edges = max_edges;
     f.cand = cand;
@@ -550,37 +463,33 @@ int launch_fused(const float* rel_pose, const int64_t* edge_src, const int64_t* 
     f.inlier_t = inlier_t;
     f.inlier_deg = inlier_deg;
     f.inliers = inliers;
-    const unsigned grid = (unsigned)((g + QP_NT / 64 - 1) / (QP_NT / 64));
-    hipLaunchKernelGGL(query_pose_fused_kernel, dim3(grid), dim3(QP_NT), 0, rpg::as_stream(stream), f);
+    hipLaunchKernelGGL(query_pose_fused_kernel, dim3(qp_grid(f.q.g)), dim3(QP_NT), 0, rpg::as_stream(stream), f);
     RPG_CHECK_LAUNCH("query_pose_fused");
     return RPG_OK;
 }
 
 }  // namespace
 
-extern "C" int rpg_query_pose_fused_f64(const float* rel_pose, const int64_t* edge_src, const int64_t* edge_dst, int64_t e,
-                                        const int64_t* node_first, const int64_t* edge_first, int g, const float* node_targets,
-                                        int64_t n, const float* map_poses, int64_t m, const int64_t* neighbours, int k,
-                                        const float* query_targets, double pose_m0, double pose_m1, double pose_m2,
-                                        double pose_s0, double pose_s1, double pose_s2, int fuse, int max_edges, double* out,
-                                        double* cand, int32_t* count, int32_t* status, void* stream) {
-    if (fuse != QF_MEAN && fuse != QF_MEDIAN) return RPG_ERR_BAD_ARG;
-    const double pm[3] = {pose_m0, pose_m1, pose_m2}, ps[3] = {pose_s0, pose_s1, pose_s2};
-    return launch_fused(rel_pose, edge_src, edge_dst, e, node_first, edge_first, g, node_targets, n, map_poses, m, neighbours, k,
-                        query_targets, pm, ps, fuse, max_edges, 0.0, 0.0, out, cand, count, nullptr, status, stream);
+extern "C" int rpg_query_pose_f64(QP_SHARED_PARAMS, int ref_node, double* out, int32_t* status, void* stream) {
+    QpArgs a;
+    if (!qp_args(a, QP_SHARED, ref_node, out, status)) return RPG_ERR_BAD_ARG;
+    hipLaunchKernelGGL(query_pose_kernel, dim3(qp_grid(g)), dim3(QP_NT), 0, rpg::as_stream(stream), a);
+    RPG_CHECK_LAUNCH("query_pose");
+    return RPG_OK;
 }
 
-extern "C" int rpg_query_pose_consensus_f64(const float* rel_pose, const int64_t* edge_src, const int64_t* edge_dst, int64_t e,
-                                            const int64_t* node_first, const int64_t* edge_first, int g,
-                                            const float* node_targets, int64_t n, const float* map_poses, int64_t m,
-                                            const int64_t* neighbours, int k, const float* query_targets, double pose_m0,
-                                            double pose_m1, double pose_m2, double pose_s0, double pose_s1, double pose_s2,
-                                            int max_edges, double inlier_t, double inlier_deg, double* out, double* cand,
-                                            int32_t* count, int32_t* inliers, int32_t* status, void* stream) {
+extern "C" int rpg_query_pose_fused_f64(QP_SHARED_PARAMS, int fuse, int max_edges, double* out, double* cand, int32_t* count,
+                                        int32_t* status, void* stream) {
+    QfArgs f;
+    if ((fuse != QF_MEAN && fuse != QF_MEDIAN) || !qp_args(f.q, QP_SHARED, 0, out, status)) return RPG_ERR_BAD_ARG;
+    return launch_fused(f, fuse, max_edges, 0.0, 0.0, cand, count, nullptr, stream);
+}
+
+extern "C" int rpg_query_pose_consensus_f64(QP_SHARED_PARAMS, int max_edges, double inlier_t, double inlier_deg, double* out,
+                                            double* cand, int32_t* count, int32_t* inliers, int32_t* status, void* stream) {
     // (written so that a NaN threshold fails the test too)
     if (!(inlier_t >= 0.0 && inlier_t < __builtin_inf()) || !(inlier_deg >= 0.0 && inlier_deg <= 360.0)) return RPG_ERR_BAD_ARG;
-    const double pm[3] = {pose_m0, pose_m1, pose_m2}, ps[3] = {pose_s0, pose_s1, pose_s2};
-    return launch_fused(rel_pose, edge_src, edge_dst, e, node_first, edge_first, g, node_targets, n, map_poses, m, neighbours, k,
-                        query_targets, pm, ps, QF_CONSENSUS, max_edges, inlier_t, inlier_deg, out, cand, count, inliers, status,
-                        stream);
+    QfArgs f;
+    if (!qp_args(f.q, QP_SHARED, 0, out, status)) return RPG_ERR_BAD_ARG;
+    return launch_fused(f, QF_CONSENSUS, max_edges, inlier_t, inlier_deg, cand, count, inliers, stream);
 }

@@ -12,6 +12,7 @@ streams, ``evaluate_stream`` and ``relocalize``, are clients of the micro-batch 
 from __future__ import annotations
 
 import os
+from collections import namedtuple
 from dataclasses import dataclass
 from typing import Iterable, List, Optional, Sequence
 
@@ -19,6 +20,8 @@ import numpy as np
 import torch
 
 from .graph import Data, fc_edge_index
+# the fused rules' names, the consensus rule's default thresholds (which see there) and their check: one home for host and device
+from .ops import FUSE_MODES, INLIER_DEG, INLIER_T, _qp_thresholds  # noqa: F401  (re-exported)
 from .pipeline import (_collate_on_device, _InputPipeline, _MicroBatchRunner, cut_per_graph,  # noqa: F401  (re-exported)
                        edges_per_graph, staging_workers)
 
@@ -57,10 +60,6 @@ def query_pose(rel_pose: np.ndarray, target: np.ndarray, edges: np.ndarray, pose
     return pred, targ
 
 
-FUSE_MODES = ("mean", "median", "consensus")
-# the consensus rule's thresholds: API defaults, not measured optima.  Both belong to the scene's scale; INLIER_T is in the unit of
-# the un-normalised translation (it is compared after `* pose_s + pose_m`), INLIER_DEG in degrees
-INLIER_T, INLIER_DEG = 0.25, 5.0
 _NO_EDGE = "graph has no edge into node 0: cannot derive the query pose"       # reference_edge's message
 
 
@@ -99,26 +98,13 @@ def medoid_angle_sums(q: np.ndarray) -> np.ndarray:
     return sums
 
 
-def _check_thresholds(who: str, inlier_t, inlier_deg):
-    """The consensus rule's thresholds as floats: both finite, inlier_t >= 0, 0 <= inlier_deg <= 360 (ValueError otherwise)."""
-    for name, v in (("inlier_t", inlier_t), ("inlier_deg", inlier_deg)):
-        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
-            raise ValueError(f"{who}: {name} must be a finite number, got {v!r}")
-    t, deg = float(inlier_t), float(inlier_deg)
-    if not (t >= 0.0 and t != float("inf")):                # (written so that NaN fails too)
-        raise ValueError(f"{who}: inlier_t must be finite and >= 0, got {inlier_t!r}")
-    if not 0.0 <= deg <= 360.0:
-        raise ValueError(f"{who}: inlier_deg must be in 0..360 degrees, got {inlier_deg!r}")
-    return t, deg
-
-
 def consensus_support(cands: np.ndarray, inlier_t: float = INLIER_T, inlier_deg: float = INLIER_DEG) -> np.ndarray:
     """bool [C, C]: whether candidates c and d of cands [C, 7] = (t, q) support each other.  A candidate with a non-finite
     component supports nothing and is supported by nothing; a finite one supports itself (by c == d, not by an angle test); two
     finite ones c != d support each other when ``sqrt((dx*dx + dy*dy) + dz*dz) <= inlier_t`` with d* = t_c - t_d, in that order
     of operations, and ``quaternion_angular_error(q_c, q_d) <= inlier_deg``.  Symmetric bit for bit: the squares and the
     products of the dot are the same numbers either way round."""
-    inlier_t, inlier_deg = _check_thresholds("consensus_support", inlier_t, inlier_deg)
+    inlier_t, inlier_deg = _qp_thresholds(inlier_t, inlier_deg, "consensus_support")
     cands = np.asarray(cands, dtype=np.float64)
     c = cands.shape[0]
     finite = np.isfinite(cands).all(axis=1)
@@ -161,28 +147,41 @@ def fuse_poses(cands: np.ndarray, fuse: str, *, inlier_t: float = INLIER_T, inli
     degrees; the defaults 0.25 / 5.0 are API defaults that belong to the scene's scale, not measured optima).  Here a non-finite
     candidate is an outlier and voids nothing, a lone candidate has no rule of its own, and NaN in every component means that
     every candidate was non-finite.  The thresholds are checked for every mode and read by this one."""
+    return _fuse(cands, fuse, inlier_t, inlier_deg)[0]
+
+
+def has_inlier_counts(fuse) -> bool:
+    """Whether a rule reports, per graph, how many candidates it averaged and how many voted: the consensus rule alone."""
+    return fuse == "consensus"
+
+
+def _fuse(cands, fuse, inlier_t, inlier_deg, who: str = "fuse_poses"):
+    """``fuse_poses`` with what it averaged: -> (pose [7], the slots I of ``consensus_inliers`` -- None for a rule without them)."""
     if fuse not in FUSE_MODES:
         raise ValueError(f"fuse must be 'mean', 'median' or 'consensus', got {fuse!r}")
-    inlier_t, inlier_deg = _check_thresholds("fuse_poses", inlier_t, inlier_deg)
+    inlier_t, inlier_deg = _qp_thresholds(inlier_t, inlier_deg, who)
     cands = np.asarray(cands, dtype=np.float64)
-    if fuse == "consensus":
+    inl = None
+    if has_inlier_counts(fuse):                             # the mean of the inliers, which are finite
         inl, _ = consensus_inliers(cands, inlier_t, inlier_deg)
-        return fuse_poses(cands[inl], "mean") if inl.size else np.full(7, np.nan)
+        if not inl.size:
+            return np.full(7, np.nan), inl
+        cands, fuse = cands[inl], "mean"
     c = cands.shape[0]
     if c == 1:
-        return cands[0].copy()
+        return cands[0].copy(), inl
     if not np.isfinite(cands).all():
-        return np.full(7, np.nan)
+        return np.full(7, np.nan), inl
     t, q = cands[:, :3], cands[:, 3:]
     if fuse == "median":
-        return np.hstack((np.median(t, axis=0), q[int(np.argmin(medoid_angle_sums(q)))]))      # argmin: the first of equals
+        return np.hstack((np.median(t, axis=0), q[int(np.argmin(medoid_angle_sums(q)))])), inl     # argmin: the first of equals
     st, sq = np.zeros(3), np.zeros(4)
     for d in range(c):
         st = st + t[d]
         dot = q[d, 0] * q[0, 0] + q[d, 1] * q[0, 1] + q[d, 2] * q[0, 2] + q[d, 3] * q[0, 3]
         sq = sq + q[d] if dot >= 0.0 else sq - q[d]
     norm = np.sqrt(sq[0] * sq[0] + sq[1] * sq[1] + sq[2] * sq[2] + sq[3] * sq[3])
-    return np.hstack((st / c, q[0] if norm == 0.0 else sq / norm))
+    return np.hstack((st / c, q[0] if norm == 0.0 else sq / norm)), inl
 
 
 def fused_query_pose(rel_pose: np.ndarray, target: np.ndarray, edges: np.ndarray, pose_m, pose_s, fuse: str, max_edges: int = 64, *,
@@ -201,14 +200,7 @@ def fused_query_row(rel_pose, target, edges, pose_m, pose_s, fuse: str, max_edge
     ``errors`` of the fused pose, except that a pose voided by a non-finite candidate (two or more candidates; with
     ``"consensus"``: a pose without a single finite candidate behind it) has NaN for both -- the rotation error of a NaN
     quaternion would be 360 by the reference's clamp."""
-    cands, targ, _ = pose_candidates(rel_pose, target, edges, pose_m, pose_s, max_edges)
-    pred = fuse_poses(cands, fuse, inlier_t=inlier_t, inlier_deg=inlier_deg)
-    with np.errstate(invalid="ignore"):
-        r = errors(pred[None], targ[None])
-    t_err, q_err = r.t_loss[0], r.q_loss[0]
-    if (cands.shape[0] > 1 or fuse == "consensus") and np.isnan(pred).any():
-        t_err = q_err = np.nan
-    return np.hstack((pred, targ, t_err, q_err))
+    return _fused_row(rel_pose, target, edges, pose_m, pose_s, fuse, max_edges, inlier_t, inlier_deg)[0]
 
 
 def consensus_query_row(rel_pose, target, edges, pose_m, pose_s, max_edges: int = 64, *, inlier_t: float = INLIER_T,
@@ -217,10 +209,20 @@ def consensus_query_row(rel_pose, target, edges, pose_m, pose_s, max_edges: int 
     inliers, used).  ``used`` = min(usable edges, max_edges) candidates voted, ``inliers`` of them support the winner and are
     averaged into the pose; ``inliers / used`` is the caller's confidence, ``inliers == 0`` a row whose pose and errors are NaN
     because every used candidate was non-finite.  (A graph without a usable edge raises, as in ``pose_candidates``.)"""
-    cands, _, _ = pose_candidates(rel_pose, target, edges, pose_m, pose_s, max_edges)
-    inl, _ = consensus_inliers(cands, inlier_t, inlier_deg)
-    row = fused_query_row(rel_pose, target, edges, pose_m, pose_s, "consensus", max_edges, inlier_t=inlier_t, inlier_deg=inlier_deg)
-    return row, int(inl.size), int(cands.shape[0])
+    return _fused_row(rel_pose, target, edges, pose_m, pose_s, "consensus", max_edges, inlier_t, inlier_deg, "consensus_support")
+
+
+def _fused_row(rel_pose, target, edges, pose_m, pose_s, fuse, max_edges, inlier_t, inlier_deg, who: str = "fuse_poses"):
+    """ONE graph under a fused rule, its candidates made once and its inliers found at most once: -> (row [16], inliers, used),
+    ``inliers`` None for a rule without them (``has_inlier_counts``)."""
+    cands, targ, _ = pose_candidates(rel_pose, target, edges, pose_m, pose_s, max_edges)
+    pred, inl = _fuse(cands, fuse, inlier_t, inlier_deg, who)
+    with np.errstate(invalid="ignore"):
+        r = errors(pred[None], targ[None])
+    t_err, q_err = r.t_loss[0], r.q_loss[0]
+    if (cands.shape[0] > 1 or inl is not None) and np.isnan(pred).any():
+        t_err = q_err = np.nan
+    return np.hstack((pred, targ, t_err, q_err)), None if inl is None else int(inl.size), int(cands.shape[0])
 
 
 @dataclass
@@ -253,44 +255,37 @@ def errors(pred_poses: np.ndarray, targ_poses: np.ndarray) -> EvalResult:
 
 class _PoseRows:
     """What a stream collects micro-batch by micro-batch, and the result made of it: the [G, 16] blocks of the device pose
-    rule (``on_device``), or the (pred, targ) rows of the host rule of test.py:213-251.  With ``fuse`` the host rule is
-    ``fused_query_row`` and collects the same [G, 16] blocks as the device.  With ``fuse="consensus"`` every block comes with
-    its int [G, 2] block of (inliers, used) (``ints``), from the device or from ``consensus_query_row``."""
+    rule (``pose``, the stream's ``QueryPose``), or the (pred, targ) rows of the host rule of test.py:213-251.  With ``fuse`` the
+    host rule is ``_fused_row`` and collects the same [G, 16] blocks as the device.  A rule with inlier counts
+    (``has_inlier_counts``) adds an int [G, 2] block of (inliers, used) to every block (``ints``), on either path."""
 
-    def __init__(self, pose_m, pose_s, ref_node: int, on_device: bool, fuse=None, max_edges: int = 64,
+    def __init__(self, pose_m, pose_s, ref_node: int, pose=None, fuse=None, max_edges: int = 64,
                  inlier_t: float = INLIER_T, inlier_deg: float = INLIER_DEG):
         self.pose_m, self.pose_s = np.asarray(pose_m, dtype=np.float64), np.asarray(pose_s, dtype=np.float64)
-        self.ref_node = ref_node
+        self.ref_node, self.pose = ref_node, pose
         self.fuse, self.max_edges = fuse, max_edges
         self.inlier_t, self.inlier_deg = inlier_t, inlier_deg
-        self.ints: Optional[List[np.ndarray]] = [] if fuse == "consensus" else None
-        self.rows: Optional[List[np.ndarray]] = [] if on_device or fuse is not None else None
+        self.ints: Optional[List[np.ndarray]] = [] if has_inlier_counts(fuse) else None
+        self.rows: Optional[List[np.ndarray]] = [] if pose is not None or fuse is not None else None
         self.preds: List[np.ndarray] = []
         self.targs: List[np.ndarray] = []
 
     def add_device(self, block: np.ndarray) -> None:
-        """One micro-batch as the device rule sent it: its [G, 16] block, or with ``fuse="consensus"`` the uint8 buffer of
-        ``query_pose.packed_rows`` -- that block and the int32 [G, 2] integers behind it, which came back in one copy."""
-        if self.ints is not None:
-            from .query_pose import unpack_rows
-            block, ints = unpack_rows(block)
+        """One micro-batch as the device rule sent it: the host copy of its output block (``QueryPose.output_block``)."""
+        rows, ints = self.pose.cut_block(block)
+        if ints is not None:
             self.ints.append(ints)
-        self.rows.append(block)
+        self.rows.append(rows)
 
     def add(self, rel: np.ndarray, targets: Iterable, cut: Iterable) -> None:
         """The host rule over one micro-batch: per graph its targets [n, 6] and its (columns of ``rel``, local edge list)."""
-        if self.fuse == "consensus":
-            both = [consensus_query_row(rel[cols], target, edges, self.pose_m, self.pose_s, self.max_edges, inlier_t=self.inlier_t,
-                                        inlier_deg=self.inlier_deg) for target, (cols, edges) in zip(targets, cut)]
-            if both:
-                self.rows.append(np.stack([row for row, _, _ in both]))
-                self.ints.append(np.asarray([[inl, used] for _, inl, used in both], dtype=np.int64))
-            return
         if self.fuse is not None:
-            rows = [fused_query_row(rel[cols], target, edges, self.pose_m, self.pose_s, self.fuse, self.max_edges)
-                    for target, (cols, edges) in zip(targets, cut)]
-            if rows:
-                self.rows.append(np.stack(rows))
+            got = [_fused_row(rel[cols], target, edges, self.pose_m, self.pose_s, self.fuse, self.max_edges, self.inlier_t,
+                              self.inlier_deg) for target, (cols, edges) in zip(targets, cut)]
+            if got:
+                self.rows.append(np.stack([row for row, _, _ in got]))
+                if self.ints is not None:
+                    self.ints.append(np.asarray([[inl, used] for _, inl, used in got], dtype=np.int64))
             return
         for target, (cols, edges) in zip(targets, cut):
             p, t = query_pose(rel[cols], target, edges, self.pose_m, self.pose_s, self.ref_node)
@@ -397,7 +392,7 @@ def _check_postprocess(who: str, postprocess, device) -> None:
 
 
 def _check_fuse(who: str, fuse, max_edges, ref_node, inlier_t=INLIER_T, inlier_deg=INLIER_DEG) -> None:
-    _check_thresholds(who, inlier_t, inlier_deg)
+    _qp_thresholds(inlier_t, inlier_deg, who)
     if fuse is None:
         return
     if fuse not in FUSE_MODES:
@@ -407,6 +402,11 @@ def _check_fuse(who: str, fuse, max_edges, ref_node, inlier_t=INLIER_T, inlier_d
     if ref_node != 0:
         raise ValueError(f"{who}: fuse={fuse!r} combines every edge into the query node, ref_node={ref_node} selects one: give "
                          "one of the two")
+
+
+# what relocalize's forward hands to its read-back: forward_map's outputs, the neighbours on the device, the retrieved ones on
+# their way to the host (None: they were given), and the pose rule's output block where a captured step has already filled it
+_Forward = namedtuple("_Forward", "abs_pose rel_pose edge_index neighbours host_neighbours back", defaults=(None, None))
 
 
 def _result_from_rows(rows: np.ndarray) -> EvalResult:
@@ -422,7 +422,7 @@ def _evaluate_stream(model, graphs, device, micro_batch, pose_m, pose_s, ref_nod
         from .query_pose import QueryPose
         qp = QueryPose(pose_m, pose_s, ref_node, fuse=fuse, max_edges=max_edges, inlier_t=inlier_t, inlier_deg=inlier_deg)
     lo, hi = shard_range(len(graphs), rank, world)
-    acc = _PoseRows(pose_m, pose_s, ref_node, on_device=qp is not None, fuse=fuse, max_edges=max_edges, inlier_t=inlier_t,
+    acc = _PoseRows(pose_m, pose_s, ref_node, pose=qp, fuse=fuse, max_edges=max_edges, inlier_t=inlier_t,
                     inlier_deg=inlier_deg)
     runner = _MicroBatchRunner(model, device, micro_batch, bf16_input, local_world, pose=qp)
 
@@ -620,11 +620,8 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
             targ_dev = t32 if t32.is_cuda else (t32 if t32.is_pinned() else t32.pin_memory()).to(device, non_blocking=True)
         if model.knn <= 0:         # forward_map's own FC list: n (n - 1) columns per graph, graph after graph
             fc_first = torch.arange(min(micro_batch, g_all) + 1, dtype=torch.int64, device=device) * fc_edges.shape[1]
-    acc = _PoseRows(pose_m, pose_s, ref_node, on_device=qp is not None, fuse=fuse, max_edges=max_edges, inlier_t=inlier_t,
+    acc = _PoseRows(pose_m, pose_s, ref_node, pose=qp, fuse=fuse, max_edges=max_edges, inlier_t=inlier_t,
                     inlier_deg=inlier_deg)
-    consensus = qp is not None and fuse == "consensus"        # the device rule also fills an int32 [G, 2] block per micro-batch
-    if consensus:
-        from .query_pose import packed_rows
     raw_abs, raw_rel = [], []
 
     def captured_step(x, qd, targ):
@@ -645,14 +642,11 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
         return step
 
     def forward(chunk, x):
-        """-> (abs, rel, edge list, the neighbours on the device, the retrieved ones on their way to the host | None, the pose
-        rule's rows when a captured step has already made them | None, the one buffer that holds them and the consensus rule's
-        integers | None)"""
         nonlocal n_replays
         b0, b1 = chunk[0].first, chunk[0].first + x.shape[0]
         if rule is None and not capture:
             ab, rel, ei = model.forward_map(x, nb_dev[b0:b1], fmap, **okw)
-            return ab, rel, ei, nb_dev[b0:b1], None, None, None
+            return _Forward(ab, rel, ei, nb_dev[b0:b1])
         qd = None
         if qd_all is not None:
             qd = qd_all[b0:b1]
@@ -674,22 +668,23 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
             # The outputs are the step's STATIC tensors, which the replay of the next micro-batch overwrites.  Their copies to
             # pinned memory (read_back here and in _MicroBatchRunner.launch, right after this returns) are enqueued on the stream
             # the replay ran on BEFORE the next launch() enqueues its replay there: stream order keeps micro-batch i's results.
-            return (out.abs_pose, out.rel_pose, out.edge_index, out.neighbours,
-                    None if rule is None else runner.read_back(out.neighbours), out.rows, step.packed)
+            return _Forward(out.abs_pose, out.rel_pose, out.edge_index, out.neighbours,
+                            None if rule is None else runner.read_back(out.neighbours), step.packed)
         ab, rel, ei, nb_mb = model.forward_map(x, None, fmap, rule=rule, query_descriptors=qd, query_groups=qg, **okw)
-        return ab, rel, ei, nb_mb, runner.read_back(nb_mb), None, None
+        return _Forward(ab, rel, ei, nb_mb, runner.read_back(nb_mb))
 
     def read_back_of(chunk, x, fwd):
-        ab, rel, ei, nb_mb, host_nb, rows, packed = fwd
         if qp is None:
-            return {"nb": host_nb, "abs": ab, "rel": rel, "ei": ei if model.knn > 0 else None}
-        if rows is None:
+            return {"nb": fwd.host_neighbours, "abs": fwd.abs_pose, "rel": fwd.rel_pose,
+                    "ei": fwd.edge_index if model.knn > 0 else None}
+        back = fwd.back
+        if back is None:                   # everything the rule writes travels back in one tensor, one copy
             b0, n = chunk[0].first, x.shape[0]
-            # consensus: the integers travel back WITH the rows, in one buffer and one copy
-            packed, out, ints = packed_rows(n, rel.device) if consensus else (None, None, None)
-            rows = qp.from_map(rel, ei, fmap, nb_mb, query_targets=None if targ_dev is None else targ_dev[b0:b0 + n],
-                               edge_first=None if fc_first is None else fc_first[:n + 1], out=out, inliers=ints)
-        return {"nb": host_nb, "rel": rows if packed is None else packed}
+            out, ints, back = qp.output_block(n, fwd.rel_pose.device)
+            qp.from_map(fwd.rel_pose, fwd.edge_index, fmap, fwd.neighbours, out=out, inliers=ints,
+                        query_targets=None if targ_dev is None else targ_dev[b0:b0 + n],
+                        edge_first=None if fc_first is None else fc_first[:n + 1])
+        return {"nb": fwd.host_neighbours, "rel": back}
 
     def target_block(g):
         target = np.zeros((n_per, 6))
@@ -703,7 +698,7 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
         if host["nb"] is not None:
             nb_h[b0:b0 + host["nb"].shape[0]] = host["nb"].numpy()
         if qp is not None:
-            acc.add_device(host["rel"].numpy())      # the [G, 16] block of the device pose rule (+ the consensus integers)
+            acc.add_device(host["rel"].numpy())
         elif poses_h is None:
             raw_abs.append(host["abs"])
             raw_rel.append(host["rel"])

@@ -91,10 +91,10 @@ class GraphedForwardMap:
     ``pose_kwargs``: ``query_targets`` (an example fp32 [G, 6]; absent: the rows' target part is zeros) and ``edge_first`` (int64
     [G + 1]; absent: the cut of forward_map's own fully-connected list, K (K + 1) columns per graph -- K per graph with
     ``outputs="query"``).
-    A ``pose`` with ``fuse="consensus"`` also fills ``self.inliers``, a static int32 [G, 2] = (inliers, used) per query, valid
-    after a replay like the rows (``MapStep`` keeps its five fields); it is None for every other rule.  Rows and integers then
-    share one static buffer, ``self.packed`` (``query_pose.packed_rows``), which a stream copies back in one piece.  The thresholds are the
-    ``QueryPose``'s: a step is captured with one rule and never replayed for another.
+    The rule's outputs are static too (``QueryPose.output_block``): the rows, ``self.inliers`` -- int32 [G, 2] = (inliers, used) per
+    query for the one rule that has them, valid after a replay like the rows (``MapStep`` keeps its five fields), None for every
+    other -- and ``self.packed``, the one tensor a stream copies back (the rows themselves, or the buffer rows and integers
+    share).  The thresholds are the ``QueryPose``'s: a step is captured with one rule and never replayed for another.
     ``outputs``: ``forward_map``'s -- ``"query"`` captures the query-only step, whose outputs are abs_pose [G, 6], rel_pose
     [G K, 6] and the G K edges into the query nodes; what that mode does not serve raises as it does there.
 
@@ -159,9 +159,7 @@ class GraphedForwardMap:
                 self.query_descriptors = qd.detach().to(dev).contiguous().clone()
             fmap.inv_norms()                      # cached on the map: made here, outside the capture, and held below
         if pose is not None:
-            if pose.fuse == "consensus":
-                from .query_pose import packed_rows
-                self.packed, self._rows_out, self.inliers = packed_rows(g, dev)
+            self._rows_out, self.inliers, self.packed = pose.output_block(g, dev)
             qt = pose_kwargs.get("query_targets")
             if qt is not None:
                 if not torch.is_tensor(qt) or qt.dtype != torch.float32 or tuple(qt.shape) != (g, 6):

@@ -590,24 +590,11 @@ def query_pose(rel_pose: torch.Tensor, edge_index: torch.Tensor, *, node_first: 
     NaN and one count in ``status`` (int32 device tensor, accumulates) -- with ``status=None`` the count is read back here (one
     synchronisation) and a non-zero count raises the ValueError of ``evaluate.reference_edge``.  Every argument is checked on
     the host before anything is launched: TypeError for a wrong type or dtype, ValueError for a wrong shape or device."""
-    rel, ei, e, g, (n, m, k), by_name, out, status, own = _qp_graphs(
-        "query_pose", rel_pose, edge_index, node_first, node_targets, map_poses, neighbours, query_targets, edge_first, status, out)
+    graphs = _qp_graphs("query_pose", rel_pose, edge_index, node_first, node_targets, map_poses, neighbours, query_targets,
+                        edge_first, status, out)
     pm, ps = _qp_triple(pose_m, "pose_m"), _qp_triple(pose_s, "pose_s")
-    ref_node = _qp_ref_node(ref_node)
-    _qp_on_one_gpu("query_pose", rel, ei, by_name, [("out", out)])
-    rel, ei = rel.contiguous(), ei.contiguous()
-    if out is None:
-        out = torch.empty((g, 16), dtype=torch.float64, device=rel.device)
-    L.check(L.lib().rpg_query_pose_f64(_p(rel), ei.data_ptr(), ei.data_ptr() + 8 * e, e, _p(by_name.get("node_first")),
-                                       _p(by_name.get("edge_first")), g, _p(by_name.get("node_targets")), n,
-                                       _p(by_name.get("map_poses")), m, _p(by_name.get("neighbours")), k,
-                                       _p(by_name.get("query_targets")), *pm, *ps, ref_node, _p(out), status.data_ptr(),
-                                       _stream()), "query_pose")
-    bad = _own_count(status, own)
-    if bad:
-        raise ValueError(f"graph has no edge into node 0: cannot derive the query pose ({bad} graph(s) of this call lack "
-                         "the reference edge, or its source lies outside the graph)")
-    return out
+    return _qp_launch("rpg_query_pose_f64", "query_pose", graphs, pm, ps, (_qp_ref_node(ref_node),), (),
+                      "lack the reference edge, or its source lies outside the graph")
 
 
 def _qp_graphs(who, rel_pose, edge_index, node_first, node_targets, map_poses, neighbours, query_targets, edge_first, status, out):
@@ -661,20 +648,39 @@ def _qp_graphs(who, rel_pose, edge_index, node_first, node_targets, map_poses, n
     return rel, ei, e, g, (n, m, k), dict(parts), out, status, own
 
 
-def _qp_on_one_gpu(who, rel, ei, by_name, outputs) -> None:
-    """Everything on rel_pose's GPU; then the inputs made contiguous in place of the given ones (``by_name`` is updated)."""
+def _qp_launch(entry: str, who: str, graphs, pm, ps, head, outputs, lack: str) -> torch.Tensor:
+    """One launch of a pose rule's C entry point over the result of ``_qp_graphs``: everything on rel_pose's GPU and contiguous,
+    ``out`` made if it was not given, then the call -- the arguments all three entry points share, up to the six pose_m / pose_s
+    doubles, then ``head``, ``out``, the optional ``outputs`` [(name, tensor | None)], the status word and the stream.  A status
+    word that is this call's own is read back and a non-zero count raises the ValueError of ``evaluate.reference_edge`` ("...
+    graph(s) of this call ``lack``").  -> out."""
+    rel, ei, e, g, (n, m, k), by_name, out, status, own = graphs
     dev = rel.device
     if dev.type != "cuda":
         raise ValueError(f"{who}: rel_pose must be on the GPU (the HIP kernel is the only compute path), got {dev}")
-    for name, t in [("edge_index", ei)] + list(by_name.items()) + list(outputs):
+    for name, t in [("edge_index", ei)] + list(by_name.items()) + [("out", out)] + list(outputs):
         if t is not None and t.device != dev:
             raise ValueError(f"{who}: {name} is on {t.device}, rel_pose on {dev}: everything must be on the same GPU")
-    for name in by_name:
-        by_name[name] = by_name[name].contiguous()
+    rel, ei = rel.contiguous(), ei.contiguous()
+    by_name = {name: t.contiguous() for name, t in by_name.items()}
+    ptr = {name: _p(t) for name, t in by_name.items()}
+    if out is None:
+        out = torch.empty((g, 16), dtype=torch.float64, device=dev)
+    L.check(getattr(L.lib(), entry)(_p(rel), ei.data_ptr(), ei.data_ptr() + 8 * e, e, ptr.get("node_first"), ptr.get("edge_first"), g,
+                                    ptr.get("node_targets"), n, ptr.get("map_poses"), m, ptr.get("neighbours"), k,
+                                    ptr.get("query_targets"), *pm, *ps, *head, _p(out), *(_p(t) for _, t in outputs),
+                                    status.data_ptr(), _stream()), who)
+    bad = _own_count(status, own)
+    if bad:
+        raise ValueError(f"graph has no edge into node 0: cannot derive the query pose ({bad} graph(s) of this call {lack})")
+    return out
 
 
 FUSE_MODES = ("mean", "median", "consensus")   # the first two: the C entry point's `fuse` is the index; the third has its own
-INLIER_T, INLIER_DEG = 0.25, 5.0               # consensus thresholds: API defaults, not measured optima (evaluate.py has the same)
+# the consensus rule's thresholds: API defaults, not measured optima.  Both belong to the scene's scale; INLIER_T is in the unit of
+# the un-normalised translation (it is compared after `* pose_s + pose_m`), INLIER_DEG in degrees.  These three and _qp_thresholds
+# are the host rule's too: evaluate.py imports them (this module needs no built library until a kernel is called)
+INLIER_T, INLIER_DEG = 0.25, 5.0
 
 
 def _qp_fuse(fuse, max_edges, who: str = "query_pose_fused"):
@@ -730,44 +736,27 @@ def query_pose_fused(rel_pose: torch.Tensor, edge_index: torch.Tensor, *, fuse: 
     ``counts`` int32 [G] (optional output): the usable edges found before the cut at ``max_edges``.  A graph without a usable
     edge, or with a used edge whose source lies outside the graph, gets a NaN row and one count in ``status``."""
     who = "query_pose_fused"
-    rel, ei, e, g, (n, m, k), by_name, out, status, own = _qp_graphs(
-        who, rel_pose, edge_index, node_first, node_targets, map_poses, neighbours, query_targets, edge_first, status, out)
+    graphs = _qp_graphs(who, rel_pose, edge_index, node_first, node_targets, map_poses, neighbours, query_targets, edge_first,
+                        status, out)
+    g = graphs[3]
     pm, ps = _qp_triple(pose_m, "pose_m"), _qp_triple(pose_s, "pose_s")
     mode, max_edges = _qp_fuse(fuse, max_edges)
     inlier_t, inlier_deg = _qp_thresholds(inlier_t, inlier_deg)
     consensus = fuse == "consensus"
     if inliers is not None and not consensus:
         raise ValueError(f"{who}: inliers is an output of fuse='consensus', got fuse={fuse!r}")
-    if candidates is not None:
-        _qp_tensor(candidates, "candidates", torch.float64, (g, max_edges, 16), who)
-    if counts is not None:
-        _qp_tensor(counts, "counts", torch.int32, (g,), who)
-    if inliers is not None:
-        _qp_tensor(inliers, "inliers", torch.int32, (g, 2), who)
-    for name, t in (("candidates", candidates), ("counts", counts), ("inliers", inliers)):
+    outputs = [("candidates", candidates), ("counts", counts)] + ([("inliers", inliers)] if consensus else [])
+    shapes = {"candidates": (torch.float64, (g, max_edges, 16)), "counts": (torch.int32, (g,)), "inliers": (torch.int32, (g, 2))}
+    for name, t in outputs:
+        if t is not None:
+            _qp_tensor(t, name, *shapes[name], who)
+    for name, t in outputs:
         if t is not None and not t.is_contiguous():
             raise ValueError(f"{who}: {name} must be contiguous")
-    _qp_on_one_gpu(who, rel, ei, by_name, [("out", out), ("candidates", candidates), ("counts", counts), ("inliers", inliers)])
-    rel, ei = rel.contiguous(), ei.contiguous()
-    if out is None:
-        out = torch.empty((g, 16), dtype=torch.float64, device=rel.device)
+    lack = "have no usable edge into their query node, or a used edge's source lies outside the graph"
     if consensus:
-        L.check(L.lib().rpg_query_pose_consensus_f64(
-            _p(rel), ei.data_ptr(), ei.data_ptr() + 8 * e, e, _p(by_name.get("node_first")), _p(by_name.get("edge_first")), g,
-            _p(by_name.get("node_targets")), n, _p(by_name.get("map_poses")), m, _p(by_name.get("neighbours")), k,
-            _p(by_name.get("query_targets")), *pm, *ps, max_edges, inlier_t, inlier_deg, _p(out), _p(candidates), _p(counts),
-            _p(inliers), status.data_ptr(), _stream()), who)
-    else:
-        L.check(L.lib().rpg_query_pose_fused_f64(_p(rel), ei.data_ptr(), ei.data_ptr() + 8 * e, e, _p(by_name.get("node_first")),
-                                                 _p(by_name.get("edge_first")), g, _p(by_name.get("node_targets")), n,
-                                                 _p(by_name.get("map_poses")), m, _p(by_name.get("neighbours")), k,
-                                                 _p(by_name.get("query_targets")), *pm, *ps, mode, max_edges, _p(out),
-                                                 _p(candidates), _p(counts), status.data_ptr(), _stream()), who)
-    bad = _own_count(status, own)
-    if bad:
-        raise ValueError(f"graph has no edge into node 0: cannot derive the query pose ({bad} graph(s) of this call have no "
-                         "usable edge into their query node, or a used edge's source lies outside the graph)")
-    return out
+        return _qp_launch("rpg_query_pose_consensus_f64", who, graphs, pm, ps, (max_edges, inlier_t, inlier_deg), outputs, lack)
+    return _qp_launch("rpg_query_pose_fused_f64", who, graphs, pm, ps, (mode, max_edges), outputs, lack)
 
 
 def _gather_sources(sources, weight: torch.Tensor, widths: Optional[Sequence[int]] = None):

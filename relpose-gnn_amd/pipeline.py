@@ -308,17 +308,12 @@ class _MicroBatchRunner:
         # back instead of the stored one: it travels to the host with the poses and is cut per graph by the consumer
         model_built = edge_index is not batch.edge_index
         if self.pose is not None:
-            # the consensus rule's (inliers, used) per graph travel back WITH the rows: one buffer, one copy (query_pose.packed_rows)
-            packed = out = ints = None
-            if self.pose.fuse == "consensus":
-                from .query_pose import packed_rows
-                packed, out, ints = packed_rows(len(chunk), rel.device)
+            # everything the rule writes travels back in one tensor, one copy (QueryPose.output_block)
+            out, ints, back = self.pose.output_block(len(chunk), rel.device)
             # a stored list is cut contiguously per graph; a model-built one is cut by its targets (edges_per_graph) in the kernel
-            rel = self.pose.from_targets(rel, edge_index, pose_in[0], pose_in[2], edge_first=None if model_built else pose_in[1],
-                                         out=out, inliers=ints)
-            if packed is not None:
-                rel = packed
-            model_built = False
+            self.pose.from_targets(rel, edge_index, pose_in[0], pose_in[2], edge_first=None if model_built else pose_in[1],
+                                   out=out, inliers=ints)
+            rel, model_built = back, False
         return {"rel": rel, "abs": ab if self.want_abs else None, "ei": edge_index if model_built else None}
 
     def read_back(self, t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
@@ -334,8 +329,7 @@ class _MicroBatchRunner:
 
     def launch(self, chunk: Sequence[Data]) -> _Launched:
         """Stage (or pick up the prefetched) chunk, run the forward, start the read-back.  With ``pose`` host["rel"] is the
-        float64 [G, 16] block of the device pose rule (with ``fuse="consensus"``: the uint8 buffer of ``query_pose.packed_rows``,
-        that block followed by the int32 [G, 2] integers) and host["ei"] is None."""
+        device pose rule's output block (``QueryPose.output_block``; ``cut_block`` cuts it) and host["ei"] is None."""
         k = self.n_batches & 1
         self.n_batches += 1
         staged = self.on_gpu and not any(g.x.is_cuda for g in chunk)

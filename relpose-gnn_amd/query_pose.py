@@ -23,6 +23,9 @@ candidates vote (two support each other when their translations lie within ``inl
 (rpg_query_pose_consensus_f64, the same kernel's third mode; ``evaluate.consensus_query_row`` is the rule in numpy).  With
 ``inliers=`` (int32 [G, 2]) every graph also gets (supporters of the winner, candidates used): their ratio is the accept /
 reject signal that goes with the pose.  A non-finite candidate is an outlier there, it does not void the pose.
+
+Whatever the rule, a stream asks the object for its output block (``output_block``: the rows, the integers if the rule has them,
+and the one tensor to copy back) and cuts the host copy with ``cut_block``; it never asks which rule runs.
 """
 from __future__ import annotations
 
@@ -71,6 +74,22 @@ class QueryPose:
                 raise ValueError(f"QueryPose: fuse={fuse!r} combines every edge into the query node, ref_node={ref_node} selects "
                                  "one: give one of the two")
         self._bad = DeferredCounters(1, self._error)          # graphs that could not be evaluated
+
+    # ---- the output block: what a stream allocates per micro-batch and copies back in one piece ----------------------------
+    def output_block(self, g: int, device):
+        """The outputs of ``g`` graphs on ``device``: -> (rows float64 [g, 16] for ``out=``, inliers int32 [g, 2] for ``inliers=``
+        or None, the ONE tensor a stream copies back).  That tensor is the rows themselves, 128 bytes per graph -- except with
+        ``fuse="consensus"``, whose two integers per graph travel behind the rows in one buffer (``packed_rows``, 136 bytes)."""
+        if self.fuse != "consensus":
+            rows = torch.empty((g, 16), dtype=torch.float64, device=device)
+            return rows, None, rows
+        buf, rows, ints = packed_rows(g, device)
+        return rows, ints, buf
+
+    def cut_block(self, host):
+        """A host copy (tensor or numpy array) of the tensor ``output_block`` says to copy back -> (rows [g, 16], inliers [g, 2]
+        or None), views of it."""
+        return unpack_rows(host) if self.fuse == "consensus" else (host, None)
 
     # ---- the two forms ---------------------------------------------------------------------------------------------------
     def from_targets(self, rel_pose, edge_index, node_first, node_targets, edge_first=None, out=None, candidates=None,

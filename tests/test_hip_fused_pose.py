@@ -126,6 +126,20 @@ def test_more_in_edges_than_lanes_and_than_one_step(dev, fuse):  # noqa: F811
     qp.check()
 
 
+def test_exactly_64_candidates_fill_the_mean(dev):  # noqa: F811
+    """A 65-node graph alone: exactly 64 candidates, one per lane and none cut -- the mean runs over the full slot mask."""
+    sizes = (65,)
+    rel, ei, nf, ef, y = _fc_case(sizes, 60, dev)
+    want = _host_rows(rel, ei, sizes, y, "mean")
+    assert np.isfinite(want).all()
+    qp = _qp("mean")
+    for edge_first in (ef, None):
+        cand, counts = _outputs(1, 64, dev)
+        _agree(qp.from_targets(rel, ei, nf, y, edge_first=edge_first, candidates=cand, counts=counts), want)
+        assert counts.cpu().tolist() == [64] and torch.isfinite(cand).all()
+    qp.check()
+
+
 @pytest.mark.parametrize("fuse", MODES)
 @pytest.mark.parametrize("max_edges", [1, 2, 4])
 def test_max_edges_below_the_candidates(dev, fuse, max_edges):  # noqa: F811
