@@ -397,6 +397,31 @@ int rpg_attention_aggregate_hidden_f32(const float* gtp, const float* hid, const
  * out[r][3:6] = x W2^T + b2 (posenet.py:1077-1091).  w6 [6][d] = cat(W1, W2), b6 [6].           */
 int rpg_pose_heads_f32(const float* x, const float* w6, const float* b6, int r, int d, float* out, void* stream);
 
+/* Monte-Carlo pose heads (csrc/mc_heads.hip): the reference's always-on F.dropout (posenet.py:1073-1075, no `training=`) and the
+ * heads behind it (posenet.py:1077-1086), evaluated under s masks from ONE read of x [r][d]; the weights come from cache.
+ *   y_k[o]  = scale * (sum over the KEPT columns c of x[c] w6[o][c]) + b6[o],   scale = 1.0f / (1.0f - (float)p), applied once
+ *   mean[o] = (the fp32 sum of y_0 .. y_{s-1} in that order) / s
+ *   var[o]  = sum_k (y_k[o] - mean[o])^2 / (s - 1), two passes in fp32; exactly 0 for s = 1
+ *   samples [s][r][6] or NULL: every y_k
+ * The mask is a pure function of (seed, draw, node ids, column, sample) -- Philox4x32-10, csrc/philox.h: key = (seed low, seed
+ * high), counter = (a, b, k | sample << 16, draw); its four words serve columns 4k .. 4k+3, and element j is kept iff word[j] >=
+ * floor(p 2^32) (evaluated in double).  state: DEVICE uint32 [2] = {draw, node_base}, read by the kernel, so that a captured graph
+ * sees new values at every replay.  With off = node_base + id_offset:  a = off + (id_a ? id_a[row] : row);  b = id_b ? off +
+ * id_b[row] : 0xFFFFFFFF (the node tag).  A node row passes its node id (or its row index) and no id_b; an edge row passes the
+ * ids of its source and target.  So a row's masks do not depend on its position, stream slot, micro-batch, the edge order, FC
+ * versus kNN graph or the "query" / "all" output mode, and two copies of the same (source, target) edge share a mask.
+ * The mask SELECTS: a dropped column enters the sum as +0 whatever x holds there, so a NaN / Inf feature poisons exactly the
+ * samples that keep it (and the mean and variance with them), where F.dropout, which multiplies by 0, poisons all of them.
+ * Limits (RPG_ERR_BAD_ARG otherwise): 0 < p < 1, 1 <= s <= 1024, d % 4 == 0, d / 4 < 65536, id_offset >= 0, id_offset + r <=
+ * 2^31 (node ids stay below 2^31: the caller's business for id_a / id_b, which are only read on the device), x and w6 16-byte
+ * aligned.  One launch, no allocation, no synchronisation (graph-capturable).                                          */
+int rpg_pose_heads_mc_f32(const float* x, const float* w6, const float* b6, int r, int d, double p, int s, uint64_t seed,
+                          const uint32_t* state, const int64_t* id_a, const int64_t* id_b, int64_t id_offset, float* mean,
+                          float* var, float* samples, void* stream);
+/* state[0] += 1 (the draw counter; wraps) by a one-thread kernel: queued once behind a forward's heads, and part of a captured
+ * step, so that every call / replay draws the next set of masks.                                                          */
+int rpg_mc_advance(uint32_t* state, void* stream);
+
 /* Everything after the encoder for use_gnn=True, use_AP=True, knn<=0 (posenet.py:1052-1091).
  * `tensors` HOST array of device pointers, order in params.py: 22 tensors (reference formulation) or 26 (adds the
  * node/edge column blocks of proj_edge, edge_mlp.0 and mlp.0 as separate matrices, which lets the node terms be

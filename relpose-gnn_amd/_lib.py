@@ -33,7 +33,7 @@ SYMBOLS = (
     "rpg_retrieve_workspace_bytes", "rpg_retrieve_max_rank", "rpg_row_inv_norms_f32", "rpg_retrieve_cosine_f32",
     "rpg_query_pose_f64", "rpg_query_pose_fused_f64", "rpg_gather_add2_relu_f32",
     "rpg_gnn_query_workspace_bytes", "rpg_gnn_forward_query_f32", "rpg_gnn_forward_query_bf16", "rpg_gemm_last_route", "rpg_get_tuning",
-    "rpg_attention_aggregate_hidden_f32", "rpg_query_pose_consensus_f64",
+    "rpg_attention_aggregate_hidden_f32", "rpg_query_pose_consensus_f64", "rpg_pose_heads_mc_f32", "rpg_mc_advance",
 )
 
 
@@ -73,6 +73,8 @@ def _declare(lib: C.CDLL) -> None:
     lib.rpg_attention_aggregate_f32.argtypes = [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]
     lib.rpg_attention_aggregate_hidden_f32.argtypes = [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]
     lib.rpg_pose_heads_f32.argtypes =[_vp, _vp, _vp, _i, _i, _vp, _vp]
+    lib.rpg_pose_heads_mc_f32.argtypes = [_vp, _vp, _vp, _i, _i, C.c_double, _i, C.c_uint64, _vp, _vp, _vp, C.c_int64, _vp, _vp, _vp, _vp]
+    lib.rpg_mc_advance.argtypes = [_vp, _vp]
     lib.rpg_gnn_workspace_bytes.argtypes = [_i, _i, _i]
     lib.rpg_gnn_workspace_bytes.restype = _sz
     lib.rpg_gnn_forward_f32.argtypes = [C.POINTER(_vp), _i, _vp, _vp, _vp, C.c_int64, _i, _i, _i, _i, _vp, _vp, _vp, _vp,

@@ -529,7 +529,7 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
     tail) and replayed with one launch per micro-batch instead of ~137.  Same kernels, same launch geometry, same order: the
     results are bit-identical to ``capture=False``.  The captured steps are kept on the model (``refresh_packed`` drops them; a
     step whose map has been extended is captured again), so a second call with the same shapes captures nothing.  What that
-    class refuses (``droprate > 0``, ``knn > 0``, ``use_attention``, ``use_AP=False``, uint8 queries) raises here, before any
+    class refuses (``droprate > 0`` without ``model.mc_dropout``, ``knn > 0``, ``use_attention``, ``use_AP=False``, uint8 queries) raises here, before any
     work is queued.  ``stats`` also receives ``graphs_captured`` (by this call) and ``graph_replays``.
 
     ``outputs="query"`` (default ``"all"``): every micro-batch runs ``forward_map(outputs="query")``, which computes only what
@@ -594,6 +594,8 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
         nb_dev = None
         nb_h = np.zeros((g_all, kk), dtype=np.int64)          # filled micro-batch by micro-batch as the copies land
     n_per = kk + 1
+    mc = getattr(model, "mc_dropout", None)
+    mc_draw = None if mc is None else mc.draw
     on_gpu = torch.device(device).type == "cuda"
     poses_h = None if fmap.poses is None else fmap.poses.cpu().numpy().astype(np.float64)
     targ_h = None if targets is None else np.asarray(torch.as_tensor(targets).cpu(), dtype=np.float64).reshape(g_all, 6)
@@ -629,7 +631,8 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
         now with the micro-batch itself as the example."""
         nonlocal n_captured
         key = ("step", tuple(x.shape), x.dtype, kk, None if rule is None else (rule.sampling_period, rule.random), postprocess,
-               fuse, max_edges, qd is not None, targ is not None, outputs, inlier_t, inlier_deg)
+               fuse, max_edges, qd is not None, targ is not None, outputs, inlier_t, inlier_deg,
+               None if mc is None else (id(mc), mc.samples, mc.seed))       # the sampler's count and seed are baked into the step
         step = captured.get(key)
         if step is None or step.fmap is not fmap or step.pose is not qp or step.stale():
             if len(captured) >= 16:
@@ -644,6 +647,10 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
     def forward(chunk, x):
         nonlocal n_replays
         b0, b1 = chunk[0].first, chunk[0].first + x.shape[0]
+        if mc is not None:
+            # query b0's graph starts at node b0 (K + 1) of the stream, whatever micro_batch is, and the whole call is ONE draw; a
+            # captured step reads both from the same device words, so they are sent ahead of the replay like its other inputs
+            mc.place(mc_draw, b0 * n_per)
         if rule is None and not capture:
             ab, rel, ei = model.forward_map(x, nb_dev[b0:b1], fmap, **okw)
             return _Forward(ab, rel, ei, nb_dev[b0:b1])
@@ -712,6 +719,8 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
                                forward=forward, outputs=read_back_of, capacity=min(micro_batch, g_all))
     runner.run(-(-g_all // micro_batch), lambda i: runner.pieces(queries[i * micro_batch:(i + 1) * micro_batch], i * micro_batch),
                finish, stats, postprocess)
+    if mc is not None:
+        mc.reset(mc_draw + 1)      # the next call draws the next masks, however many micro-batches this one took
     if stats is not None:
         stats["neighbours"] = nb_h
         if capture:

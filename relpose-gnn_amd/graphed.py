@@ -98,6 +98,11 @@ class GraphedForwardMap:
     ``outputs``: ``forward_map``'s -- ``"query"`` captures the query-only step, whose outputs are abs_pose [G, 6], rel_pose
     [G K, 6] and the G K edges into the query nodes; what that mode does not serve raises as it does there.
 
+    A model with ``droprate > 0`` is captured only with ``model.mc_dropout`` set (mc_dropout.McDropout): the step then returns the
+    means over its dropout samples, the one-thread kernel that advances the draw counter is part of the graph, so every replay
+    draws the next masks, and ``node_base`` is read from the device state a caller sets ahead of the replay.  ``self.spread``
+    holds the variances (static, like the outputs).
+
     The graph reads the packed weights, the workspaces, the map's tensors and the counters in place.  All of them are held
     here, so nothing it reads is freed under it, and every call compares them with what the model and the map hold NOW:
     after ``refresh_packed()`` / ``load_state_dict`` / ``.to()`` / a dtype switch / ``FeatureMap.extend`` the call raises
@@ -175,14 +180,25 @@ class GraphedForwardMap:
         self.graph = torch.cuda.CUDAGraph()
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream())
+        mc = getattr(model, "mc_dropout", None)
         with torch.cuda.stream(side):
+            # model.mc_dropout: every warm-up forward advances the draw counter on the device; it is put back behind them, so that
+            # capturing a step draws nothing and the first replay has the masks the next eager forward would have had
+            mc_saved = None if mc is None else mc.state(dev).clone()
+            mc_draw = None if mc is None else mc.draw
             for _ in range(max(1, warmup)):       # packs weights, sizes the workspace pool, builds the _map_graph edge list
                 self._step()
+            if mc_saved is not None:
+                mc.state(dev).copy_(mc_saved)
             model.check_edge_index()              # one sync, before the capture: the warm-up's inputs were valid
             if pose is not None:
                 pose.check()
             with torch.cuda.graph(self.graph, stream=side):
                 self.out = self._step()
+            if mc is not None:
+                mc._init[0] = mc._word(mc_draw)   # the host's count of the draws, which the warm-up forwards moved on as well
+        # the variances of a replay (mc_dropout.McSpread): static like the outputs, handed to model.mc_dropout.last by every call
+        self.spread = None if mc is None else mc.last
         torch.cuda.current_stream().wait_stream(side)
         # everything the graph reads besides its static inputs, held so that it outlives the graph, and what a call compares
         self._held = self._reads()
@@ -196,7 +212,9 @@ class GraphedForwardMap:
         if queries.dtype == torch.uint8:
             raise TypeError("GraphedForwardMap does not take uint8 frames: capture the model on its fp32 / bf16 input "
                             "(frame_transform.apply(frames) outside the graph)")
-        if getattr(model, "droprate", 0) > 0 or getattr(model, "knn", -1) > 0:
+        # the always-on dropout is captured only as model.mc_dropout samples it: its masks are made on the device from a counter
+        # the captured step itself advances (rpg_mc_advance), where torch's generator would replay one mask for ever
+        if (getattr(model, "droprate", 0) > 0 and getattr(model, "mc_dropout", None) is None) or getattr(model, "knn", -1) > 0:
             raise NotImplementedError(_FC_ONLY)
         if getattr(model, "use_attention", False) or not getattr(model, "use_AP", True):
             raise NotImplementedError(_FC_ONLY + "; use_attention and use_AP=False take the one-stream path, which allocates and "
@@ -225,6 +243,7 @@ class GraphedForwardMap:
                 "fc_graph": m._map_graphs.get((self.g, self.k + 1, str(self.queries.device))),
                 "query_sel": (m._map_queries.get((self.g, self.k + 1, str(self.queries.device)))
                               if self.outputs == "query" else None),
+                "mc_state": None if getattr(m, "mc_dropout", None) is None else m.mc_dropout._state,
                 "counters": m._counters.counters, "pose_counters": None if self.pose is None else self.pose._bad.counters,
                 "features": f.features, "poses": f.poses, "descriptors": f.descriptors, "groups": f.groups,
                 "inv_norms": f._inv_norms if self.rule is not None else None}
@@ -234,7 +253,7 @@ class GraphedForwardMap:
         """Objects by identity, the map's storage by (address, rows): what must be unchanged for the graph to be replayed."""
         return (id(r["library"]), id(r["encoder"]), id(r["gnn"]), id(r["gnn_bf16"]), r["dtypes"], id(r["counters"]),
                 id(r["pose_counters"]), _storage(r["features"]), _storage(r["poses"]), _storage(r["descriptors"]),
-                _storage(r["groups"]), _storage(r["inv_norms"]))
+                _storage(r["groups"]), _storage(r["inv_norms"]), id(r["mc_state"]))
 
     def stale(self) -> bool:
         """True once the model or the map no longer hold what the graph was captured over."""
@@ -307,6 +326,9 @@ class GraphedForwardMap:
             else:
                 self.query_groups.copy_(qg_dev, non_blocking=True)
         self.graph.replay()
+        if self.spread is not None:               # the replayed step advanced the draw counter on the device
+            self.model.mc_dropout.last = self.spread
+            self.model.mc_dropout.advanced()
         self.model.publish_status()               # bad neighbours / ranks / edges counted by the replayed kernels
         if self.pose is not None:
             self.pose.publish()                   # ... and graphs without a usable reference edge

@@ -23,7 +23,9 @@ loop is still consuming the previous micro-batch -- and then yields the graphs o
 * ``len(loader)``, ``loader.batch_size``, ``loader.dataset``: the wrapped loader's.
 
 A call with anything that was not the graph just yielded (a second forward, another loader's batch) runs the wrapped module
-directly.  The reference's always-on dropout (posenet.py:1073-1075) draws its mask per micro-batch instead of per graph.
+directly.  The reference's always-on dropout (posenet.py:1073-1075) draws its mask per micro-batch instead of per graph; with
+``model.mc_dropout`` set (mc_dropout.McDropout) the poses are means over masks that follow the node ids of the whole stream, so
+they do not depend on ``micro_batch``.
 """
 from __future__ import annotations
 
@@ -186,6 +188,7 @@ class Lookahead:
         try:
             yield from self._drain(start)
         finally:
+            runner.end_draw()                # model.mc_dropout: one draw per pass over the loader
             self.__dict__["_in_loop"] = False
             self.__dict__["_expect"] = None
 

@@ -892,6 +892,62 @@ def pose_heads(x: torch.Tensor, w6: torch.Tensor, b6: torch.Tensor, out: Optiona
     return out
 
 
+def _mc_ids(ids, r: int, dev):
+    """``pose_heads_mc``'s ``ids``: None (node rows, numbered by their row), int64 [r] (node rows with their ids), int64 [2, r] or a
+    pair of int64 [r] (edge rows: the ids of source and target).  -> (id_a, id_b), each None or a contiguous int64 [r]."""
+    if ids is None:
+        return None, None
+    if torch.is_tensor(ids):
+        if ids.dim() == 1:
+            ids = (ids,)
+        elif ids.dim() == 2 and ids.shape[0] == 2:
+            ids = (ids[0], ids[1])
+        else:
+            raise ValueError(f"pose_heads_mc: ids must be int64 [r] (nodes) or [2, r] (edges), got {tuple(ids.shape)}")
+    if not isinstance(ids, (tuple, list)) or len(ids) not in (1, 2):
+        raise TypeError("pose_heads_mc: ids must be None, an int64 tensor [r] / [2, r] or a pair of int64 tensors [r]")
+    out = tuple(_req(t, "ids", torch.int64) for t in ids)
+    if any(t.dim() != 1 or t.numel() != r or t.device != dev for t in out):
+        raise ValueError(f"pose_heads_mc: every id vector must be int64 [{r}] on the inputs' GPU")
+    return out[0], (out[1] if len(out) == 2 else None)
+
+
+def pose_heads_mc(x: torch.Tensor, w6: torch.Tensor, b6: torch.Tensor, p: float, samples: int, seed: int, state: torch.Tensor,
+                  ids=None, id_offset: int = 0, want_samples: bool = False, out=None):
+    """The heads under ``samples`` dropout masks of rate ``p`` from one read of x [r, d] (rpg_pose_heads_mc_f32): -> (mean [r, 6],
+    var [r, 6]) over the samples, and with ``want_samples`` the samples themselves [samples, r, 6] as a third element.  ``state``:
+    device int32 / uint32 [2] = (draw, node_base), read by the kernel; ``seed``: 64 bits.  The masks are a function of (seed, draw,
+    ids, column, sample) only: ``ids`` None numbers node rows by node_base + id_offset + row, an int64 [r] gives their ids, an int64
+    [2, r] (or a pair of [r]) the ids of an edge row's source and target, all offset by node_base + id_offset.  ``out``: (mean, var)
+    to write into.  ValueError for p outside (0, 1), samples outside 1..1024, d % 4, d / 4 >= 65536, ids beyond 2^31."""
+    x, w6, b6 = _req(x, "x"), _req(w6, "w6"), _req(b6, "b6")
+    if not torch.is_tensor(state) or not state.is_cuda or state.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)):
+        raise TypeError("pose_heads_mc: state must be a 32-bit integer tensor [2] = (draw, node_base) on the GPU")
+    if state.numel() != 2 or not state.is_contiguous() or state.device != x.device:
+        raise ValueError("pose_heads_mc: state must hold (draw, node_base), contiguous, on the inputs' GPU")
+    if x.dim() != 2 or w6.dim() != 2 or tuple(w6.shape) != (6, x.shape[1]) or b6.numel() != 6:
+        raise ValueError(f"pose_heads_mc: x [r, d], w6 [6, d] and b6 [6], got {tuple(x.shape)}, {tuple(w6.shape)}, {tuple(b6.shape)}")
+    r, d = x.shape
+    samples, seed, id_offset = int(samples), int(seed), int(id_offset)
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError("pose_heads_mc: seed must fit 64 bits")
+    id_a, id_b = _mc_ids(ids, r, x.device)
+    mean_out, var_out = (None, None) if out is None else out
+    mean = _out(mean_out, (r, 6), torch.float32, x.device, "pose_heads_mc")
+    var = _out(var_out, (r, 6), torch.float32, x.device, "pose_heads_mc")
+    smp = torch.empty((max(samples, 0), r, 6), dtype=torch.float32, device=x.device) if want_samples else None
+    L.check(L.lib().rpg_pose_heads_mc_f32(_p(x), _p(w6), _p(b6), r, d, float(p), samples, seed, _p(state), _p(id_a), _p(id_b),
+                                          id_offset, _p(mean), _p(var), _p(smp), _stream()), "pose_heads_mc")
+    return (mean, var, smp) if want_samples else (mean, var)
+
+
+def mc_advance(state: torch.Tensor) -> None:
+    """draw += 1 in ``state`` (see ``pose_heads_mc``) on the current stream (rpg_mc_advance)."""
+    if not torch.is_tensor(state) or not state.is_cuda or state.numel() != 2 or state.element_size() != 4:
+        raise TypeError("mc_advance: state must be a 32-bit integer tensor [2] on the GPU")
+    L.check(L.lib().rpg_mc_advance(_p(state), _stream()), "mc_advance")
+
+
 def gnn_forward_query(tensors: Sequence[torch.Tensor], feat: torch.Tensor, edge_index: torch.Tensor, sel: torch.Tensor,
                       qnodes: torch.Tensor, gnn_recursion: int = 2, weights_bf16: Optional[Sequence[torch.Tensor]] = None,
                       node_offset: int = 0, want_features: bool = False, status: Optional[torch.Tensor] = None,

@@ -225,6 +225,8 @@ class _MicroBatchRunner:
         self.on_gpu = torch.device(device).type == "cuda"
         self.pipes = {}                    # staging dtype -> _InputPipeline (at most two: the configured dtype, fp32 for pinned sources)
         self.n_batches = 0
+        self.nodes_seen = 0                # nodes of the micro-batches forwarded so far: model.mc_dropout's node_base of the next one
+        self.mc_draw = None                # model.mc_dropout's draw counter when the stream began (held until end_draw)
         self.h2d_bytes = 0
         self.d2h_bytes = 0                 # payload copied back per micro-batch (poses / edge list / pose rows; not the status words)
         self._prefetched = None            # (chunk, pipe, stage_begin handle) of the chunk the next launch() is expected to get
@@ -300,7 +302,21 @@ class _MicroBatchRunner:
 
     def _forward(self, chunk, batch):
         pose_in = self._pose_inputs(chunk) if self.pose is not None else None
+        mc = getattr(self.model, "mc_dropout", None)
+        if mc is not None:
+            # global node ids and ONE draw for the whole stream: a graph's dropout masks do not depend on how the stream was cut
+            if self.mc_draw is None:
+                self.mc_draw = mc.draw
+            mc.place(self.mc_draw, self.nodes_seen)
+        self.nodes_seen += int(batch.x.shape[0])
         return (pose_in,) + tuple(self.model(batch))
+
+    def end_draw(self) -> None:
+        """The stream is over: model.mc_dropout's next forward draws the next masks (one draw per stream, not per micro-batch)."""
+        mc = getattr(self.model, "mc_dropout", None)
+        if mc is not None and self.mc_draw is not None:
+            mc.reset(self.mc_draw + 1)
+        self.mc_draw, self.nodes_seen = None, 0
 
     def _outputs(self, chunk, batch, fwd):
         pose_in, ab, rel, edge_index = fwd
@@ -381,6 +397,7 @@ class _MicroBatchRunner:
             self.arrived(item)
             finish(item)
         drive(n, chunk_at, self.launch, self.prefetch, done)
+        self.end_draw()
         check = getattr(self.model, "check_edge_index", None)
         if check is not None:
             check()                                    # everything has been issued: wait for the last report

@@ -14,7 +14,12 @@ constructor / forward flags of the reference -- ``use_attention`` (posenet.py:10
 (extra ``gnn2..`` parameter sets that the reference creates but never uses, :950-953, :1061-1069) -- run through the
 same kernels with a few more fine-grained calls.  The reference's always-on dropout (``F.dropout`` without ``training=``, posenet.py:1073-1075) is honoured: with
 ``droprate>0`` the node/edge features come back from the GNN call, ``F.dropout`` is applied, and the heads kernel runs on
-the result; parity tests use ``droprate=0``.  Everything runs on the GPU; CPU tensors raise (no fallback).
+the result; parity tests use ``droprate=0``.  ``model.mc_dropout = McDropout(samples, seed)`` (mc_dropout.py; default None) samples
+that dropout instead of drawing it once: every forward then returns the MEAN of the heads over ``samples`` masks in place of
+abs_pose / rel_pose (same shapes) and leaves the variances in ``mc_dropout.last``; the masks are made on the device from (seed,
+draw, node ids, column, sample) by one kernel per head (``rpg_pose_heads_mc_f32``), so they do not depend on stream slots,
+micro-batches or the ``outputs`` mode, and the captured map step takes such a model.  Everything runs on the GPU; CPU tensors
+raise (no fallback).
 
 Index validation.  The reference's aten indexing raises ``IndexError`` for a node id outside ``[0, N)``.  Here every call
 is validated on the device (``rpg_graph_prepare`` counts the offending edges, clamps them and leaves them out of the
@@ -36,6 +41,7 @@ from . import _lib as _L
 from . import ops
 from .params import pack_gnn, pack_gnn_bf16, pack_gnn_mean_first
 from .resnet import EncoderRunner, WorkspacePool
+from .mc_dropout import McSpread
 from .status import DeferredCounters
 
 
@@ -155,6 +161,9 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
         # optional frames.FrameTransform: with it forward() also takes uint8 frames data.x [n, H, W, 3] (RGB, HWC) on the GPU and
         # runs the reference's image transform there (a plain attribute: not a module, parameter or buffer -- state_dict unchanged)
         self.frame_transform = None
+        # optional mc_dropout.McDropout: with it (and droprate > 0) every forward returns the MEAN of the heads over its dropout
+        # samples in place of abs_pose / rel_pose and leaves their variances in mc_dropout.last (a plain attribute as well)
+        self.mc_dropout = None
         self._enc_digest: Optional[str] = None        # encoder_digest() cache (cleared wherever the packed weights are)
         self._map_graphs: Dict[tuple, Tuple[torch.Tensor, torch.Tensor]] = {}   # forward_map: (G, K+1, device) -> (edges, batch)
         # forward_map(outputs="query"): same key -> (selected columns [G K], query nodes [G], the selected edges [2, G K])
@@ -299,11 +308,42 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
                 torch.cuda.current_stream().cuda_stream)
         _L.check(rc, name)
 
-    def _drop_heads(self, node_f, edge_f, abs_out, rel_out):
+    def _mc(self):
+        """``mc_dropout`` if set -- after the checks every forward makes before it queues anything."""
+        mc = self.mc_dropout
+        if mc is None:
+            return None
+        if not self.droprate > 0:
+            raise ValueError("mc_dropout samples the always-on dropout: it needs droprate > 0 (set model.mc_dropout = None for a "
+                             "model without dropout)")
+        if not self.use_AP:
+            raise NotImplementedError("mc_dropout does not serve use_AP=False (its absolute poses are a Linear over pairs of "
+                                      "dropped node features, not the six-wide heads)")
+        return mc
+
+    def _pool_rows(self, key, rows: int, d: int, dev) -> torch.Tensor:
+        """fp32 [rows, d] in the workspace pool under ``key``: the feature buffers of the Monte-Carlo heads, which a captured
+        step must not allocate."""
+        nbytes = max(rows, 1) * d * 4
+        return self._ws_pool.get(key, nbytes, dev)[:nbytes].view(torch.float32).view(max(rows, 1), d)[:rows]
+
+    def _drop_heads(self, node_f, edge_f, abs_out, rel_out, mc=None):
         """The reference's always-on dropout (posenet.py:1073-1075), then the heads kernel on the dropped features, which
         overwrites the poses the GNN call made from the undropped ones (the node heads only with ``use_AP``: without it the
-        caller makes abs_pose from the returned, dropped node features)."""
+        caller makes abs_pose from the returned, dropped node features).  ``mc`` (with ``mc_dropout``): (node ids or None, their
+        offset, (edge sources, edge targets), their offset, abs_var, rel_var) -- the sample means go to abs_out / rel_out, the
+        variances to the last two, and the masks follow the ids (ops.pose_heads_mc), not torch's generator."""
         t = self._gnn_packed
+        if mc is not None:
+            node_ids, node_off, edge_ids, edge_off, abs_var, rel_var = mc
+            md = self.mc_dropout
+            state = md.state(node_f.device)
+            ops.pose_heads_mc(node_f, t[18], t[19], self.droprate, md.samples, md.seed, state, node_ids, node_off,
+                              out=(abs_out, abs_var))
+            if edge_f.shape[0]:
+                ops.pose_heads_mc(edge_f, t[20], t[21], self.droprate, md.samples, md.seed, state, edge_ids, edge_off,
+                                  out=(rel_out, rel_var))
+            return node_f
         node_f = F.dropout(node_f, p=self.droprate)
         if self.use_AP:
             ops.pose_heads(node_f, t[18], t[19], out=abs_out)
@@ -403,6 +443,7 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
                                "(there is no CPU fallback)")
         if not torch.is_tensor(edge_index) or edge_index.device != x.device:
             raise RuntimeError("data.edge_index must be a tensor on the same GPU as data.x")
+        self._mc()
         x, lib, _ = self._prepare(x, "data.x")
         # The multi-stream schedule serves the reference's default CLI flags too (round 5; testing/test.py:308-309: --knn 4
         # --droprate 0.5): the kNN graph is built per stream slot from that slot's encoder output, dropout + heads run per slot.
@@ -445,14 +486,24 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
         status = self._counters.counters[0:1]
         drop = self.droprate > 0
         want_feats = drop or not self.use_AP
-        node_f = torch.empty((n_out, d), dtype=torch.float32, device=dev) if want_feats else None
-        edge_f = torch.empty((e_out, d), dtype=torch.float32, device=dev) if drop else None
+        md = self._mc()
+        if md is not None:
+            node_f, edge_f = self._pool_rows((600, 99), n_out, d, dev), self._pool_rows((700, 99), e_out, d, dev)
+        else:
+            node_f = torch.empty((n_out, d), dtype=torch.float32, device=dev) if want_feats else None
+            edge_f = torch.empty((e_out, d), dtype=torch.float32, device=dev) if drop else None
         self._gnn_call(lib, feat, ei.data_ptr(), ei.data_ptr() + 8 * e, 0, n, e, abs_pose, rel_pose, node_f, edge_f, status, 0,
                        None if query is None else query[:2])
 
         self.publish_status()                     # every call is validated; nothing blocks in "deferred" mode
 
-        if drop:
+        if md is not None:
+            # node rows are numbered by their row (the query rows by their node id), edge rows by their end points
+            md.last = McSpread(torch.empty_like(abs_pose), torch.empty_like(rel_pose))
+            ids = (None, ei) if query is None else (query[1], query[2])
+            self._drop_heads(node_f, edge_f, abs_pose, rel_pose, (ids[0], 0, (ids[1][0], ids[1][1]), 0, *md.last))
+            md.advance(dev)
+        elif drop:
             node_f = self._drop_heads(node_f, edge_f, abs_pose, rel_pose)
         if query is not None:                     # use_AP, no kNN graph: refused by forward_map otherwise
             return abs_pose, rel_pose, query[2].clone()
@@ -568,8 +619,9 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
         K of K(K+1) columns per graph and its node rows on the queries only (rpg_gnn_forward_query_*): every value is the one
         ``outputs="all"`` gives at the same row, up to the summation order of differently tiled GEMMs.  Same two-stream schedule,
         same workspace pool.  ``droprate > 0`` is served as for ``"all"``, but ``F.dropout`` is drawn over [G, D] and [G*K, D], so a
-        seeded run draws OTHER masks than the full forward does.  ``knn > 0``, an explicit ``k``, ``use_attention`` and
-        ``use_AP=False`` raise NotImplementedError (the selection would depend on the data, or the path allocates between its
+        seeded run draws OTHER masks than the full forward does -- unless ``model.mc_dropout`` is set: its masks follow the node
+        ids (a query row's id is its node's, an edge row's the pair of its end points), so both modes draw the same ones.
+        ``knn > 0``, an explicit ``k``, ``use_attention`` and ``use_AP=False`` raise NotImplementedError (the selection would depend on the data, or the path allocates between its
         launches); an unknown value raises ValueError.
 
         ``_static`` (graphed.GraphedForwardMap only): ``(ranks int32 [G, K], query groups int64 [G] or None)`` already on the
@@ -650,6 +702,7 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
         """``neighbours_of(qf, g0, g1, status, wkey)``: the map rows int64 [g1 - g0, K] of queries g0..g1, whose encoder features
         are ``qf``, made on the current (slot) stream."""
         fmap.check(self)
+        self._mc()
         x, lib, status = self._prepare(queries, "queries")
         dev = x.device
         n_per = kk + 1
@@ -757,17 +810,32 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
         status = self._counters.counters
         cur, streams = self._fork(1 + max(p[4] for p in parts), dev)
         d = self.feature_extractor.fc.out_features
+        md = self._mc()
+        abs_var = None if md is None else torch.empty_like(abs_pose)
 
-        def heads(feat, n0, n1, ei_ptrs, node_off, e, rel_out, slot, wkey, q_slot=None):
+        def heads(feat, n0, n1, ei_ptrs, node_off, e, rel_out, slot, wkey, q_slot=None, mc_edges=None):
+            """``mc_edges`` (with mc_dropout): (edge sources, edge targets, the offset that makes them ids of the whole batch, the
+            slot's rows of rel_var)."""
             abs_out, n_out, e_out = abs_pose[n0:n1], n1 - n0, e
             if q_slot is not None:                # (first graph, selected columns, query nodes) of this slot
                 n_out, e_out = q_slot[2].numel(), q_slot[1].numel()
                 abs_out = abs_pose[q_slot[0]:q_slot[0] + n_out]
-            node_f = torch.empty((n_out, d), dtype=torch.float32, device=dev) if drop else None
-            edge_f = torch.empty((e_out, d), dtype=torch.float32, device=dev) if drop else None
+            if md is not None:
+                # from the pool (a captured step allocates nothing); the slot's stream orders the reuse by the next call
+                node_f = self._pool_rows((600 + wkey[0], wkey[1]), n_out, d, dev)
+                edge_f = self._pool_rows((700 + wkey[0], wkey[1]), e_out, d, dev)
+            else:
+                node_f = torch.empty((n_out, d), dtype=torch.float32, device=dev) if drop else None
+                edge_f = torch.empty((e_out, d), dtype=torch.float32, device=dev) if drop else None
             self._gnn_call(lib, feat, ei_ptrs[0], ei_ptrs[1], node_off, n1 - n0, e, abs_out, rel_out, node_f, edge_f,
                            status[slot:slot + 1], wkey, None if q_slot is None else q_slot[1:])
-            if drop:
+            if md is not None:
+                # the slot's node rows are rows n0 .. of the batch; its query rows carry their node ids themselves
+                var_out = abs_var[n0:n1] if q_slot is None else abs_var[q_slot[0]:q_slot[0] + n_out]
+                node_ids, node_id_off = (None, n0) if q_slot is None else (q_slot[2], 0)
+                self._drop_heads(node_f, edge_f, abs_out, rel_out,
+                                 (node_ids, node_id_off, mc_edges[:2], mc_edges[2], var_out, mc_edges[3]))
+            elif drop:
                 self._drop_heads(node_f, edge_f, abs_out, rel_out)
                 for buf in (node_f, edge_f):
                     buf.record_stream(torch.cuda.current_stream())
@@ -775,6 +843,7 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
         if not knn:
             e_total = edge_index.size(1)
             rel_pose = torch.empty((e_total if query is None else query[0].numel(), 6), dtype=torch.float32, device=dev)
+            rel_var = None if md is None else torch.empty_like(rel_pose)
             base = edge_index.data_ptr()
             for gi, (n0, n1, e0, e1, slot) in enumerate(parts):
                 st = streams[slot]
@@ -783,17 +852,25 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
                     # but a different shape would re-allocate every call
                     wkey = (slot, gi)
                     feat = features(n0, n1, wkey)
-                    rel_out, q_slot = rel_pose[e0:e1], None
+                    rel_out, q_slot, c0, c1 = rel_pose[e0:e1], None, e0, e1
                     if query is not None:
                         # the slot's graphs g0 .. g1: their query nodes (ids of the whole batch, like the slot's edges) and, the
                         # list being one pattern per graph, the first (g1 - g0) K entries of the selection as its local columns
                         n_per, k_sel = per_graph
                         g0, g1 = n0 // n_per, n1 // n_per
                         q_slot = (g0, query[0][:(g1 - g0) * k_sel], query[1][g0:g1])
-                        rel_out = rel_pose[g0 * k_sel:g1 * k_sel]
-                    heads(feat, n0, n1, (base + 8 * e0, base + 8 * (e_total + e0)), n0, e1 - e0, rel_out, slot, wkey, q_slot)
+                        c0, c1 = g0 * k_sel, g1 * k_sel
+                        rel_out = rel_pose[c0:c1]
+                    mc_edges = None
+                    if md is not None:            # the rows' end points, ids of the whole batch: the list's (or the selection's) columns
+                        ends = edge_index if query is None else query[2]
+                        mc_edges = (ends[0, c0:c1], ends[1, c0:c1], 0, rel_var[c0:c1])
+                    heads(feat, n0, n1, (base + 8 * e0, base + 8 * (e_total + e0)), n0, e1 - e0, rel_out, slot, wkey, q_slot, mc_edges)
                     feat.record_stream(st)
             self._join(cur, streams)
+            if md is not None:                    # once per forward, behind every slot's heads: the next call draws new masks
+                md.last = McSpread(abs_var, rel_var)
+                md.advance(dev)
             self.publish_status()
             return abs_pose, rel_pose, (edge_index if query is None else query[2].clone())
 
@@ -810,7 +887,7 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
                 ev = torch.cuda.Event()
                 ev.record(st)
                 pend.append((feat, ei_buf, meta, meta_h, ev, wkey))
-        rels, eis = [], []
+        rels, eis, rel_vars = [], [], []
         for (n0, n1, _, _, slot), (feat, ei_buf, meta, meta_h, ev, wkey) in zip(parts, pend):
             ev.synchronize()
             total, bad = int(meta_h[0]), int(meta_h[1])
@@ -823,7 +900,12 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
             with torch.cuda.stream(st):
                 cap = ei_buf.size(1)
                 rel = torch.empty((total, 6), dtype=torch.float32, device=dev)
-                heads(feat, n0, n1, (ei_buf.data_ptr(), ei_buf.data_ptr() + 8 * cap), 0, total, rel, slot, wkey)
+                mc_edges = None
+                if md is not None:                # the kNN edges' end points are ids of the slot: n0 makes them the batch's
+                    rel_vars.append(torch.empty_like(rel))
+                    rel_vars[-1].record_stream(cur)
+                    mc_edges = (ei_buf[0, :total], ei_buf[1, :total], n0, rel_vars[-1])
+                heads(feat, n0, n1, (ei_buf.data_ptr(), ei_buf.data_ptr() + 8 * cap), 0, total, rel, slot, wkey, None, mc_edges)
                 ei_g = ei_buf[:, :total] + n0                                     # node ids of the whole batch (posenet.py:1048)
                 eis.append(ei_g)
                 rels.append(rel)
@@ -832,5 +914,8 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
                 for buf in (rel, ei_g):                # allocated on the slot's stream, concatenated on the caller's below
                     buf.record_stream(cur)
         self._join(cur, streams)
+        if md is not None:
+            md.last = McSpread(abs_var, torch.cat(rel_vars))
+            md.advance(dev)
         self.publish_status()
         return abs_pose, torch.cat(rels), torch.cat(eis, dim=1)
