@@ -692,6 +692,11 @@ int rpg_resize_table_bilinear(int in, int out, int32_t* bounds, int32_t* weights
  * One launch, no allocation, no synchronisation (graph-capturable).  rpg_frames_workspace_bytes: workspace of the launch;
  * the fused kernel keeps its intermediate in LDS, so it is 0 for every geometry taken today.                              */
 size_t rpg_frames_workspace_bytes(int n, int in_h, int in_w, int out_h, int out_w);
+/* HOST: the tile plan rpg_frames_u8_to_* launches this geometry with (the launcher's own planner; no device needed):
+ * plan8 = {tile rows, tile columns, row tiles, column tiles per frame, source rows a tile stages (max over tiles), LDS bytes
+ * per staged row, LDS bytes of a workgroup, horizontal pass | vertical pass << 1}.  RPG_ERR_BAD_ARG for the sizes the launch
+ * refuses (non-positive, downscale beyond 31x, frames beyond 2^40 bytes or 2^36 output pixels).                          */
+int rpg_frames_plan(int in_h, int in_w, int out_h, int out_w, int32_t* plan8);
 int rpg_frames_u8_to_f32(const uint8_t* frames, int n, int in_h, int in_w, int out_h, int out_w, const int32_t* h_bounds,
                          const int32_t* h_weights, const int32_t* v_bounds, const int32_t* v_weights, float mean0, float mean1,
                          float mean2, float std0, float std1, float std2, float* out, void* workspace, size_t workspace_bytes,

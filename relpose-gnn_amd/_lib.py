@@ -29,7 +29,7 @@ SYMBOLS = (
     "rpg_attention_aggregate_f32", "rpg_stem_conv7x7s2_bn_relu_maxpool_bf16", "rpg_stem_conv7x7s2_bn_relu_maxpool_bf16_xbf16",
     "rpg_resnet_forward_bf16_xbf16", "rpg_host_f32_to_bf16", "rpg_basicblock64_bf16", "rpg_linear_gather_ex_f32", "rpg_probe_mfma_bf16", "rpg_host_f32_to_bf16_isa",
     "rpg_resize_table_ksize", "rpg_resize_table_bilinear", "rpg_frames_workspace_bytes", "rpg_frames_u8_to_f32",
-    "rpg_frames_u8_to_bf16", "rpg_gather_graph_nodes_f32", "rpg_linear_bf16_ex", "rpg_conv_pair_bf16",
+    "rpg_frames_u8_to_bf16", "rpg_frames_plan", "rpg_gather_graph_nodes_f32", "rpg_linear_bf16_ex", "rpg_conv_pair_bf16",
     "rpg_retrieve_workspace_bytes", "rpg_retrieve_max_rank", "rpg_row_inv_norms_f32", "rpg_retrieve_cosine_f32",
     "rpg_query_pose_f64", "rpg_query_pose_fused_f64", "rpg_gather_add2_relu_f32",
     "rpg_gnn_query_workspace_bytes", "rpg_gnn_forward_query_f32", "rpg_gnn_forward_query_bf16", "rpg_gemm_last_route", "rpg_get_tuning",
@@ -123,6 +123,7 @@ def _declare(lib: C.CDLL) -> None:
     lib.rpg_frames_workspace_bytes.restype = _sz
     lib.rpg_frames_u8_to_f32.argtypes = [_vp] + [_i] * 5 + [_vp] * 4 + [C.c_float] * 6 + [_vp, _vp, _sz, _vp]
     lib.rpg_frames_u8_to_bf16.argtypes = lib.rpg_frames_u8_to_f32.argtypes
+    lib.rpg_frames_plan.argtypes = [_i] * 4 + [_vp]
     lib.rpg_gather_graph_nodes_f32.argtypes = [_vp, _vp, _vp, _i, _i, C.c_int64, _i, _vp, _vp, _vp]
     lib.rpg_retrieve_workspace_bytes.argtypes = [_i, C.c_int64, _i]
     lib.rpg_retrieve_workspace_bytes.restype = _sz

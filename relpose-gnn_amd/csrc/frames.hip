@@ -28,8 +28,7 @@ namespace {
 
 constexpr int NT = 256;
 constexpr int kPrec = 22;                        // Pillow's PRECISION_BITS for 8-bit images (32 - 8 - 2)
-constexpr size_t kLdsBudget = 48 * 1024;         // preferred workgroup LDS (3 workgroups per CU)
-constexpr size_t kLdsMax = 64 * 1024;            // hard limit (no opt-in attribute needed)
+constexpr size_t kLdsBudget = 48 * 1024;         // workgroup LDS (3 workgroups per CU); see make_plan for why it always suffices
 constexpr int kMaxTaps = 64;                     // host-side weight buffer of one output index (downscale <= 31x)
 
 // ---- host: Pillow's coefficient rule (Resample.c precompute_coeffs, bilinear filter, support 1) ----------------------
@@ -116,16 +115,23 @@ bool plan_for(int in_h, int in_w, int out_h, int out_w, size_t budget, int tr, i
 }
 
 // Widest tiles first (full output rows: every store instruction writes contiguous columns), then the most rows per tile.
+// The search ends at a 1 x 1 tile, which fits kLdsBudget for every geometry size_ok admits: at most kMaxTaps - 1 = 63 source
+// rows of 63 columns (pitch 208) are staged, 3072 + 260 + 260 + 63 * 208 + 189 bytes in all, about 17 KiB.  So there is no
+// second, larger budget, and the final return is never taken for sizes that passed size_ok.
 bool make_plan(int in_h, int in_w, int out_h, int out_w, Plan* p) {
     static const int kRows[] = {16, 8, 4, 2, 1};
-    for (size_t budget : {kLdsBudget, kLdsMax}) {
-        for (int tc = out_w;; tc = (tc + 1) / 2) {
-            for (int tr : kRows)
-                if (plan_for(in_h, in_w, out_h, out_w, budget, tr < out_h ? tr : out_h, tc, p)) return true;
-            if (tc == 1) break;
-        }
+    for (int tc = out_w;; tc = (tc + 1) / 2) {
+        for (int tr : kRows)
+            if (plan_for(in_h, in_w, out_h, out_w, kLdsBudget, tr < out_h ? tr : out_h, tc, p)) return true;
+        if (tc == 1) break;
     }
     return false;
+}
+
+// the geometries launch_frames takes (the tables, the pointers and the statistics are its own business)
+bool geometry_ok(int in_h, int in_w, int out_h, int out_w) {
+    if (!size_ok(in_h, out_h) || !size_ok(in_w, out_w)) return false;
+    return (long)in_h * in_w * 3 <= (1L << 40) && (long)out_h * out_w <= (1L << 36);
 }
 
 // ---- device ----------------------------------------------------------------------------------------------------------
@@ -295,11 +301,10 @@ __global__ __launch_bounds__(NT) void frames_kernel(Args a, Plan p, OutT* __rest
 template <typename OutT>
 int launch_frames(const uint8_t* frames, int n, int in_h, int in_w, int out_h, int out_w, const int32_t* hb, const int32_t* hw,
                   const int32_t* vb, const int32_t* vw, const float* mean, const float* stdv, OutT* out, hipStream_t s) {
-    if (!frames || !out || n <= 0 || !size_ok(in_h, out_h) || !size_ok(in_w, out_w) ||
+    if (!frames || !out || n <= 0 || !geometry_ok(in_h, in_w, out_h, out_w) ||
         (reinterpret_cast<uintptr_t>(out) % sizeof(OutT)) != 0)
         return RPG_ERR_BAD_ARG;
     if ((in_w != out_w && (!hb || !hw)) || (in_h != out_h && (!vb || !vw))) return RPG_ERR_BAD_ARG;
-    if ((long)in_h * in_w * 3 > (1L << 40) || (long)out_h * out_w > (1L << 36)) return RPG_ERR_BAD_ARG;
     for (int c = 0; c < 3; ++c)
         if (!(stdv[c] != 0.0f) || !isfinite(stdv[c]) || !isfinite(mean[c])) return RPG_ERR_BAD_ARG;
     Plan p;
@@ -331,6 +336,15 @@ int launch_frames(const uint8_t* frames, int n, int in_h, int in_w, int out_h, i
 }  // namespace
 
 extern "C" int rpg_resize_table_ksize(int in, int out) { return size_ok(in, out) ? ksize_of(in, out) : RPG_ERR_BAD_ARG; }
+
+extern "C" int rpg_frames_plan(int in_h, int in_w, int out_h, int out_w, int32_t* plan8) {
+    Plan p;
+    if (!plan8 || !geometry_ok(in_h, in_w, out_h, out_w) || !make_plan(in_h, in_w, out_h, out_w, &p)) return RPG_ERR_BAD_ARG;
+    const int32_t v[8] = {p.tr, p.tc, (int32_t)p.tiles_y, (int32_t)p.tiles_x, p.rows_max, p.pitch, (int32_t)p.lds,
+                          (int32_t)p.need_h | (int32_t)p.need_v << 1};
+    for (int i = 0; i < 8; ++i) plan8[i] = v[i];
+    return RPG_OK;
+}
 
 extern "C" int rpg_resize_table_bilinear(int in, int out, int32_t* bounds, int32_t* weights) {
     if (!bounds || !weights || !size_ok(in, out)) return RPG_ERR_BAD_ARG;

@@ -215,6 +215,24 @@ def f32_to_bf16(x: torch.Tensor, out: Optional[torch.Tensor] = None, col_off: in
     return out
 
 
+def _frames_axis_tables(axis: str, n_in: int, n_out: int, bounds, weights, dev) -> None:
+    """The tables of one axis of a frame launch are ``resize_table(n_in, n_out)``'s, on ``dev``, in shape and type; None where
+    the size does not change.  The kernel indexes them by the sizes alone, so anything else is refused here (ValueError)."""
+    if n_in == n_out:
+        if bounds is not None or weights is not None:
+            raise ValueError(f"frames: the {axis} size does not change ({n_in}), so its tables must be None")
+        return
+    ks = L.lib().rpg_resize_table_ksize(int(n_in), int(n_out))
+    if ks <= 0:
+        raise ValueError(f"frames: unsupported {axis} sizes {n_in} -> {n_out}")
+    for name, t, shape in (("bounds", bounds, (n_out, 2)), ("weights", weights, (n_out, ks))):
+        if (not torch.is_tensor(t) or t.dtype != torch.int32 or tuple(t.shape) != shape or not t.is_contiguous()
+                or t.device != dev):
+            got = f"{t.dtype} {list(t.shape)} on {t.device}" if torch.is_tensor(t) else type(t).__name__
+            raise ValueError(f"frames: the {axis} {name} of {n_in} -> {n_out} must be a contiguous int32 {list(shape)} tensor "
+                             f"on the frames' GPU (resize_table), got {got}")
+
+
 def _frames(frames: torch.Tensor, out_hw: Tuple[int, int], tables, mean: Sequence[float], std: Sequence[float],
             dtype, out: Optional[torch.Tensor]) -> torch.Tensor:
     frames = _req(frames, "frames", torch.uint8)
@@ -223,6 +241,8 @@ def _frames(frames: torch.Tensor, out_hw: Tuple[int, int], tables, mean: Sequenc
     n, h, w, _ = frames.shape
     oh, ow = int(out_hw[0]), int(out_hw[1])
     hb, hw, vb, vw = tables
+    _frames_axis_tables("horizontal", w, ow, hb, hw, frames.device)
+    _frames_axis_tables("vertical", h, oh, vb, vw, frames.device)
     out = _out(out, (n, 3, oh, ow), dtype, frames.device, "frames")
     fn = L.lib().rpg_frames_u8_to_bf16 if dtype == torch.bfloat16 else L.lib().rpg_frames_u8_to_f32
     L.check(fn(_p(frames), n, h, w, oh, ow, _p(hb), _p(hw), _p(vb), _p(vw), *[float(v) for v in mean], *[float(v) for v in std],
@@ -256,6 +276,22 @@ def resize_table(n_in: int, n_out: int):
     if rc != ks:
         raise ValueError(f"resize_table: unsupported sizes {n_in} -> {n_out}")
     return bounds, weights
+
+
+PLAN_FIELDS = ("tr", "tc", "tiles_y", "tiles_x", "rows_max", "pitch", "lds_bytes")
+
+
+def frames_plan(in_h: int, in_w: int, out_h: int, out_w: int) -> Dict[str, object]:
+    """HOST: the tile plan frames_u8_to_* launches this geometry with (rpg_frames_plan: the launcher's own planner): tile rows
+    ``tr`` x columns ``tc``, ``tiles_y`` x ``tiles_x`` tiles per frame, ``rows_max`` staged source rows, ``pitch`` LDS bytes per
+    staged row, ``lds_bytes`` per workgroup, and which passes run (``need_h``, ``need_v``).  ValueError for sizes the launch
+    refuses."""
+    raw = (C.c_int32 * 8)()
+    if L.lib().rpg_frames_plan(int(in_h), int(in_w), int(out_h), int(out_w), raw) != 0:
+        raise ValueError(f"frames_plan: unsupported sizes {in_h} x {in_w} -> {out_h} x {out_w}")
+    plan: Dict[str, object] = {k: int(raw[i]) for i, k in enumerate(PLAN_FIELDS)}
+    plan["need_h"], plan["need_v"] = bool(raw[7] & 1), bool(raw[7] & 2)
+    return plan
 
 
 def _linear_bf16_args(a, weight, bias, residual, res_idx, residual2, res2_idx, strided: bool = False):
