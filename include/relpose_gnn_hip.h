@@ -299,6 +299,43 @@ int rpg_query_pose_consensus_f64(const float* rel_pose, const int64_t* edge_src,
                                  int max_edges, double inlier_t, double inlier_deg, double* out, double* cand, int32_t* count,
                                  int32_t* inliers, int32_t* status, void* stream);
 
+/* A query's reference edges weighted by their Monte-Carlo variance, with the predicted deviation of the fused pose: a further mode
+ * of the kernel behind rpg_query_pose_fused_f64, for its fuse 0 (consensus = 0) and for rpg_query_pose_consensus_f64 (consensus =
+ * 1).  Candidates (used, C, t_c, q_c), the graphs' two forms, arithmetic, row layout, cand, count, bad graphs, status, the voting,
+ * I and inliers are those of the two; the thresholds are checked always and read with consensus = 1.  Beyond them:
+ *   rel_var [e][6] fp32   row for row with rel_pose: the variance of ONE dropout sample of that relative pose (what
+ *                         rpg_pose_heads_mc_f32 leaves); v_c[0..5] = its row at used column c, read as float64
+ *   var_floor             added to every variance before the division; finite, >= 1e-30
+ *   w_cj   = 1.0 / (v_c[j] + var_floor), j = 0..2                     the translation weights, per component
+ *   wq_c   = 1.0 / (((v_c[3] + v_c[4]) + v_c[5]) + var_floor)         the rotation weight, one scalar
+ *   v_c is UNUSABLE when one of its six values is NaN, negative or +inf
+ *   over a slot set I of two or more, every sum sequential in column order:
+ *            W_j = sum w_cj,  t_j = (sum w_cj t_cj) / W_j;   Wq = sum wq_c,  q = S / |S| with S = sum of (wq_c q_c if <q_c, q_first>
+ *            >= 0 else -wq_c q_c), q_first the first slot of I, and q_first itself where |S| = 0
+ *   over a set I of one slot the candidate as it is, W_j and Wq its own weights
+ *   consensus 0   I = all C used candidates.  C >= 2 and a used candidate with a non-finite component OR an unusable variance: pred[7]
+ *                 and both errors NaN (targ as always); not a bad graph.  C = 1: the candidate as it is, whatever its variance
+ *   consensus 1   a candidate with an unusable variance is treated like one with a non-finite component: it supports nothing and is
+ *                 supported by nothing.  The voting itself is unweighted; I = the inliers, and the weighted mean replaces the plain one
+ *   spread [g][2] float64 or NULL   (sigma_t, sigma_q) = (sqrt((s_0 s_0 / W_0 + s_1 s_1 / W_1) + s_2 s_2 / W_2), sqrt(1.0 / Wq)) with
+ *                 s = pose_s: the predicted standard deviation of the fused translation in the un-normalised unit and of the fused
+ *                 rotation in log-quaternion units (2 sigma_q radians ~ the deviation of the rotation angle).  Both NaN where a
+ *                 component of pred is NaN, for a bad graph, and for C = 1 under consensus 0 with an unusable variance
+ *   when every v + var_floor of the used candidates is the same power of two, pred and the errors are those of the unweighted
+ *                 mode bit for bit (scaling by a power of two commutes with every operation above)
+ * rel_var not NULL and 4-byte aligned, spread 16-byte aligned, var_floor finite and >= 1e-30, consensus 0 or 1, inliers NULL with
+ * consensus 0 (RPG_ERR_BAD_ARG otherwise).  Lane c reads its six variances where it makes candidate c and writes its four weights
+ * to LDS beside it; usability is one more ballot next to the finite one; lane 0 runs the weighted sums over the masked slots in
+ * slot order; the row goes out by the same eight 16-byte stores and spread by one more.  No floating-point atomics.  One launch,
+ * no allocation, no synchronisation (graph-capturable).                                                                    */
+int rpg_query_pose_weighted_f64(const float* rel_pose, const int64_t* edge_src, const int64_t* edge_dst, int64_t e,
+                                const int64_t* node_first, const int64_t* edge_first, int g, const float* node_targets, int64_t n,
+                                const float* map_poses, int64_t m, const int64_t* neighbours, int k, const float* query_targets,
+                                double pose_m0, double pose_m1, double pose_m2, double pose_s0, double pose_s1, double pose_s2,
+                                int max_edges, double inlier_t, double inlier_deg, const float* rel_var, double var_floor,
+                                int consensus, double* out, double* cand, int32_t* count, int32_t* inliers, double* spread,
+                                int32_t* status, void* stream);
+
 /* torch_cluster.knn_graph(x, k, batch, loop=False, flow='source_to_target') (posenet.py:1043-1050): for every node
  * the k nearest OTHER nodes of its graph by squared Euclidean distance (k+1 nearest including itself by
  * (distance, index), self match dropped).  x [n][d]; batch [n] int64 graph id per node, nodes of a graph contiguous,

@@ -207,6 +207,14 @@ __global__ __launch_bounds__(QP_NT) void query_pose_kernel(const QpArgs a) {
 // an angle test); the same kind of butterfly takes the lexicographic maximum of (support, lowest c); every lane then tests itself
 // against that winner, one ballot is the inlier mask in slot order and its popcount the inlier count; lane 0 runs the mean's
 // sequential sums over the masked slots.  A non-finite candidate is an outlier here, it does not void the pose.
+//
+// Inverse-variance weights (rpg_query_pose_weighted_f64) are a further mode of `mean` and of `consensus`, not a rule of their own:
+// lane c reads its column's six variances where it makes candidate c, turns them into three translation weights and one rotation
+// weight, 1 / (v + var_floor), and writes the four beside the candidate in LDS (4 waves x 64 x 4 doubles = 8 KB more); whether the
+// six can be used (none NaN, negative or +inf) is one more ballot next to the finite one, and an unusable variance counts wherever
+// a non-finite candidate does.  The voting is unchanged and unweighted.  Lane 0 then runs mean_of_weighted in place of mean_of over
+// the same slot mask, again sequentially in slot order, and writes the two predicted deviations of the fused pose (`spread`) with
+// one 16-byte store.  Without weights none of this is read or written and mean_of is what runs.
 constexpr int QF_MEAN = 0, QF_MEDIAN = 1, QF_CONSENSUS = 2;
 constexpr int QF_MAX = 64;            // candidates per graph: one per lane
 
@@ -217,7 +225,32 @@ struct QfArgs {
     int32_t* count;                   // [g] | null
     double inlier_t, inlier_deg;      // consensus: the two thresholds
     int32_t* inliers;                 // consensus: [g][2] = (inliers, used) | null
+    const float* rel_var;             // weighted: [e][6], row for row with rel_pose | null = unweighted
+    double var_floor;                 // weighted: added to every variance before the division
+    double* spread;                   // weighted: [g][2] = (sigma_t, sigma_q) | null
 };
+
+// the two predicted deviations of a fused pose from its weight sums W[3] and Wq
+__device__ __forceinline__ void spread_of(const double* sw, double swq, const double* pose_s, double* sp) {
+#pragma clang fp contract(off)
+    sp[0] = sqrt((pose_s[0] * pose_s[0] / sw[0] + pose_s[1] * pose_s[1] / sw[1]) + pose_s[2] * pose_s[2] / sw[2]);
+    sp[1] = sqrt(1.0 / swq);
+}
+
+// `spread` of graph gi (when asked for): one 16-byte store; NaN where the pose has a NaN component
+__device__ __forceinline__ void store_spread(double* spread, int64_t gi, const double* pt, const double* pq, const double* sp) {
+    if (!spread) return;
+    bool nan = false;
+    for (int i = 0; i < 3; ++i) nan = nan || isnan(pt[i]);
+    for (int i = 0; i < 4; ++i) nan = nan || isnan(pq[i]);
+    const double v = __builtin_nan("");
+    *reinterpret_cast<double2*>(spread + gi * 2) = nan ? make_double2(v, v) : make_double2(sp[0], sp[1]);
+}
+
+__device__ __forceinline__ void store_nan_spread(double* spread, int64_t gi) {
+    const double v = __builtin_nan("");
+    if (spread) *reinterpret_cast<double2*>(spread + gi * 2) = make_double2(v, v);
+}
 
 // The `mean` of the candidates (t[3], q[4]) whose slot is set in `mask` (never empty), every sum sequential in slot order:
 // t = the sum / n; q = S / |S| with S the sum of q_c where <q_c, q_0> >= 0 and of -q_c elsewhere, q_0 = the first set slot, and
@@ -237,6 +270,32 @@ __device__ __forceinline__ void mean_of(const double (*cand)[7], unsigned long l
     for (int i = 0; i < 4; ++i) fq[i] = norm == 0.0 ? c0[3 + i] : sq[i] / norm;
 }
 
+// The weighted form of mean_of over the same kind of mask (two or more slots): `wt` holds per slot the translation weights w[3] and
+// the rotation weight wq.  t_j = (sum w_j t_j) / W_j with W_j = sum w_j; q = S / |S| with S the sum of +/- wq q_c, the sign as in
+// mean_of; every sum sequential in slot order.  sp = (sqrt((s_0 s_0 / W_0 + s_1 s_1 / W_1) + s_2 s_2 / W_2), sqrt(1 / Wq)), s = pose_s.
+__device__ __forceinline__ void mean_of_weighted(const double (*cand)[7], const double (*wt)[4], unsigned long long mask,
+                                                 const double* pose_s, double* ft, double* fq, double* sp) {
+#pragma clang fp contract(off)
+    const double* c0 = cand[__ffsll((long long)mask) - 1];
+    double st[3] = {0.0, 0.0, 0.0}, sw[3] = {0.0, 0.0, 0.0}, sq[4] = {0.0, 0.0, 0.0, 0.0}, swq = 0.0;
+    for (unsigned long long rest = mask; rest != 0ull; rest &= rest - 1ull) {
+        const int c = __ffsll((long long)rest) - 1;
+        const double* cd = cand[c];
+        const double* w = wt[c];
+        for (int i = 0; i < 3; ++i) {
+            st[i] = st[i] + w[i] * cd[i];
+            sw[i] = sw[i] + w[i];
+        }
+        const double dot = cd[3] * c0[3] + cd[4] * c0[4] + cd[5] * c0[5] + cd[6] * c0[6];
+        for (int i = 0; i < 4; ++i) sq[i] = dot >= 0.0 ? sq[i] + w[3] * cd[3 + i] : sq[i] - w[3] * cd[3 + i];
+        swq = swq + w[3];
+    }
+    for (int i = 0; i < 3; ++i) ft[i] = st[i] / sw[i];
+    const double norm = sqrt(sq[0] * sq[0] + sq[1] * sq[1] + sq[2] * sq[2] + sq[3] * sq[3]);
+    for (int i = 0; i < 4; ++i) fq[i] = norm == 0.0 ? c0[3 + i] : sq[i] / norm;
+    spread_of(sw, swq, pose_s, sp);
+}
+
 // whether two FINITE candidates (t[3], q[4]) support each other: symmetric bit for bit -- the squares and the products of the dot
 // are the same numbers either way round
 __device__ __forceinline__ bool cons_support(const double* c, const double* d, double inlier_t, double inlier_deg) {
@@ -248,10 +307,12 @@ __global__ __launch_bounds__(QP_NT) void query_pose_fused_kernel(const QfArgs f)
 #pragma clang fp contract(off)
     __shared__ double s_cand[QP_NT / 64][QF_MAX][7];      // per wave: candidate c = t[3], q[4]
     __shared__ long long s_col[QP_NT / 64][QF_MAX];       // per wave: the column of candidate c
+    __shared__ double s_wt[QP_NT / 64][QF_MAX][4];        // per wave, weighted only: candidate c's weights w[3], wq
     const QpArgs& a = f.q;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int64_t gi = (int64_t)blockIdx.x * (QP_NT / 64) + w;
     const bool active = gi < a.g;                         // (wave-uniform; no wave leaves before the last barrier)
+    const bool weighted = f.rel_var != nullptr;
 
     // ---- the usable columns, in column order: target = the graph's first node, source != that node -------------------------------
     QpSpan s = {0, 0, 0, 0};
@@ -278,6 +339,7 @@ __global__ __launch_bounds__(QP_NT) void query_pose_fused_kernel(const QfArgs f)
     const bool mine = active && lane < cn;
     bool bad = false, void_row = false;
     unsigned long long finite = 0ull;                     // the used candidates without a non-finite component, by slot
+    unsigned long long unusable_any = 0ull;               // weighted: the used candidates whose variance cannot be used, by slot
     double pt[3], pq[4], tt[3], tq[4], t_err = 0.0, q_err = 0.0;
     for (int i = 0; i < 3; ++i) pt[i] = tt[i] = 0.0;
     for (int i = 0; i < 4; ++i) pq[i] = tq[i] = 0.0;
@@ -307,9 +369,24 @@ __global__ __launch_bounds__(QP_NT) void query_pose_fused_kernel(const QfArgs f)
                     nf_lane = nf_lane || !isfinite(pq[i]);
                 }
             }
-            const unsigned long long nf = __ballot(nf_lane);
+            unsigned long long nf = __ballot(nf_lane);
+            if (weighted) {                               // an unusable variance counts wherever a non-finite candidate does
+                bool unusable = false;
+                if (mine) {
+                    const float* vrow = f.rel_var + col * 6;
+                    double v[6];
+                    for (int i = 0; i < 6; ++i) {
+                        v[i] = (double)vrow[i];
+                        unusable = unusable || !(v[i] >= 0.0) || v[i] == __builtin_inf();
+                    }
+                    for (int i = 0; i < 3; ++i) s_wt[w][lane][i] = 1.0 / (v[i] + f.var_floor);
+                    s_wt[w][lane][3] = 1.0 / (((v[3] + v[4]) + v[5]) + f.var_floor);
+                }
+                unusable_any = __ballot(unusable);
+                if (f.fuse == QF_CONSENSUS) nf |= unusable_any;
+            }
             finite = __ballot(mine) & ~nf;
-            void_row = cn > 1 && nf != 0ull;              // a non-finite candidate voids the fused pose (not C = 1)
+            void_row = cn > 1 && (nf | unusable_any) != 0ull;     // a non-finite candidate voids the fused pose (not C = 1)
         }
         if (f.cand && lane < f.max_edges) {
             double* crow = f.cand + (gi * f.max_edges + lane) * 16;
@@ -327,12 +404,13 @@ __global__ __launch_bounds__(QP_NT) void query_pose_fused_kernel(const QfArgs f)
         if (lane == 0) {
             atomicAdd(a.status, 1);
             store_nan_row(a.out + gi * 16);
+            store_nan_spread(f.spread, gi);
             if (f.inliers) *reinterpret_cast<int2*>(f.inliers + gi * 2) = make_int2(0, cn);
         }
         return;
     }
     // ---- the fused pose (the whole wave is here: cross-lane moves below; lane 0 stores it) -----------------------------------------
-    double ft[3], fq[4];
+    double ft[3], fq[4], sp[2] = {0.0, 0.0};
     if (f.fuse == QF_CONSENSUS) {                         // the candidates vote
         const bool fin = ((finite >> lane) & 1ull) != 0ull;
         double me[7];
@@ -364,24 +442,44 @@ __global__ __launch_bounds__(QP_NT) void query_pose_fused_kernel(const QfArgs f)
         if (f.inliers) *reinterpret_cast<int2*>(f.inliers + gi * 2) = make_int2(ni, cn);
         if (ni == 0) {                                    // every candidate is non-finite
             store_void_row(a.out + gi * 16, tt, tq);
+            store_nan_spread(f.spread, gi);
             return;
         }
         if (ni == 1) {                                    // one inlier as it is
-            const double* c0 = s_cand[w][__ffsll((long long)mask) - 1];
+            const int c = __ffsll((long long)mask) - 1;
+            const double* c0 = s_cand[w][c];
             for (int i = 0; i < 3; ++i) ft[i] = c0[i];
             for (int i = 0; i < 4; ++i) fq[i] = c0[3 + i];
+            if (weighted) spread_of(s_wt[w][c], s_wt[w][c][3], a.pose_s, sp);
+        } else if (weighted) {
+            mean_of_weighted(s_cand[w], s_wt[w], mask, a.pose_s, ft, fq, sp);
         } else {
             mean_of(s_cand[w], mask, ft, fq);
         }
     } else if (cn == 1) {                                 // the candidate as it is: the single-edge rule's row
-        if (lane == 0) store_row(a.out + gi * 16, pt, pq, tt, tq, t_err, q_err);
+        if (lane == 0) {
+            store_row(a.out + gi * 16, pt, pq, tt, tq, t_err, q_err);
+            if (weighted && unusable_any == 0ull) {
+                spread_of(s_wt[w][0], s_wt[w][0][3], a.pose_s, sp);
+                store_spread(f.spread, gi, pt, pq, sp);
+            } else {
+                store_nan_spread(f.spread, gi);
+            }
+        }
         return;
     } else if (void_row) {
-        if (lane == 0) store_void_row(a.out + gi * 16, tt, tq);
+        if (lane == 0) {
+            store_void_row(a.out + gi * 16, tt, tq);
+            store_nan_spread(f.spread, gi);
+        }
         return;
     } else if (f.fuse == QF_MEAN) {
         if (lane != 0) return;
-        mean_of(s_cand[w], ~0ull >> (64 - cn), ft, fq);    // slots 0 .. cn - 1 (cn can be 64: no 1ull << cn)
+        if (weighted) {
+            mean_of_weighted(s_cand[w], s_wt[w], ~0ull >> (64 - cn), a.pose_s, ft, fq, sp);
+        } else {
+            mean_of(s_cand[w], ~0ull >> (64 - cn), ft, fq);    // slots 0 .. cn - 1 (cn can be 64: no 1ull << cn)
+        }
     } else {
         // component-wise median of t: every lane ranks its own value, ties by slot, and the middle rank(s) are read
         for (int j = 0; j < 3; ++j) {
@@ -417,11 +515,12 @@ __global__ __launch_bounds__(QP_NT) void query_pose_fused_kernel(const QfArgs f)
         for (int i = 0; i < 4; ++i) fq[i] = s_cand[w][best][3 + i];
     }
     store_row(a.out + gi * 16, ft, fq, tt, tq, trans_dist(ft, tt), quat_angle(fq, tq));
+    store_spread(f.spread, gi, ft, fq, sp);
 }
 
 inline bool misaligned(const void* p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
 
-// what the three entry points share, as they declare it and as they hand it on
+// what the four entry points share, as they declare it and as they hand it on
 #define QP_SHARED_PARAMS                                                                                                        \
     const float *rel_pose, const int64_t *edge_src, const int64_t *edge_dst, int64_t e, const int64_t *node_first,             \
         const int64_t *edge_first, int g, const float *node_targets, int64_t n, const float *map_poses, int64_t m,              \
@@ -452,10 +551,18 @@ bool qp_args(QpArgs& a, QP_SHARED_PARAMS, int ref_node, double* out, int32_t* st
 inline unsigned qp_grid(int g) { return (unsigned)((g + QP_NT / 64 - 1) / (QP_NT / 64)); }
 
 // the fused kernel over `f`, whose `q` qp_args has filled: what is the fused rule's own is checked and set here
+// (`weighted`: rel_var [e][6] and var_floor are read and spread may be written; otherwise the three are null / 0 / null)
 int launch_fused(QfArgs& f, int fuse, int max_edges, double inlier_t, double inlier_deg, double* cand, int32_t* count,
-                 int32_t* inliers, void* stream) {
+                 int32_t* inliers, bool weighted, const float* rel_var, double var_floor, double* spread, void* stream) {
     if (max_edges < 1 || max_edges > QF_MAX) return RPG_ERR_BAD_ARG;
     if (misaligned(count, 3) || misaligned(inliers, 7) || (cand && !rpg::aligned16(cand))) return RPG_ERR_BAD_ARG;
+    if (weighted) {                                       // (written so that a NaN floor fails the test too)
+        if (!rel_var || misaligned(rel_var, 3) || (spread && !rpg::aligned16(spread))) return RPG_ERR_BAD_ARG;
+        if (!(var_floor >= 1e-30 && var_floor < __builtin_inf())) return RPG_ERR_BAD_ARG;
+    }
+    f.rel_var = weighted ? rel_var : nullptr;
+    f.var_floor = weighted ? var_floor : 0.0;
+    f.spread = weighted ? spread : nullptr;
     f.fuse = fuse;
     f.max_edges = max_edges;
     f.cand = cand;
@@ -482,7 +589,7 @@ extern "C" int rpg_query_pose_fused_f64(QP_SHARED_PARAMS, int fuse, int max_edge
                                         int32_t* status, void* stream) {
     QfArgs f;
     if ((fuse != QF_MEAN && fuse != QF_MEDIAN) || !qp_args(f.q, QP_SHARED, 0, out, status)) return RPG_ERR_BAD_ARG;
-    return launch_fused(f, fuse, max_edges, 0.0, 0.0, cand, count, nullptr, stream);
+    return launch_fused(f, fuse, max_edges, 0.0, 0.0, cand, count, nullptr, false, nullptr, 0.0, nullptr, stream);
 }
 
 extern "C" int rpg_query_pose_consensus_f64(QP_SHARED_PARAMS, int max_edges, double inlier_t, double inlier_deg, double* out,
@@ -491,5 +598,16 @@ extern "C" int rpg_query_pose_consensus_f64(QP_SHARED_PARAMS, int max_edges, dou
     if (!(inlier_t >= 0.0 && inlier_t < __builtin_inf()) || !(inlier_deg >= 0.0 && inlier_deg <= 360.0)) return RPG_ERR_BAD_ARG;
     QfArgs f;
     if (!qp_args(f.q, QP_SHARED, 0, out, status)) return RPG_ERR_BAD_ARG;
-    return launch_fused(f, QF_CONSENSUS, max_edges, inlier_t, inlier_deg, cand, count, inliers, stream);
+    return launch_fused(f, QF_CONSENSUS, max_edges, inlier_t, inlier_deg, cand, count, inliers, false, nullptr, 0.0, nullptr, stream);
+}
+
+extern "C" int rpg_query_pose_weighted_f64(QP_SHARED_PARAMS, int max_edges, double inlier_t, double inlier_deg, const float* rel_var,
+                                           double var_floor, int consensus, double* out, double* cand, int32_t* count,
+                                           int32_t* inliers, double* spread, int32_t* status, void* stream) {
+    if (!(inlier_t >= 0.0 && inlier_t < __builtin_inf()) || !(inlier_deg >= 0.0 && inlier_deg <= 360.0)) return RPG_ERR_BAD_ARG;
+    if ((consensus != 0 && consensus != 1) || (consensus == 0 && inliers)) return RPG_ERR_BAD_ARG;
+    QfArgs f;
+    if (!qp_args(f.q, QP_SHARED, 0, out, status)) return RPG_ERR_BAD_ARG;
+    return launch_fused(f, consensus ? QF_CONSENSUS : QF_MEAN, max_edges, inlier_t, inlier_deg, cand, count, consensus ? inliers : nullptr,
+                        true, rel_var, var_floor, spread, stream);
 }

@@ -21,7 +21,7 @@ import torch
 
 from .graph import Data, fc_edge_index
 # the fused rules' names, the consensus rule's default thresholds (which see there) and their check: one home for host and device
-from .ops import FUSE_MODES, INLIER_DEG, INLIER_T, _qp_thresholds  # noqa: F401  (re-exported)
+from .ops import FUSE_MODES, INLIER_DEG, INLIER_T, VAR_FLOOR, _qp_thresholds, _qp_weights  # noqa: F401  (re-exported)
 from .pipeline import (_collate_on_device, _InputPipeline, _MicroBatchRunner, cut_per_graph,  # noqa: F401  (re-exported)
                        edges_per_graph, staging_workers)
 
@@ -225,6 +225,107 @@ def _fused_row(rel_pose, target, edges, pose_m, pose_s, fuse, max_edges, inlier_
     return np.hstack((pred, targ, t_err, q_err)), None if inl is None else int(inl.size), int(cands.shape[0])
 
 
+# ---- the fused rules weighted by the edges' Monte-Carlo variance -------------------------------------------------------------
+def used_columns(edges: np.ndarray, max_edges: int = 64) -> np.ndarray:
+    """The columns ``pose_candidates`` makes its candidates from, in its order: target 0, source not 0, the first ``max_edges``."""
+    edges = np.asarray(edges)
+    return np.flatnonzero((edges[1] == 0) & (edges[0] != 0))[:max_edges]
+
+
+def variance_weights(var: np.ndarray, var_floor: float = VAR_FLOOR):
+    """var [C, 6] (the candidates' rows of ``rel_var``, read as float64) -> (w [C, 3], wq [C], usable bool [C]): the translation
+    weights ``w_cj = 1.0 / (v_c[j] + var_floor)`` per component, the rotation weight ``wq_c = 1.0 / (((v_c[3] + v_c[4]) + v_c[5]) +
+    var_floor)`` in that order of additions, and whether the variance can be used: none of its six values NaN, negative or +inf
+    (the weights of an unusable one are never read)."""
+    var = np.asarray(var, dtype=np.float64).reshape(-1, 6)
+    with np.errstate(all="ignore"):
+        usable = ~(np.isnan(var) | (var < 0.0) | (var == np.inf)).any(axis=1)
+        w = 1.0 / (var[:, :3] + var_floor)
+        wq = 1.0 / (((var[:, 3] + var[:, 4]) + var[:, 5]) + var_floor)
+    return w, wq, usable
+
+
+def pose_spread(sw, swq, pose_s) -> np.ndarray:
+    """(sigma_t, sigma_q) of a pose fused with the weight sums W [3] and Wq: ``sqrt((s_0 s_0 / W_0 + s_1 s_1 / W_1) + s_2 s_2 /
+    W_2)`` with s = ``pose_s``, the predicted standard deviation of the translation in the un-normalised unit, and ``sqrt(1.0 /
+    Wq)``, that of the rotation in log-quaternion units."""
+    s = np.asarray(pose_s, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        return np.array([np.sqrt((s[0] * s[0] / sw[0] + s[1] * s[1] / sw[1]) + s[2] * s[2] / sw[2]), np.sqrt(1.0 / swq)])
+
+
+def weighted_mean(cands: np.ndarray, w: np.ndarray, wq: np.ndarray):
+    """The weighted form of ``fuse_poses(cands, "mean")`` over two or more finite candidates: -> (pose [7], W [3], Wq).  Every sum
+    sequential in row order: ``t_j = (sum_c w_cj t_cj) / W_j`` with ``W_j = sum_c w_cj``; ``q = S / |S|`` with S the sum of ``wq_c
+    q_c`` where <q_c, q_0> >= 0 and of ``-wq_c q_c`` elsewhere, ``q_0`` where |S| = 0; ``Wq = sum_c wq_c``."""
+    t, q = cands[:, :3], cands[:, 3:]
+    st, sw, sq, swq = np.zeros(3), np.zeros(3), np.zeros(4), 0.0
+    with np.errstate(all="ignore"):
+        for d in range(cands.shape[0]):
+            st = st + w[d] * t[d]
+            sw = sw + w[d]
+            dot = q[d, 0] * q[0, 0] + q[d, 1] * q[0, 1] + q[d, 2] * q[0, 2] + q[d, 3] * q[0, 3]
+            sq = sq + wq[d] * q[d] if dot >= 0.0 else sq - wq[d] * q[d]
+            swq = swq + wq[d]
+        norm = np.sqrt(sq[0] * sq[0] + sq[1] * sq[1] + sq[2] * sq[2] + sq[3] * sq[3])
+        return np.hstack((st / sw, q[0] if norm == 0.0 else sq / norm)), sw, swq
+
+
+def fuse_poses_weighted(cands: np.ndarray, var: np.ndarray, fuse: str, pose_s=(1.0, 1.0, 1.0), *, inlier_t: float = INLIER_T,
+                        inlier_deg: float = INLIER_DEG, var_floor: float = VAR_FLOOR):
+    """``fuse_poses`` for ``fuse="mean"`` / ``"consensus"`` with every candidate weighted by the inverse of its variance: cands
+    [C, 7], var [C, 6] (candidate c's row of ``rel_var``: the variance of ONE dropout sample of its relative pose) -> (pose [7],
+    spread [2] = ``pose_spread`` over the same candidates, the inlier slots -- None for ``"mean"``).
+
+    The weights are ``variance_weights``; the slot set I is all C candidates for ``"mean"`` and ``consensus_inliers`` for
+    ``"consensus"``, whose voting is unchanged and unweighted -- except that a candidate with an unusable variance is treated
+    like a non-finite one there: it supports nothing and is supported by nothing.  Over two or more slots the pose is
+    ``weighted_mean``; one slot is returned as it is, with its own weights as W and Wq.  ``"mean"`` with C >= 2 and a non-finite
+    candidate or an unusable variance gives NaN in every component, as today's ``"mean"`` does for the former.  The spread is
+    NaN wherever a component of the pose is, and for C = 1 under ``"mean"`` with an unusable variance.  When every ``v +
+    var_floor`` is the same power of two the pose is ``fuse_poses(cands, fuse)`` bit for bit: scaling by a power of two commutes
+    with every operation here.  ``var_floor``: finite, >= 1e-30; 1e-12 is an API default, not a tuned value."""
+    _, var_floor = _qp_weights("variance", fuse, var_floor, "fuse_poses_weighted")
+    inlier_t, inlier_deg = _qp_thresholds(inlier_t, inlier_deg, "fuse_poses_weighted")
+    cands = np.asarray(cands, dtype=np.float64)
+    w, wq, usable = variance_weights(var, var_floor)
+    nan7, nan2 = np.full(7, np.nan), np.full(2, np.nan)
+    inl = None
+    if has_inlier_counts(fuse):
+        voters = cands.copy()
+        voters[~usable] = np.nan
+        inl, _ = consensus_inliers(voters, inlier_t, inlier_deg)
+        if not inl.size:
+            return nan7, nan2, inl
+        cands, w, wq, usable = cands[inl], w[inl], wq[inl], usable[inl]
+    if cands.shape[0] == 1:
+        pose, spread = cands[0].copy(), pose_spread(w[0], wq[0], pose_s) if usable[0] else nan2
+    elif not (np.isfinite(cands).all() and usable.all()):
+        pose, spread = nan7, nan2
+    else:
+        pose, sw, swq = weighted_mean(cands, w, wq)
+        spread = pose_spread(sw, swq, pose_s)
+    return pose, nan2 if np.isnan(pose).any() else spread, inl
+
+
+def weighted_query_row(rel_pose, rel_var, target, edges, pose_m, pose_s, fuse: str, max_edges: int = 64, *,
+                       inlier_t: float = INLIER_T, inlier_deg: float = INLIER_DEG, var_floor: float = VAR_FLOOR):
+    """ONE graph under a weighted rule: -> (row [16], spread [2], inliers -- None for ``"mean"`` --, used).  The candidates, the
+    cut at ``max_edges``, the row layout, the errors and the two integers are those of ``fused_query_row`` /
+    ``consensus_query_row``; ``rel_var`` [E, 6] is read at the candidates' columns (``used_columns``) and the pose and the spread
+    are ``fuse_poses_weighted``.  The statement the device kernel (rpg_query_pose_weighted_f64) is held to, and the host path
+    of ``weights="variance"`` in the two streams."""
+    cands, targ, _ = pose_candidates(rel_pose, target, edges, pose_m, pose_s, max_edges)
+    var = np.asarray(rel_var, dtype=np.float64)[used_columns(edges, max_edges)]
+    pred, spread, inl = fuse_poses_weighted(cands, var, fuse, pose_s, inlier_t=inlier_t, inlier_deg=inlier_deg, var_floor=var_floor)
+    with np.errstate(invalid="ignore"):
+        r = errors(pred[None], targ[None])
+    t_err, q_err = r.t_loss[0], r.q_loss[0]
+    if (cands.shape[0] > 1 or inl is not None) and np.isnan(pred).any():
+        t_err = q_err = np.nan
+    return np.hstack((pred, targ, t_err, q_err)), spread, None if inl is None else int(inl.size), int(cands.shape[0])
+
+
 @dataclass
 class EvalResult:
     pred_poses: np.ndarray      # [G, 7]
@@ -233,6 +334,8 @@ class EvalResult:
     q_loss: np.ndarray          # [G] degrees
     inliers: Optional[np.ndarray] = None     # [G] int, fuse="consensus" only: the candidates averaged into the pose
     used: Optional[np.ndarray] = None        # [G] int, fuse="consensus" only: the candidates that voted; inliers / used = confidence
+    sigma_t: Optional[np.ndarray] = None     # [G] float, weights="variance" only: predicted deviation of the fused translation
+    sigma_q: Optional[np.ndarray] = None     # [G] float, weights="variance" only: that of the rotation, in log-quaternion units
 
     @property
     def median_t(self) -> float:
@@ -257,28 +360,44 @@ class _PoseRows:
     """What a stream collects micro-batch by micro-batch, and the result made of it: the [G, 16] blocks of the device pose
     rule (``pose``, the stream's ``QueryPose``), or the (pred, targ) rows of the host rule of test.py:213-251.  With ``fuse`` the
     host rule is ``_fused_row`` and collects the same [G, 16] blocks as the device.  A rule with inlier counts
-    (``has_inlier_counts``) adds an int [G, 2] block of (inliers, used) to every block (``ints``), on either path."""
+    (``has_inlier_counts``) adds an int [G, 2] block of (inliers, used) to every block (``ints``), a weighted rule a float [G, 2]
+    block of (sigma_t, sigma_q) (``spreads``), on either path."""
 
     def __init__(self, pose_m, pose_s, ref_node: int, pose=None, fuse=None, max_edges: int = 64,
-                 inlier_t: float = INLIER_T, inlier_deg: float = INLIER_DEG):
+                 inlier_t: float = INLIER_T, inlier_deg: float = INLIER_DEG, weights=None, var_floor: float = VAR_FLOOR):
         self.pose_m, self.pose_s = np.asarray(pose_m, dtype=np.float64), np.asarray(pose_s, dtype=np.float64)
         self.ref_node, self.pose = ref_node, pose
         self.fuse, self.max_edges = fuse, max_edges
         self.inlier_t, self.inlier_deg = inlier_t, inlier_deg
+        self.weights, self.var_floor = weights, var_floor
         self.ints: Optional[List[np.ndarray]] = [] if has_inlier_counts(fuse) else None
+        self.spreads: Optional[List[np.ndarray]] = [] if weights is not None else None
         self.rows: Optional[List[np.ndarray]] = [] if pose is not None or fuse is not None else None
         self.preds: List[np.ndarray] = []
         self.targs: List[np.ndarray] = []
 
     def add_device(self, block: np.ndarray) -> None:
         """One micro-batch as the device rule sent it: the host copy of its output block (``QueryPose.output_block``)."""
-        rows, ints = self.pose.cut_block(block)
+        rows, ints, spread = self.pose.cut_block(block)
         if ints is not None:
             self.ints.append(ints)
+        if spread is not None:
+            self.spreads.append(spread)
         self.rows.append(rows)
 
-    def add(self, rel: np.ndarray, targets: Iterable, cut: Iterable) -> None:
-        """The host rule over one micro-batch: per graph its targets [n, 6] and its (columns of ``rel``, local edge list)."""
+    def add(self, rel: np.ndarray, targets: Iterable, cut: Iterable, var: Optional[np.ndarray] = None) -> None:
+        """The host rule over one micro-batch: per graph its targets [n, 6] and its (columns of ``rel``, local edge list); a
+        weighted rule also reads ``var``, the variances of ``rel``'s rows."""
+        if self.weights is not None:
+            got = [weighted_query_row(rel[cols], var[cols], target, edges, self.pose_m, self.pose_s, self.fuse, self.max_edges,
+                                      inlier_t=self.inlier_t, inlier_deg=self.inlier_deg, var_floor=self.var_floor)
+                   for target, (cols, edges) in zip(targets, cut)]
+            if got:
+                self.rows.append(np.stack([row for row, _, _, _ in got]))
+                self.spreads.append(np.stack([spread for _, spread, _, _ in got]))
+                if self.ints is not None:
+                    self.ints.append(np.asarray([[inl, used] for _, _, inl, used in got], dtype=np.int64))
+            return
         if self.fuse is not None:
             got = [_fused_row(rel[cols], target, edges, self.pose_m, self.pose_s, self.fuse, self.max_edges, self.inlier_t,
                               self.inlier_deg) for target, (cols, edges) in zip(targets, cut)]
@@ -293,9 +412,10 @@ class _PoseRows:
             self.targs.append(t)
 
     def result(self, gather=None, with_targets: bool = True):
-        """EvalResult of everything collected (``gather(pred, targ, ints)``: all ranks' rows in place of this rank's); without
-        targets only the predicted poses [G, 7].  ``ints`` is None or, with ``fuse="consensus"``, the int64 [G, 2] block of
-        (inliers, used): it fills the result's two arrays, and without targets it is what ``self.integers()`` hands out."""
+        """EvalResult of everything collected (``gather(pred, targ, ints, spread)``: all ranks' rows in place of this rank's);
+        without targets only the predicted poses [G, 7].  ``ints`` is None or, with ``fuse="consensus"``, the int64 [G, 2] block of
+        (inliers, used): it fills the result's two arrays, and without targets it is what ``self.integers()`` hands out.
+        ``spread`` likewise: None or a weighted rule's float64 [G, 2] block of (sigma_t, sigma_q), ``self.spread()``."""
         all_rows = None
         if self.rows is not None:
             all_rows = np.concatenate(self.rows) if self.rows else np.zeros((0, 16))
@@ -305,15 +425,23 @@ class _PoseRows:
             targ = np.stack(self.targs) if self.targs else np.zeros((0, 7))
         if not with_targets:
             return np.ascontiguousarray(pred)
-        ints = self.integers()
+        ints, spread = self.integers(), self.spread()
         if gather is not None:
-            pred, targ, ints = gather(pred, targ, ints)
+            pred, targ, ints, spread = gather(pred, targ, ints, spread)
             res = errors(pred, targ)
         else:
             res = _result_from_rows(all_rows) if all_rows is not None else errors(pred, targ)
         if ints is not None:
             res.inliers, res.used = ints[:, 0].copy(), ints[:, 1].copy()
+        if spread is not None:
+            res.sigma_t, res.sigma_q = spread[:, 0].copy(), spread[:, 1].copy()
         return res
+
+    def spread(self) -> Optional[np.ndarray]:
+        """float64 [G, 2] = (sigma_t, sigma_q) of everything collected; None unless the rule is weighted."""
+        if self.spreads is None:
+            return None
+        return np.concatenate(self.spreads).astype(np.float64) if self.spreads else np.zeros((0, 2))
 
     def integers(self) -> Optional[np.ndarray]:
         """int64 [G, 2] = (inliers, used) of everything collected; None unless ``fuse="consensus"``."""
@@ -327,7 +455,7 @@ def evaluate_stream(model, graphs: Sequence[Data], device, micro_batch: int = 64
                     pose_s=(1.0, 1.0, 1.0), ref_node: int = 0, rank: int = 0, world: int = 1,
                     stats: Optional[dict] = None, bf16_input: Optional[bool] = None, postprocess: str = "host",
                     fuse: Optional[str] = None, max_edges: int = 64, inlier_t: float = INLIER_T,
-                    inlier_deg: float = INLIER_DEG) -> EvalResult:
+                    inlier_deg: float = INLIER_DEG, weights: Optional[str] = None, var_floor: float = VAR_FLOOR) -> EvalResult:
     """Run ``model`` over a stream of single-graph ``Data`` objects (x, edge_index, y) and post-process like test.py.
     With world > 1 every rank evaluates its contiguous block (shard_range) and the [G,7] rows are all-gathered.
 
@@ -367,10 +495,23 @@ def evaluate_stream(model, graphs: Sequence[Data], device, micro_batch: int = 64
     graph (``stats["d2h_bytes"]`` counts them); under ``world > 1`` they are gathered in graph order like the poses.  The
     defaults 0.25 / 5.0 are API defaults, not measured optima: both belong to the scene's scale, and ``inlier_t`` is compared
     after ``* pose_s + pose_m``, i.e. in the unit of the un-normalised translation.  Both must be finite, ``inlier_t >= 0``
-    and ``0 <= inlier_deg <= 360`` (ValueError)."""
+    and ``0 <= inlier_deg <= 360`` (ValueError).
+
+    ``weights="variance"`` (default None; with ``fuse="mean"`` or ``"consensus"``, ValueError otherwise): the mean of those
+    rules weighs every estimate by the inverse of its Monte-Carlo variance, ``1 / (v + var_floor)`` (``fuse_poses_weighted``),
+    so an edge the network is unsure of pulls less, and every graph gets the predicted standard deviation of its fused pose: the
+    result's ``sigma_t`` (un-normalised unit of the translation) and ``sigma_q`` (log-quaternion units; ``2 * sigma_q`` radians
+    is approximately the rotation angle's deviation), float [G], None for every other mode.  It needs ``model.mc_dropout`` with
+    ``samples >= 2`` (ValueError before anything is queued): the variances are ``model.mc_dropout.last.rel_var``, those of ONE
+    dropout sample, so the spread is the predictive deviation, not that of the S-sample mean.  The host path reads them back
+    with the relative poses; the device path hands them to the kernel and 16 more bytes per graph come back
+    (``stats["d2h_bytes"]``: 144 per graph for ``"mean"``, 152 for ``"consensus"``); under ``world > 1`` the two ride in the
+    gathered rows like the integers.  ``var_floor`` (finite, >= 1e-30, checked always): 1e-12 is an API default, not a tuned
+    value.  Whether ``sigma_t`` orders right and wrong poses on a dataset has not been measured."""
     from .shard import rank_host_slice
     _check_postprocess("evaluate_stream", postprocess, device)
     _check_fuse("evaluate_stream", fuse, max_edges, ref_node, inlier_t, inlier_deg)
+    weights, var_floor = _check_weights("evaluate_stream", model, weights, fuse, var_floor)
     if world > 1 and torch.device(device).type == "cuda":
         # one process per GPU on a shared host: this rank's staging threads and pinned buffers stay on its share of the
         # cores / its GPU's NUMA node for the duration of the call (shard.rank_host_slice puts the caller's mask back on
@@ -379,9 +520,9 @@ def evaluate_stream(model, graphs: Sequence[Data], device, micro_batch: int = 64
         local_world = int(os.environ.get("LOCAL_WORLD_SIZE", world))
         with rank_host_slice(int(os.environ.get("LOCAL_RANK", rank)), local_world, torch.device(device).index):
             return _evaluate_stream(model, graphs, device, micro_batch, pose_m, pose_s, ref_node, rank, world, stats, bf16_input, local_world,
-                                    postprocess, fuse, max_edges, inlier_t, inlier_deg)
+                                    postprocess, fuse, max_edges, inlier_t, inlier_deg, weights, var_floor)
     return _evaluate_stream(model, graphs, device, micro_batch, pose_m, pose_s, ref_node, rank, world, stats, bf16_input, 1, postprocess,
-                            fuse, max_edges, inlier_t, inlier_deg)
+                            fuse, max_edges, inlier_t, inlier_deg, weights, var_floor)
 
 
 def _check_postprocess(who: str, postprocess, device) -> None:
@@ -404,6 +545,17 @@ def _check_fuse(who: str, fuse, max_edges, ref_node, inlier_t=INLIER_T, inlier_d
                          "one of the two")
 
 
+def _check_weights(who: str, model, weights, fuse, var_floor):
+    """``weights`` / ``var_floor`` of a stream, checked before anything is queued: -> (weights, var_floor as a float)."""
+    weights, var_floor = _qp_weights(weights, fuse, var_floor, who)
+    if weights is not None:
+        mc = getattr(model, "mc_dropout", None)
+        if mc is None or mc.samples < 2:
+            raise ValueError(f"{who}: weights={weights!r} reads the Monte-Carlo variances of the relative poses: set "
+                             "model.mc_dropout = McDropout(samples >= 2) (one sample has no variance)")
+    return weights, var_floor
+
+
 # what relocalize's forward hands to its read-back: forward_map's outputs, the neighbours on the device, the retrieved ones on
 # their way to the host (None: they were given), and the pose rule's output block where a captured step has already filled it
 _Forward = namedtuple("_Forward", "abs_pose rel_pose edge_index neighbours host_neighbours back", defaults=(None, None))
@@ -415,16 +567,20 @@ def _result_from_rows(rows: np.ndarray) -> EvalResult:
 
 
 def _evaluate_stream(model, graphs, device, micro_batch, pose_m, pose_s, ref_node, rank, world, stats, bf16_input, local_world,
-                     postprocess="host", fuse=None, max_edges=64, inlier_t=INLIER_T, inlier_deg=INLIER_DEG):
+                     postprocess="host", fuse=None, max_edges=64, inlier_t=INLIER_T, inlier_deg=INLIER_DEG, weights=None,
+                     var_floor=VAR_FLOOR):
     from .shard import gather_rows, shard_counts, shard_range
     qp = None
     if postprocess == "device":
         from .query_pose import QueryPose
-        qp = QueryPose(pose_m, pose_s, ref_node, fuse=fuse, max_edges=max_edges, inlier_t=inlier_t, inlier_deg=inlier_deg)
+        qp = QueryPose(pose_m, pose_s, ref_node, fuse=fuse, max_edges=max_edges, inlier_t=inlier_t, inlier_deg=inlier_deg,
+                       weights=weights, var_floor=var_floor)
     lo, hi = shard_range(len(graphs), rank, world)
     acc = _PoseRows(pose_m, pose_s, ref_node, pose=qp, fuse=fuse, max_edges=max_edges, inlier_t=inlier_t,
-                    inlier_deg=inlier_deg)
-    runner = _MicroBatchRunner(model, device, micro_batch, bf16_input, local_world, pose=qp)
+                    inlier_deg=inlier_deg, weights=weights, var_floor=var_floor)
+    # the host rule of a weighted stream reads the variances too: they come back with the relative poses
+    runner = _MicroBatchRunner(model, device, micro_batch, bf16_input, local_world, pose=qp,
+                               want_var=weights is not None and qp is None)
 
     def finish(item):
         chunk, host = item.chunk, item.host
@@ -432,7 +588,8 @@ def _evaluate_stream(model, graphs, device, micro_batch, pose_m, pose_s, ref_nod
             return acc.add_device(host["rel"].numpy())
         ei = None if host["ei"] is None else host["ei"].numpy()              # a model-built (kNN) edge list
         acc.add(host["rel"].numpy(), (g.y.cpu().numpy() for g in chunk),
-                cut_per_graph([g.num_nodes for g in chunk], ei, (g.edge_index.cpu().numpy() for g in chunk)))
+                cut_per_graph([g.num_nodes for g in chunk], ei, (g.edge_index.cpu().numpy() for g in chunk)),
+                None if host.get("var") is None else host["var"].numpy())
 
     def chunk_at(i):
         return [graphs[j] for j in range(lo + i * micro_batch, min(hi, lo + (i + 1) * micro_batch))]
@@ -445,14 +602,17 @@ def _evaluate_stream(model, graphs, device, micro_batch, pose_m, pose_s, ref_nod
         # tensors of a device="cpu" run -- ADVICE r5; before round 5 world = 1 never reached a collective)
         grouped = torch.device(device).type == "cuda" or dist.get_backend() != "nccl"
 
-    def gather(pred, targ, ints=None):
+    def gather(pred, targ, ints=None, spread=None):
         # under a process group the collective runs at ANY world size, 1 included: a one-GPU box then executes the same RCCL
         # all-gather the 4- / 8-GPU stream does (tools/eval_stream.py under torch.distributed.run).  The consensus rule's two
-        # integers ride in the same rows as two more float64 columns (small integers: exact), so they arrive in graph order too
-        parts = [pred, targ] if ints is None else [pred, targ, ints.astype(np.float64)]
+        # integers ride in the same rows as two more float64 columns (small integers: exact), so they arrive in graph order too;
+        # a weighted rule's two deviations ride behind them in the same way
+        parts = [pred, targ] + ([] if ints is None else [ints.astype(np.float64)]) + ([] if spread is None else [spread])
         both = torch.from_numpy(np.concatenate(parts, 1)).to(device)
         both = gather_rows(both, shard_counts(len(graphs), world), always=True).cpu().numpy()
-        return both[:, :7], both[:, 7:14], None if ints is None else both[:, 14:].astype(np.int64)
+        at = 14 if ints is None else 16
+        return (both[:, :7], both[:, 7:14], None if ints is None else both[:, 14:16].astype(np.int64),
+                None if spread is None else both[:, at:at + 2])
     return acc.result(gather if world > 1 or grouped else None)
 
 
@@ -489,7 +649,8 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
                pose_s=(1.0, 1.0, 1.0), ref_node: int = 0, stats: Optional[dict] = None, targets=None,
                bf16_input: Optional[bool] = None, *, rule=None, query_descriptors=None, query_groups=None,
                postprocess: str = "host", fuse: Optional[str] = None, max_edges: int = 64, capture: bool = False,
-               outputs: str = "all", inlier_t: float = INLIER_T, inlier_deg: float = INLIER_DEG):
+               outputs: str = "all", inlier_t: float = INLIER_T, inlier_deg: float = INLIER_DEG,
+               weights: Optional[str] = None, var_floor: float = VAR_FLOOR):
     """The evaluation stream of the map path (``PoseNetX_R2.forward_map``): query g's graph is the query followed by the map
     rows ``neighbours[g]`` (its retrieved database images, dataset_7Scenes_multi.py:340-345).  Single process.
 
@@ -523,6 +684,12 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
     ``stats["used"]``, int [G]; a caller accepts a pose when ``inliers / used`` is high enough for its use.  On the device path
     the integers travel with the rows (8 more bytes per query in ``stats["d2h_bytes"]``); a captured step is keyed by the
     thresholds too, so other thresholds capture a new step instead of replaying the old one.
+
+    ``weights="variance"`` / ``var_floor`` (as in ``evaluate_stream``, which see; needs ``model.mc_dropout`` with ``samples >=
+    2``): the K estimates are weighted by the inverse of their Monte-Carlo variance and every query gets ``sigma_t`` and
+    ``sigma_q``, the predicted standard deviation of its pose -- on the ``EvalResult`` when there are targets, else in
+    ``stats["sigma_t"]`` / ``stats["sigma_q"]``, float [G].  On the device path they travel with the rows (16 more bytes per
+    query); a captured step reads its own static variances and is keyed by ``weights`` and ``var_floor`` too.
 
     ``capture=True`` (GPU map only): a micro-batch's device step -- ``forward_map`` with its retrieval, and the device pose rule
     behind it -- is captured into a HIP graph once per shape (``graphed.GraphedForwardMap``: the full micro-batch and a ragged
@@ -565,6 +732,7 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
     _check_postprocess("relocalize", postprocess, device)
     _check_fuse("relocalize", fuse, max_edges, ref_node, inlier_t, inlier_deg)
     inlier_t, inlier_deg = float(inlier_t), float(inlier_deg)
+    weights, var_floor = _check_weights("relocalize", model, weights, fuse, var_floor)
     if capture:
         if torch.device(device).type != "cuda":
             raise ValueError(f"relocalize: capture=True replays a HIP graph, the feature map is on {device}")
@@ -610,11 +778,11 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
         from .query_pose import QueryPose
         # a captured step counts its bad graphs in the status word of the rule it was captured with: that rule is kept with it
         qp_key = ("pose", tuple(float(v) for v in pose_m), tuple(float(v) for v in pose_s), ref_node, fuse, max_edges, inlier_t,
-                  inlier_deg)
+                  inlier_deg, weights, var_floor)
         qp = captured.get(qp_key) if capture else None
         if qp is None:
             qp = QueryPose(np.asarray(pose_m, dtype=np.float64), np.asarray(pose_s, dtype=np.float64), ref_node, fuse=fuse,
-                           max_edges=max_edges, inlier_t=inlier_t, inlier_deg=inlier_deg)
+                           max_edges=max_edges, inlier_t=inlier_t, inlier_deg=inlier_deg, weights=weights, var_floor=var_floor)
             if capture:
                 captured[qp_key] = qp
         if targets is not None:
@@ -623,7 +791,7 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
         if model.knn <= 0:         # forward_map's own FC list: n (n - 1) columns per graph, graph after graph
             fc_first = torch.arange(min(micro_batch, g_all) + 1, dtype=torch.int64, device=device) * fc_edges.shape[1]
     acc = _PoseRows(pose_m, pose_s, ref_node, pose=qp, fuse=fuse, max_edges=max_edges, inlier_t=inlier_t,
-                    inlier_deg=inlier_deg)
+                    inlier_deg=inlier_deg, weights=weights, var_floor=var_floor)
     raw_abs, raw_rel = [], []
 
     def captured_step(x, qd, targ):
@@ -631,7 +799,7 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
         now with the micro-batch itself as the example."""
         nonlocal n_captured
         key = ("step", tuple(x.shape), x.dtype, kk, None if rule is None else (rule.sampling_period, rule.random), postprocess,
-               fuse, max_edges, qd is not None, targ is not None, outputs, inlier_t, inlier_deg,
+               fuse, max_edges, qd is not None, targ is not None, outputs, inlier_t, inlier_deg, weights, var_floor,
                None if mc is None else (id(mc), mc.samples, mc.seed))       # the sampler's count and seed are baked into the step
         step = captured.get(key)
         if step is None or step.fmap is not fmap or step.pose is not qp or step.stale():
@@ -682,13 +850,16 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
 
     def read_back_of(chunk, x, fwd):
         if qp is None:
+            # (a weighted host rule: the variances this forward -- or this replay -- has just left, row for row with rel_pose)
             return {"nb": fwd.host_neighbours, "abs": fwd.abs_pose, "rel": fwd.rel_pose,
-                    "ei": fwd.edge_index if model.knn > 0 else None}
+                    "ei": fwd.edge_index if model.knn > 0 else None,
+                    "var": mc.last.rel_var if weights is not None and poses_h is not None else None}
         back = fwd.back
         if back is None:                   # everything the rule writes travels back in one tensor, one copy
             b0, n = chunk[0].first, x.shape[0]
-            out, ints, back = qp.output_block(n, fwd.rel_pose.device)
-            qp.from_map(fwd.rel_pose, fwd.edge_index, fmap, fwd.neighbours, out=out, inliers=ints,
+            out, ints, back, spread = qp.output_block(n, fwd.rel_pose.device)
+            qp.from_map(fwd.rel_pose, fwd.edge_index, fmap, fwd.neighbours, out=out, inliers=ints, spread=spread,
+                        rel_var=None if spread is None else mc.last.rel_var,
                         query_targets=None if targ_dev is None else targ_dev[b0:b0 + n],
                         edge_first=None if fc_first is None else fc_first[:n + 1])
         return {"nb": fwd.host_neighbours, "rel": back}
@@ -712,7 +883,8 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
         else:
             n_g = host["abs"].shape[0] // rows_per
             ei = None if host["ei"] is None else host["ei"].numpy()      # a model-built (kNN) edge list
-            acc.add(host["rel"].numpy(), (target_block(g) for g in range(b0, b0 + n_g)), cut_per_graph([n_per] * n_g, ei, [fc_edges] * n_g))
+            acc.add(host["rel"].numpy(), (target_block(g) for g in range(b0, b0 + n_g)), cut_per_graph([n_per] * n_g, ei, [fc_edges] * n_g),
+                    None if host.get("var") is None else host["var"].numpy())
 
     # only the queries are staged, by the rules of evaluate_stream; everything else of a micro-batch goes inside its launch
     runner = _MicroBatchRunner(model, device, micro_batch, bf16_input, pose=qp, collate=lambda chunk, x_dev: chunk[0].x if x_dev is None else x_dev,
@@ -733,4 +905,7 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
     elif stats is not None and acc.ints is not None:          # no EvalResult to carry them: the two arrays go to stats
         ints = acc.integers()
         stats["inliers"], stats["used"] = ints[:, 0].copy(), ints[:, 1].copy()
+    if targ_h is None and stats is not None and acc.spreads is not None:
+        spread = acc.spread()
+        stats["sigma_t"], stats["sigma_q"] = spread[:, 0].copy(), spread[:, 1].copy()
     return res

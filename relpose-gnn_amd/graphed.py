@@ -93,8 +93,11 @@ class GraphedForwardMap:
     ``outputs="query"``).
     The rule's outputs are static too (``QueryPose.output_block``): the rows, ``self.inliers`` -- int32 [G, 2] = (inliers, used) per
     query for the one rule that has them, valid after a replay like the rows (``MapStep`` keeps its five fields), None for every
-    other -- and ``self.packed``, the one tensor a stream copies back (the rows themselves, or the buffer rows and integers
-    share).  The thresholds are the ``QueryPose``'s: a step is captured with one rule and never replayed for another.
+    other --, ``self.sigma`` -- float64 [G, 2] = (sigma_t, sigma_q) per query for a weighted rule, None for every other -- and
+    ``self.packed``, the one tensor a stream copies back (the rows themselves, or the buffer that rows, spread and integers
+    share).  A weighted rule reads the variances of the step's own forward (``self.spread.rel_var``, static), so it needs
+    ``model.mc_dropout``.  The thresholds, the weighting and its floor are the ``QueryPose``'s: a step is captured with one rule
+    and never replayed for another.
     ``outputs``: ``forward_map``'s -- ``"query"`` captures the query-only step, whose outputs are abs_pose [G, 6], rel_pose
     [G K, 6] and the G K edges into the query nodes; what that mode does not serve raises as it does there.
 
@@ -144,7 +147,7 @@ class GraphedForwardMap:
         # ---- the static inputs --------------------------------------------------------------------------------------------------
         self.queries = q.detach().clone(memory_format=torch.contiguous_format)
         self.neighbours = self.ranks = self.query_groups = self.query_descriptors = self.query_targets = self.edge_first = None
-        self.inliers = self.packed = self._rows_out = None
+        self.inliers = self.sigma = self.packed = self._rows_out = None
         if rule is None:
             self.neighbours = torch.zeros((g, k), dtype=torch.int64, device=dev)          # row 0: valid for any map
         else:
@@ -164,7 +167,9 @@ class GraphedForwardMap:
                 self.query_descriptors = qd.detach().to(dev).contiguous().clone()
             fmap.inv_norms()                      # cached on the map: made here, outside the capture, and held below
         if pose is not None:
-            self._rows_out, self.inliers, self.packed = pose.output_block(g, dev)
+            self._rows_out, self.inliers, self.packed, self.sigma = pose.output_block(g, dev)
+            if self.sigma is not None and getattr(model, "mc_dropout", None) is None:
+                raise ValueError("GraphedForwardMap: a weighted pose rule reads the Monte-Carlo variances: set model.mc_dropout")
             qt = pose_kwargs.get("query_targets")
             if qt is not None:
                 if not torch.is_tensor(qt) or qt.dtype != torch.float32 or tuple(qt.shape) != (g, 6):
@@ -230,8 +235,10 @@ class GraphedForwardMap:
                                             outputs=self.outputs, _static=(self.ranks, self.query_groups))
         rows = None
         if self.pose is not None:
+            # (a weighted rule: the variances this forward has just left -- in the capture, the step's static spread.rel_var)
+            var = None if self.sigma is None else m.mc_dropout.last.rel_var
             rows = self.pose.from_map(rel, ei, self.fmap, nb, query_targets=self.query_targets, edge_first=self.edge_first,
-                                      out=self._rows_out, inliers=self.inliers)
+                                      out=self._rows_out, inliers=self.inliers, rel_var=var, spread=self.sigma)
         return MapStep(ab, rel, ei, nb, rows)
 
     # ---- validity ------------------------------------------------------------------------------------------------------------------

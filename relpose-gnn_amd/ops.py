@@ -686,7 +686,7 @@ def _qp_graphs(who, rel_pose, edge_index, node_first, node_targets, map_poses, n
 
 def _qp_launch(entry: str, who: str, graphs, pm, ps, head, outputs, lack: str) -> torch.Tensor:
     """One launch of a pose rule's C entry point over the result of ``_qp_graphs``: everything on rel_pose's GPU and contiguous,
-    ``out`` made if it was not given, then the call -- the arguments all three entry points share, up to the six pose_m / pose_s
+    ``out`` made if it was not given, then the call -- the arguments all four entry points share, up to the six pose_m / pose_s
     doubles, then ``head``, ``out``, the optional ``outputs`` [(name, tensor | None)], the status word and the stream.  A status
     word that is this call's own is read back and a non-zero count raises the ValueError of ``evaluate.reference_edge`` ("...
     graph(s) of this call ``lack``").  -> out."""
@@ -744,6 +744,31 @@ def _qp_thresholds(inlier_t, inlier_deg, who: str = "query_pose_fused") -> Tuple
     return t, deg
 
 
+# the weighted rules' floor under every variance: an API default like the thresholds above, not a tuned value.  It only has to keep
+# 1 / (v + floor) finite for a variance of exactly 0 (McDropout(samples=1), a dead feature row); it is in the unit of the variances,
+# i.e. of the NORMALISED pose squared.  _qp_weights is the host rule's check too (evaluate.py imports it)
+VAR_FLOOR = 1e-12
+WEIGHT_MODES = ("variance",)
+
+
+def _qp_weights(weights, fuse, var_floor, who: str = "query_pose_fused") -> Tuple[Optional[str], float]:
+    """The weighting of a fused rule and its floor, checked (ValueError): ``weights`` None or ``"variance"``, the latter with
+    ``fuse="mean"`` or ``"consensus"`` only (there is no weighted single edge, median or medoid); ``var_floor`` a finite number
+    >= 1e-30, checked always and read with weights only."""
+    if isinstance(var_floor, bool) or not isinstance(var_floor, numbers.Real):
+        raise ValueError(f"{who}: var_floor must be a finite number >= 1e-30, got {var_floor!r}")
+    floor = float(var_floor)
+    if not (floor >= 1e-30 and floor != float("inf")):       # (written so that NaN fails too)
+        raise ValueError(f"{who}: var_floor must be finite and >= 1e-30, got {var_floor!r}")
+    if weights is None:
+        return None, floor
+    if weights not in WEIGHT_MODES:
+        raise ValueError(f"{who}: weights must be None or 'variance', got {weights!r}")
+    if fuse not in ("mean", "consensus"):
+        raise ValueError(f"{who}: weights={weights!r} weights the mean of fuse='mean' or 'consensus', got fuse={fuse!r}")
+    return weights, floor
+
+
 def query_pose_fused(rel_pose: torch.Tensor, edge_index: torch.Tensor, *, fuse: str, max_edges: int = 64,
                      node_first: Optional[torch.Tensor] = None, node_targets: Optional[torch.Tensor] = None,
                      map_poses: Optional[torch.Tensor] = None, neighbours: Optional[torch.Tensor] = None,
@@ -751,7 +776,9 @@ def query_pose_fused(rel_pose: torch.Tensor, edge_index: torch.Tensor, *, fuse: 
                      pose_m=(0.0, 0.0, 0.0), pose_s=(1.0, 1.0, 1.0), status: Optional[torch.Tensor] = None,
                      out: Optional[torch.Tensor] = None, candidates: Optional[torch.Tensor] = None,
                      counts: Optional[torch.Tensor] = None, inlier_t: float = INLIER_T, inlier_deg: float = INLIER_DEG,
-                     inliers: Optional[torch.Tensor] = None) -> torch.Tensor:
+                     inliers: Optional[torch.Tensor] = None, weights: Optional[str] = None,
+                     rel_var: Optional[torch.Tensor] = None, var_floor: float = VAR_FLOOR,
+                     spread: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``query_pose`` over ALL the edges into every graph's query node (rpg_query_pose_fused_f64; evaluate.fused_query_pose on
     the device): each such edge whose source is not the query itself is one estimate of the query's pose, the first
     ``max_edges`` (1..64) of them in column order are combined by ``fuse`` -- ``"mean"`` (mean translation, sign-aligned
@@ -770,7 +797,18 @@ def query_pose_fused(rel_pose: torch.Tensor, edge_index: torch.Tensor, *, fuse: 
 
     ``candidates`` float64 [G, max_edges, 16] (optional output): used candidate c as a full row, NaN past the graph's count;
     ``counts`` int32 [G] (optional output): the usable edges found before the cut at ``max_edges``.  A graph without a usable
-    edge, or with a used edge whose source lies outside the graph, gets a NaN row and one count in ``status``."""
+    edge, or with a used edge whose source lies outside the graph, gets a NaN row and one count in ``status``.
+
+    ``weights="variance"`` (rpg_query_pose_weighted_f64; ``evaluate.weighted_query_row`` in numpy; with ``fuse="mean"`` or
+    ``"consensus"`` only, ValueError otherwise): the mean of those two rules weights every candidate by the inverse of its
+    Monte-Carlo variance.  ``rel_var`` fp32 [E, 6], row for row with ``rel_pose`` (``McSpread.rel_var``: the variance of ONE
+    dropout sample), is required exactly then.  Translation component j of candidate c weighs ``1 / (v_c[j] + var_floor)``, its
+    quaternion ``1 / (v_c[3] + v_c[4] + v_c[5] + var_floor)``; the voting of ``"consensus"`` stays unweighted.  A variance that
+    is NaN, negative or +inf counts wherever a non-finite candidate does.  ``var_floor`` (finite, >= 1e-30, ValueError; 1e-12 is
+    an API default, not a tuned value) is checked always.  ``spread`` float64 [G, 2] (optional output, this mode only): per graph
+    the predicted standard deviation of the fused translation, in the un-normalised unit, and of the fused rotation in
+    log-quaternion units (``2 * sigma_q`` radians ~ the rotation angle's deviation); NaN where the pose is.  They are the
+    deviations of one dropout sample's prediction, not of the S-sample mean."""
     who = "query_pose_fused"
     graphs = _qp_graphs(who, rel_pose, edge_index, node_first, node_targets, map_poses, neighbours, query_targets, edge_first,
                         status, out)
@@ -778,11 +816,23 @@ def query_pose_fused(rel_pose: torch.Tensor, edge_index: torch.Tensor, *, fuse: 
     pm, ps = _qp_triple(pose_m, "pose_m"), _qp_triple(pose_s, "pose_s")
     mode, max_edges = _qp_fuse(fuse, max_edges)
     inlier_t, inlier_deg = _qp_thresholds(inlier_t, inlier_deg)
+    weights, var_floor = _qp_weights(weights, fuse, var_floor)
     consensus = fuse == "consensus"
     if inliers is not None and not consensus:
         raise ValueError(f"{who}: inliers is an output of fuse='consensus', got fuse={fuse!r}")
-    outputs = [("candidates", candidates), ("counts", counts)] + ([("inliers", inliers)] if consensus else [])
-    shapes = {"candidates": (torch.float64, (g, max_edges, 16)), "counts": (torch.int32, (g,)), "inliers": (torch.int32, (g, 2))}
+    if weights is None and (rel_var is not None or spread is not None):
+        raise ValueError(f"{who}: rel_var / spread belong to weights='variance', got weights=None")
+    if weights is not None:
+        if rel_var is None:
+            raise ValueError(f"{who}: weights={weights!r} needs rel_var fp32 [E, 6], the variances of rel_pose's rows")
+        _qp_tensor(rel_var, "rel_var", torch.float32, (graphs[2], 6), who)
+        if rel_var.device != graphs[0].device:
+            raise ValueError(f"{who}: rel_var is on {rel_var.device}, rel_pose on {graphs[0].device}: everything must be on the "
+                             "same GPU")
+    outputs = [("candidates", candidates), ("counts", counts)] + ([("inliers", inliers)] if consensus or weights else [])
+    outputs += [("spread", spread)] if weights else []
+    shapes = {"candidates": (torch.float64, (g, max_edges, 16)), "counts": (torch.int32, (g,)), "inliers": (torch.int32, (g, 2)),
+              "spread": (torch.float64, (g, 2))}
     for name, t in outputs:
         if t is not None:
             _qp_tensor(t, name, *shapes[name], who)
@@ -790,6 +840,10 @@ def query_pose_fused(rel_pose: torch.Tensor, edge_index: torch.Tensor, *, fuse: 
         if t is not None and not t.is_contiguous():
             raise ValueError(f"{who}: {name} must be contiguous")
     lack = "have no usable edge into their query node, or a used edge's source lies outside the graph"
+    if weights:                                      # (rel_var is kept alive by the caller's own reference until the launch returns)
+        var = rel_var.contiguous()
+        return _qp_launch("rpg_query_pose_weighted_f64", who, graphs, pm, ps,
+                          (max_edges, inlier_t, inlier_deg, _p(var), var_floor, int(consensus)), outputs, lack)
     if consensus:
         return _qp_launch("rpg_query_pose_consensus_f64", who, graphs, pm, ps, (max_edges, inlier_t, inlier_deg), outputs, lack)
     return _qp_launch("rpg_query_pose_fused_f64", who, graphs, pm, ps, (mode, max_edges), outputs, lack)

@@ -212,12 +212,15 @@ class _MicroBatchRunner:
     forward's own tensors are handed on."""
 
     def __init__(self, model, device, micro_batch: int, bf16_input: Optional[bool] = None, local_world: int = 1,
-                 want_abs: bool = False, pose=None, collate=None, forward=None, outputs=None, capacity: Optional[int] = None):
+                 want_abs: bool = False, pose=None, collate=None, forward=None, outputs=None, capacity: Optional[int] = None,
+                 want_var: bool = False):
         self.model, self.device, self.micro_batch = model, device, int(micro_batch)
         # pose (query_pose.QueryPose, GPU only): the pose rule of test.py:213-267 runs on the device behind the forward, and what
         # comes back is its [G, 16] block (pred, targ, errors) INSTEAD of the relative poses and a model-built edge list
         self.pose = pose
         self.bf16_input, self.local_world, self.want_abs = bf16_input, local_world, want_abs
+        # want_var: the variances model.mc_dropout leaves behind the forward come back with the relative poses (a weighted host rule)
+        self.want_var = want_var
         self.rounding_workers = staging_workers(False, local_world)      # what staging_dtype weighs for pinned fp32 sources
         self.collate, self.forward, self.outputs = collate or self._collate, forward or self._forward, outputs or self._outputs
         # rows of a staging buffer: what the client says its largest micro-batch holds, else the chunk's largest graph x micro_batch
@@ -325,12 +328,15 @@ class _MicroBatchRunner:
         model_built = edge_index is not batch.edge_index
         if self.pose is not None:
             # everything the rule writes travels back in one tensor, one copy (QueryPose.output_block)
-            out, ints, back = self.pose.output_block(len(chunk), rel.device)
+            out, ints, back, spread = self.pose.output_block(len(chunk), rel.device)
+            # a rule with a spread reads the variances the forward has just left, row for row with rel (mc_dropout.McSpread)
+            var = None if spread is None else self.model.mc_dropout.last.rel_var
             # a stored list is cut contiguously per graph; a model-built one is cut by its targets (edges_per_graph) in the kernel
             self.pose.from_targets(rel, edge_index, pose_in[0], pose_in[2], edge_first=None if model_built else pose_in[1],
-                                   out=out, inliers=ints)
+                                   out=out, inliers=ints, rel_var=var, spread=spread)
             rel, model_built = back, False
-        return {"rel": rel, "abs": ab if self.want_abs else None, "ei": edge_index if model_built else None}
+        return {"rel": rel, "abs": ab if self.want_abs else None, "ei": edge_index if model_built else None,
+                "var": self.model.mc_dropout.last.rel_var if self.want_var else None}
 
     def read_back(self, t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
         """Device tensor -> pinned host tensor by a non-blocking copy on the current stream, its bytes counted; the event

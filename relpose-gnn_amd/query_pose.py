@@ -24,8 +24,14 @@ candidates vote (two support each other when their translations lie within ``inl
 ``inliers=`` (int32 [G, 2]) every graph also gets (supporters of the winner, candidates used): their ratio is the accept /
 reject signal that goes with the pose.  A non-finite candidate is an outlier there, it does not void the pose.
 
+``QueryPose(fuse="mean" | "consensus", weights="variance", var_floor=...)`` weights the mean of those two rules by the inverse of
+every edge's Monte-Carlo variance (``rel_var=``, fp32 [E, 6]: ``model.mc_dropout.last.rel_var`` of the forward whose ``rel_pose``
+it reads) and, with ``spread=`` (float64 [G, 2]), gives every graph the predicted standard deviation of its fused translation and
+rotation (rpg_query_pose_weighted_f64, a further mode of the same kernel; ``evaluate.weighted_query_row`` is the rule in numpy).
+
 Whatever the rule, a stream asks the object for its output block (``output_block``: the rows, the integers if the rule has them,
-and the one tensor to copy back) and cuts the host copy with ``cut_block``; it never asks which rule runs.
+the one tensor to copy back, and the spread if the rule has one -- ``rel_var`` is handed over exactly then) and cuts the host copy
+with ``cut_block``; it never asks which rule runs.
 """
 from __future__ import annotations
 
@@ -36,38 +42,49 @@ from .status import DeferredCounters
 
 
 ROW_BYTES, INT_BYTES = 16 * 8, 2 * 4       # per graph: the row of 16 doubles, and the consensus rule's (inliers, used)
+SPREAD_BYTES = 2 * 8                       # per graph: a weighted rule's (sigma_t, sigma_q)
 
 
-def packed_rows(g: int, device):
-    """The consensus rule's two outputs of ``g`` graphs in ONE allocation, so that a stream brings both back with one copy: ->
-    (buf uint8 [g * 136], rows float64 [g, 16] = its first g * 128 bytes, inliers int32 [g, 2] = the rest).  ``unpack_rows`` cuts
-    the host copy of ``buf`` the same way."""
-    buf = torch.empty(g * (ROW_BYTES + INT_BYTES), dtype=torch.uint8, device=device)
-    return buf, buf[:g * ROW_BYTES].view(torch.float64).view(g, 16), buf[g * ROW_BYTES:].view(torch.int32).view(g, 2)
+def packed_block(g: int, device, spread: bool, ints: bool):
+    """The outputs of ``g`` graphs in ONE allocation, section after section: the rows (128 B per graph), then -- if the rule has
+    them -- the spread (16 B per graph), then the integers (8 B per graph).  -> (buf uint8, rows float64 [g, 16], spread float64
+    [g, 2] | None, inliers int32 [g, 2] | None), views of ``buf``; every section starts 16-byte aligned wherever ``buf`` does.
+    ``unpack_block`` cuts the host copy the same way."""
+    buf = torch.empty(g * (ROW_BYTES + (SPREAD_BYTES if spread else 0) + (INT_BYTES if ints else 0)), dtype=torch.uint8,
+                      device=device)
+    return (buf,) + unpack_block(buf, spread, ints)
 
 
-def unpack_rows(buf):
-    """uint8 [g * 136] (a tensor or a numpy array, on the host) -> (rows float64 [g, 16], inliers int32 [g, 2]), views of it."""
-    g = buf.shape[0] // (ROW_BYTES + INT_BYTES)
+def unpack_block(buf, spread: bool, ints: bool):
+    """A buffer of ``packed_block`` (a tensor or a numpy array) -> (rows [g, 16], spread [g, 2] | None, inliers [g, 2] | None)."""
+    g = buf.shape[0] // (ROW_BYTES + (SPREAD_BYTES if spread else 0) + (INT_BYTES if ints else 0))
+    r, s = g * ROW_BYTES, g * (ROW_BYTES + (SPREAD_BYTES if spread else 0))
     if torch.is_tensor(buf):
-        return buf[:g * ROW_BYTES].view(torch.float64).view(g, 16), buf[g * ROW_BYTES:].view(torch.int32).view(g, 2)
-    return buf[:g * ROW_BYTES].view("<f8").reshape(g, 16), buf[g * ROW_BYTES:].view("<i4").reshape(g, 2)
+        return (buf[:r].view(torch.float64).view(g, 16), buf[r:s].view(torch.float64).view(g, 2) if spread else None,
+                buf[s:].view(torch.int32).view(g, 2) if ints else None)
+    return (buf[:r].view("<f8").reshape(g, 16), buf[r:s].view("<f8").reshape(g, 2) if spread else None,
+            buf[s:].view("<i4").reshape(g, 2) if ints else None)
 
 
 class QueryPose:
     def __init__(self, pose_m=(0.0, 0.0, 0.0), pose_s=(1.0, 1.0, 1.0), ref_node: int = 0, fuse=None, max_edges: int = 64,
-                 inlier_t: float = ops.INLIER_T, inlier_deg: float = ops.INLIER_DEG):
+                 inlier_t: float = ops.INLIER_T, inlier_deg: float = ops.INLIER_DEG, weights=None,
+                 var_floor: float = ops.VAR_FLOOR):
         """``pose_m`` / ``pose_s``: translation mean / std (test.py:126-130, 248-251); ``ref_node``: which of the edges into the
         query node is the reference edge (test.py:227-229).  ``fuse``: None (that one edge), or ``"mean"`` / ``"median"`` /
         ``"consensus"``: the first ``max_edges`` (1..64) edges into the query node combined -- there is no reference edge then,
         so ``ref_node`` must stay 0.  ``inlier_t`` / ``inlier_deg``: the thresholds of ``"consensus"`` (checked always, used by
         that mode only).  Their defaults 0.25 / 5.0 are API defaults, not measured optima: they belong to the scene's scale, and
         ``inlier_t`` is compared after ``* pose_s + pose_m``, i.e. in the unit of the un-normalised translation.  Both finite,
-        ``inlier_t >= 0``, ``0 <= inlier_deg <= 360`` (ValueError)."""
+        ``inlier_t >= 0``, ``0 <= inlier_deg <= 360`` (ValueError).  ``weights``: None, or ``"variance"`` with ``fuse="mean"`` /
+        ``"consensus"`` (ValueError with the other rules): the mean weighs every candidate by ``1 / (variance + var_floor)``
+        (``ops.query_pose_fused``).  ``var_floor``: finite and >= 1e-30 (checked always); 1e-12 is an API default, not a tuned
+        value."""
         self.pose_m, self.pose_s = ops._qp_triple(pose_m, "pose_m"), ops._qp_triple(pose_s, "pose_s")
         self.ref_node = ops._qp_ref_node(ref_node)
         self.fuse, self.max_edges = fuse, max_edges
         self.inlier_t, self.inlier_deg = ops._qp_thresholds(inlier_t, inlier_deg, "QueryPose")
+        self.weights, self.var_floor = ops._qp_weights(weights, fuse, var_floor, "QueryPose")
         if fuse is not None:
             ops._qp_fuse(fuse, max_edges, "QueryPose")
             if self.ref_node != 0:
@@ -78,48 +95,62 @@ class QueryPose:
     # ---- the output block: what a stream allocates per micro-batch and copies back in one piece ----------------------------
     def output_block(self, g: int, device):
         """The outputs of ``g`` graphs on ``device``: -> (rows float64 [g, 16] for ``out=``, inliers int32 [g, 2] for ``inliers=``
-        or None, the ONE tensor a stream copies back).  That tensor is the rows themselves, 128 bytes per graph -- except with
-        ``fuse="consensus"``, whose two integers per graph travel behind the rows in one buffer (``packed_rows``, 136 bytes)."""
-        if self.fuse != "consensus":
+        or None, the ONE tensor a stream copies back, spread float64 [g, 2] for ``spread=`` or None).  That tensor is the rows
+        themselves, 128 bytes per graph -- except where the rule writes more: a weighted rule's spread (16 bytes per graph) and
+        the two integers of ``fuse="consensus"`` (8 bytes) travel behind the rows in one buffer (``packed_block``: 136 bytes per
+        graph for ``"consensus"``, 144 for weighted ``"mean"``, 152 for weighted ``"consensus"``).  A caller hands ``rel_var=``
+        to ``from_targets`` / ``from_map`` exactly when the spread is not None."""
+        spread, ints = self.weights is not None, self.fuse == "consensus"
+        if not spread and not ints:
             rows = torch.empty((g, 16), dtype=torch.float64, device=device)
-            return rows, None, rows
-        buf, rows, ints = packed_rows(g, device)
-        return rows, ints, buf
+            return rows, None, rows, None
+        buf, rows, sp, ints = packed_block(g, device, spread, ints)
+        return rows, ints, buf, sp
 
     def cut_block(self, host):
         """A host copy (tensor or numpy array) of the tensor ``output_block`` says to copy back -> (rows [g, 16], inliers [g, 2]
-        or None), views of it."""
-        return unpack_rows(host) if self.fuse == "consensus" else (host, None)
+        or None, spread [g, 2] or None), views of it."""
+        spread, ints = self.weights is not None, self.fuse == "consensus"
+        if not spread and not ints:
+            return host, None, None
+        rows, sp, ints = unpack_block(host, spread, ints)
+        return rows, ints, sp
 
     # ---- the two forms ---------------------------------------------------------------------------------------------------
     def from_targets(self, rel_pose, edge_index, node_first, node_targets, edge_first=None, out=None, candidates=None,
-                     counts=None, inliers=None) -> torch.Tensor:
+                     counts=None, inliers=None, rel_var=None, spread=None) -> torch.Tensor:
         """Graphs with collated targets (``evaluate_stream``): ``node_first`` int64 [G + 1], ``node_targets`` fp32 [N, 6] =
         the batch's ``data.y``.  -> float64 [G, 16] on the device.  With ``fuse``, optional outputs: ``candidates`` float64
         [G, max_edges, 16] (every used candidate as a row) and ``counts`` int32 [G] (usable edges before the cut); with
-        ``fuse="consensus"`` also ``inliers`` int32 [G, 2] = (supporters of the winning candidate, candidates used)."""
+        ``fuse="consensus"`` also ``inliers`` int32 [G, 2] = (supporters of the winning candidate, candidates used).  With
+        ``weights``: ``rel_var`` fp32 [E, 6], the variances of ``rel_pose``'s rows (required), and the optional output ``spread``
+        float64 [G, 2] = (sigma_t, sigma_q) of the fused pose."""
         return self._run(rel_pose, dict(edge_index=edge_index, node_first=node_first, node_targets=node_targets,
-                                        edge_first=edge_first, out=out), candidates, counts, inliers)
+                                        edge_first=edge_first, out=out), candidates, counts, inliers, rel_var, spread)
 
     def from_map(self, rel_pose, edge_index, fmap, neighbours, query_targets=None, edge_first=None, out=None, candidates=None,
-                 counts=None, inliers=None) -> torch.Tensor:
+                 counts=None, inliers=None, rel_var=None, spread=None) -> torch.Tensor:
         """Graphs of the map path (``forward_map`` / ``relocalize``): graph g is query g followed by the rows ``neighbours[g]``
         of ``fmap``, whose ``poses`` are the database images' targets; ``query_targets`` fp32 [G, 6] are the queries' own (None:
         zeros, the rows' ``targ`` part and errors then mean nothing).  -> float64 [G, 16] on the device.  ``candidates`` /
-        ``counts`` / ``inliers``: as in ``from_targets``."""
+        ``counts`` / ``inliers`` / ``rel_var`` / ``spread``: as in ``from_targets``."""
         poses = getattr(fmap, "poses", None)
         if poses is None:
             raise ValueError("QueryPose.from_map: the feature map holds no poses (build it with poses=...): a query's pose is "
                              "its database image's pose minus the predicted relative pose")
         return self._run(rel_pose, dict(edge_index=edge_index, map_poses=poses, neighbours=neighbours,
-                                        query_targets=query_targets, edge_first=edge_first, out=out), candidates, counts, inliers)
+                                        query_targets=query_targets, edge_first=edge_first, out=out), candidates, counts, inliers,
+                         rel_var, spread)
 
-    def _run(self, rel_pose, kw, candidates=None, counts=None, inliers=None) -> torch.Tensor:
+    def _run(self, rel_pose, kw, candidates=None, counts=None, inliers=None, rel_var=None, spread=None) -> torch.Tensor:
         if self.fuse is None and (candidates is not None or counts is not None):
             raise ValueError("QueryPose: candidates / counts are outputs of the fused rule (fuse='mean', 'median' or "
                              "'consensus')")
         if self.fuse != "consensus" and inliers is not None:
             raise ValueError(f"QueryPose: inliers is an output of fuse='consensus', this rule has fuse={self.fuse!r}")
+        if self.weights is None and (rel_var is not None or spread is not None):
+            raise ValueError("QueryPose: rel_var / spread belong to a weighted rule (weights='variance'), this rule has "
+                             "weights=None")
         if torch.is_tensor(rel_pose) and rel_pose.is_cuda:      # (anything else is refused by ops.query_pose below)
             status = self._bad.tensor(rel_pose.device)
         else:
@@ -131,7 +162,8 @@ class QueryPose:
         else:
             rows = ops.query_pose_fused(rel_pose, fuse=self.fuse, max_edges=self.max_edges, pose_m=self.pose_m, pose_s=self.pose_s,
                                         status=status, candidates=candidates, counts=counts, inlier_t=self.inlier_t,
-                                        inlier_deg=self.inlier_deg, inliers=inliers, **kw)
+                                        inlier_deg=self.inlier_deg, inliers=inliers, weights=self.weights, rel_var=rel_var,
+                                        var_floor=self.var_floor, spread=spread, **kw)
         self._bad.publish()                       # the counter's copy to pinned memory, behind this call's kernel
         return rows
 

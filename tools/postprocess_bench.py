@@ -25,11 +25,18 @@ device+consensus --against device+median``) holds a new mode of this checkout ag
 same box in the same minutes; reported are every round's rates, the median and spread over all of a side's timed calls, and
 whether this side is slower by more than the larger of 3 % and the observed spread.
 
+``--mc-samples S`` builds the model with ``droprate = 0.5`` and ``model.mc_dropout = McDropout(S, seed 0)`` (the fused Monte-Carlo
+heads) on both sides; a mode ending in ``+var`` (``device+mean+var``, ``host+consensus+var``) then runs the fused rule with
+``weights="variance"``, which reads the variances those heads leave.  ``--modes device+mean+var --against device+mean --mc-samples
+16`` holds the weighted rule against the baseline checkout's unweighted ``"mean"`` under the same sampler.
+
 usage: tools/postprocess_bench.py [--reps 3] [--baseline-root DIR] [--out profiles/query_pose_bench.json]
        tools/postprocess_bench.py --fuse mean,median --baseline-root DIR --out profiles/query_pose_fused_bench.json
        tools/postprocess_bench.py --capture --baseline-root DIR --out profiles/relocalize_capture_bench.json
        tools/postprocess_bench.py --modes device+consensus --against device+median --baseline-root DIR --legs 224x224_f32,224x224_bf16 \
-                                  --out profiles/consensus_pose_bench.json"""
+                                  --out profiles/consensus_pose_bench.json
+       tools/postprocess_bench.py --modes device+mean+var --against device+mean --mc-samples 16 --baseline-root DIR \
+                                  --legs 224x224_f32,224x224_bf16 --out profiles/weighted_pose_bench.json"""
 import argparse
 import json
 import os
@@ -96,13 +103,14 @@ def alternate(args):
         row = {}
         for side, (root, mode) in sides.items():
             cmd = [sys.executable, os.path.abspath(__file__), "--root", root, "--modes", mode, "--reps", str(args.reps), "--queries",
-                   str(args.queries), "--legs", args.legs or ",".join(f"{h}x{w}_{p}" for p in ("f32", "bf16") for h, w in GEOMS)]
+                   str(args.queries), "--legs", args.legs or ",".join(f"{h}x{w}_{p}" for p in ("f32", "bf16") for h, w in GEOMS),
+                   "--mc-samples", str(args.mc_samples)]
             res = subprocess.run(cmd, stdout=subprocess.PIPE, text=True, timeout=900)
             if res.returncode != 0:
                 raise SystemExit(f"the {side} run failed with exit status {res.returncode}")
             doc = json.loads(res.stdout.strip().splitlines()[-1])
             info[side] = {"mode": mode, "library_digest": doc["library_digest"]}
-            info.update({k: doc[k] for k in ("K", "map_rows", "queries", "micro_batch", "reps", "device", "host", "cpus")})
+            info.update({k: doc[k] for k in ("K", "map_rows", "queries", "micro_batch", "reps", "device", "host", "cpus", "mc_samples")})
             row[side] = {key: leg[mode] for key, leg in doc["relocalize"].items()}
             print(f"round {len(rounds)} {side} {mode}: " + ", ".join(f"{k} {v['median']}" for k, v in row[side].items()),
                   file=sys.stderr, flush=True)
@@ -144,6 +152,8 @@ def main():
     ap.add_argument("--against", default=None, help="a mode of the --baseline-root checkout (e.g. device+median) to hold the one "
                     "mode of --modes against, in alternating child processes")
     ap.add_argument("--rounds", type=int, default=3, help="--against: how often each side is run")
+    ap.add_argument("--mc-samples", type=int, default=0, help="S > 0: droprate = 0.5 and model.mc_dropout = McDropout(S, 0); the "
+                    "+var modes need S >= 2")
     args = ap.parse_args()
     if args.against:
         return alternate(args)
@@ -164,14 +174,19 @@ def main():
     only_leg, only_mode = (args.only.split(":") + [None])[:2] if args.only else (None, None)
     if only_mode:
         modes = [only_mode]
+    if any(mo.endswith("+var") for mo in modes) and args.mc_samples < 2:
+        raise SystemExit("a +var mode weights by the Monte-Carlo variances: give --mc-samples S >= 2")
     dev = torch.device("cuda:0")
-    m = PoseNetX_R2(resnet34(), droprate=0.0, pretrained=False, feat_dim=D, edge_feat_dim=D, node_dim=D, input_img_height=224,
+    m = PoseNetX_R2(resnet34(), droprate=0.5 if args.mc_samples else 0.0, pretrained=False, feat_dim=D, edge_feat_dim=D, node_dim=D, input_img_height=224,
                     use_gnn=True, knn=-1, use_AP=True, gnn_recursion=2)
     m.load_state_dict(S.synth_state_dict(S.posenet_r2_param_shapes(D, D, D), seed=1))
     m = m.to(dev).eval()
+    if args.mc_samples:
+        from relpose_gnn_amd.mc_dropout import McDropout
+        m.mc_dropout = McDropout(args.mc_samples, 0)
     gen = torch.Generator(device=dev).manual_seed(0)
     doc = {"metric": "query_pose_postprocess", "K": K, "map_rows": MAP_ROWS, "queries": args.queries, "micro_batch": 64,
-           "reps": args.reps, "root": "this checkout" if args.root is None else "another checkout",
+           "reps": args.reps, "mc_samples": args.mc_samples, "root": "this checkout" if args.root is None else "another checkout",
            "library_digest": B.source_digest(), "device": torch.cuda.get_device_name(0), "host": os.uname().nodename,
            "cpus": len(os.sched_getaffinity(0)), "relocalize": {}, "evaluate_stream": {}}
 
@@ -180,8 +195,8 @@ def main():
             return {}
         mode, *extra = mode.split("+")
         kw = {"postprocess": mode}
-        for e in extra:                                    # "capture", or the fuse mode
-            kw.update({"capture": True} if e == "capture" else {"fuse": e})
+        for e in extra:                                    # "capture", "var" (the weighted rule), or the fuse mode
+            kw.update({"capture": True} if e == "capture" else {"weights": "variance"} if e == "var" else {"fuse": e})
         return kw
 
     n = args.queries
