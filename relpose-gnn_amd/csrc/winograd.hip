@@ -76,8 +76,42 @@ __device__ __forceinline__ float4 sub(const float4& x, const float4& y) {
 //     11 packed instructions per pair instead of ~30 scalar ones.
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+// The two tile orders of the one-tile 8-wave kernel and its fix-up (template parameter RM; the persistent kernel keeps the
+// first: it measured 4 % slower in the second).  Tile index m counts (image row, tile column):
+//   RM = false, consecutive rows: m = (img * H + ho) * Tw + tw; a workgroup's 128 tiles are whatever rows come next, so the
+//     kernel rows that fall outside the image are a per-lane property (rowbits, offsets switched off per kernel row);
+//   RM = true, one image row per item (launches with n * Tw a multiple of 128): m = ho * ntw + img * Tw + tw, ntw = n * Tw.
+//     All 128 tiles of an item (and all 32 of a wave) share ho, so the kernel rows an item walks are a scalar range
+//     [kh0, kh0 + nkh): the rows of the top / bottom image row that would multiply zero padding are not issued at all.
+//     Items are walked down the image first (m-block j -> column j / H of 128 tiles, row j % H), so that the workgroups that
+//     are resident together on an XCD read neighbouring input rows of the same images, as in the other order.
+// The skipped products are exact zeros: every output is the same sum in the same order in both orders.
+struct RowOrder { int H, ntw; };
+template <bool RM>
+__device__ __forceinline__ int wino43_block_m0(int j, const RowOrder& ro) {       // first tile of m-block j (128 tiles)
+    if constexpr (RM) {
+        const int col = j / ro.H, ho = j - col * ro.H;
+        return ho * ro.ntw + col * 128;
+    } else
+        return j * 128;
+}
+// tile m -> image row index t = img * H + ho and tile column tw
+template <bool RM>
+__device__ __forceinline__ void wino43_tile_row(int m, int Tw, const RowOrder& ro, int& t, int& tw) {
+    if constexpr (RM) {
+        const int ho = m / ro.ntw, i = m - ho * ro.ntw, img = i / Tw;
+        t = img * ro.H + ho;
+        tw = i - img * Tw;
+    } else {
+        t = m / Tw;
+        tw = m - t * Tw;
+    }
+}
+
+template <bool RM = false>
 __device__ __forceinline__ void wino43_epilogue(const f32x16 (&acc)[P], float* slab, int lane, int mw0, int nw0, int M,
-                                                int Tw, int W, int Cout, const Epi& ep) {
+                                                int Tw, int W, int Cout, const Epi& ep, const RowOrder& ord = RowOrder{0, 0}) {
     constexpr int EP = 32 + 4;                              // slab pitch: 32 channels + pad
     constexpr unsigned OOB = 0x80000000u;
     const int c4 = lane & 7, pr = lane >> 3;                // 8 lanes cover a row's 32 channels; 8 rows per pass
@@ -88,20 +122,29 @@ __device__ __forceinline__ void wino43_epilogue(const f32x16 (&acc)[P], float* s
     if (n_ok && ep.shift) sh = *reinterpret_cast<const float4*>(ep.shift + nb);
 
     // this lane stores pixel column 4*tw + (pr & 1) [+ 2 in the second half] of tiles mw0 + (pr >> 1) + 4*it, it = 0..7
-    const int t_first = mw0 / Tw;                           // wave-uniform: first image row (n*H + ho) of the wave
+    // wave-uniform: first image row (n*H + ho) of the wave; RM: the wave's tiles are row ho of consecutive images, so the
+    // rows of consecutive t lie a whole image apart
+    int i0 = mw0, t_scale = 1, t_add = 0, row_px = W;
+    if constexpr (RM) {
+        t_add = mw0 / ord.ntw;
+        i0 = mw0 - t_add * ord.ntw;
+        t_scale = ord.H;
+        row_px = ord.H * W;
+    }
+    const int q_first = i0 / Tw, t_first = q_first * t_scale + t_add;
     const size_t row0 = (size_t)t_first * W * Cout;
     const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(ep.out + row0, 0, 0x7fffffff, 0x00020000);
     const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<float*>(ep.residual ? ep.residual + row0 : ep.out + row0), 0, 0x7fffffff, 0x00020000);
     const int step_t = 4 / Tw, step_tw = 4 % Tw;            // wave-uniform
     int mt = mw0 + (pr >> 1);
-    int trel = mt / Tw - t_first, tw = mt % Tw;
+    int trel = (i0 + (pr >> 1)) / Tw - q_first, tw = (i0 + (pr >> 1)) % Tw;
     unsigned voff[2][8];
 #pragma unroll
     for (int it = 0; it < 8; ++it) {
         const int wo = 4 * tw + (pr & 1);
         const bool ok = n_ok && mt < M;
-        const unsigned o = 4u * (unsigned)((trel * W + wo) * Cout + nb);
+        const unsigned o = 4u * (unsigned)((trel * row_px + wo) * Cout + nb);
         voff[0][it] = ok && wo < W ? o : OOB;
         voff[1][it] = ok && wo + 2 < W ? o + 8u * (unsigned)Cout : OOB;
         mt += 4;
@@ -560,11 +603,14 @@ __device__ unsigned long long* g_wino_trace = nullptr;
 #endif
 
 // BatchNorm / residual / ReLU / store of one 16-byte group of a summed tail tile: pixel p (0..511) x channel quad c4 (0..15)
+template <bool RM>
 __device__ __forceinline__ void wino43_finish_quad(const float4& s, const Epi& ep, int tile, int p, int c4, int M, int Tw, int W,
-                                                   int Cout, int tiles_n) {
-    const int m = (tile / tiles_n) * BMT8 + (p >> 2), nb = (tile % tiles_n) * BN + 4 * c4;
+                                                   int Cout, int tiles_n, const RowOrder& ord) {
+    const int m = wino43_block_m0<RM>(tile / tiles_n, ord) + (p >> 2), nb = (tile % tiles_n) * BN + 4 * c4;
     if (m >= M || nb >= Cout) return;
-    const int t = m / Tw, wo = 4 * (m - t * Tw) + (p & 3);
+    int t, tw;
+    wino43_tile_row<RM>(m, Tw, ord, t, tw);
+    const int wo = 4 * tw + (p & 3);
     if (wo >= W) return;
     const size_t o = ((size_t)t * W + wo) * Cout + nb;
     float4 sc = make_float4(1.f, 1.f, 1.f, 1.f), sh = f4zero(), rs = f4zero();
@@ -584,8 +630,9 @@ __device__ __forceinline__ void wino43_finish_quad(const float4& s, const Epi& e
 // back like the others: the bits do not depend on who came last), applies the epilogue and puts the counter back to zero --
 // the work of wino43_fixup_kernel without the launch.  Nobody waits (no spinning: the workgroups of two streams share the
 // CUs).  `flag`: one int of LDS that no wave is using.  8 of a thread's 16 groups at a time: 8 loads in flight per thread.
+template <bool RM>
 __device__ __forceinline__ void wino43_combine_last(const Split& sp, int tt, const Epi& ep, int M, int Tw, int W, int Cout,
-                                                    int tiles_n, int* flag) {
+                                                    int tiles_n, const RowOrder& ord, int* flag) {
     if (!rpg::last_arriver(sp.arrive + tt, (unsigned)sp.parts, flag)) return;
     const __amdgpu_buffer_rsrc_t rs = rpg::agent_rsrc(sp.partial + (size_t)tt * sp.parts * (BMT8 * 4 * BN));
     constexpr unsigned SLAB_B = BMT8 * 4 * BN * 4;
@@ -607,14 +654,15 @@ __device__ __forceinline__ void wino43_combine_last(const Split& sp, int tt, con
 #pragma unroll
         for (int c = 0; c < 8; ++c) {
             const int idx = tid_c + NT8 * (8 * h + c);
-            wino43_finish_quad(sum[c], ep, tile, idx >> 4, idx & 15, M, Tw, W, Cout, tiles_n);
+            wino43_finish_quad<RM>(sum[c], ep, tile, idx >> 4, idx & 15, M, Tw, W, Cout, tiles_n, ord);
         }
     }
 }
 
+template <bool RM>
 __global__ __launch_bounds__(NT8) void wino43_conv8_kernel(const float* __restrict__ x, const float* __restrict__ U, int H,
                                                           int W, int Cin, int Cout, int Tw, int M, Epi ep, int tiles_n,
-                                                          Split sp) {
+                                                          Split sp, int ntw) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
 #ifdef RPG_WINO_TRACE
     if (g_wino_trace && threadIdx.x == 0) g_wino_trace[5 * blockIdx.x] = __builtin_amdgcn_s_getreg(0xF804);   // HW_ID
@@ -627,21 +675,35 @@ __global__ __launch_bounds__(NT8) void wino43_conv8_kernel(const float* __restri
     // consecutive K steps.  (Kernel-row major, the order of round 1, re-read it after Cin/16 steps, by when the resident
     // workgroups of an XCD (32 x 160 KB at layer 1) had pushed it out of the 4-MB L2: PMC showed 2.0x the algorithmic
     // read traffic, FETCH_SIZE calibrated with tools/probes/fetch_calib_probe.hip.)
+    // RM (one image row ho per workgroup): a channel block is walked in the nkh kernel rows kh0 .. kh0 + nkh - 1 that lie
+    // inside the image (2 in the top and bottom image row, else 3), and K steps are counted from the part's first: [0, nk).
+    const RowOrder ord{H, ntw};
     const int kpr = (Cin + BK - 1) / BK;               // channel blocks = K steps per kernel row
     int tile, kb = 0, nk = 3 * kpr;                    // this workgroup's tile and K-step range [kb, nk), multiples of 3
+    int cb0 = 0, cb1 = kpr;                            // ... as channel blocks
     const bool is_split = (int)blockIdx.x < sp.n_split;       // workgroup-uniform
     if (is_split) {
         const int tt = blockIdx.x / sp.parts, part = blockIdx.x - tt * sp.parts;
         tile = sp.tile_base + tt;
-        kb = 3 * (part * kpr / sp.parts);
-        nk = 3 * ((part + 1) * kpr / sp.parts);
+        cb0 = part * kpr / sp.parts;
+        cb1 = (part + 1) * kpr / sp.parts;
+        kb = 3 * cb0;
+        nk = 3 * cb1;
     } else {
         const int nwg = gridDim.x - sp.n_split, bid = blockIdx.x - sp.n_split;
         const int xcd = bid & 7, loc = bid >> 3, q = nwg >> 3, r8 = nwg & 7;
         tile = (xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q) + loc;
     }
-    const int m0 = (tile / tiles_n) * BMT8;
+    const int m0 = wino43_block_m0<RM>(tile / tiles_n, ord);
     const int n0 = (tile % tiles_n) * BN;
+    int kh0 = 0, kh_end = 3;                           // RM: the item's kernel rows [kh0, kh_end)
+    if constexpr (RM) {
+        const int ho = m0 / ntw;
+        kh0 = ho == 0 ? 1 : 0;
+        kh_end = ho == H - 1 ? 2 : 3;
+        kb = 0;
+        nk = (kh_end - kh0) * (cb1 - cb0);
+    }
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
@@ -649,20 +711,22 @@ __global__ __launch_bounds__(NT8) void wino43_conv8_kernel(const float* __restri
     const int brow = row & 63, bhalf = tid >> 8;       // B: channel-row brow, positions 3*bhalf .. 3*bhalf+2
 
     // ---- K-invariant staging addresses (see wino43_conv_kernel for the buffer-load conventions)
-    const int n_first = (m0 / Tw) / H;
+    const int n_first = RM ? (m0 % ntw) / Tw : (m0 / Tw) / H;
     const size_t img_floats = (size_t)H * W * Cin;
     const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<float*>(x + n_first * img_floats) - (size_t)W * Cin, 0, 0x7fffffff, 0x00020000);
     const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(U), 0, 0x7fffffff, 0x00020000);
     constexpr unsigned OOB = 0x80000000u;
-    unsigned va[P], va3[3][P];            // va3[kh]: offsets of the six pixels for kernel row kh, OOB where the row is outside
+    // va3[kh]: offsets of the six pixels for kernel row kh, OOB where the row is outside.  RM: the kernel rows outside are not
+    // walked, the kernel row is a scalar offset and one set (va3[0]) serves them all
+    unsigned va[P], va3[RM ? 1 : 3][P];
     unsigned rowbits = 0;                 // bit kh set <=> image row ho-1+kh exists (and the tile itself does)
     {
         const int m = m0 + row;
         int img_off = 0, ho = 0, wi0 = -(1 << 24);
         if (m < M) {
-            const int tw = m % Tw;
-            const int t = m / Tw;
+            int t, tw;
+            wino43_tile_row<RM>(m, Tw, ord, t, tw);
             ho = t % H;
             img_off = (t / H - n_first) * (int)img_floats;
             wi0 = 4 * tw - 1;
@@ -677,14 +741,15 @@ __global__ __launch_bounds__(NT8) void wino43_conv8_kernel(const float* __restri
     const unsigned ustride_b = (unsigned)Cout * K * 4u;
     const unsigned vb = n0 + brow < Cout ? 4u * (unsigned)((n0 + brow) * K + 4 * slot) + 3u * bhalf * ustride_b : OOB;
     unsigned vb_eff;
-    int f_kt = kb, f_c0 = (kb / 3) * BK;  // the K step / channel block the next fetches load (wave-uniform)
+    int f_kt = kb, f_c0 = cb0 * BK;       // the K step / channel block the next fetches load (wave-uniform)
+    int f_kh = kh0;                       // RM: ... and its kernel row
     const unsigned row_b = 4u * (unsigned)(W * Cin), krow_b = 4u * (unsigned)Cin;       // bytes per image row / per kernel row of U
     auto refresh = [&]() {                // effective offsets of channel block f_c0: row borders, channel tail, past the end
         asm volatile("" ::: "memory");    // keeps this a (rarely taken) branch
         const bool cv = f_kt < nk && f_c0 + 4 * slot < Cin;
 #pragma unroll
-        for (int kh = 0; kh < 3; ++kh) {
-            const bool rv = cv && ((rowbits >> kh) & 1u);
+        for (int kh = 0; kh < (RM ? 1 : 3); ++kh) {
+            const bool rv = cv && (RM || ((rowbits >> kh) & 1u));
 #pragma unroll
             for (int j = 0; j < P; ++j) va3[kh][j] = rv ? va[j] : OOB;
         }
@@ -693,20 +758,26 @@ __global__ __launch_bounds__(NT8) void wino43_conv8_kernel(const float* __restri
     refresh();
 
     float4 d[P], ub[3];
-    // fetch_one(i, kh), i = 0..8: pixels 0..5 of kernel row kh (compile-time), then this thread's 3 U positions
-    auto fetch_one = [&](int i, int kh) {
+    // fetch_one(i, kh), i = 0..8: pixels 0..5 of kernel row kh (compile-time; RM: of the scalar f_kh), then this thread's 3 U positions
+    auto fetch_one = [&](int i, int kh_c) {
+        const unsigned kh = RM ? (unsigned)f_kh : (unsigned)kh_c;
         if (i < P) {
-            const unsigned sa = (unsigned)kh * row_b + 4u * (unsigned)f_c0;
-            d[i] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(ra, va3[kh][i], sa, 0));
+            const unsigned sa = kh * row_b + 4u * (unsigned)f_c0;
+            d[i] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(ra, va3[RM ? 0 : kh_c][i], sa, 0));
         } else {
-            const unsigned sb = (unsigned)kh * krow_b + 4u * (unsigned)f_c0 + (unsigned)(i - P) * ustride_b;
+            const unsigned sb = kh * krow_b + 4u * (unsigned)f_c0 + (unsigned)(i - P) * ustride_b;
             ub[i - P] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rb, vb_eff, sb, 0));
         }
     };
-    // after the fetches of kernel row kh: next step; a new channel block starts after kernel row 2
+    // after the fetches of kernel row kh: next step; a new channel block starts after kernel row 2 (RM: after the item's last)
     auto fetch_next = [&](int kh) {
         ++f_kt;
-        if (kh == 2) {
+        bool wrap = kh == 2;
+        if constexpr (RM) {
+            wrap = ++f_kh == kh_end;
+            if (wrap) f_kh = kh0;
+        }
+        if (wrap) {
             f_c0 += BK;
             if (f_c0 + BK > Cin || f_kt >= nk) refresh();       // rare: channel tail (Cin % 16 != 0) and past the end
         }
@@ -804,18 +875,26 @@ __global__ __launch_bounds__(NT8) void wino43_conv8_kernel(const float* __restri
     for (int i = 0; i < 4; ++i) frag_one(0, 0, i, 0);
     RPG_TRACE(2);
     int kt = kb;
-    for (; kt + 5 < nk; kt += 6) {
-        kstep(0, IMG8_FLOATS, 2);
-        kstep(IMG8_FLOATS, 0, 0);
-        kstep(0, IMG8_FLOATS, 1);
-        kstep(IMG8_FLOATS, 0, 2);
-        kstep(0, IMG8_FLOATS, 0);
-        kstep(IMG8_FLOATS, 0, 1);
-    }
-    if (kt < nk) {                       // (nk - kb) % 6 == 3: three more steps
-        kstep(0, IMG8_FLOATS, 2);
-        kstep(IMG8_FLOATS, 0, 0);
-        kstep(0, IMG8_FLOATS, 1);
+    if constexpr (RM) {                  // the kernel row is a scalar: only the LDS image toggles at compile time
+        for (; kt + 1 < nk; kt += 2) {
+            kstep(0, IMG8_FLOATS, 0);
+            kstep(IMG8_FLOATS, 0, 0);
+        }
+        if (kt < nk) kstep(0, IMG8_FLOATS, 0);       // an odd count: 3 kernel rows x an odd number of channel blocks
+    } else {
+        for (; kt + 5 < nk; kt += 6) {
+            kstep(0, IMG8_FLOATS, 2);
+            kstep(IMG8_FLOATS, 0, 0);
+            kstep(0, IMG8_FLOATS, 1);
+            kstep(IMG8_FLOATS, 0, 2);
+            kstep(0, IMG8_FLOATS, 0);
+            kstep(IMG8_FLOATS, 0, 1);
+        }
+        if (kt < nk) {                   // (nk - kb) % 6 == 3: three more steps
+            kstep(0, IMG8_FLOATS, 2);
+            kstep(IMG8_FLOATS, 0, 0);
+            kstep(0, IMG8_FLOATS, 1);
+        }
     }
     __syncthreads();                     // LDS becomes the epilogue slabs
     RPG_TRACE(3);
@@ -823,9 +902,9 @@ __global__ __launch_bounds__(NT8) void wino43_conv8_kernel(const float* __restri
     if (is_split) {
         wino43_epilogue_partial(acc, lds + ws * (64 * 36), lane, (ws >> 1) * 32, (ws & 1) * 32,
                                 sp.partial + (size_t)blockIdx.x * (BMT8 * 4 * BN));
-        if (sp.arrive) wino43_combine_last(sp, tile - sp.tile_base, ep, M, Tw, W, Cout, tiles_n, reinterpret_cast<int*>(lds));
+        if (sp.arrive) wino43_combine_last<RM>(sp, tile - sp.tile_base, ep, M, Tw, W, Cout, tiles_n, ord, reinterpret_cast<int*>(lds));
     } else
-        wino43_epilogue(acc, lds + ws * (64 * 36), lane, m0 + (ws >> 1) * 32, n0 + (ws & 1) * 32, M, Tw, W, Cout, ep);
+        wino43_epilogue<RM>(acc, lds + ws * (64 * 36), lane, m0 + (ws >> 1) * 32, n0 + (ws & 1) * 32, M, Tw, W, Cout, ep, ord);
 #ifdef RPG_WINO_TRACE
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #endif
@@ -1118,8 +1197,9 @@ __global__ __launch_bounds__(NT8) void wino43_conv8p_kernel(const float* __restr
 
 // Sums the `parts` partial slabs of tail tile blockIdx.x / 32 in k order and applies BatchNorm / residual / ReLU (the separate
 // fix-up launch: RPG_TUNE_INKERNEL_FIXUP = 0, and launches whose part count is above what one workgroup should add up).
+template <bool RM>
 __global__ __launch_bounds__(256) void wino43_fixup_kernel(const float* __restrict__ partial, Epi ep, int M, int Tw, int W,
-                                                           int Cout, int tiles_n, Split sp) {
+                                                           int Cout, int tiles_n, Split sp, RowOrder ord) {
     const int tt = blockIdx.x >> 5, idx = (blockIdx.x & 31) * 256 + threadIdx.x;      // 512 px x 16 channel quads
     const float* src = partial + (size_t)tt * sp.parts * (BMT8 * 4 * BN) + 4 * idx;
     float4 s = *reinterpret_cast<const float4*>(src);
@@ -1127,7 +1207,7 @@ __global__ __launch_bounds__(256) void wino43_fixup_kernel(const float* __restri
         const float4 v = *reinterpret_cast<const float4*>(src + (size_t)i * (BMT8 * 4 * BN));
         s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
     }
-    wino43_finish_quad(s, ep, sp.tile_base + tt, idx >> 4, idx & 15, M, Tw, W, Cout, tiles_n);
+    wino43_finish_quad<RM>(s, ep, sp.tile_base + tt, idx >> 4, idx & 15, M, Tw, W, Cout, tiles_n, ord);
 }
 
 // U[xi][co][kh][c] = sum_j G[xi][j] * w[co][kh][j][c], evaluated in double and rounded once.
@@ -1215,16 +1295,32 @@ int launch_conv_wino(const float* x, const float* u, const float* scale, const f
         // tiles a small fix-up kernel adds in k order.
         static bool attr8[64] = {};
         if (!attr8[dev]) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wino43_conv8_kernel),
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wino43_conv8_kernel<false>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, LDS8_BYTES);
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wino43_conv8_kernel<true>),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, LDS8_BYTES);
             attr8[dev] = true;
         }
         const long T = tm8 * tn;
         const int S = num_cus(), kpr = (cin + BK - 1) / BK, nk = 3 * kpr;
-        executed = (double)T * nk * 48.0 * 8.0 * 4096.0;
         long t_main = T;
         Split sp{0, 1, 0, nullptr, nullptr};
         const long tail = T % S;
+        // One image row per item (RowOrder, RM = true) where a row of tiles over all images is whole items.  32-bit offsets in
+        // that order: an item's 128 tiles are one row of at most 128 / tw + 2 images, addressed from one row above the first
+        // (+ 3 rows of scalar offset); a wave's 32 output tiles are one row of at most 32 / tw + 2 images.  The split-K tail
+        // decides which outputs are summed in parts, and the two orders put different outputs into the tail tiles: to keep every
+        // output's bits the order is taken only where the tail is empty or is every tile (rm_split below).
+        const long ntw = (long)n * tw;
+        const bool rm_fits = ntw % BMT8 == 0 && h >= 2 && (128L / tw + 4) * h * w * cin * 4 < (1L << 31) &&
+                             (32L / tw + 3) * h * w * cout * 4 < (1L << 31);
+        auto rm_split = [&]() { return sp.n_split == 0 || t_main == 0; };
+        // matrix-pipe FLOP really issued: K steps x 48 MFMAs x 8 waves x 4096; RM: 2 kernel rows in the top and bottom image row
+        auto executed_flop = [&](bool rm) {
+            const double steps = rm ? (double)T / h * kpr * (3.0 * h - 2.0) : (double)T * nk;
+            return steps * 48.0 * 8.0 * 4096.0;
+        };
+        const RowOrder ord{h, (int)ntw};
         if (tuning().wino.persist && cin % BK == 0 && (T > S || tuning().wino.persist == 2) && h >= 2) {
             // more tiles than CUs: the persistent kernel, S workgroups walking items b, b + S, ...; the tail tiles are cut
             // into parts of whole channel blocks (3 K steps) handed to the first workgroups
@@ -1243,14 +1339,17 @@ int launch_conv_wino(const float* x, const float* u, const float* scale, const f
                 }
             }
             const long items = sp.n_split + t_main;
+            // (the consecutive-row order: in the row order a workgroup's three kernel rows are three different image rows, not
+            // rows its neighbouring tiles also read, and the persistent kernel measured 4 % slower with it)
             hipLaunchKernelGGL(wino43_conv8p_kernel, dim3((unsigned)(items < S ? items : S)), dim3(NT8), LDS8_BYTES, s, x, u, h, w,
                                cin, cout, tw, (int)M, ep, tn, sp, (int)items);
             if (sp.n_split) {
                 hipStream_t fs = fixup_hop_begin(s);                                     // RPG_TUNE_FIXUP_PRIO: high-priority companion stream
-                hipLaunchKernelGGL(wino43_fixup_kernel, dim3((unsigned)(T - t_main) * 32), dim3(256), 0, fs, sp.partial, ep, (int)M,
-                                   tw, w, cout, tn, sp);
+                hipLaunchKernelGGL(wino43_fixup_kernel<false>, dim3((unsigned)(T - t_main) * 32), dim3(256), 0, fs, sp.partial, ep,
+                                   (int)M, tw, w, cout, tn, sp, ord);
                 fixup_hop_end(s, fs);
             }
+            executed = executed_flop(false);
             timing_end(slot, 2.0 * (double)n * h * w * cout * 9.0 * cin, s, executed);
             RPG_CHECK_LAUNCH("conv3x3_wino43");
             return RPG_OK;
@@ -1267,14 +1366,25 @@ int launch_conv_wino(const float* x, const float* u, const float* scale, const f
             }
         }
         // one launch: the split workgroups first, then the whole tiles
-        hipLaunchKernelGGL(wino43_conv8_kernel, dim3((unsigned)(sp.n_split + t_main)), dim3(NT8), LDS8_BYTES, s, x, u, h, w, cin,
-                           cout, tw, (int)M, ep, tn, sp);
+        const bool rm = rm_fits && rm_split();
+        const dim3 grid((unsigned)(sp.n_split + t_main));
+        if (rm)
+            hipLaunchKernelGGL(wino43_conv8_kernel<true>, grid, dim3(NT8), LDS8_BYTES, s, x, u, h, w, cin, cout, tw, (int)M, ep, tn, sp,
+                               ord.ntw);
+        else
+            hipLaunchKernelGGL(wino43_conv8_kernel<false>, grid, dim3(NT8), LDS8_BYTES, s, x, u, h, w, cin, cout, tw, (int)M, ep, tn, sp,
+                               ord.ntw);
         if (sp.n_split && !sp.arrive) {
             hipStream_t fs = fixup_hop_begin(s);
-            hipLaunchKernelGGL(wino43_fixup_kernel, dim3((unsigned)(T - t_main) * 32), dim3(256), 0, fs, sp.partial, ep, (int)M, tw, w,
-                               cout, tn, sp);
+            if (rm)
+                hipLaunchKernelGGL(wino43_fixup_kernel<true>, dim3((unsigned)(T - t_main) * 32), dim3(256), 0, fs, sp.partial, ep, (int)M,
+                                   tw, w, cout, tn, sp, ord);
+            else
+                hipLaunchKernelGGL(wino43_fixup_kernel<false>, dim3((unsigned)(T - t_main) * 32), dim3(256), 0, fs, sp.partial, ep, (int)M,
+                                   tw, w, cout, tn, sp, ord);
             fixup_hop_end(s, fs);
         }
+        executed = executed_flop(rm);
     } else {
         const int tm = (int)((M + BMT - 1) / BMT);
         executed = (double)tm * tn * (3 * ((cin + BK - 1) / BK)) * 48.0 * 4.0 * 4096.0;
