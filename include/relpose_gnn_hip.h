@@ -346,6 +346,22 @@ int rpg_query_pose_weighted_f64(const float* rel_pose, const int64_t* edge_src, 
 int rpg_knn_graph_f32(const float* x, const int64_t* batch, int n, int d, int k, int64_t* edge_index,
                       int32_t* cand, int32_t* cnt, int32_t* total, int32_t* status, void* stream);
 
+/* The same graph for g graphs of n_per nodes each (x [g*n_per][d], graph after graph), with every column at a position known
+ * before the call: k' = min(k, n_per - 1), column (v k' + t) of node v (id within the batch, 0 .. g n_per) holds its t-th nearest
+ * other node in src and v in dst, both plus node_offset; src / dst [g*n_per*k'] each.  The neighbours and their order are those
+ * rpg_knn_graph_f32 writes for the same x with a batch vector of g blocks of n_per: the per-pair sum rounds like that kernel's
+ * (lane c adds float4 columns c, c + 64, ..., then the xor-shuffle tree 32..1), near ties included.  q_src / q_dst (both NULL or
+ * both set): [g*k'], the columns into node 0 of every graph, i.e. columns g n_per k' + [0, k') of src / dst.
+ * A node whose self match is not among its k+1 nearest by (distance, index) -- k+1 or more lower-numbered nodes of its graph
+ * with a bit-identical row, or non-finite rows; only possible with n_per - 1 > k -- keeps k'+1 edges in the reference
+ * ("irregular").  Here it gets the first k' entries of that list, which is a valid graph but not the reference's, and
+ * irregular[0] += 1 per such node: a caller that needs the reference's graph reads the counter and takes rpg_knn_graph_f32.
+ * Limits (RPG_ERR_BAD_ARG otherwise): g >= 1, 2 <= n_per <= 2048, g*n_per <= 2^20, 1 <= k <= 64, d % 4 == 0, x 16-byte aligned,
+ * node_offset >= 0.  One workgroup per graph up to 64 nodes per graph (every unordered pair evaluated once), one per node above.
+ * One launch, no allocation, no synchronisation, no count for the host (graph-capturable).                                   */
+int rpg_knn_graph_uniform_f32(const float* x, int g, int n_per, int d, int k, int64_t node_offset, int64_t* src, int64_t* dst,
+                              int64_t* q_src, int64_t* q_dst, int32_t* irregular, void* stream);
+
 /* compute_edge_features (posenet.py:999-1019): out[e] = [x[min(s,t)], x[max(s,t)]], [e][2d]. */
 int rpg_edge_concat_gather_f32(const float* x, const int64_t* edge_index, int e, int d, float* out, void* stream);
 

@@ -7,9 +7,9 @@ __all__ = ["Batch", "Data", "fc_batch", "fc_edge_index"]
 
 
 def __getattr__(name):          # lazy: importing the package must not require torch.cuda or the built library
-    if name in ("PoseNetX_R2",):
-        from .posenet import PoseNetX_R2
-        return PoseNetX_R2
+    if name in ("PoseNetX_R2", "IrregularKnnGraph"):
+        from . import posenet
+        return getattr(posenet, name)
     if name == "QueryPose":
         from .query_pose import QueryPose
         return QueryPose

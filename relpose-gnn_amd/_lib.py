@@ -34,7 +34,7 @@ SYMBOLS = (
     "rpg_query_pose_f64", "rpg_query_pose_fused_f64", "rpg_gather_add2_relu_f32",
     "rpg_gnn_query_workspace_bytes", "rpg_gnn_forward_query_f32", "rpg_gnn_forward_query_bf16", "rpg_gemm_last_route", "rpg_get_tuning",
     "rpg_attention_aggregate_hidden_f32", "rpg_query_pose_consensus_f64", "rpg_pose_heads_mc_f32", "rpg_mc_advance",
-    "rpg_query_pose_weighted_f64",
+    "rpg_query_pose_weighted_f64", "rpg_knn_graph_uniform_f32",
 )
 
 
@@ -106,6 +106,7 @@ def _declare(lib: C.CDLL) -> None:
     lib.rpg_wino43_weights_floats.restype = C.c_size_t
     lib.rpg_conv3x3_wino43_bn_act_nhwc_f32.argtypes = [_vp] * 6 + [_i] * 6 + [_vp]
     lib.rpg_knn_graph_f32.argtypes = [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]
+    lib.rpg_knn_graph_uniform_f32.argtypes = [_vp, _i, _i, _i, _i, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp]
     lib.rpg_timing_read.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_longlong), C.POINTER(C.c_double)]
     lib.rpg_timing_read_ex.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_longlong), C.POINTER(C.c_double),
                                        C.POINTER(C.c_double)]

@@ -454,6 +454,108 @@ __global__ __launch_bounds__(GP_NT) void knn_compact_kernel(const int* __restric
     if (tid == 0) *total = s_carry;
 }
 
+// ------------------------------------------------------------------------------------------------
+// kNN graph of g graphs of n_per nodes each, at fixed positions (rpg_knn_graph_uniform_f32): every node has k' = min(k, n_per - 1)
+// incoming edges, so column (v k' + t) is known before anything runs and no count goes to the host.  The per-pair sum is
+// knn_candidates_kernel's, operation for operation (lane c adds float4 columns c, c + 64, ..., then the xor tree 32..1), and so is
+// the selection, so the neighbours and their order are that kernel's on every input.
+// ------------------------------------------------------------------------------------------------
+constexpr int KNN_SMALL = 64;         // nodes per graph up to which one workgroup holds the graph's whole distance matrix in LDS
+
+__device__ __forceinline__ float knn_pair_dist(const float4* __restrict__ xi, const float4* __restrict__ xj, int d4, int lane) {
+    float acc = 0.f;
+    for (int c = lane; c < d4; c += 64) {
+        const float4 a = xi[c], b = xj[c];
+        const float dx = a.x - b.x, dy = a.y - b.y, dz = a.z - b.z, dw = a.w - b.w;
+        acc += dx * dx + dy * dy + dz * dz + dw * dw;
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off);
+    return acc;
+}
+
+// Node v (id within its graph) of graph gi picks from its distance row (stride 1, m = n_per entries) like knn_candidates_kernel's
+// thread 0 and writes its k' columns.  A list without the self match holds k' + 1 other nodes (the reference keeps them all): the
+// first k' go out and the node is counted.
+__device__ __forceinline__ void knn_uniform_select(const float* __restrict__ dist, int m, int v, int gi, int k, int kp,
+                                                   int64_t node_offset, int64_t* __restrict__ src, int64_t* __restrict__ dst,
+                                                   int64_t* __restrict__ q_src, int64_t* __restrict__ q_dst,
+                                                   int* __restrict__ irregular) {
+    float bd[KNN_MAX_K + 1];
+    int bi[KNN_MAX_K + 1];
+    const int kk = k + 1;
+    int have = 0;
+    for (int j = 0; j < m; ++j) {
+        const float dj = dist[j];
+        if (have < kk || dj < bd[have - 1]) {
+            int p = have < kk ? have : kk - 1;
+            while (p > 0 && dj < bd[p - 1]) { bd[p] = bd[p - 1]; bi[p] = bi[p - 1]; --p; }
+            bd[p] = dj; bi[p] = j;
+            if (have < kk) ++have;
+        }
+    }
+    const int64_t first = (int64_t)gi * m + node_offset;       // id of the graph's node 0
+    const size_t col = ((size_t)gi * m + v) * kp;
+    int c = 0;
+    for (int t = 0; t < have; ++t) {
+        if (bi[t] == v) continue;
+        if (c < kp) {
+            src[col + c] = first + bi[t];
+            dst[col + c] = first + v;
+            if (q_src && v == 0) {
+                q_src[(size_t)gi * kp + c] = first + bi[t];
+                q_dst[(size_t)gi * kp + c] = first;
+            }
+        }
+        ++c;
+    }
+    if (c != kp) atomicAdd(irregular, 1);
+}
+
+// n_per <= KNN_SMALL: one workgroup per graph; its waves take the unordered pairs in turn ((a - b)^2 is (b - a)^2 bit for bit),
+// then thread v selects for node v.  Row stride n_per + 1 keeps the selecting threads on different LDS banks.
+__global__ __launch_bounds__(NT) void knn_uniform_graph_kernel(const float* __restrict__ x, int n_per, int d4, int k, int kp,
+                                                               int64_t node_offset, int64_t* __restrict__ src,
+                                                               int64_t* __restrict__ dst, int64_t* __restrict__ q_src,
+                                                               int64_t* __restrict__ q_dst, int* __restrict__ irregular) {
+    __shared__ float s_dist[KNN_SMALL * (KNN_SMALL + 1)];
+    const int gi = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int ld = n_per + 1;
+    const float4* xg = reinterpret_cast<const float4*>(x) + (size_t)gi * n_per * d4;
+    const int pairs = n_per * (n_per - 1) / 2;
+    for (int p = wave; p < pairs; p += NT / 64) {
+        int i = 0, rem = p;
+        while (rem >= n_per - 1 - i) { rem -= n_per - 1 - i; ++i; }
+        const int j = i + 1 + rem;
+        const float acc = knn_pair_dist(xg + (size_t)i * d4, xg + (size_t)j * d4, d4, lane);
+        if (lane == 0) { s_dist[i * ld + j] = acc; s_dist[j * ld + i] = acc; }
+    }
+    for (int i = wave; i < n_per; i += NT / 64) {     // the self match, evaluated like any pair: x - x is NaN for a non-finite x
+        const float acc = knn_pair_dist(xg + (size_t)i * d4, xg + (size_t)i * d4, d4, lane);
+        if (lane == 0) s_dist[i * ld + i] = acc;
+    }
+    __syncthreads();
+    if (tid < n_per) knn_uniform_select(s_dist + tid * ld, n_per, tid, gi, k, kp, node_offset, src, dst, q_src, q_dst, irregular);
+}
+
+// n_per > KNN_SMALL: one workgroup per node, knn_candidates_kernel's shape with the graph's range computed instead of scanned.
+__global__ __launch_bounds__(NT) void knn_uniform_node_kernel(const float* __restrict__ x, int n_per, int d4, int k, int kp,
+                                                              int64_t node_offset, int64_t* __restrict__ src,
+                                                              int64_t* __restrict__ dst, int64_t* __restrict__ q_src,
+                                                              int64_t* __restrict__ q_dst, int* __restrict__ irregular) {
+    __shared__ float s_dist[KNN_MAX_GRAPH];
+    const int node = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int gi = node / n_per, v = node - gi * n_per;
+    const float4* xg = reinterpret_cast<const float4*>(x) + (size_t)gi * n_per * d4;
+    const float4* xi = xg + (size_t)v * d4;
+    for (int j = wave; j < n_per; j += NT / 64) {
+        const float acc = knn_pair_dist(xi, xg + (size_t)j * d4, d4, lane);
+        if (lane == 0) s_dist[j] = acc;
+    }
+    __syncthreads();
+    if (tid == 0) knn_uniform_select(s_dist, n_per, v, gi, k, kp, node_offset, src, dst, q_src, q_dst, irregular);
+}
+
 inline int capped_grid(long items) {
     long g = (items + NT - 1) / NT;
     return (int)(g < 1 ? 1 : (g > 8192 ? 8192 : g));
@@ -592,5 +694,23 @@ extern "C" int rpg_knn_graph_f32(const float* x, const int64_t* batch, int n, in
     hipLaunchKernelGGL(knn_candidates_kernel, dim3(n), dim3(NT), 0, s, x, batch, n, d / 4, k, cand, cnt, status);
     hipLaunchKernelGGL(knn_compact_kernel, dim3(1), dim3(GP_NT), 0, s, cand, cnt, n, k + 1, n * (k + 1), edge_index, total);
     RPG_CHECK_LAUNCH("knn_graph");
+    return RPG_OK;
+}
+
+extern "C" int rpg_knn_graph_uniform_f32(const float* x, int g, int n_per, int d, int k, int64_t node_offset, int64_t* src,
+                                         int64_t* dst, int64_t* q_src, int64_t* q_dst, int32_t* irregular, void* stream) {
+    if (!x || !src || !dst || !irregular || (q_src == nullptr) != (q_dst == nullptr) || g <= 0 || n_per < 2 ||
+        n_per > KNN_MAX_GRAPH || d <= 0 || (d & 3) || k <= 0 || k > KNN_MAX_K || node_offset < 0 ||
+        (long)g * n_per > (1 << 20) || !rpg::aligned16(x))
+        return RPG_ERR_BAD_ARG;
+    hipStream_t s = rpg::as_stream(stream);
+    const int kp = k < n_per - 1 ? k : n_per - 1;
+    if (n_per <= KNN_SMALL)
+        hipLaunchKernelGGL(knn_uniform_graph_kernel, dim3(g), dim3(NT), 0, s, x, n_per, d / 4, k, kp, node_offset, src, dst, q_src,
+                           q_dst, irregular);
+    else
+        hipLaunchKernelGGL(knn_uniform_node_kernel, dim3(g * n_per), dim3(NT), 0, s, x, n_per, d / 4, k, kp, node_offset, src, dst,
+                           q_src, q_dst, irregular);
+    RPG_CHECK_LAUNCH("knn_graph_uniform");
     return RPG_OK;
 }

@@ -696,7 +696,7 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
     tail) and replayed with one launch per micro-batch instead of ~137.  Same kernels, same launch geometry, same order: the
     results are bit-identical to ``capture=False``.  The captured steps are kept on the model (``refresh_packed`` drops them; a
     step whose map has been extended is captured again), so a second call with the same shapes captures nothing.  What that
-    class refuses (``droprate > 0`` without ``model.mc_dropout``, ``knn > 0``, ``use_attention``, ``use_AP=False``, uint8 queries) raises here, before any
+    class refuses (``droprate > 0`` without ``model.mc_dropout``, ``knn > 0`` without ``model.static_knn``, ``use_attention``, ``use_AP=False``, uint8 queries) raises here, before any
     work is queued.  ``stats`` also receives ``graphs_captured`` (by this call) and ``graph_replays``.
 
     ``outputs="query"`` (default ``"all"``): every micro-batch runs ``forward_map(outputs="query")``, which computes only what
@@ -708,7 +708,16 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
     (a captured ``"all"`` step is never replayed for ``"query"``, nor the reverse).  A map without poses then returns the REDUCED
     raw tensors ``(abs_pose [G, 6], rel_pose [G*K, 6])``.  A map that is not on a GPU takes the synchronous path as for ``"all"``:
     the model's ``forward_map`` is called with ``outputs="query"`` and the host rule reads what it returns (``PoseNetX_R2`` itself
-    has no CPU compute path and raises there)."""
+    has no CPU compute path and raises there).
+
+    A model with ``knn > 0`` and ``model.static_knn`` set (``PoseNetX_R2.forward_map``, which see): every micro-batch builds its kNN
+    graph at fixed positions, k' = min(knn, K) edges into every node, so ``outputs="query"`` and ``capture=True`` serve it and the
+    device rule reads the step's edge list with a fixed cut.  ``ref_node >= k'`` raises ValueError up front (test.py:229 takes the
+    ``ref_node``-th edge into the query, and there are k').  The count of nodes whose reference list is irregular (the same map
+    row named knn + 1 times or more for one query, non-finite features) comes back with each micro-batch's results, one more
+    word behind the same event; a micro-batch that reports one is run AGAIN through the general path (``static_knn`` off,
+    ``outputs="all"``, uncaptured, on the neighbours it had) and its rows replaced, so every query's result is what the model gives
+    without ``static_knn``.  ``stats["knn_irregular_batches"]`` counts these re-runs."""
     device = fmap.device
     if outputs not in ("all", "query"):
         raise ValueError(f"relocalize: outputs must be 'all' or 'query', got {outputs!r}")
@@ -762,6 +771,13 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
         nb_dev = None
         nb_h = np.zeros((g_all, kk), dtype=np.int64)          # filled micro-batch by micro-batch as the copies land
     n_per = kk + 1
+    # model.static_knn (PoseNetX_R2 with knn > 0): forward_map builds its kNN graph at fixed positions, k' columns into every node
+    static_columns = getattr(model, "_static_columns", None)
+    kp = static_columns(None, kk) if static_columns is not None and getattr(model, "knn", -1) > 0 else 0
+    if kp and ref_node >= kp:
+        raise ValueError(f"relocalize: ref_node = {ref_node}, but the kNN graph has k' = min(knn, K) = {kp} edges into a query "
+                         f"(test.py:229 takes the ref_node-th of them)")
+    n_irregular = 0
     mc = getattr(model, "mc_dropout", None)
     mc_draw = None if mc is None else mc.draw
     on_gpu = torch.device(device).type == "cuda"
@@ -790,16 +806,32 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
             targ_dev = t32 if t32.is_cuda else (t32 if t32.is_pinned() else t32.pin_memory()).to(device, non_blocking=True)
         if model.knn <= 0:         # forward_map's own FC list: n (n - 1) columns per graph, graph after graph
             fc_first = torch.arange(min(micro_batch, g_all) + 1, dtype=torch.int64, device=device) * fc_edges.shape[1]
+        elif kp:                   # the kNN list at fixed positions: k' columns per node (per query in the query mode)
+            fc_first = torch.arange(min(micro_batch, g_all) + 1, dtype=torch.int64, device=device) * (kp if outputs == "query" else kp * n_per)
     acc = _PoseRows(pose_m, pose_s, ref_node, pose=qp, fuse=fuse, max_edges=max_edges, inlier_t=inlier_t,
                     inlier_deg=inlier_deg, weights=weights, var_floor=var_floor)
     raw_abs, raw_rel = [], []
+    # static_knn: the nodes of a micro-batch whose reference kNN list is irregular are counted here (zeroed ahead of every eager
+    # forward; a captured step has its own), and the word comes back behind the micro-batch's event with its other results
+    irr_dev = torch.zeros(1, dtype=torch.int32, device=device) if kp and not capture else None
+    ikw = {} if irr_dev is None else {"_irregular": irr_dev}
+
+    # ... into ONE pinned block of the call, a word per micro-batch (a status word like the deferred counters': not in d2h_bytes)
+    irr_host = torch.zeros(-(-g_all // micro_batch), dtype=torch.int32, pin_memory=True) if kp and on_gpu else None
+
+    def irregular_back(t, b0):
+        if t is None or irr_host is None:
+            return None
+        host = irr_host[b0 // micro_batch:b0 // micro_batch + 1]
+        host.copy_(t, non_blocking=True)
+        return host
 
     def captured_step(x, qd, targ):
         """The captured step of this micro-batch's shape and of this call's configuration: from the model's cache, or captured
         now with the micro-batch itself as the example."""
         nonlocal n_captured
         key = ("step", tuple(x.shape), x.dtype, kk, None if rule is None else (rule.sampling_period, rule.random), postprocess,
-               fuse, max_edges, qd is not None, targ is not None, outputs, inlier_t, inlier_deg, weights, var_floor,
+               fuse, max_edges, qd is not None, targ is not None, outputs, inlier_t, inlier_deg, weights, var_floor, kp,
                None if mc is None else (id(mc), mc.samples, mc.seed))       # the sampler's count and seed are baked into the step
         step = captured.get(key)
         if step is None or step.fmap is not fmap or step.pose is not qp or step.stale():
@@ -819,9 +851,11 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
             # query b0's graph starts at node b0 (K + 1) of the stream, whatever micro_batch is, and the whole call is ONE draw; a
             # captured step reads both from the same device words, so they are sent ahead of the replay like its other inputs
             mc.place(mc_draw, b0 * n_per)
+        if irr_dev is not None:
+            irr_dev.zero_()
         if rule is None and not capture:
-            ab, rel, ei = model.forward_map(x, nb_dev[b0:b1], fmap, **okw)
-            return _Forward(ab, rel, ei, nb_dev[b0:b1])
+            ab, rel, ei = model.forward_map(x, nb_dev[b0:b1], fmap, **okw, **ikw)
+            return _Forward(ab, rel, ei, nb_dev[b0:b1]), irregular_back(irr_dev, b0)
         qd = None
         if qd_all is not None:
             qd = qd_all[b0:b1]
@@ -843,17 +877,19 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
             # The outputs are the step's STATIC tensors, which the replay of the next micro-batch overwrites.  Their copies to
             # pinned memory (read_back here and in _MicroBatchRunner.launch, right after this returns) are enqueued on the stream
             # the replay ran on BEFORE the next launch() enqueues its replay there: stream order keeps micro-batch i's results.
-            return _Forward(out.abs_pose, out.rel_pose, out.edge_index, out.neighbours,
-                            None if rule is None else runner.read_back(out.neighbours), step.packed)
-        ab, rel, ei, nb_mb = model.forward_map(x, None, fmap, rule=rule, query_descriptors=qd, query_groups=qg, **okw)
-        return _Forward(ab, rel, ei, nb_mb, runner.read_back(nb_mb))
+            return (_Forward(out.abs_pose, out.rel_pose, out.edge_index, out.neighbours,
+                             None if rule is None else runner.read_back(out.neighbours), step.packed),
+                    irregular_back(getattr(step, "irregular", None), b0))
+        ab, rel, ei, nb_mb = model.forward_map(x, None, fmap, rule=rule, query_descriptors=qd, query_groups=qg, **okw, **ikw)
+        return _Forward(ab, rel, ei, nb_mb, runner.read_back(nb_mb)), irregular_back(irr_dev, b0)
 
     def read_back_of(chunk, x, fwd):
+        fwd, irr = fwd
         if qp is None:
             # (a weighted host rule: the variances this forward -- or this replay -- has just left, row for row with rel_pose)
             return {"nb": fwd.host_neighbours, "abs": fwd.abs_pose, "rel": fwd.rel_pose,
                     "ei": fwd.edge_index if model.knn > 0 else None,
-                    "var": mc.last.rel_var if weights is not None and poses_h is not None else None}
+                    "var": mc.last.rel_var if weights is not None and poses_h is not None else None, "irr": irr}
         back = fwd.back
         if back is None:                   # everything the rule writes travels back in one tensor, one copy
             b0, n = chunk[0].first, x.shape[0]
@@ -862,7 +898,29 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
                         rel_var=None if spread is None else mc.last.rel_var,
                         query_targets=None if targ_dev is None else targ_dev[b0:b0 + n],
                         edge_first=None if fc_first is None else fc_first[:n + 1])
-        return {"nb": fwd.host_neighbours, "rel": back}
+        return {"nb": fwd.host_neighbours, "rel": back, "irr": irr}
+
+    def general_again(b0, n):
+        """A micro-batch that reported an irregular graph, once more through the general kNN build (static_knn off, the whole
+        output, uncaptured) on the neighbours it had: -> its results on the host, in the layout of ``outputs="all"``.  Rare, so it
+        simply waits."""
+        x = queries[b0:b0 + n].to(device)
+        nb_mb = torch.from_numpy(nb_h[b0:b0 + n]).to(device)
+        model.static_knn = False
+        try:
+            if mc is not None:
+                mc.place(mc_draw, b0 * n_per)
+            ab, rel, ei = model.forward_map(x, nb_mb, fmap)
+            var = None if mc is None else mc.last.rel_var
+            if qp is None:
+                return {"nb": None, "abs": ab.cpu(), "rel": rel.cpu(), "ei": ei.cpu(),
+                        "var": var.cpu() if weights is not None and poses_h is not None else None}
+            out, ints, back, spread = qp.output_block(n, rel.device)
+            qp.from_map(rel, ei, fmap, nb_mb, out=out, inliers=ints, spread=spread, rel_var=None if spread is None else var,
+                        query_targets=None if targ_dev is None else targ_dev[b0:b0 + n])
+            return {"nb": None, "rel": back.cpu()}
+        finally:
+            model.static_knn = True
 
     def target_block(g):
         target = np.zeros((n_per, 6))
@@ -872,16 +930,24 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
         return target
 
     def finish(item):
+        nonlocal n_irregular
         b0, host = item.chunk[0].first, item.host
         if host["nb"] is not None:
             nb_h[b0:b0 + host["nb"].shape[0]] = host["nb"].numpy()
+        rows_of = rows_per
+        if host.get("irr") is not None and int(host["irr"][0]):
+            host, rows_of = general_again(b0, sum(int(c.x.shape[0]) for c in item.chunk)), n_per
+            n_irregular += 1
         if qp is not None:
             acc.add_device(host["rel"].numpy())
         elif poses_h is None:
+            if rows_of != rows_per:        # the query mode's rows of a micro-batch that was run again in full
+                into = (host["ei"][1] % n_per) == 0
+                host = dict(host, abs=host["abs"][::n_per], rel=host["rel"][into])
             raw_abs.append(host["abs"])
             raw_rel.append(host["rel"])
         else:
-            n_g = host["abs"].shape[0] // rows_per
+            n_g = host["abs"].shape[0] // rows_of
             ei = None if host["ei"] is None else host["ei"].numpy()      # a model-built (kNN) edge list
             acc.add(host["rel"].numpy(), (target_block(g) for g in range(b0, b0 + n_g)), cut_per_graph([n_per] * n_g, ei, [fc_edges] * n_g),
                     None if host.get("var") is None else host["var"].numpy())
@@ -897,6 +963,8 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
         stats["neighbours"] = nb_h
         if capture:
             stats.update(graphs_captured=n_captured, graph_replays=n_replays)
+        if kp:
+            stats["knn_irregular_batches"] = n_irregular
     if poses_h is None:
         return torch.cat(raw_abs), torch.cat(raw_rel)
     res = acc.result(with_targets=targ_h is not None)

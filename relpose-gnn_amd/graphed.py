@@ -106,6 +106,13 @@ class GraphedForwardMap:
     draws the next masks, and ``node_base`` is read from the device state a caller sets ahead of the replay.  ``self.spread``
     holds the variances (static, like the outputs).
 
+    A model with ``knn > 0`` is captured only with ``model.static_knn`` set (``PoseNetX_R2.forward_map``): the kNN graph is then
+    built at fixed positions inside the graph, from every replay's own features, k' = min(knn, K) edges into every node -- the
+    default ``edge_first`` is the cut of that list, K + 1 times k' columns per graph (k' with ``outputs="query"``).  ``self.irregular``
+    (int32 [1], static, valid after a replay like the outputs; None for every other model) is the number of nodes of the replayed
+    step whose reference list is irregular: the step counts them there and not in the model's counters, so nothing raises, a
+    caller that needs the reference's graph looks at it, and the step stays usable.
+
     The graph reads the packed weights, the workspaces, the map's tensors and the counters in place.  All of them are held
     here, so nothing it reads is freed under it, and every call compares them with what the model and the map hold NOW:
     after ``refresh_packed()`` / ``load_state_dict`` / ``.to()`` / a dtype switch / ``FeatureMap.extend`` the call raises
@@ -143,6 +150,11 @@ class GraphedForwardMap:
         dev = q.device
         self.model, self.fmap, self.rule, self.pose = model, fmap, rule, pose
         self.g, self.k, self.outputs = g, k, outputs
+        # model.static_knn: k' = min(knn, K) columns per node, rebuilt from every replay's features inside the graph; the nodes whose
+        # reference list is irregular are counted into self.irregular (int32 [1], static, zeroed by the step itself: valid after a
+        # replay like the outputs), not into the model's counters -- a caller looks at it, the step stays usable
+        self.kp = model._static_columns(None, k) if getattr(model, "knn", -1) > 0 else 0
+        self.irregular = torch.zeros(1, dtype=torch.int32, device=dev) if self.kp else None
 
         # ---- the static inputs --------------------------------------------------------------------------------------------------
         self.queries = q.detach().clone(memory_format=torch.contiguous_format)
@@ -179,7 +191,8 @@ class GraphedForwardMap:
                 ef = pose_kwargs["edge_first"]
                 self.edge_first = None if ef is None else ef.detach().to(device=dev, dtype=torch.int64).contiguous().clone()
             else:
-                self.edge_first = torch.arange(g + 1, dtype=torch.int64, device=dev) * (k if outputs == "query" else k * (k + 1))
+                per_node = self.kp or k           # incoming edges of every node: k' of the fixed-position kNN list, K of the FC one
+                self.edge_first = torch.arange(g + 1, dtype=torch.int64, device=dev) * (per_node if outputs == "query" else per_node * (k + 1))
 
         # ---- warm-up, validation, capture (the pattern of GraphedForward) ---------------------------------------------------------
         self.graph = torch.cuda.CUDAGraph()
@@ -219,7 +232,10 @@ class GraphedForwardMap:
                             "(frame_transform.apply(frames) outside the graph)")
         # the always-on dropout is captured only as model.mc_dropout samples it: its masks are made on the device from a counter
         # the captured step itself advances (rpg_mc_advance), where torch's generator would replay one mask for ever
-        if (getattr(model, "droprate", 0) > 0 and getattr(model, "mc_dropout", None) is None) or getattr(model, "knn", -1) > 0:
+        # a model-built kNN graph is captured only at fixed positions (model.static_knn: rpg_knn_graph_uniform_f32 writes no edge
+        # count for the host), where the general build waits for one
+        if ((getattr(model, "droprate", 0) > 0 and getattr(model, "mc_dropout", None) is None)
+                or (getattr(model, "knn", -1) > 0 and not getattr(model, "static_knn", False))):
             raise NotImplementedError(_FC_ONLY)
         if getattr(model, "use_attention", False) or not getattr(model, "use_AP", True):
             raise NotImplementedError(_FC_ONLY + "; use_attention and use_AP=False take the one-stream path, which allocates and "
@@ -227,12 +243,16 @@ class GraphedForwardMap:
 
     def _step(self) -> MapStep:
         m = self.model
+        kw = {}
+        if self.irregular is not None:
+            self.irregular.zero_()
+            kw["_irregular"] = self.irregular
         if self.rule is None:
-            ab, rel, ei = m.forward_map(self.queries, self.neighbours, self.fmap, outputs=self.outputs)
+            ab, rel, ei = m.forward_map(self.queries, self.neighbours, self.fmap, outputs=self.outputs, **kw)
             nb = self.neighbours
         else:
             ab, rel, ei, nb = m.forward_map(self.queries, None, self.fmap, rule=self.rule, query_descriptors=self.query_descriptors,
-                                            outputs=self.outputs, _static=(self.ranks, self.query_groups))
+                                            outputs=self.outputs, _static=(self.ranks, self.query_groups), **kw)
         rows = None
         if self.pose is not None:
             # (a weighted rule: the variances this forward has just left -- in the capture, the step's static spread.rel_var)
@@ -246,10 +266,12 @@ class GraphedForwardMap:
         from . import _lib as L
         m, f = self.model, self.fmap
         return {"library": L.lib(), "encoder": m._enc._packed, "gnn": m._gnn_packed, "gnn_bf16": m._gnn_bf16,
-                "dtypes": (m.encoder_dtype, m.gnn_dtype), "workspaces": list(m._ws_pool._buf.values()),
+                "dtypes": (m.encoder_dtype, m.gnn_dtype, bool(getattr(m, "static_knn", False))), "workspaces": list(m._ws_pool._buf.values()),
                 "fc_graph": m._map_graphs.get((self.g, self.k + 1, str(self.queries.device))),
                 "query_sel": (m._map_queries.get((self.g, self.k + 1, str(self.queries.device)))
                               if self.outputs == "query" else None),
+                "knn_sel": (m._map_queries.get(("knn", self.g, self.k + 1, self.kp, str(self.queries.device)))
+                            if self.outputs == "query" and self.kp else None),
                 "mc_state": None if getattr(m, "mc_dropout", None) is None else m.mc_dropout._state,
                 "counters": m._counters.counters, "pose_counters": None if self.pose is None else self.pose._bad.counters,
                 "features": f.features, "poses": f.poses, "descriptors": f.descriptors, "groups": f.groups,

@@ -459,6 +459,47 @@ def knn_graph(x: torch.Tensor, k: int, batch: Optional[torch.Tensor] = None) -> 
     return ei[:, :total].contiguous()
 
 
+def _edge_rows(out, cols: int, dev, what: str):
+    """``out`` of knn_graph_uniform: None (allocated, [2, cols]), an int64 [2, cols] tensor, or a pair of int64 [cols] tensors
+    (two row slices of a larger list) -- every row contiguous, on ``dev``.  -> (what to return, source row, target row)."""
+    if out is None:
+        out = torch.empty((2, cols), dtype=torch.int64, device=dev)
+    if len(out) != 2:
+        raise ValueError(f"{what} must be an int64 [2, {cols}] tensor or a pair of int64 [{cols}] tensors")
+    for row in (out[0], out[1]):
+        if (not torch.is_tensor(row) or row.dtype != torch.int64 or row.device != dev or tuple(row.shape) != (cols,)
+                or not row.is_contiguous()):
+            raise ValueError(f"{what} must be an int64 [2, {cols}] tensor or a pair of int64 [{cols}] tensors, rows contiguous, on "
+                             f"the inputs' GPU")
+    return out, out[0], out[1]
+
+
+def knn_graph_uniform(x: torch.Tensor, g: int, n_per: int, k: int, node_offset: int = 0, out=None, q_out=None,
+                      irregular: Optional[torch.Tensor] = None):
+    """knn_graph over ``g`` graphs of ``n_per`` nodes each (x [g * n_per, d]) with every column at a fixed position
+    (rpg_knn_graph_uniform_f32): k' = min(k, n_per - 1), column v k' + t = (t-th nearest other node of v, v), both plus
+    ``node_offset`` -- knn_graph's neighbours in knn_graph's order, but nothing for the host to wait for.  ``out``: where the list
+    goes (int64 [2, g n_per k'] or a pair of rows; allocated if None); ``q_out``: likewise [2, g k'] for the columns into node 0 of
+    every graph, ``True`` allocates them, None leaves them out; ``irregular``: int32 counter, += the nodes whose reference
+    in-degree is k' + 1 (their list here is its first k' entries; see the header), a zeroed one of this call's own if None.
+    -> (out, q_out or None, irregular); nothing synchronises."""
+    x = _req(x, "x")
+    g, n_per, k = int(g), int(n_per), int(k)
+    if x.dim() != 2 or g < 1 or n_per < 2 or k < 1 or x.shape[0] != g * n_per:
+        raise ValueError(f"knn_graph_uniform: x must be [g * n_per, d] with g >= 1 graphs of n_per >= 2 nodes and k >= 1, got "
+                         f"{tuple(x.shape)} for g = {g}, n_per = {n_per}, k = {k}")
+    kp = min(k, n_per - 1)
+    dev = x.device
+    out, src, dst = _edge_rows(out, g * n_per * kp, dev, "knn_graph_uniform: out")
+    q_src = q_dst = None
+    if q_out is not None:
+        q_out, q_src, q_dst = _edge_rows(None if q_out is True else q_out, g * kp, dev, "knn_graph_uniform: q_out")
+    irregular, _ = _status_arg(irregular, dev, "knn_graph_uniform")
+    L.check(L.lib().rpg_knn_graph_uniform_f32(_p(x), g, n_per, x.shape[1], k, int(node_offset), _p(src), _p(dst), _p(q_src),
+                                              _p(q_dst), _p(irregular), _stream()), "knn_graph_uniform")
+    return out, q_out, irregular
+
+
 def edge_concat_gather(x: torch.Tensor, edge_index: torch.Tensor) -> torch.Tensor:
     x, ei = _req(x, "x"), _req(edge_index, "edge_index", torch.int64)
     e, d = ei.shape[1], x.shape[1]

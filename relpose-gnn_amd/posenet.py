@@ -74,10 +74,30 @@ class simpleConvEdge_upt(nn.Module):  # noqa: N801 - reference spelling (my_gnn_
         self.att = AttentionBlock(in_channels)
 
 
-def _bad_index_error(counts: torch.Tensor) -> IndexError:
-    """``counts``: host int32 [16], the bad-edge counters (slots 0..7) and forward_map's bad-neighbour counters (8..15)."""
-    edges, nbrs = int(counts[:8].sum()), int(counts[8:].sum())
+# forward_map with static_knn and the bf16 GNN is cut into stream slots only when every slot gets at least this many graphs.
+# Measured (profiles/knn_map_bench.json, "schedule"; K = 7, D = 2048): at 32 graphs of 224 x 224 two slots of 16 run at 0.95x of
+# one stream -- the fully-connected bf16 step shows the same 0.95x there, so it is the schedule, not the kNN build -- at 64 graphs
+# two slots of 32 are 1.01x of one stream, at 256 graphs 1.05-1.10x of the general one-stream path.
+_STATIC_BF16_SLOT_GRAPHS = 32
+
+
+class IrregularKnnGraph(ValueError):
+    """``static_knn``: a graph of the map step has a node whose reference kNN list keeps one edge more than the fixed layout holds
+    (k + 1 or more lower-numbered nodes of its graph with a bit-identical feature row, or non-finite rows)."""
+
+
+def _bad_index_error(counts: torch.Tensor) -> Exception:
+    """``counts``: host int32 [24], the bad-edge counters (slots 0..7), forward_map's bad-neighbour counters (8..15) and the
+    ``static_knn`` map step's irregular-node counters (16..23)."""
+    edges, nbrs, irregular = int(counts[:8].sum()), int(counts[8:16].sum()), int(counts[16:].sum())
+    if irregular and not edges and not nbrs:
+        return IrregularKnnGraph(f"forward_map with static_knn: {irregular} node(s) whose reference kNN list has k + 1 edges (duplicate "
+                                 "or non-finite feature rows), so the edge list returned for that call is not the reference's: set "
+                                 "model.static_knn = False for such inputs (the waiting path reproduces the extra edges) "
+                                 "(detected on the device; with index_check='deferred' this refers to an EARLIER forward_map call)")
     what = []
+    if irregular:
+        what.append(f"static_knn: {irregular} node(s) whose reference kNN list has k + 1 edges (set model.static_knn = False)")
     if edges:
         what.append(f"edge_index has {edges} edge(s) with a node id outside its graph group / [0, N)")
     if nbrs:
@@ -156,14 +176,20 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
         self._gnn_dtype = "f32"
         self._extra: Dict[str, torch.Tensor] = {}
         self.index_check = "deferred"            # "deferred" | "sync" (see the module docstring)
-        # device int32 [16]: bad-edge counters, one per stream slot, then the map path's bad-neighbour counters, one per slot
-        self._counters = DeferredCounters(16, _bad_index_error)
+        # device int32 [24]: bad-edge counters, one per stream slot, then the map path's bad-neighbour counters, one per slot, then
+        # the static_knn map step's irregular-node counters, one per slot
+        self._counters = DeferredCounters(24, _bad_index_error)
         # optional frames.FrameTransform: with it forward() also takes uint8 frames data.x [n, H, W, 3] (RGB, HWC) on the GPU and
         # runs the reference's image transform there (a plain attribute: not a module, parameter or buffer -- state_dict unchanged)
         self.frame_transform = None
         # optional mc_dropout.McDropout: with it (and droprate > 0) every forward returns the MEAN of the heads over its dropout
         # samples in place of abs_pose / rel_pose and leaves their variances in mc_dropout.last (a plain attribute as well)
         self.mc_dropout = None
+        # with knn > 0: forward_map builds the kNN graph of its equal-sized graphs at fixed positions (rpg_knn_graph_uniform_f32):
+        # no edge count for the host to wait for, so the two-stream schedule, outputs="query" and the captured step serve the
+        # model; a graph whose reference list is irregular raises IrregularKnnGraph by the index_check contract (a plain
+        # attribute as well; False: every path and refusal as without it)
+        self.static_knn = False
         self._enc_digest: Optional[str] = None        # encoder_digest() cache (cleared wherever the packed weights are)
         self._map_graphs: Dict[tuple, Tuple[torch.Tensor, torch.Tensor]] = {}   # forward_map: (G, K+1, device) -> (edges, batch)
         # forward_map(outputs="query"): same key -> (selected columns [G K], query nodes [G], the selected edges [2, G K])
@@ -194,7 +220,10 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
         """'f32' (default; the 1e-4 parity path) or 'bf16': the GNN's Linears on the bf16 matrix pipe (inputs rounded to
         bf16 per Linear, fp32 accumulation / bias / residual / output; attention rows, scatter-mean and heads stay fp32).
         Meant to go with encoder_dtype = 'bf16' (BASELINE configs[2]/[4]); needs the default flags (use_AP, no
-        use_attention, knn <= 0) and D % 64 == 0."""
+        use_attention, knn <= 0) and D % 64 == 0.  With knn > 0 it runs on one stream, except in ``forward_map`` with
+        ``static_knn``, which serves it per stream slot (the bf16 forward takes any edge list, and that step's poses are held
+        to the one-stream path's in tests/test_hip_knn_map.py; why the waiting kNN build was kept off the slots with the bf16
+        GNN is not recorded, so that path stays as it is)."""
         return self._gnn_dtype
 
     @gnn_dtype.setter
@@ -458,10 +487,18 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
         feat = self._encode_small(x)                                              # posenet.py:1037
         return self._forward_tail(lib, feat, edge_index, getattr(data, "batch", None), k)
 
-    def _forward_tail(self, lib, feat, edge_index, batch, k, query=None):
+    def _forward_tail(self, lib, feat, edge_index, batch, k, query=None, uniform=None):
         """Everything after the encoder on one stream (posenet.py:1040-1091): feat [N, d] are the node features.  ``query``: None,
-        or forward_map's (selected columns, query nodes, selected edges) -- the outputs then cover those rows only."""
+        or forward_map's (selected columns, query nodes, selected edges) -- the outputs then cover those rows only.  ``uniform``
+        (forward_map with static_knn): (graphs, nodes per graph, the caller's irregular counter or None) -- the kNN graph is built
+        at fixed positions, and ``query`` comes without its edges, which are made here."""
         n, d = feat.shape
+        if uniform is not None:
+            irr = uniform[2] if uniform[2] is not None else self._counters.counters[16:17]
+            edge_index, q_edges, _ = ops.knn_graph_uniform(feat, uniform[0], uniform[1], int(self.knn), 0,
+                                                           q_out=None if query is None else True, irregular=irr)
+            if query is not None:
+                query = (query[0], query[1], q_edges)
         if self.use_attention:                                                    # posenet.py:1040-1041
             ex = self._extra
             y = ops.attention_rows(ops.linear_gather([(feat, None)], ex["att_gtp_w"], ex["att_gtp_b"], n))
@@ -470,7 +507,7 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
         edge_index_knn = None                                                     # posenet.py:1043-1050
         if k is not None:
             edge_index_knn = ops.knn_graph(feat, int(k), batch)
-        if self.knn > 0:
+        if self.knn > 0 and uniform is None:
             edge_index = ops.knn_graph(feat, int(self.knn), batch)
         elif k is not None:
             edge_index = edge_index_knn
@@ -505,8 +542,8 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
             md.advance(dev)
         elif drop:
             node_f = self._drop_heads(node_f, edge_f, abs_pose, rel_pose)
-        if query is not None:                     # use_AP, no kNN graph: refused by forward_map otherwise
-            return abs_pose, rel_pose, query[2].clone()
+        if query is not None:                     # use_AP, no general kNN graph: refused by forward_map otherwise
+            return abs_pose, rel_pose, (query[2] if uniform is not None else query[2].clone())
         if not self.use_AP:                                                       # posenet.py:1080-1083
             # index plumbing (compute_edge_features).  Clamped like the GNN's own copy of the end points (rpg_graph_prepare):
             # with index_check="deferred" an out-of-range node id is REPORTED by the device-side counter (IndexError at the
@@ -575,6 +612,28 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
             self._map_queries[key] = hit
         return hit
 
+    def _static_columns(self, k, kk: int) -> int:
+        """k' = min(knn, K), the incoming edges of every node of a K + 1-node graph, if ``forward_map`` builds its kNN graph at
+        fixed positions (``static_knn``, on the flags the multi-stream schedule serves); 0 otherwise."""
+        if self.static_knn and self.knn > 0 and k is None and self.use_AP and not self.use_attention:
+            return min(int(self.knn), int(kk))
+        return 0
+
+    def _map_query_knn(self, g: int, n_per: int, kp: int, dev) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(sel int64 [G k'], qnodes int64 [G]) of the fixed-position kNN list of G graphs of ``n_per`` nodes on ``dev``: node v's
+        columns are v k' + [0, k'), so query g's (node g n_per) are g n_per k' + [0, k') whatever the features are.  As for
+        ``_map_query`` the first j k' entries of ``sel`` are the selection of any j consecutive graphs."""
+        key = ("knn", g, n_per, kp, str(dev))
+        hit = self._map_queries.get(key)
+        if hit is None:
+            qn = torch.arange(g, dtype=torch.int64) * n_per
+            sel = ((qn * kp)[:, None] + torch.arange(kp, dtype=torch.int64)[None, :]).reshape(-1)
+            hit = (sel.to(dev), qn.to(dev))
+            if len(self._map_queries) >= 16:
+                self._map_queries.clear()
+            self._map_queries[key] = hit
+        return hit
+
     def _check_outputs(self, outputs, k) -> None:
         """``forward_map``'s ``outputs``: an unknown value and what the query-only mode does not serve raise here, before anything
         is queued."""
@@ -583,7 +642,7 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
         if outputs == "all":
             return
         why = "the selected columns would depend on the features"
-        if self.knn > 0:
+        if self.knn > 0 and not self.static_knn:
             raise NotImplementedError(f"forward_map(outputs='query') does not serve knn > 0 (a model-built kNN graph: {why})")
         if k is not None:
             raise NotImplementedError(f"forward_map(outputs='query') does not serve an explicit k (a kNN graph: {why})")
@@ -596,7 +655,8 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
 
     @torch.no_grad()
     def forward_map(self, queries: torch.Tensor, neighbours: Optional[torch.Tensor], fmap, k=None, *, rule=None,
-                    query_descriptors: Optional[torch.Tensor] = None, query_groups=None, outputs: str = "all", _static=None):
+                    query_descriptors: Optional[torch.Tensor] = None, query_groups=None, outputs: str = "all", _static=None,
+                    _irregular: Optional[torch.Tensor] = None):
         """The forward of G graphs, each query g followed by the K database images ``neighbours[g]`` of the feature map ``fmap``
         (dataset_7Scenes_multi.py:340-345) -- with only the G queries through the encoder.  Returns what
         ``forward(fc_batch(assembled, K + 1), k)`` returns for the assembled images: (abs_pose [G*(K+1), 6], rel_pose [E, 6],
@@ -621,18 +681,34 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
         same workspace pool.  ``droprate > 0`` is served as for ``"all"``, but ``F.dropout`` is drawn over [G, D] and [G*K, D], so a
         seeded run draws OTHER masks than the full forward does -- unless ``model.mc_dropout`` is set: its masks follow the node
         ids (a query row's id is its node's, an edge row's the pair of its end points), so both modes draw the same ones.
-        ``knn > 0``, an explicit ``k``, ``use_attention`` and ``use_AP=False`` raise NotImplementedError (the selection would depend on the data, or the path allocates between its
-        launches); an unknown value raises ValueError.
+        ``knn > 0`` without ``static_knn``, an explicit ``k``, ``use_attention`` and ``use_AP=False`` raise NotImplementedError (the
+        selected columns of a general kNN list depend on the features, or the path allocates between its launches); an unknown
+        value raises ValueError.
+
+        ``model.static_knn = True`` with ``knn > 0`` (no explicit ``k``, ``use_AP``, no ``use_attention``; otherwise it is ignored):
+        all graphs of this call have K + 1 nodes, so every node has exactly k' = min(knn, K) incoming edges, the list has G (K + 1)
+        k' columns, node v's are v k' + [0, k') and only the SOURCE ids depend on the features.  The graph is then built at those
+        positions on the device (``rpg_knn_graph_uniform_f32``: the general kernel's neighbours in its order) with nothing for the
+        host to wait for: the multi-stream schedule runs without an event per slot, the bf16 GNN is served on it (from 32 graphs per
+        slot on; below, one stream, as on the general path, measured faster), and
+        ``outputs="query"`` is accepted -- abs_pose [G, 6], rel_pose [G k', 6], edge_index [2, G k'], the columns g (K + 1) k' + [0, k')
+        of the full list.  The one exception: a node whose self match is not among its knn + 1 nearest by (distance, index) -- knn + 1
+        or more lower-numbered nodes of its graph with a bit-identical feature row (the same map row named again and again), or
+        non-finite rows; only with K > knn -- keeps k' + 1 edges in the reference.  Such a call is reported by the ``index_check``
+        contract as ``IrregularKnnGraph`` (a ValueError: at the call under ``"sync"``, at the next look under ``"deferred"``); its
+        outputs are a valid graph's, not the reference's, and ``static_knn = False`` reproduces the reference's.
 
         ``_static`` (graphed.GraphedForwardMap only): ``(ranks int32 [G, K], query groups int64 [G] or None)`` already on the
-        device, read in place of the two per-call host products above, so that nothing of the call depends on host data."""
+        device, read in place of the two per-call host products above, so that nothing of the call depends on host data.
+        ``_irregular`` (relocalize, GraphedForwardMap): an int32 [1] device counter of the caller's that the irregular nodes are
+        added to INSTEAD of the model's own counters -- the caller looks at it and nothing raises."""
         self._check_outputs(outputs, k)
         if neighbours is not None and rule is not None:
             raise ValueError("forward_map: give neighbours or a retrieval rule, not both")
         if rule is None and (query_descriptors is not None or query_groups is not None):
             raise ValueError("forward_map: query_descriptors / query_groups belong to retrieval: pass a rule (and neighbours=None)")
         if rule is not None:
-            return self._forward_map_retrieve(queries, fmap, k, rule, query_descriptors, query_groups, _static, outputs)
+            return self._forward_map_retrieve(queries, fmap, k, rule, query_descriptors, query_groups, _static, outputs, _irregular)
         if not torch.is_tensor(queries) or not torch.is_tensor(neighbours):
             raise TypeError("forward_map: queries and neighbours must be tensors")
         if neighbours.dtype != torch.int64 or neighbours.dim() != 2:
@@ -645,7 +721,7 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
             raise ValueError(f"forward_map: {queries.size(0)} queries but neighbours has {g} rows")
         self._map_devices(queries, fmap, "neighbours", neighbours)
         nb = neighbours.contiguous()
-        return self._forward_map_run(queries, fmap, k, g, kk, lambda qf, g0, g1, st, wkey: nb[g0:g1], outputs)
+        return self._forward_map_run(queries, fmap, k, g, kk, lambda qf, g0, g1, st, wkey: nb[g0:g1], outputs, _irregular)
 
     @staticmethod
     def _map_devices(queries, fmap, name: str, t: Optional[torch.Tensor]) -> None:
@@ -657,7 +733,8 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
             raise RuntimeError(f"forward_map: queries ({queries.device}), {name}{where} and the feature map ({fmap.device}) "
                                f"must be on the same GPU")
 
-    def _forward_map_retrieve(self, queries, fmap, k, rule, query_descriptors, query_groups, static=None, outputs="all"):
+    def _forward_map_retrieve(self, queries, fmap, k, rule, query_descriptors, query_groups, static=None, outputs="all",
+                              irregular=None):
         """``forward_map`` with the neighbours retrieved per stream slot from that slot's query features (or descriptors).
         ``static``: see ``forward_map``'s ``_static``."""
         if not torch.is_tensor(queries):
@@ -696,38 +773,52 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
             return ops.retrieve(qf if qd is None else qd[g0:g1], db, ranks[g0:g1], db_inv_norm=inv,
                                 q_group=None if qg_dev is None else qg_dev[g0:g1], db_group=db_groups, status=st, workspace=ws,
                                 out=nb_out[g0:g1])
-        return (*self._forward_map_run(queries, fmap, k, g, kk, neighbours_of, outputs), nb_out)
+        return (*self._forward_map_run(queries, fmap, k, g, kk, neighbours_of, outputs, irregular), nb_out)
 
-    def _forward_map_run(self, queries, fmap, k, g, kk, neighbours_of, outputs="all"):
+    def _forward_map_run(self, queries, fmap, k, g, kk, neighbours_of, outputs="all", irregular=None):
         """``neighbours_of(qf, g0, g1, status, wkey)``: the map rows int64 [g1 - g0, K] of queries g0..g1, whose encoder features
-        are ``qf``, made on the current (slot) stream."""
+        are ``qf``, made on the current (slot) stream.  ``irregular``: ``forward_map``'s ``_irregular``."""
         fmap.check(self)
         self._mc()
         x, lib, status = self._prepare(queries, "queries")
         dev = x.device
         n_per = kk + 1
-        edge_index, batch = self._map_graph(g, n_per, dev)
-        query = self._map_query(g, n_per, dev) if outputs == "query" else None
-        if query is None:
-            edge_index = edge_index.clone()       # the caller's to keep (the cached copy serves the next call)
+        kp = self._static_columns(k, kk)          # > 0: the kNN graph at fixed positions (static_knn)
+        uniform = None
+        if kp:
+            edge_index, batch = None, None        # built per slot, on the device
+            query = self._map_query_knn(g, n_per, kp, dev) if outputs == "query" else None
+            uniform = (g, n_per, irregular)
+        else:
+            edge_index, batch = self._map_graph(g, n_per, dev)
+            query = self._map_query(g, n_per, dev) if outputs == "query" else None
+            if query is None:
+                edge_index = edge_index.clone()   # the caller's to keep (the cached copy serves the next call)
         enc_sd = self.feature_extractor.state_dict
 
         parts = None
-        if self._fast(k):
+        if kp or self._fast(k):
             from .graph import Data
             spec = Data()
             spec.graph_sizes = ([n_per] * g, [n_per * kk] * g)
             parts = self._partition(spec, g * n_per, edge_index.size(1) if self.knn <= 0 else None)
+            # static_knn with the bf16 GNN: the general path it stands in for runs on ONE stream, and stream slots of fewer than
+            # _STATIC_BF16_SLOT_GRAPHS graphs measured slower than that (see the constant).  Below it the step keeps the general
+            # path's schedule -- the same launches without the wait -- unless the caller set a schedule of their own.
+            if (kp and self._gnn_dtype == "bf16" and parts is not None and not self.stream_schedule
+                    and g < _STATIC_BF16_SLOT_GRAPHS * len(parts)):
+                parts = None
         if parts is not None:
             def features(n0, n1, wkey):           # the slot's queries through the encoder, then its graphs' nodes
                 g0, g1 = n0 // n_per, n1 // n_per
                 qf = self._enc.run(enc_sd, "", x[g0:g1], slot=wkey)
                 st = status[8 + wkey[0]:9 + wkey[0]]
                 return ops.gather_graph_nodes(qf, fmap.features, neighbours_of(qf, g0, g1, st, wkey), status=st)
-            return self._forward_streams(lib, features, g * n_per, dev, edge_index, parts, batch, query=query, per_graph=(n_per, kk))
+            return self._forward_streams(lib, features, g * n_per, dev, edge_index, parts, batch, query=query,
+                                         per_graph=(n_per, kp or kk), uniform=uniform)
         qf = self._encode_small(x)
         feat = ops.gather_graph_nodes(qf, fmap.features, neighbours_of(qf, 0, g, status[8:9], (-1, 0)), status=status[8:9])
-        return self._forward_tail(lib, feat, edge_index, batch, k, query)
+        return self._forward_tail(lib, feat, edge_index, batch, k, query, uniform)
 
     def _encoder_input(self, x: torch.Tensor, what: str) -> torch.Tensor:
         """Images as the encoder takes them: uint8 frames through ``frame_transform``, dtype checked, viewed as [n, 3, H, W]."""
@@ -793,7 +884,7 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
         for st in streams:
             cur.wait_stream(st)
 
-    def _forward_streams(self, lib, features, n_total, dev, edge_index, parts, batch=None, query=None, per_graph=None):
+    def _forward_streams(self, lib, features, n_total, dev, edge_index, parts, batch=None, query=None, per_graph=None, uniform=None):
         """use_AP / no extra attention / no explicit k, on ``len(parts)`` concurrent streams.  ``features(n0, n1, wkey)`` makes the
         node features [n1 - n0, d] of nodes n0..n1 on the current (slot) stream: the encoder over those images for ``forward``,
         the queries' encoder + node assembly from a feature map for ``forward_map``.  With ``knn > 0`` (the reference's
@@ -803,7 +894,9 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
         busy meanwhile -- before it enqueues the slot's GNN.  With ``droprate > 0`` the always-on dropout and the heads
         (posenet.py:1073-1086) run per slot on the slot's stream.  ``query`` (forward_map's query-only mode; ``per_graph`` =
         (nodes, selected columns) of every graph): the outputs cover the query nodes and the selected columns, and every slot
-        computes the rows of its own graphs."""
+        computes the rows of its own graphs.  ``uniform`` (forward_map with static_knn; ``per_graph`` = (nodes, k') then): see
+        ``_forward_tail`` -- every slot builds its kNN graph at fixed positions (ops.knn_graph_uniform) straight into its column
+        range of the outputs, and its GNN is enqueued behind it with the edge count known: no pinned copy, no event, no wait."""
         knn = int(self.knn) if self.knn > 0 else 0
         drop = self.droprate > 0
         abs_pose = torch.empty((n_total if query is None else query[1].numel(), 6), dtype=torch.float32, device=dev)
@@ -873,6 +966,42 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
                 md.advance(dev)
             self.publish_status()
             return abs_pose, rel_pose, (edge_index if query is None else query[2].clone())
+
+        if uniform is not None:
+            # ---- knn > 0 at fixed positions (static_knn): every graph has n_per nodes, so slot and column ranges are known here
+            n_per, kp = per_graph
+            e_per = n_per * kp
+            g_total = n_total // n_per
+            edge_index = torch.empty((2, g_total * e_per), dtype=torch.int64, device=dev)
+            q_edges = None if query is None else torch.empty((2, g_total * kp), dtype=torch.int64, device=dev)
+            ends = edge_index if query is None else q_edges
+            rel_pose = torch.empty((ends.size(1), 6), dtype=torch.float32, device=dev)
+            rel_var = None if md is None else torch.empty_like(rel_pose)
+            for gi, (n0, n1, _, _, slot) in enumerate(parts):
+                st = streams[slot]
+                with torch.cuda.stream(st):
+                    wkey = (slot, gi)
+                    feat = features(n0, n1, wkey)
+                    g0, g1 = n0 // n_per, n1 // n_per
+                    e0, e1 = g0 * e_per, g1 * e_per
+                    src, dst = edge_index[0, e0:e1], edge_index[1, e0:e1]
+                    q_slot, c0, c1 = None, e0, e1
+                    if query is not None:
+                        c0, c1 = g0 * kp, g1 * kp
+                        q_slot = (g0, query[0][:c1 - c0], query[1][g0:g1])
+                    ops.knn_graph_uniform(feat, g1 - g0, n_per, knn, n0, out=(src, dst),
+                                          q_out=None if query is None else (q_edges[0, c0:c1], q_edges[1, c0:c1]),
+                                          irregular=uniform[2] if uniform[2] is not None else status[16 + slot:17 + slot])
+                    # the rows' end points, ids of the whole batch, read from the device list the kernel has just written
+                    mc_edges = None if md is None else (ends[0, c0:c1], ends[1, c0:c1], 0, rel_var[c0:c1])
+                    heads(feat, n0, n1, (src.data_ptr(), dst.data_ptr()), n0, e1 - e0, rel_pose[c0:c1], slot, wkey, q_slot, mc_edges)
+                    feat.record_stream(st)
+            self._join(cur, streams)
+            if md is not None:
+                md.last = McSpread(abs_var, rel_var)
+                md.advance(dev)
+            self.publish_status()
+            return abs_pose, rel_pose, ends
 
         # ---- knn > 0: phase 1 = encoder + kNN build per slot (no host wait), phase 2 = GNN per slot once its edge count is in
         pend = []
