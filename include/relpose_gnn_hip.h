@@ -214,6 +214,34 @@ int rpg_retrieve_cosine_f32(const float* q, const float* db, const float* db_inv
                             const int64_t* db_group, const int32_t* ranks, int g, int k, int64_t m, int d,
                             int64_t* neighbours, float* sims, void* workspace, size_t workspace_bytes, int32_t* status,
                             void* stream);
+/* rpg_retrieve_cosine_f32 with a pose gate: retrieval restricted to the map rows near a prior pose (no counterpart in the
+ * reference, whose obtain_KNNs, dataset_7Scenes_multi.py:238-264, ranks the whole split; the quaternion test is the angular
+ * error of pose_utils.py:420-431, 2 acos |<p, q>| <= max_deg, stated on the cosine).  db_gate float64 [m][7] and prior float64
+ * [g][7] hold (t[3], q[4] = w x y z): the un-normalised translation and the unit quaternion, the first seven columns of the
+ * rows of rpg_query_pose_*_f64.  For query g:
+ *   a non-finite prior component: ranked as by rpg_retrieve_cosine_f32, gate_info[g] = (1, 0)
+ *   row r is inside when all 7 of db_gate[r] are finite, ((dx dx + dy dy) + dz dz) <= r2 and, with rot_gate != 0,
+ *     fabs(((w1 w2 + x1 x2) + y1 y2) + z1 z2) >= cos_half -- in double, every product and sum rounded on its own
+ *   rows_inside = the rows inside that the group filter allows; need = the largest of ranks[g] + 1
+ *   rows_inside >= need: the rows outside are excluded like rows of the query's group, gate_info[g] = (0, rows_inside)
+ *   otherwise: ranked by the group filter alone, gate_info[g] = (2, rows_inside)
+ * status counts bad ranks against the rows actually ranked.  db_gate, prior and gate_info (int32 [g][2]) are given together
+ * or all NULL (then this IS rpg_retrieve_cosine_f32: same launches, same bits); r2 >= 0, cos_half a number (RPG_ERR_BAD_ARG
+ * otherwise).  One more sweep over m per gated query inside the selection launch; no further launch, workspace as before. */
+int rpg_retrieve_cosine_gated_f32(const float* q, const float* db, const float* db_inv_norm, const int64_t* q_group,
+                                  const int64_t* db_group, const int32_t* ranks, int g, int k, int64_t m, int d,
+                                  const double* db_gate, const double* prior, double r2, double cos_half, int rot_gate,
+                                  int32_t* gate_info, int64_t* neighbours, float* sims, void* workspace, size_t workspace_bytes,
+                                  int32_t* status, void* stream);
+/* The update launch of a tracking loop (no counterpart in the reference, which relocalises every frame on its own,
+ * testing/test.py:192-267): for each of s cameras, from this frame's pose-rule row rows [s][16] (its first seven doubles the
+ * predicted (t, q)) and the consensus integers inliers int32 [s][2] = (inliers, used) of rpg_query_pose_consensus_f64:
+ *   accepted when the 7 doubles are finite, inliers >= min_inliers and (double)inliers >= min_ratio * (double)used:
+ *     prior[i] = rows[i][0:7], lost[i] = 0, accepted[i] = 1
+ *   otherwise accepted[i] = 0, lost[i] += 1 (saturating at INT32_MAX), and once lost[i] > max_lost prior[i] = NaN (7 of them)
+ * prior float64 [s][7], lost / accepted int32 [s].  One launch, one thread per camera; graph-capturable.               */
+int rpg_track_update_f64(const double* rows, const int32_t* inliers, int s, int min_inliers, double min_ratio, int max_lost,
+                         double* prior, int32_t* lost, int32_t* accepted, void* stream);
 
 /* Pose recovery of an evaluation stream: per graph of ONE forward's output the query's pose and its errors, what eval_RP does
  * on the host with the model outputs (testing/test.py:213-267; pose_utils.py:340-348 qexp, :420-431 the angular error).  In

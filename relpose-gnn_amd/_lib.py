@@ -34,7 +34,7 @@ SYMBOLS = (
     "rpg_query_pose_f64", "rpg_query_pose_fused_f64", "rpg_gather_add2_relu_f32",
     "rpg_gnn_query_workspace_bytes", "rpg_gnn_forward_query_f32", "rpg_gnn_forward_query_bf16", "rpg_gemm_last_route", "rpg_get_tuning",
     "rpg_attention_aggregate_hidden_f32", "rpg_query_pose_consensus_f64", "rpg_pose_heads_mc_f32", "rpg_mc_advance",
-    "rpg_query_pose_weighted_f64", "rpg_knn_graph_uniform_f32",
+    "rpg_query_pose_weighted_f64", "rpg_knn_graph_uniform_f32", "rpg_retrieve_cosine_gated_f32", "rpg_track_update_f64",
 )
 
 
@@ -132,6 +132,9 @@ def _declare(lib: C.CDLL) -> None:
     lib.rpg_retrieve_max_rank.argtypes = []
     lib.rpg_row_inv_norms_f32.argtypes = [_vp, C.c_int64, _i, _vp, _vp]
     lib.rpg_retrieve_cosine_f32.argtypes = [_vp] * 6 + [_i, _i, C.c_int64, _i, _vp, _vp, _vp, _sz, _vp, _vp]
+    lib.rpg_retrieve_cosine_gated_f32.argtypes = ([_vp] * 6 + [_i, _i, C.c_int64, _i, _vp, _vp, C.c_double, C.c_double, _i, _vp,
+                                                  _vp, _vp, _vp, _sz, _vp, _vp])
+    lib.rpg_track_update_f64.argtypes = [_vp, _vp, _i, _i, C.c_double, _i, _vp, _vp, _vp, _vp]
     # the pose rules' four entry points: rel_pose .. query_targets and the six pose_m / pose_s doubles, then each rule's own
     qp = [_vp, _vp, _vp, C.c_int64, _vp, _vp, _i, _vp, C.c_int64, _vp, C.c_int64, _vp, _i, _vp] + [C.c_double] * 6
     lib.rpg_query_pose_f64.argtypes = qp + [_i, _vp, _vp, _vp]

@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.join(HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "librelpose_gnn_hip.so")
-SOURCES = ("gemm_f32.hip", "winograd.hip", "stem.hip", "stem_bf16.hip", "conv_bf16.hip", "encoder_ops.hip", "gnn_ops.hip", "forward.hip", "timing.hip", "host_ops.hip", "frames.hip", "graph_nodes.hip", "retrieve.hip", "query_pose.hip", "query_select.hip", "mc_heads.hip")
+SOURCES = ("gemm_f32.hip", "winograd.hip", "stem.hip", "stem_bf16.hip", "conv_bf16.hip", "encoder_ops.hip", "gnn_ops.hip", "forward.hip", "timing.hip", "host_ops.hip", "frames.hip", "graph_nodes.hip", "retrieve.hip", "query_pose.hip", "query_select.hip", "mc_heads.hip", "track.hip")
 ARCH = "gfx950"
 # What a PMC profile of the dominant (Winograd) kernel is stamped with: its translation unit + the one header whose DEVICE code it
 # inlines (rpg_coherent.h: agent-scope slab accesses, arrival ticket; split out of rpg_common.h in round 5).  rpg_common.h

@@ -17,7 +17,13 @@
 //                               (R = largest rank + 1 <= R_MAX), the R pairs collected and sorted in LDS, ranks read off.
 // The LDS atomics of (3) count integers (histogram bins, list slots whose order the sort erases): the result does not depend on
 // their arrival order.  No floating-point atomics anywhere.
+//
+// The pose gate (rpg_retrieve_cosine_gated_f32; pose_gate.h) is a second instantiation of (3): with a finite prior pose, query g's
+// select workgroup first counts the allowed rows inside the gate -- one more sweep over m, ahead of the key-writing pass -- and,
+// when they cover its largest rank, gives the rows outside the key of an excluded row.  Null gate pointers launch the
+// instantiation without any of it.
 #include "rpg_common.h"
+#include "pose_gate.h"
 
 #include <float.h>
 
@@ -152,13 +158,33 @@ __device__ __forceinline__ float key_sim(uint32_t key) {
     return __uint_as_float((asc & 0x80000000u) ? (asc & 0x7FFFFFFFu) : ~asc);
 }
 
+// ---- the pose gate of the selection ---------------------------------------------------------------------------------------------
+struct GateOn {
+    const double* db_gate;     // [m][7]
+    const double* prior;       // [g][7]
+    double r2, cos_half;
+    int rot;
+    int32_t* info;             // [g][2]
+};
+struct GateOff {};
+template <bool GATED>
+struct GateArgs { typedef GateOff type; };
+template <>
+struct GateArgs<true> { typedef GateOn type; };
+
+constexpr int GATE_ROW = 7;                               // doubles per gate row
+constexpr int GATE_UNROLL = 4;                            // rows a thread has in flight in a sweep over the gate rows
+
+// GATED = false is the kernel as it was before the gate existed (an empty struct more in its arguments): rpg_retrieve_cosine_f32
+// and the new entry point with null gate pointers launch that one.
+template <bool GATED>
 __global__ __launch_bounds__(RS_NT) void retrieve_select_kernel(float* __restrict__ part, int nsplit,
                                                                 const float* __restrict__ q_inv, const float* __restrict__ db_inv,
                                                                 const int64_t* __restrict__ q_group,
                                                                 const int64_t* __restrict__ db_group,
                                                                 const int32_t* __restrict__ ranks, int g, int k, int64_t m,
                                                                 int64_t* __restrict__ nbrs, float* __restrict__ sims,
-                                                                int32_t* __restrict__ status) {
+                                                                int32_t* __restrict__ status, const typename GateArgs<GATED>::type ga) {
     __shared__ unsigned hist[256];
     __shared__ unsigned long long list[R_MAX];
     __shared__ int s_rank[K_MAX];
@@ -174,16 +200,79 @@ __global__ __launch_bounds__(RS_NT) void retrieve_select_kernel(float* __restric
         s_cnt = 0;
     }
     __syncthreads();
-    {
-        const float qi = q_inv[gi];
-        const int64_t qg = q_group ? q_group[gi] : -1;
+    const int64_t qg = q_group ? q_group[gi] : -1;
+    const float qi = q_inv[gi];
+    // similarity -> key of row mm, or KEY_EXCLUDED for a row the query does not rank; -> whether it is ranked
+    auto write_key = [&](int64_t mm, bool allowed) {
+        float dot = part[(int64_t)gi * m + mm];
+        for (int s = 1; s < nsplit; ++s) dot += part[((int64_t)s * g + gi) * m + mm];          // slice order
+        const float sim = dot * qi * db_inv[mm];
+        keys[mm] = allowed ? sim_key(sim) : KEY_EXCLUDED;
+    };
+    bool gated = false;
+    if constexpr (GATED) {
+        // state 1 = no prior (a non-finite component), 0 = gated, 2 = fewer allowed rows inside than the largest rank needs: ranked
+        // by the groups alone.  Every branch here is uniform over the workgroup.
+        __shared__ unsigned s_inside;
+        double p[GATE_ROW];
+        for (int i = 0; i < GATE_ROW; ++i) p[i] = ga.prior[(int64_t)gi * GATE_ROW + i];
+        // One sweep over the gate rows: body(mm, inside) for this thread's rows mm = tid, tid + RS_NT, ... (the rows whose keys it
+        // owns).  The map's 56 bytes per row come from beyond the L2 and one workgroup has little else to hide that latency with,
+        // so a thread loads GATE_UNROLL rows before it judges the first (a row past the end reads row `base` again, unused).
+        auto sweep = [&](auto&& body) {
+            for (int64_t base = tid; base < m; base += (int64_t)GATE_UNROLL * RS_NT) {
+                double r[GATE_UNROLL][GATE_ROW];
+#pragma unroll
+                for (int u = 0; u < GATE_UNROLL; ++u) {
+                    const int64_t mm = base + (int64_t)u * RS_NT;
+                    const double* src = ga.db_gate + (mm < m ? mm : base) * GATE_ROW;
+#pragma unroll
+                    for (int c = 0; c < GATE_ROW; ++c) r[u][c] = src[c];
+                }
+#pragma unroll
+                for (int u = 0; u < GATE_UNROLL; ++u) {
+                    const int64_t mm = base + (int64_t)u * RS_NT;
+                    if (mm < m) body(mm, rpg::pose_gate_inside(r[u], p, ga.r2, ga.cos_half, ga.rot != 0));
+                }
+            }
+        };
+        int state = 1;
+        unsigned inside = 0;
+        if (rpg::pose_gate_finite7(p)) {
+            if (tid == 0) s_inside = 0;
+            __syncthreads();
+            unsigned local = 0;
+            sweep([&](int64_t mm, bool in) { local += in && !(qg != -1 && db_group[mm] == qg); });
+            if (local) atomicAdd(&s_inside, local);
+            __syncthreads();
+            inside = s_inside;
+            int64_t need = (int64_t)ranks[(int64_t)gi * k] + 1;
+            for (int j = 1; j < k; ++j) {
+                const int64_t r = (int64_t)ranks[(int64_t)gi * k + j] + 1;
+                need = r > need ? r : need;
+            }
+            gated = (int64_t)inside >= need;
+            state = gated ? 0 : 2;
+        }
+        if (tid == 0) {
+            ga.info[2 * (int64_t)gi] = state;
+            ga.info[2 * (int64_t)gi + 1] = (int32_t)inside;
+        }
+        if (gated) {                                      // the key-writing pass of a gated query: the rows outside are excluded
+            unsigned local = 0;
+            sweep([&](int64_t mm, bool in) {
+                const bool allowed = in && !(qg != -1 && db_group[mm] == qg);
+                write_key(mm, allowed);
+                local += allowed;
+            });
+            if (local) atomicAdd(&s_allowed, local);
+        }
+    }
+    if (!gated) {
         unsigned local = 0;
         for (int64_t mm = tid; mm < m; mm += RS_NT) {
-            float dot = part[(int64_t)gi * m + mm];
-            for (int s = 1; s < nsplit; ++s) dot += part[((int64_t)s * g + gi) * m + mm];      // slice order
-            const float sim = dot * qi * db_inv[mm];
             const bool allowed = !(qg != -1 && db_group[mm] == qg);
-            keys[mm] = allowed ? sim_key(sim) : KEY_EXCLUDED;
+            write_key(mm, allowed);
             local += allowed;
         }
         if (local) atomicAdd(&s_allowed, local);
@@ -343,10 +432,11 @@ extern "C" int rpg_row_inv_norms_f32(const float* x, int64_t m, int d, float* in
     return launch_inv_norms(x, m, d, inv_norm, rpg::as_stream(stream));
 }
 
-extern "C" int rpg_retrieve_cosine_f32(const float* q, const float* db, const float* db_inv_norm, const int64_t* q_group,
-                                       const int64_t* db_group, const int32_t* ranks, int g, int k, int64_t m, int d,
-                                       int64_t* neighbours, float* sims, void* workspace, size_t workspace_bytes,
-                                       int32_t* status, void* stream) {
+extern "C" int rpg_retrieve_cosine_gated_f32(const float* q, const float* db, const float* db_inv_norm, const int64_t* q_group,
+                                             const int64_t* db_group, const int32_t* ranks, int g, int k, int64_t m, int d,
+                                             const double* db_gate, const double* prior, double r2, double cos_half, int rot_gate,
+                                             int32_t* gate_info, int64_t* neighbours, float* sims, void* workspace,
+                                             size_t workspace_bytes, int32_t* status, void* stream) {
     if (!q || !db || !ranks || !neighbours || !workspace || !status || g < 1 || k < 1 || k > K_MAX || m < k ||
         m >= ((int64_t)1 << 31) || d <= 0 || (d & 3) || !rpg::aligned16(q) || !rpg::aligned16(db) || !rpg::aligned16(workspace) ||
         ((q_group == nullptr) != (db_group == nullptr)) || (reinterpret_cast<uintptr_t>(neighbours) & 7u) ||
@@ -354,6 +444,11 @@ extern "C" int rpg_retrieve_cosine_f32(const float* q, const float* db, const fl
         (reinterpret_cast<uintptr_t>(ranks) & 3u) || (reinterpret_cast<uintptr_t>(status) & 3u) ||
         (reinterpret_cast<uintptr_t>(sims) & 3u) || (reinterpret_cast<uintptr_t>(db_inv_norm) & 3u) ||
         (g + RT_QCHUNK - 1) / RT_QCHUNK > 65535)
+        return RPG_ERR_BAD_ARG;
+    // the gate: its three pointers together or not at all, a radius that is a number
+    if ((db_gate == nullptr) != (prior == nullptr) || (db_gate == nullptr) != (gate_info == nullptr) ||
+        (reinterpret_cast<uintptr_t>(db_gate) & 7u) || (reinterpret_cast<uintptr_t>(prior) & 7u) ||
+        (reinterpret_cast<uintptr_t>(gate_info) & 3u) || (db_gate && (!(r2 >= 0.0) || cos_half != cos_half)))
         return RPG_ERR_BAD_ARG;
     const WsLayout w = ws_layout(g, m, d);
     if (workspace_bytes < w.total) return RPG_ERR_WORKSPACE;
@@ -380,8 +475,22 @@ extern "C" int rpg_retrieve_cosine_f32(const float* q, const float* db, const fl
     else
         hipLaunchKernelGGL(retrieve_dot_kernel<4>, grid, dim3(RT_NT), 0, s, q, db, g, m, d, bps, part);
     RPG_CHECK_LAUNCH("retrieve_dot");
-    hipLaunchKernelGGL(retrieve_select_kernel, dim3(g), dim3(RS_NT), 0, s, part, ns, q_inv, db_inv_norm, q_group, db_group, ranks,
-                       g, k, m, neighbours, sims, status);
+    if (db_gate) {
+        const GateOn ga = {db_gate, prior, r2, cos_half, rot_gate, gate_info};
+        hipLaunchKernelGGL(retrieve_select_kernel<true>, dim3(g), dim3(RS_NT), 0, s, part, ns, q_inv, db_inv_norm, q_group, db_group,
+                           ranks, g, k, m, neighbours, sims, status, ga);
+    } else {
+        hipLaunchKernelGGL(retrieve_select_kernel<false>, dim3(g), dim3(RS_NT), 0, s, part, ns, q_inv, db_inv_norm, q_group, db_group,
+                           ranks, g, k, m, neighbours, sims, status, GateOff{});
+    }
     RPG_CHECK_LAUNCH("retrieve_select");
     return RPG_OK;
+}
+
+extern "C" int rpg_retrieve_cosine_f32(const float* q, const float* db, const float* db_inv_norm, const int64_t* q_group,
+                                       const int64_t* db_group, const int32_t* ranks, int g, int k, int64_t m, int d,
+                                       int64_t* neighbours, float* sims, void* workspace, size_t workspace_bytes,
+                                       int32_t* status, void* stream) {
+    return rpg_retrieve_cosine_gated_f32(q, db, db_inv_norm, q_group, db_group, ranks, g, k, m, d, nullptr, nullptr, 0.0, 0.0, 0,
+                                         nullptr, neighbours, sims, workspace, workspace_bytes, status, stream);
 }

@@ -336,6 +336,7 @@ class EvalResult:
     used: Optional[np.ndarray] = None        # [G] int, fuse="consensus" only: the candidates that voted; inliers / used = confidence
     sigma_t: Optional[np.ndarray] = None     # [G] float, weights="variance" only: predicted deviation of the fused translation
     sigma_q: Optional[np.ndarray] = None     # [G] float, weights="variance" only: that of the rotation, in log-quaternion units
+    gate_state: Optional[np.ndarray] = None  # [G] int, relocalize(priors=, gate=) only: 0 gated, 1 no prior, 2 fell back to the whole map
 
     @property
     def median_t(self) -> float:
@@ -558,7 +559,7 @@ def _check_weights(who: str, model, weights, fuse, var_floor):
 
 # what relocalize's forward hands to its read-back: forward_map's outputs, the neighbours on the device, the retrieved ones on
 # their way to the host (None: they were given), and the pose rule's output block where a captured step has already filled it
-_Forward = namedtuple("_Forward", "abs_pose rel_pose edge_index neighbours host_neighbours back", defaults=(None, None))
+_Forward = namedtuple("_Forward", "abs_pose rel_pose edge_index neighbours host_neighbours back gate_info", defaults=(None, None, None))
 
 
 def _result_from_rows(rows: np.ndarray) -> EvalResult:
@@ -650,7 +651,7 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
                bf16_input: Optional[bool] = None, *, rule=None, query_descriptors=None, query_groups=None,
                postprocess: str = "host", fuse: Optional[str] = None, max_edges: int = 64, capture: bool = False,
                outputs: str = "all", inlier_t: float = INLIER_T, inlier_deg: float = INLIER_DEG,
-               weights: Optional[str] = None, var_floor: float = VAR_FLOOR):
+               weights: Optional[str] = None, var_floor: float = VAR_FLOOR, priors=None, gate=None):
     """The evaluation stream of the map path (``PoseNetX_R2.forward_map``): query g's graph is the query followed by the map
     rows ``neighbours[g]`` (its retrieved database images, dataset_7Scenes_multi.py:340-345).  Single process.
 
@@ -669,6 +670,13 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
     for ``query_descriptors`` [G, Dd] -- host or device, staged per micro-batch -- and ``query_groups`` [G], host integers): the
     neighbours of micro-batch i come back to the host with its poses, by the same pinned non-blocking copy behind the same
     event.  The chosen rows, int64 [G, K], are left in ``stats["neighbours"]`` and on an ``EvalResult`` as ``.neighbours``.
+
+    ``gate`` (retrieval.PoseGate) with ``priors`` [G, 7] = (t[3], q[4]) per query, in the coordinates of the returned poses (host
+    or device; a row of NaN: no prior), with a ``rule`` without random draws only: every query's retrieval is restricted to the
+    map rows near its prior pose (``forward_map(prior=, gate=)``, which see).  The priors are staged per micro-batch next to the
+    descriptors; what the gate did comes back with each micro-batch's results: ``stats["gate_state"]`` (0 = gated, 1 = no prior,
+    2 = too few rows inside, ranked against the whole map) and ``stats["gate_rows"]`` (allowed rows inside), int [G], and
+    ``.gate_state`` on an ``EvalResult``.  A captured step is keyed by the gate's parameters too.
 
     ``postprocess="device"`` (default ``"host"``): the pose rule runs on the GPU behind every ``forward_map``
     (``query_pose.QueryPose.from_map`` on the map's poses and the device neighbours -- with a rule the rows ``forward_map`` has
@@ -738,6 +746,20 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
         raise ValueError("relocalize: query_descriptors / query_groups belong to retrieval: pass a rule (and no neighbours)")
     if micro_batch < 1:
         raise ValueError("relocalize: micro_batch must be >= 1")
+    pr_all = gate_h = None
+    if priors is not None or gate is not None:
+        if rule is None:
+            raise ValueError("relocalize: a pose gate restricts retrieval: pass a rule and no neighbours (given neighbours are used "
+                             "as they are)")
+        fmap.check_gate("relocalize", rule, priors, gate)
+        pr_all = torch.as_tensor(priors)
+        if pr_all.dim() != 2 or tuple(pr_all.shape) != (int(queries.shape[0]), 7) or not pr_all.dtype.is_floating_point:
+            raise ValueError(f"relocalize: priors must be floating point [{int(queries.shape[0])}, 7] (t[3], q[4] per query), got "
+                             f"{tuple(pr_all.shape)} {pr_all.dtype}")
+        pr_all = pr_all.to(dtype=torch.float64)
+        fmap.gate_rows(gate)                      # (a map without poses raises here, before any work is queued)
+        gate_h = np.zeros((int(queries.shape[0]), 2), dtype=np.int32)
+    gkw = {} if gate is None else {"gate": gate}
     _check_postprocess("relocalize", postprocess, device)
     _check_fuse("relocalize", fuse, max_edges, ref_node, inlier_t, inlier_deg)
     inlier_t, inlier_deg = float(inlier_t), float(inlier_deg)
@@ -832,6 +854,7 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
         nonlocal n_captured
         key = ("step", tuple(x.shape), x.dtype, kk, None if rule is None else (rule.sampling_period, rule.random), postprocess,
                fuse, max_edges, qd is not None, targ is not None, outputs, inlier_t, inlier_deg, weights, var_floor, kp,
+               None if gate is None else gate.key,
                None if mc is None else (id(mc), mc.samples, mc.seed))       # the sampler's count and seed are baked into the step
         step = captured.get(key)
         if step is None or step.fmap is not fmap or step.pose is not qp or step.stale():
@@ -840,7 +863,7 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
                 if qp is not None:
                     captured[qp_key] = qp
             step = captured[key] = GraphedForwardMap(model, fmap, x, kk, rule=rule, query_descriptors=qd, pose=qp,
-                                                     pose_kwargs=None if targ is None else {"query_targets": targ}, **okw)
+                                                     pose_kwargs=None if targ is None else {"query_targets": targ}, **okw, **gkw)
             n_captured += 1
         return step
 
@@ -862,6 +885,7 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
             if on_gpu and not qd.is_cuda:
                 qd = (qd if qd.is_pinned() else qd.pin_memory()).to(device, non_blocking=True)
         qg = None if qg_all is None else qg_all[b0:b1]
+        pkw = {} if pr_all is None else {"prior": fmap.prior_tensor(pr_all[b0:b1], b1 - b0, "relocalize")}
         if capture:
             targ = None if qp is None or targ_dev is None else targ_dev[b0:b1]
             step = captured_step(x, qd, targ)
@@ -872,16 +896,17 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
             # x is one of the pipeline's two staging buffers (the copy of micro-batch i + 1 into the other one runs under this
             # replay), so the step copies it into its one static input: a device copy of the queries, ~1 % of the step
             out = step(x, None if rule is not None else nb_dev[b0:b1], ranks=ranks, query_descriptors=qd, query_groups=qg,
-                       query_targets=targ)
+                       query_targets=targ, **pkw)
             n_replays += 1
             # The outputs are the step's STATIC tensors, which the replay of the next micro-batch overwrites.  Their copies to
             # pinned memory (read_back here and in _MicroBatchRunner.launch, right after this returns) are enqueued on the stream
             # the replay ran on BEFORE the next launch() enqueues its replay there: stream order keeps micro-batch i's results.
             return (_Forward(out.abs_pose, out.rel_pose, out.edge_index, out.neighbours,
-                             None if rule is None else runner.read_back(out.neighbours), step.packed),
+                             None if rule is None else runner.read_back(out.neighbours), step.packed, step.gate_info),
                     irregular_back(getattr(step, "irregular", None), b0))
-        ab, rel, ei, nb_mb = model.forward_map(x, None, fmap, rule=rule, query_descriptors=qd, query_groups=qg, **okw, **ikw)
-        return _Forward(ab, rel, ei, nb_mb, runner.read_back(nb_mb)), irregular_back(irr_dev, b0)
+        ab, rel, ei, nb_mb = model.forward_map(x, None, fmap, rule=rule, query_descriptors=qd, query_groups=qg, **okw, **ikw, **pkw, **gkw)
+        return (_Forward(ab, rel, ei, nb_mb, runner.read_back(nb_mb), gate_info=model.gate_info if gate is not None else None),
+                irregular_back(irr_dev, b0))
 
     def read_back_of(chunk, x, fwd):
         fwd, irr = fwd
@@ -889,7 +914,8 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
             # (a weighted host rule: the variances this forward -- or this replay -- has just left, row for row with rel_pose)
             return {"nb": fwd.host_neighbours, "abs": fwd.abs_pose, "rel": fwd.rel_pose,
                     "ei": fwd.edge_index if model.knn > 0 else None,
-                    "var": mc.last.rel_var if weights is not None and poses_h is not None else None, "irr": irr}
+                    "var": mc.last.rel_var if weights is not None and poses_h is not None else None, "irr": irr,
+                    "gate": fwd.gate_info}
         back = fwd.back
         if back is None:                   # everything the rule writes travels back in one tensor, one copy
             b0, n = chunk[0].first, x.shape[0]
@@ -898,7 +924,7 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
                         rel_var=None if spread is None else mc.last.rel_var,
                         query_targets=None if targ_dev is None else targ_dev[b0:b0 + n],
                         edge_first=None if fc_first is None else fc_first[:n + 1])
-        return {"nb": fwd.host_neighbours, "rel": back, "irr": irr}
+        return {"nb": fwd.host_neighbours, "rel": back, "irr": irr, "gate": fwd.gate_info}
 
     def general_again(b0, n):
         """A micro-batch that reported an irregular graph, once more through the general kNN build (static_knn off, the whole
@@ -934,6 +960,8 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
         b0, host = item.chunk[0].first, item.host
         if host["nb"] is not None:
             nb_h[b0:b0 + host["nb"].shape[0]] = host["nb"].numpy()
+        if host.get("gate") is not None:
+            gate_h[b0:b0 + host["gate"].shape[0]] = host["gate"].numpy()
         rows_of = rows_per
         if host.get("irr") is not None and int(host["irr"][0]):
             host, rows_of = general_again(b0, sum(int(c.x.shape[0]) for c in item.chunk)), n_per
@@ -961,6 +989,8 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
         mc.reset(mc_draw + 1)      # the next call draws the next masks, however many micro-batches this one took
     if stats is not None:
         stats["neighbours"] = nb_h
+        if gate_h is not None:
+            stats["gate_state"], stats["gate_rows"] = gate_h[:, 0].copy(), gate_h[:, 1].copy()
         if capture:
             stats.update(graphs_captured=n_captured, graph_replays=n_replays)
         if kp:
@@ -970,6 +1000,8 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
     res = acc.result(with_targets=targ_h is not None)
     if targ_h is not None:
         res.neighbours = nb_h
+        if gate_h is not None:
+            res.gate_state = gate_h[:, 0].copy()
     elif stats is not None and acc.ints is not None:          # no EvalResult to carry them: the two arrays go to stats
         ints = acc.integers()
         stats["inliers"], stats["used"] = ints[:, 0].copy(), ints[:, 1].copy()

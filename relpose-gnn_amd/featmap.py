@@ -83,6 +83,7 @@ class FeatureMap:
         self.groups = None if groups is None else self.groups_host.to(features.device)
         self._inv_norms = None
         self._group_counts = None
+        self._gate_rows = {}
         self.meta = {"feat_dim": int(meta["feat_dim"]), "precision": str(meta["precision"]),
                      "encoder_digest": str(meta["encoder_digest"])}
 
@@ -164,6 +165,7 @@ class FeatureMap:
             self.groups = self.groups_host.to(self.device)
         self.features = torch.cat([self.features, feats])
         self._inv_norms, self._group_counts = None, None      # of the rows as they were: recomputed on the next retrieval
+        self._gate_rows = {}
         return self
 
     # ---- retrieval ------------------------------------------------------------------------------------------------------
@@ -207,11 +209,63 @@ class FeatureMap:
             self._group_counts = dict(zip(ids.tolist(), counts.tolist()))
         return np.asarray([m if q == -1 else m - self._group_counts.get(q, 0) for q in query_groups_host.tolist()], dtype=np.int64)
 
-    def retrieve(self, query_descriptors: torch.Tensor, rule, query_groups=None, status=None, workspace=None) -> torch.Tensor:
+    def gate_rows(self, gate) -> torch.Tensor:
+        """float64 [M, 7] on the device: what a ``retrieval.PoseGate`` compares a prior pose with -- per map row the
+        un-normalised translation ``t * pose_s + pose_m`` and the unit quaternion ``qexp(log q)`` of ``poses``, in the layout of
+        the pose rule's rows.  Made once on the host, in float64, per ``(pose_m, pose_s)``; ``extend`` drops it."""
+        if self.poses is None:
+            raise ValueError("FeatureMap.gate_rows: the feature map holds no poses (build it with poses=...): a pose gate "
+                             "compares the prior with the database images' poses")
+        key = (tuple(gate.pose_m), tuple(gate.pose_s))
+        rows = self._gate_rows.get(key)
+        if rows is None or rows.shape[0] != len(self):
+            import numpy as np
+            from .evaluate import qexp
+            p = self.poses.detach().cpu().numpy().astype(np.float64)
+            out = np.empty((p.shape[0], 7), dtype=np.float64)
+            out[:, :3] = p[:, :3] * np.asarray(gate.pose_s, dtype=np.float64) + np.asarray(gate.pose_m, dtype=np.float64)
+            for i in range(p.shape[0]):
+                out[i, 3:] = qexp(p[i, 3:])
+            rows = self._gate_rows[key] = torch.from_numpy(out).to(self.device)
+        return rows
+
+    def prior_tensor(self, prior, g: int, who: str = "retrieve") -> torch.Tensor:
+        """``prior`` [g, 7] (t[3], q[4]; NaN rows: no prior) as a float64 tensor on the map's device: a device tensor as it is, a
+        host array staged through pinned memory without blocking."""
+        if torch.is_tensor(prior) and prior.is_cuda:
+            if prior.dtype != torch.float64 or tuple(prior.shape) != (g, 7) or prior.device != self.device:
+                raise ValueError(f"{who}: prior must be float64 [{g}, 7] on the map's device, got {prior.dtype} {tuple(prior.shape)} "
+                                 f"on {prior.device}")
+            return prior.contiguous()
+        host = torch.as_tensor(prior)
+        if host.dim() != 2 or tuple(host.shape) != (g, 7) or not host.dtype.is_floating_point:
+            raise ValueError(f"{who}: prior must be floating point [{g}, 7] (t[3], q[4] per query), got {tuple(host.shape)} {host.dtype}")
+        host = host.to(dtype=torch.float64).contiguous()
+        if self.device.type != "cuda":
+            return host.to(self.device)
+        return (host if host.is_pinned() else host.pin_memory()).to(self.device, non_blocking=True)
+
+    @staticmethod
+    def check_gate(who: str, rule, prior, gate) -> None:
+        """``prior`` and ``gate`` go together, with a rule whose ranks do not depend on a host-side row count."""
+        if (prior is None) != (gate is None):
+            raise ValueError(f"{who}: prior [G, 7] and gate (retrieval.PoseGate) go together (both or neither)")
+        if gate is not None and rule is not None and rule.random:
+            raise ValueError(f"{who}: a rule with random draws sizes them by each query's allowed-row count on the host, which a "
+                             "pose gate changes on the device: use a rule without drop / random_start with a gate")
+
+    def retrieve(self, query_descriptors: torch.Tensor, rule, query_groups=None, status=None, workspace=None, prior=None,
+                 gate=None, gate_info=None) -> torch.Tensor:
         """int64 [G, K] on the map's device: per query the map rows ``rule`` picks from the ranking of ``descriptor_matrix`` by
         cosine similarity to ``query_descriptors`` fp32 [G, Dd] (on the map's device), rows of the query's group left out
-        (``query_groups`` [G], host integers; -1 or None: nothing left out).  ``status`` / ``workspace``: as ``ops.retrieve``."""
+        (``query_groups`` [G], host integers; -1 or None: nothing left out).  ``status`` / ``workspace``: as ``ops.retrieve``.
+        ``gate`` (retrieval.PoseGate) with ``prior`` float64 [G, 7] (a device tensor, or a host array, staged): the ranking is
+        restricted to the rows near each query's prior pose (``ops.retrieve_gated``); ``gate_info`` int32 [G, 2] receives (state,
+        rows inside) -- pass a tensor to read them.  A rule with random draws raises ValueError with a gate."""
         from . import ops
+        self.check_gate("retrieve", rule, prior, gate)
+        if gate is None and gate_info is not None:
+            raise ValueError("retrieve: gate_info is an output of gated retrieval: pass prior and gate")
         if not torch.is_tensor(query_descriptors) or query_descriptors.dim() != 2:
             raise ValueError("retrieve: query_descriptors must be a tensor [G, Dd]")
         db = self.descriptor_matrix
@@ -220,8 +274,15 @@ class FeatureMap:
             raise ValueError(f"retrieve: query descriptors have {query_descriptors.shape[1]} columns, the map's have {db.shape[1]}")
         if rule.k > len(self):
             raise ValueError(f"retrieve: the rule picks {rule.k} rows, the map has {len(self)}")
+        if gate is not None:
+            gate_rows, prior = self.gate_rows(gate), self.prior_tensor(prior, g)
         qg_host, qg_dev = self._query_groups(query_groups, g)
         ranks = rule.device_ranks(self.n_allowed(qg_host, g), self.device)
+        if gate is not None:
+            return ops.retrieve_gated(query_descriptors, db, ranks, gate_rows, prior, gate.r2,
+                                      gate.cos_half, gate.rot, db_inv_norm=self.inv_norms(), q_group=qg_dev,
+                                      db_group=None if qg_dev is None else self.groups, status=status, workspace=workspace,
+                                      gate_info=gate_info)[0]
         return ops.retrieve(query_descriptors, db, ranks, db_inv_norm=self.inv_norms(), q_group=qg_dev,
                             db_group=None if qg_dev is None else self.groups, status=status, workspace=workspace)
 

@@ -101,6 +101,13 @@ class GraphedForwardMap:
     ``outputs``: ``forward_map``'s -- ``"query"`` captures the query-only step, whose outputs are abs_pose [G, 6], rel_pose
     [G K, 6] and the G K edges into the query nodes; what that mode does not serve raises as it does there.
 
+    ``gate`` (retrieval.PoseGate; with a rule without random draws and a map with poses): the retrieval inside the graph is
+    restricted to the map rows near a prior pose (``forward_map(prior=, gate=)``).  ``self.prior`` -- float64 [G, 7], static -- is
+    filled with NaN at the capture, so the warm-up and the capture rank the whole map, valid for any map; ``prior=`` of a call is
+    copied into it, and a call WITHOUT ``prior`` leaves it as it is: whatever wrote it on the device since -- the update launch of
+    ``tracking.Tracker``, captured with this step -- gates the next replay.  ``self.gate_info`` int32 [G, 2] = (state, rows
+    inside), static, valid after a replay like the outputs.
+
     A model with ``droprate > 0`` is captured only with ``model.mc_dropout`` set (mc_dropout.McDropout): the step then returns the
     means over its dropout samples, the one-thread kernel that advances the draw counter is part of the graph, so every replay
     draws the next masks, and ``node_base`` is read from the device state a caller sets ahead of the replay.  ``self.spread``
@@ -119,7 +126,7 @@ class GraphedForwardMap:
     ``RuntimeError`` instead of replaying over storage that is no longer the model's or the map's."""
 
     def __init__(self, model, fmap, example_queries: torch.Tensor, k: Optional[int] = None, *, rule=None, query_descriptors=None,
-                 pose=None, pose_kwargs: Optional[dict] = None, warmup: int = 2, outputs: str = "all"):
+                 pose=None, pose_kwargs: Optional[dict] = None, warmup: int = 2, outputs: str = "all", gate=None, _after=None):
         self.refuse(model, example_queries)
         model._check_outputs(outputs, None)
         q = example_queries
@@ -139,6 +146,10 @@ class GraphedForwardMap:
             raise ValueError("GraphedForwardMap: query_descriptors belong to retrieval: pass a rule")
         if rule is not None and (fmap.descriptors is None) != (query_descriptors is None):
             raise ValueError("GraphedForwardMap: query_descriptors must be given exactly when the map holds its own descriptors")
+        if gate is not None:
+            if rule is None:
+                raise ValueError("GraphedForwardMap: a pose gate restricts retrieval: pass a rule")
+            fmap.check_gate("GraphedForwardMap", rule, True, gate)          # (the prior is the step's own static buffer)
         pose_kwargs = dict(pose_kwargs or {})
         if pose is None and pose_kwargs:
             raise ValueError("GraphedForwardMap: pose_kwargs without a pose rule")
@@ -150,6 +161,14 @@ class GraphedForwardMap:
         dev = q.device
         self.model, self.fmap, self.rule, self.pose = model, fmap, rule, pose
         self.g, self.k, self.outputs = g, k, outputs
+        # _after (tracking.Tracker): called with this object and every step's MapStep behind its launches -- in the warm-up and in the capture, so
+        # what it launches is part of the graph
+        self.gate, self._after = gate, _after
+        self.prior = self.gate_info = None
+        if gate is not None:
+            fmap.gate_rows(gate)                  # cached on the map: made here, outside the capture, and held below
+            self.prior = torch.full((g, 7), float("nan"), dtype=torch.float64, device=dev)
+            self.gate_info = torch.zeros((g, 2), dtype=torch.int32, device=dev)
         # model.static_knn: k' = min(knn, K) columns per node, rebuilt from every replay's features inside the graph; the nodes whose
         # reference list is irregular are counted into self.irregular (int32 [1], static, zeroed by the step itself: valid after a
         # replay like the outputs), not into the model's counters -- a caller looks at it, the step stays usable
@@ -206,6 +225,8 @@ class GraphedForwardMap:
             mc_draw = None if mc is None else mc.draw
             for _ in range(max(1, warmup)):       # packs weights, sizes the workspace pool, builds the _map_graph edge list
                 self._step()
+                if self.prior is not None:        # (an _after that accepted the warm-up's pose: the capture starts without a prior)
+                    self.prior.fill_(float("nan"))
             if mc_saved is not None:
                 mc.state(dev).copy_(mc_saved)
             model.check_edge_index()              # one sync, before the capture: the warm-up's inputs were valid
@@ -251,15 +272,24 @@ class GraphedForwardMap:
             ab, rel, ei = m.forward_map(self.queries, self.neighbours, self.fmap, outputs=self.outputs, **kw)
             nb = self.neighbours
         else:
+            if self.gate is not None:
+                kw.update(gate=self.gate, _static=(self.ranks, self.query_groups, self.prior, self.gate_info))
+            else:
+                kw["_static"] = (self.ranks, self.query_groups)
             ab, rel, ei, nb = m.forward_map(self.queries, None, self.fmap, rule=self.rule, query_descriptors=self.query_descriptors,
-                                            outputs=self.outputs, _static=(self.ranks, self.query_groups), **kw)
+                                            outputs=self.outputs, **kw)
+        if self.gate is not None:
+            m.gate_info = self.gate_info
         rows = None
         if self.pose is not None:
             # (a weighted rule: the variances this forward has just left -- in the capture, the step's static spread.rel_var)
             var = None if self.sigma is None else m.mc_dropout.last.rel_var
             rows = self.pose.from_map(rel, ei, self.fmap, nb, query_targets=self.query_targets, edge_first=self.edge_first,
                                       out=self._rows_out, inliers=self.inliers, rel_var=var, spread=self.sigma)
-        return MapStep(ab, rel, ei, nb, rows)
+        out = MapStep(ab, rel, ei, nb, rows)
+        if self._after is not None:
+            self._after(self, out)
+        return out
 
     # ---- validity ------------------------------------------------------------------------------------------------------------------
     def _reads(self) -> dict:
@@ -275,14 +305,15 @@ class GraphedForwardMap:
                 "mc_state": None if getattr(m, "mc_dropout", None) is None else m.mc_dropout._state,
                 "counters": m._counters.counters, "pose_counters": None if self.pose is None else self.pose._bad.counters,
                 "features": f.features, "poses": f.poses, "descriptors": f.descriptors, "groups": f.groups,
-                "inv_norms": f._inv_norms if self.rule is not None else None}
+                "inv_norms": f._inv_norms if self.rule is not None else None,
+                "gate_rows": None if self.gate is None else f._gate_rows.get((tuple(self.gate.pose_m), tuple(self.gate.pose_s)))}
 
     @staticmethod
     def _sign(r: dict) -> tuple:
         """Objects by identity, the map's storage by (address, rows): what must be unchanged for the graph to be replayed."""
         return (id(r["library"]), id(r["encoder"]), id(r["gnn"]), id(r["gnn_bf16"]), r["dtypes"], id(r["counters"]),
                 id(r["pose_counters"]), _storage(r["features"]), _storage(r["poses"]), _storage(r["descriptors"]),
-                _storage(r["groups"]), _storage(r["inv_norms"]), id(r["mc_state"]))
+                _storage(r["groups"]), _storage(r["inv_norms"]), id(r["mc_state"]), _storage(r["gate_rows"]))
 
     def stale(self) -> bool:
         """True once the model or the map no longer hold what the graph was captured over."""
@@ -290,6 +321,8 @@ class GraphedForwardMap:
         if now["encoder"] is None or now["gnn"] is None:
             return True
         if self.rule is not None and now["inv_norms"] is None:
+            return True
+        if self.gate is not None and now["gate_rows"] is None:
             return True
         return self._sign(now) != self._signature
 
@@ -301,11 +334,12 @@ class GraphedForwardMap:
 
     @torch.no_grad()
     def __call__(self, queries: torch.Tensor, neighbours: Optional[torch.Tensor] = None, ranks=None, query_descriptors=None,
-                 query_groups=None, query_targets=None) -> MapStep:
+                 query_groups=None, query_targets=None, prior=None) -> MapStep:
         """Copy the given inputs into the static buffers (non-blocking, on the current stream; a tensor that IS the static buffer
         -- ``self.queries`` filled by the caller -- is not copied), replay, publish the deferred counters.  ``ranks``: int32 [G, K]
         (tensor or array) in place of the rule's own, which are otherwise drawn here, on the host, as ``forward_map`` draws them;
-        ``query_groups`` [G]: host integers, as ``forward_map`` takes them."""
+        ``query_groups`` [G]: host integers, as ``forward_map`` takes them.  ``prior`` [G, 7] (a gated step only): copied into the
+        static prior; None leaves that buffer as it is."""
         if self.stale():
             raise RuntimeError("GraphedForwardMap is stale: the model's packed weights / precision or the feature map's storage "
                                "have changed since the capture (refresh_packed, load_state_dict, .to(), FeatureMap.extend): "
@@ -325,6 +359,11 @@ class GraphedForwardMap:
                                  f"{given.dtype} {tuple(given.shape)}")
         if self.rule is None and (ranks is not None or query_groups is not None):
             raise ValueError("GraphedForwardMap: ranks / query_groups belong to retrieval: the graph was captured without a rule")
+        prior_dev = None
+        if prior is not None:
+            if self.gate is None:
+                raise ValueError("GraphedForwardMap: prior given, but the graph was captured without a gate")
+            prior_dev = self.fmap.prior_tensor(prior, self.g, "GraphedForwardMap")
         self.model._counters.poll()               # as the eager call starts: the report of the previous call, if it has landed
         host_ranks, qg_dev, fixed = None, None, False
         if self.rule is not None:
@@ -346,6 +385,8 @@ class GraphedForwardMap:
                               (self.query_descriptors, query_descriptors), (self.query_targets, query_targets)):
             if static is not None:
                 self._copy_in(static, given)
+        if prior_dev is not None:
+            self._copy_in(self.prior, prior_dev)
         if host_ranks is not None:
             self.ranks.copy_(host_ranks, non_blocking=True)
             self._ranks_fixed = fixed
@@ -355,6 +396,8 @@ class GraphedForwardMap:
             else:
                 self.query_groups.copy_(qg_dev, non_blocking=True)
         self.graph.replay()
+        if self.gate is not None:
+            self.model.gate_info = self.gate_info
         if self.spread is not None:               # the replayed step advanced the draw counter on the device
             self.model.mc_dropout.last = self.spread
             self.model.mc_dropout.advanced()

@@ -572,6 +572,38 @@ def retrieve(q: torch.Tensor, db: torch.Tensor, ranks, db_inv_norm: Optional[tor
     ``R_MAX``, or a row of ranks that does not ascend, is counted into ``status`` (int32 device tensor, accumulates; the rank
     is clamped) -- with ``status=None`` the count is read back here (one synchronisation) and a non-zero count raises
     IndexError.  ``workspace``: a uint8 device tensor to use instead of allocating one; ``out``: the neighbours' tensor."""
+    return _retrieve(q, db, ranks, db_inv_norm, q_group, db_group, return_sims, status, workspace, out, None)
+
+
+def retrieve_gated(q: torch.Tensor, db: torch.Tensor, ranks, db_gate: torch.Tensor, prior: torch.Tensor, r2: float,
+                   cos_half: float = 0.0, rot_gate: bool = False, db_inv_norm: Optional[torch.Tensor] = None,
+                   q_group: Optional[torch.Tensor] = None, db_group: Optional[torch.Tensor] = None, return_sims: bool = False,
+                   status: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
+                   out: Optional[torch.Tensor] = None, gate_info: Optional[torch.Tensor] = None):
+    """``retrieve`` restricted to the map rows near a prior pose (rpg_retrieve_cosine_gated_f32): ``db_gate`` float64 [M, 7] and
+    ``prior`` float64 [G, 7] hold (t[3], q[4]), the un-normalised translation and the unit quaternion.  Per query: a non-finite
+    prior ranks as ``retrieve`` does (state 1); otherwise the allowed rows with squared distance <= ``r2`` (and, with
+    ``rot_gate``, ``|<q_row, q_prior>| >= cos_half``) are the only ones ranked (state 0) when they cover the query's largest
+    rank, and all allowed rows are (state 2) when they do not.  -> (neighbours [, sims], gate_info int32 [G, 2] = (state, allowed
+    rows inside)); ``gate_info``: the tensor to write them to.  Everything else as ``retrieve``."""
+    dbg, pr = _req(db_gate, "db_gate", torch.float64), _req(prior, "prior", torch.float64)
+    if not torch.is_tensor(q) or not torch.is_tensor(db) or q.dim() != 2 or db.dim() != 2:
+        raise ValueError("retrieve_gated: q [G, d] and db [M, d] must be 2-D tensors")
+    g, m = q.shape[0], db.shape[0]
+    if tuple(dbg.shape) != (m, 7) or tuple(pr.shape) != (g, 7) or dbg.device != q.device or pr.device != q.device:
+        raise ValueError(f"retrieve_gated: db_gate must be float64 [{m}, 7] and prior float64 [{g}, 7] on the inputs' GPU, got "
+                         f"{tuple(dbg.shape)} and {tuple(pr.shape)}")
+    r2, cos_half = float(r2), float(cos_half)
+    if not r2 >= 0.0 or cos_half != cos_half:
+        raise ValueError(f"retrieve_gated: r2 must be >= 0 and cos_half a number, got {r2} and {cos_half}")
+    info = _out(gate_info, (g, 2), torch.int32, q.device, "retrieve_gated")
+    res = _retrieve(q, db, ranks, db_inv_norm, q_group, db_group, return_sims, status, workspace, out,
+                    (dbg, pr, r2, cos_half, int(bool(rot_gate)), info))
+    return (*res, info) if return_sims else (res, info)
+
+
+def _retrieve(q, db, ranks, db_inv_norm, q_group, db_group, return_sims, status, workspace, out, gate):
+    """``retrieve`` / ``retrieve_gated``: ``gate`` = None, or (db_gate, prior, r2, cos_half, rot_gate, gate_info) checked."""
     q, db = _req(q, "q"), _req(db, "db")
     if q.dim() != 2 or db.dim() != 2:
         raise ValueError("retrieve: q [G, d] and db [M, d] must be 2-D")
@@ -607,9 +639,16 @@ def retrieve(q: torch.Tensor, db: torch.Tensor, ranks, db_inv_norm: Optional[tor
     nbrs = _out(out, (g, k), torch.int64, q.device, "retrieve")
     sims = torch.empty((g, k), dtype=torch.float32, device=q.device) if return_sims else None
     status, own = _status_arg(status, q.device, "retrieve")
-    L.check(lib.rpg_retrieve_cosine_f32(_p(q), _p(db), _p(db_inv_norm), _p(q_group), _p(db_group), _p(ranks), g, k, m, d,
-                                        _p(nbrs), _p(sims), workspace.data_ptr(), workspace.numel(), status.data_ptr(),
-                                        _stream()), "retrieve")
+    if gate is None:
+        L.check(lib.rpg_retrieve_cosine_f32(_p(q), _p(db), _p(db_inv_norm), _p(q_group), _p(db_group), _p(ranks), g, k, m, d,
+                                            _p(nbrs), _p(sims), workspace.data_ptr(), workspace.numel(), status.data_ptr(),
+                                            _stream()), "retrieve")
+    else:
+        dbg, pr, r2, cos_half, rot, info = gate
+        L.check(lib.rpg_retrieve_cosine_gated_f32(_p(q), _p(db), _p(db_inv_norm), _p(q_group), _p(db_group), _p(ranks), g, k, m, d,
+                                                  _p(dbg), _p(pr), r2, cos_half, rot, _p(info), _p(nbrs), _p(sims),
+                                                  workspace.data_ptr(), workspace.numel(), status.data_ptr(), _stream()),
+                "retrieve_gated")
     bad = _own_count(status, own)
     if bad:
         raise IndexError(f"ranks has {bad} entry(ies) outside a query's allowed rows / the kernel's R_MAX, or rows that do "
@@ -1202,3 +1241,29 @@ def tuned(keys):
         yield
     finally:
         reset_tuning()
+
+
+def track_update(rows: torch.Tensor, inliers: torch.Tensor, prior: torch.Tensor, lost: torch.Tensor, accepted: torch.Tensor,
+                 min_inliers: int, min_ratio: float, max_lost: int) -> torch.Tensor:
+    """The update launch of a tracking loop (rpg_track_update_f64), in place: per camera s, the pose in ``rows[s, :7]`` (float64
+    [S, 16], the pose rule's rows) is accepted when it is finite, ``inliers[s, 0] >= min_inliers`` and ``inliers[s, 0] >=
+    min_ratio * inliers[s, 1]`` (int32 [S, 2], the consensus rule's (inliers, used)); then ``prior[s]`` (float64 [S, 7]) becomes
+    that pose, ``lost[s] = 0`` and ``accepted[s] = 1``; otherwise ``accepted[s] = 0``, ``lost[s]`` counts one more frame and past
+    ``max_lost`` the prior becomes NaN.  ``lost`` / ``accepted``: int32 [S].  Returns ``accepted``."""
+    rows, inliers = _req(rows, "rows", torch.float64), _req(inliers, "inliers", torch.int32)
+    s = rows.shape[0]
+    if rows.dim() != 2 or rows.shape[1] != 16 or s < 1 or tuple(inliers.shape) != (s, 2):
+        raise ValueError(f"track_update: rows must be float64 [S >= 1, 16] and inliers int32 [S, 2], got {tuple(rows.shape)} and "
+                         f"{tuple(inliers.shape)}")
+    for t, name, dtype, shape in ((prior, "prior", torch.float64, (s, 7)), (lost, "lost", torch.int32, (s,)),
+                                  (accepted, "accepted", torch.int32, (s,))):
+        if (not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous()
+                or t.device != rows.device):
+            raise ValueError(f"track_update: {name} must be a contiguous {dtype} {list(shape)} tensor on the rows' GPU (it is "
+                             "written in place)")
+    min_ratio = float(min_ratio)
+    if min_ratio != min_ratio:
+        raise ValueError("track_update: min_ratio is NaN")
+    L.check(L.lib().rpg_track_update_f64(_p(rows), _p(inliers), s, int(min_inliers), min_ratio, int(max_lost), _p(prior), _p(lost),
+                                         _p(accepted), _stream()), "track_update")
+    return accepted

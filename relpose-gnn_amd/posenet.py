@@ -185,6 +185,8 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
         # optional mc_dropout.McDropout: with it (and droprate > 0) every forward returns the MEAN of the heads over its dropout
         # samples in place of abs_pose / rel_pose and leaves their variances in mc_dropout.last (a plain attribute as well)
         self.mc_dropout = None
+        # what the last forward_map's pose gate did, int32 [G, 2] = (state, rows inside) on the device; None without a gate
+        self.gate_info = None
         # with knn > 0: forward_map builds the kNN graph of its equal-sized graphs at fixed positions (rpg_knn_graph_uniform_f32):
         # no edge count for the host to wait for, so the two-stream schedule, outputs="query" and the captured step serve the
         # model; a graph whose reference list is irregular raises IrregularKnnGraph by the index_check contract (a plain
@@ -656,7 +658,7 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
     @torch.no_grad()
     def forward_map(self, queries: torch.Tensor, neighbours: Optional[torch.Tensor], fmap, k=None, *, rule=None,
                     query_descriptors: Optional[torch.Tensor] = None, query_groups=None, outputs: str = "all", _static=None,
-                    _irregular: Optional[torch.Tensor] = None):
+                    _irregular: Optional[torch.Tensor] = None, prior=None, gate=None):
         """The forward of G graphs, each query g followed by the K database images ``neighbours[g]`` of the feature map ``fmap``
         (dataset_7Scenes_multi.py:340-345) -- with only the G queries through the encoder.  Returns what
         ``forward(fc_batch(assembled, K + 1), k)`` returns for the assembled images: (abs_pose [G*(K+1), 6], rel_pose [E, 6],
@@ -698,8 +700,18 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
         contract as ``IrregularKnnGraph`` (a ValueError: at the call under ``"sync"``, at the next look under ``"deferred"``); its
         outputs are a valid graph's, not the reference's, and ``static_knn = False`` reproduces the reference's.
 
+        ``gate`` (retrieval.PoseGate) with ``prior`` float64 [G, 7] = (t[3], q[4]) per query, a device tensor or a host array
+        (staged through pinned memory), with a ``rule`` only (``neighbours=`` given: ValueError; a rule with random draws:
+        ValueError): retrieval is restricted to the map rows near each query's prior pose (``ops.retrieve_gated``: a NaN prior
+        row ranks the whole map; a gate that holds fewer allowed rows than the rule's largest rank needs falls back to the whole
+        map).  Both ``outputs`` modes and ``static_knn``.  The states are left on the model as ``self.gate_info`` -- int32 [G, 2]
+        = (state, rows inside) on the device, valid behind this call's launches like ``mc_dropout.last`` -- and None by every
+        call without a gate.
+
         ``_static`` (graphed.GraphedForwardMap only): ``(ranks int32 [G, K], query groups int64 [G] or None)`` already on the
-        device, read in place of the two per-call host products above, so that nothing of the call depends on host data.
+        device, read in place of the two per-call host products above, so that nothing of the call depends on host data; with a
+        gate two more elements, ``(..., prior float64 [G, 7], gate_info int32 [G, 2])``: the step's static prior (which a
+        tracking loop updates on the device) and where the states go.
         ``_irregular`` (relocalize, GraphedForwardMap): an int32 [1] device counter of the caller's that the irregular nodes are
         added to INSTEAD of the model's own counters -- the caller looks at it and nothing raises."""
         self._check_outputs(outputs, k)
@@ -707,8 +719,17 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
             raise ValueError("forward_map: give neighbours or a retrieval rule, not both")
         if rule is None and (query_descriptors is not None or query_groups is not None):
             raise ValueError("forward_map: query_descriptors / query_groups belong to retrieval: pass a rule (and neighbours=None)")
+        if gate is not None and rule is None:
+            raise ValueError("forward_map: a pose gate restricts retrieval: pass a rule and neighbours=None (given neighbours are "
+                             "used as they are)")
+        if _static is not None and len(_static) > 2:
+            prior = _static[2]
+        if prior is not None or gate is not None:
+            fmap.check_gate("forward_map", rule, prior, gate)
+        self.gate_info = None
         if rule is not None:
-            return self._forward_map_retrieve(queries, fmap, k, rule, query_descriptors, query_groups, _static, outputs, _irregular)
+            return self._forward_map_retrieve(queries, fmap, k, rule, query_descriptors, query_groups, _static, outputs, _irregular,
+                                              prior, gate)
         if not torch.is_tensor(queries) or not torch.is_tensor(neighbours):
             raise TypeError("forward_map: queries and neighbours must be tensors")
         if neighbours.dtype != torch.int64 or neighbours.dim() != 2:
@@ -734,7 +755,7 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
                                f"must be on the same GPU")
 
     def _forward_map_retrieve(self, queries, fmap, k, rule, query_descriptors, query_groups, static=None, outputs="all",
-                              irregular=None):
+                              irregular=None, prior=None, gate=None):
         """``forward_map`` with the neighbours retrieved per stream slot from that slot's query features (or descriptors).
         ``static``: see ``forward_map``'s ``_static``."""
         if not torch.is_tensor(queries):
@@ -762,7 +783,16 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
             qg_host, qg_dev = fmap._query_groups(query_groups, g)
             ranks = rule.device_ranks(fmap.n_allowed(qg_host, g), dev)
         else:                                     # the host's per-call products, already in the caller's device buffers
-            ranks, qg_dev = static
+            ranks, qg_dev = static[:2]
+        gate_rows = prior_dev = info = None
+        if gate is not None:
+            gate_rows = fmap.gate_rows(gate)
+            if static is not None and len(static) > 2:
+                prior_dev, info = static[2], static[3]
+            else:
+                prior_dev = fmap.prior_tensor(prior, g, "forward_map")
+                info = torch.empty((g, 2), dtype=torch.int32, device=dev)
+            self.gate_info = info
         inv, db = fmap.inv_norms(), fmap.descriptor_matrix
         db_groups = None if qg_dev is None else fmap.groups
         nb_out = torch.empty((g, kk), dtype=torch.int64, device=dev)
@@ -770,6 +800,10 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
 
         def neighbours_of(qf, g0, g1, st, wkey):
             ws = self._ws_pool.get((400 + wkey[0], wkey[1]), int(ws_bytes(g1 - g0, db.shape[0], db.shape[1])), dev)
+            if gate is not None:
+                return ops.retrieve_gated(qf if qd is None else qd[g0:g1], db, ranks[g0:g1], gate_rows, prior_dev[g0:g1], gate.r2,
+                                          gate.cos_half, gate.rot, db_inv_norm=inv, q_group=None if qg_dev is None else qg_dev[g0:g1],
+                                          db_group=db_groups, status=st, workspace=ws, out=nb_out[g0:g1], gate_info=info[g0:g1])[0]
             return ops.retrieve(qf if qd is None else qd[g0:g1], db, ranks[g0:g1], db_inv_norm=inv,
                                 q_group=None if qg_dev is None else qg_dev[g0:g1], db_group=db_groups, status=st, workspace=ws,
                                 out=nb_out[g0:g1])

@@ -105,3 +105,39 @@ class RetrievalRule:
                 self._dev_ranks.clear()
             self._dev_ranks[key] = r
         return r
+
+
+class PoseGate:
+    """Restricts retrieval to the map rows near a prior pose (``FeatureMap.retrieve(prior=, gate=)``, ``forward_map(prior=,
+    gate=)``, ``tracking.Tracker``): a row is inside when its translation lies within ``radius`` of the prior's and -- with
+    ``max_deg`` -- its rotation within ``max_deg`` degrees.  ``radius`` is in the unit of the UN-normalised translation (``t *
+    pose_s + pose_m``, what ``relocalize`` returns), finite and >= 0; ``max_deg`` in [0, 360] or None for no rotation test
+    (ValueError otherwise).  ``pose_m`` / ``pose_s``: the translation mean / std the map's poses are normalised by, as the pose
+    rule takes them.  ``r2`` and ``cos_half`` (cos of ``max_deg / 2``: the kernel compares ``|<q1, q2>|`` with it) are computed
+    once, here, as Python floats -- the numbers the kernel gets."""
+
+    def __init__(self, radius: float, max_deg: Optional[float] = None, pose_m=(0.0, 0.0, 0.0), pose_s=(1.0, 1.0, 1.0)):
+        radius = float(radius)
+        if not np.isfinite(radius) or radius < 0.0:
+            raise ValueError(f"PoseGate: radius must be finite and >= 0, got {radius}")
+        if max_deg is not None:
+            max_deg = float(max_deg)
+            if not 0.0 <= max_deg <= 360.0:                   # (a NaN fails both comparisons)
+                raise ValueError(f"PoseGate: max_deg must be in [0, 360] (or None: no rotation gate), got {max_deg}")
+        self.pose_m = tuple(float(v) for v in np.asarray(pose_m, dtype=np.float64).reshape(3))
+        self.pose_s = tuple(float(v) for v in np.asarray(pose_s, dtype=np.float64).reshape(3))
+        self.radius, self.max_deg = radius, max_deg
+        self.r2 = radius * radius
+        self.cos_half = 0.0 if max_deg is None else float(np.cos(np.deg2rad(max_deg / 2.0)))
+
+    @property
+    def rot(self) -> bool:
+        return self.max_deg is not None
+
+    @property
+    def key(self) -> tuple:
+        """What a captured step is keyed by: two gates with the same key are the same gate."""
+        return (self.r2, self.cos_half, self.rot, self.pose_m, self.pose_s)
+
+    def __repr__(self) -> str:
+        return f"PoseGate(radius={self.radius}, max_deg={self.max_deg}, pose_m={self.pose_m}, pose_s={self.pose_s})"
