@@ -86,7 +86,14 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 //     [kh0, kh0 + nkh): the rows of the top / bottom image row that would multiply zero padding are not issued at all.
 //     Items are walked down the image first (m-block j -> column j / H of 128 tiles, row j % H), so that the workgroups that
 //     are resident together on an XCD read neighbouring input rows of the same images, as in the other order.
-// The skipped products are exact zeros: every output is the same sum in the same order in both orders.
+//   RM = true, TU = true, the tail-uniform layout of the row order for Tw = 2: the same 128 tiles per item (64 images x 2 tile
+//     columns of row ho), but row r of the item is image col * 64 + (r & 63), tile column r >> 6 instead of image r >> 1, column
+//     r & 1.  Rows 0-63 (waves 0-3) are then first tiles only and rows 64-127 (waves 4-7) last tiles only.  Where W % 4 != 0
+//     the fourth output column of a last tile is outside the image; it is the only reader of Winograd position 5 (y3 = .. + m5),
+//     so waves 4-7 issue neither that position's MFMAs nor its input transform nor its operand reads (kstep's skip5).  A SIMD
+//     holds waves w and w + 4: each of the four matrix pipes loses the same 8 of 96 MFMAs per K step.
+// The skipped products are exact zeros or feed only a dropped pixel: every stored output is the same sum in the same order in
+// all three.
 struct RowOrder { int H, ntw; };
 template <bool RM>
 __device__ __forceinline__ int wino43_block_m0(int j, const RowOrder& ro) {       // first tile of m-block j (128 tiles)
@@ -97,9 +104,13 @@ __device__ __forceinline__ int wino43_block_m0(int j, const RowOrder& ro) {     
         return j * 128;
 }
 // tile m -> image row index t = img * H + ho and tile column tw
-template <bool RM>
+template <bool RM, bool TU = false>
 __device__ __forceinline__ void wino43_tile_row(int m, int Tw, const RowOrder& ro, int& t, int& tw) {
-    if constexpr (RM) {
+    if constexpr (RM && TU) {                         // Tw == 2, ntw a multiple of 128
+        const int ho = m / ro.ntw, i = m - ho * ro.ntw, r = i & 127;
+        t = (((i - r) >> 1) + (r & 63)) * ro.H + ho;
+        tw = r >> 6;
+    } else if constexpr (RM) {
         const int ho = m / ro.ntw, i = m - ho * ro.ntw, img = i / Tw;
         t = img * ro.H + ho;
         tw = i - img * Tw;
@@ -109,7 +120,7 @@ __device__ __forceinline__ void wino43_tile_row(int m, int Tw, const RowOrder& r
     }
 }
 
-template <bool RM = false>
+template <bool RM = false, bool TU = false>
 __device__ __forceinline__ void wino43_epilogue(const f32x16 (&acc)[P], float* slab, int lane, int mw0, int nw0, int M,
                                                 int Tw, int W, int Cout, const Epi& ep, const RowOrder& ord = RowOrder{0, 0}) {
     constexpr int EP = 32 + 4;                              // slab pitch: 32 channels + pad
@@ -131,14 +142,16 @@ __device__ __forceinline__ void wino43_epilogue(const f32x16 (&acc)[P], float* s
         t_scale = ord.H;
         row_px = ord.H * W;
     }
-    const int q_first = i0 / Tw, t_first = q_first * t_scale + t_add;
+    // TU: the wave's 32 tiles are tile column (i0 & 127) >> 6 of 32 consecutive images
+    const int r0 = i0 & 127;
+    const int q_first = TU ? ((i0 - r0) >> 1) + (r0 & 63) : i0 / Tw, t_first = q_first * t_scale + t_add;
     const size_t row0 = (size_t)t_first * W * Cout;
     const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(ep.out + row0, 0, 0x7fffffff, 0x00020000);
     const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<float*>(ep.residual ? ep.residual + row0 : ep.out + row0), 0, 0x7fffffff, 0x00020000);
-    const int step_t = 4 / Tw, step_tw = 4 % Tw;            // wave-uniform
+    const int step_t = TU ? 4 : 4 / Tw, step_tw = TU ? 0 : 4 % Tw;            // wave-uniform
     int mt = mw0 + (pr >> 1);
-    int trel = (i0 + (pr >> 1)) / Tw - q_first, tw = (i0 + (pr >> 1)) % Tw;
+    int trel = TU ? pr >> 1 : (i0 + (pr >> 1)) / Tw - q_first, tw = TU ? r0 >> 6 : (i0 + (pr >> 1)) % Tw;
     unsigned voff[2][8];
 #pragma unroll
     for (int it = 0; it < 8; ++it) {
@@ -603,13 +616,13 @@ __device__ unsigned long long* g_wino_trace = nullptr;
 #endif
 
 // BatchNorm / residual / ReLU / store of one 16-byte group of a summed tail tile: pixel p (0..511) x channel quad c4 (0..15)
-template <bool RM>
+template <bool RM, bool TU>
 __device__ __forceinline__ void wino43_finish_quad(const float4& s, const Epi& ep, int tile, int p, int c4, int M, int Tw, int W,
                                                    int Cout, int tiles_n, const RowOrder& ord) {
     const int m = wino43_block_m0<RM>(tile / tiles_n, ord) + (p >> 2), nb = (tile % tiles_n) * BN + 4 * c4;
     if (m >= M || nb >= Cout) return;
     int t, tw;
-    wino43_tile_row<RM>(m, Tw, ord, t, tw);
+    wino43_tile_row<RM, TU>(m, Tw, ord, t, tw);
     const int wo = 4 * tw + (p & 3);
     if (wo >= W) return;
     const size_t o = ((size_t)t * W + wo) * Cout + nb;
@@ -630,7 +643,7 @@ __device__ __forceinline__ void wino43_finish_quad(const float4& s, const Epi& e
 // back like the others: the bits do not depend on who came last), applies the epilogue and puts the counter back to zero --
 // the work of wino43_fixup_kernel without the launch.  Nobody waits (no spinning: the workgroups of two streams share the
 // CUs).  `flag`: one int of LDS that no wave is using.  8 of a thread's 16 groups at a time: 8 loads in flight per thread.
-template <bool RM>
+template <bool RM, bool TU>
 __device__ __forceinline__ void wino43_combine_last(const Split& sp, int tt, const Epi& ep, int M, int Tw, int W, int Cout,
                                                     int tiles_n, const RowOrder& ord, int* flag) {
     if (!rpg::last_arriver(sp.arrive + tt, (unsigned)sp.parts, flag)) return;
@@ -654,15 +667,16 @@ __device__ __forceinline__ void wino43_combine_last(const Split& sp, int tt, con
 #pragma unroll
         for (int c = 0; c < 8; ++c) {
             const int idx = tid_c + NT8 * (8 * h + c);
-            wino43_finish_quad<RM>(sum[c], ep, tile, idx >> 4, idx & 15, M, Tw, W, Cout, tiles_n, ord);
+            wino43_finish_quad<RM, TU>(sum[c], ep, tile, idx >> 4, idx & 15, M, Tw, W, Cout, tiles_n, ord);
         }
     }
 }
 
-template <bool RM>
+template <bool RM, bool TU = false>
 __global__ __launch_bounds__(NT8) void wino43_conv8_kernel(const float* __restrict__ x, const float* __restrict__ U, int H,
                                                           int W, int Cin, int Cout, int Tw, int M, Epi ep, int tiles_n,
                                                           Split sp, int ntw) {
+    static_assert(RM || !TU, "the tail-uniform layout is a form of the row order");
     extern __shared__ __attribute__((aligned(16))) float lds[];
 #ifdef RPG_WINO_TRACE
     if (g_wino_trace && threadIdx.x == 0) g_wino_trace[5 * blockIdx.x] = __builtin_amdgcn_s_getreg(0xF804);   // HW_ID
@@ -726,7 +740,7 @@ __global__ __launch_bounds__(NT8) void wino43_conv8_kernel(const float* __restri
         int img_off = 0, ho = 0, wi0 = -(1 << 24);
         if (m < M) {
             int t, tw;
-            wino43_tile_row<RM>(m, Tw, ord, t, tw);
+            wino43_tile_row<RM, TU>(m, Tw, ord, t, tw);
             ho = t % H;
             img_off = (t / H - n_first) * (int)img_floats;
             wi0 = 4 * tw - 1;
@@ -830,22 +844,34 @@ __global__ __launch_bounds__(NT8) void wino43_conv8_kernel(const float* __restri
     //   groups 0-5, MFMAs 0-3: the 4 operand reads of the next group (group 5: of the next K step's group 0, from nxt)
     //   groups 0-2, MFMAs 4-7: stage pieces 0..8 -> nxt        groups 3-5, MFMAs 4-7: buffer loads 0..8
     //   barrier after group 4: every wave has written nxt and issued its last reads of cur
-    auto kstep = [&](int cur, int nxt, int khf) {
+    // skip5 (compile time; the waves that hold only last tiles whose fourth output column is outside the image): position 5 is
+    // dead.  Groups 2 and 5 keep their four position-4 MFMAs, which carry the four operand reads of the next group; piece 5
+    // (pixel 5 -- outside the image for these tiles anyway -- and its transform) is not fetched or staged, and the U piece 8
+    // that sat behind a dropped MFMA takes its slot behind group 1 / 4; groups 1 and 4 do not read position 5's operands.
+    // Every access still sits singly behind an MFMA, and the barrier is the same one.
+    auto kstep = [&](int cur, int nxt, int khf, bool skip5) {
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int g = 0; g < 6; ++g) {
             const int set = g & 1, x0 = 2 * (g % 3);
+            const bool dead = skip5 && g % 3 == 2;                    // this group's odd MFMAs are position 5
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
                 const int j = i & 1, e = i >> 1;
+                if (dead && j) continue;
                 const float av = e == 0 ? fa[set][j].x : e == 1 ? fa[set][j].y : e == 2 ? fa[set][j].z : fa[set][j].w;
                 const float bv = e == 0 ? fb[set][j].x : e == 1 ? fb[set][j].y : e == 2 ? fb[set][j].z : fb[set][j].w;
                 acc[x0 + j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[x0 + j], 0, 0, 0);
-                if (i < 4) {
-                    if (g < 5) frag_one(g + 1, set ^ 1, i, cur);
-                    else frag_one(0, 0, i, nxt);
+                const int q = dead ? e : i;                           // slot behind this MFMA (a dead group has slots 0..3)
+                if (q < 4) {
+                    const bool pos5 = skip5 && (g + 1) % 3 == 2 && q >= 2;      // a[1], b[1] of the next group = position 5
+                    if (!pos5) {
+                        if (g < 5) frag_one(g + 1, set ^ 1, q, cur);
+                        else frag_one(0, 0, q, nxt);
+                    }
                 } else {
-                    const int s = 4 * (g % 3) + (i - 4);              // 0..11, pieces 0..8 used
+                    int s = 4 * (g % 3) + (q - 4);                    // 0..11, pieces 0..8 used
+                    if (skip5 && s == 5) s = 8;
                     if (s < 9) {
                         if (g < 3) stage_one(s, nxt);
                         else fetch_one(s, khf);
@@ -875,25 +901,34 @@ __global__ __launch_bounds__(NT8) void wino43_conv8_kernel(const float* __restri
     for (int i = 0; i < 4; ++i) frag_one(0, 0, i, 0);
     RPG_TRACE(2);
     int kt = kb;
-    if constexpr (RM) {                  // the kernel row is a scalar: only the LDS image toggles at compile time
+    // TU: waves 4-7 hold the last tiles; their position 5 is dead where the row's last output column group is ragged.  Wave-uniform,
+    // decided once: the two loops differ only in what a wave issues between the same barriers.
+    const bool skip5 = TU && (W & 3) != 0 && __builtin_amdgcn_readfirstlane(wave) >= 4;
+    if (skip5) {
         for (; kt + 1 < nk; kt += 2) {
-            kstep(0, IMG8_FLOATS, 0);
-            kstep(IMG8_FLOATS, 0, 0);
+            kstep(0, IMG8_FLOATS, 0, true);
+            kstep(IMG8_FLOATS, 0, 0, true);
         }
-        if (kt < nk) kstep(0, IMG8_FLOATS, 0);       // an odd count: 3 kernel rows x an odd number of channel blocks
+        if (kt < nk) kstep(0, IMG8_FLOATS, 0, true);
+    } else if constexpr (RM) {           // the kernel row is a scalar: only the LDS image toggles at compile time
+        for (; kt + 1 < nk; kt += 2) {
+            kstep(0, IMG8_FLOATS, 0, false);
+            kstep(IMG8_FLOATS, 0, 0, false);
+        }
+        if (kt < nk) kstep(0, IMG8_FLOATS, 0, false);       // an odd count: 3 kernel rows x an odd number of channel blocks
     } else {
         for (; kt + 5 < nk; kt += 6) {
-            kstep(0, IMG8_FLOATS, 2);
-            kstep(IMG8_FLOATS, 0, 0);
-            kstep(0, IMG8_FLOATS, 1);
-            kstep(IMG8_FLOATS, 0, 2);
-            kstep(0, IMG8_FLOATS, 0);
-            kstep(IMG8_FLOATS, 0, 1);
+            kstep(0, IMG8_FLOATS, 2, false);
+            kstep(IMG8_FLOATS, 0, 0, false);
+            kstep(0, IMG8_FLOATS, 1, false);
+            kstep(IMG8_FLOATS, 0, 2, false);
+            kstep(0, IMG8_FLOATS, 0, false);
+            kstep(IMG8_FLOATS, 0, 1, false);
         }
         if (kt < nk) {                   // (nk - kb) % 6 == 3: three more steps
-            kstep(0, IMG8_FLOATS, 2);
-            kstep(IMG8_FLOATS, 0, 0);
-            kstep(0, IMG8_FLOATS, 1);
+            kstep(0, IMG8_FLOATS, 2, false);
+            kstep(IMG8_FLOATS, 0, 0, false);
+            kstep(0, IMG8_FLOATS, 1, false);
         }
     }
     __syncthreads();                     // LDS becomes the epilogue slabs
@@ -902,9 +937,9 @@ __global__ __launch_bounds__(NT8) void wino43_conv8_kernel(const float* __restri
     if (is_split) {
         wino43_epilogue_partial(acc, lds + ws * (64 * 36), lane, (ws >> 1) * 32, (ws & 1) * 32,
                                 sp.partial + (size_t)blockIdx.x * (BMT8 * 4 * BN));
-        if (sp.arrive) wino43_combine_last<RM>(sp, tile - sp.tile_base, ep, M, Tw, W, Cout, tiles_n, ord, reinterpret_cast<int*>(lds));
+        if (sp.arrive) wino43_combine_last<RM, TU>(sp, tile - sp.tile_base, ep, M, Tw, W, Cout, tiles_n, ord, reinterpret_cast<int*>(lds));
     } else
-        wino43_epilogue<RM>(acc, lds + ws * (64 * 36), lane, m0 + (ws >> 1) * 32, n0 + (ws & 1) * 32, M, Tw, W, Cout, ep, ord);
+        wino43_epilogue<RM, TU>(acc, lds + ws * (64 * 36), lane, m0 + (ws >> 1) * 32, n0 + (ws & 1) * 32, M, Tw, W, Cout, ep, ord);
 #ifdef RPG_WINO_TRACE
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #endif
@@ -1197,7 +1232,7 @@ __global__ __launch_bounds__(NT8) void wino43_conv8p_kernel(const float* __restr
 
 // Sums the `parts` partial slabs of tail tile blockIdx.x / 32 in k order and applies BatchNorm / residual / ReLU (the separate
 // fix-up launch: RPG_TUNE_INKERNEL_FIXUP = 0, and launches whose part count is above what one workgroup should add up).
-template <bool RM>
+template <bool RM, bool TU = false>
 __global__ __launch_bounds__(256) void wino43_fixup_kernel(const float* __restrict__ partial, Epi ep, int M, int Tw, int W,
                                                            int Cout, int tiles_n, Split sp, RowOrder ord) {
     const int tt = blockIdx.x >> 5, idx = (blockIdx.x & 31) * 256 + threadIdx.x;      // 512 px x 16 channel quads
@@ -1207,7 +1242,7 @@ __global__ __launch_bounds__(256) void wino43_fixup_kernel(const float* __restri
         const float4 v = *reinterpret_cast<const float4*>(src + (size_t)i * (BMT8 * 4 * BN));
         s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
     }
-    wino43_finish_quad<RM>(s, ep, sp.tile_base + tt, idx >> 4, idx & 15, M, Tw, W, Cout, tiles_n, ord);
+    wino43_finish_quad<RM, TU>(s, ep, sp.tile_base + tt, idx >> 4, idx & 15, M, Tw, W, Cout, tiles_n, ord);
 }
 
 // U[xi][co][kh][c] = sum_j G[xi][j] * w[co][kh][j][c], evaluated in double and rounded once.
@@ -1299,6 +1334,8 @@ int launch_conv_wino(const float* x, const float* u, const float* scale, const f
                                       hipFuncAttributeMaxDynamicSharedMemorySize, LDS8_BYTES);
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wino43_conv8_kernel<true>),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, LDS8_BYTES);
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wino43_conv8_kernel<true, true>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, LDS8_BYTES);
             attr8[dev] = true;
         }
         const long T = tm8 * tn;
@@ -1315,10 +1352,14 @@ int launch_conv_wino(const float* x, const float* u, const float* scale, const f
         const bool rm_fits = ntw % BMT8 == 0 && h >= 2 && (128L / tw + 4) * h * w * cin * 4 < (1L << 31) &&
                              (32L / tw + 3) * h * w * cout * 4 < (1L << 31);
         auto rm_split = [&]() { return sp.n_split == 0 || t_main == 0; };
-        // matrix-pipe FLOP really issued: K steps x 48 MFMAs x 8 waves x 4096; RM: 2 kernel rows in the top and bottom image row
-        auto executed_flop = [&](bool rm) {
+        // The tail-uniform layout of that order (TU) where Tw = 2: the same items, so the same staging limits, but a wave's 32
+        // output tiles are one tile column of 32 images (not 16), addressed from the first one's row: 33 images of output.
+        const bool tu_fits = tw == 2 && 33L * h * w * cout * 4 < (1L << 31);
+        // matrix-pipe FLOP really issued: K steps x 48 MFMAs x 8 waves x 4096; RM: 2 kernel rows in the top and bottom image row;
+        // TU with a ragged last tile (w % 4 != 0): waves 4-7 issue 40 of the 48, 44 per wave on average
+        auto executed_flop = [&](bool rm, bool tu) {
             const double steps = rm ? (double)T / h * kpr * (3.0 * h - 2.0) : (double)T * nk;
-            return steps * 48.0 * 8.0 * 4096.0;
+            return steps * (tu && (w & 3) ? 44.0 : 48.0) * 8.0 * 4096.0;
         };
         const RowOrder ord{h, (int)ntw};
         if (tuning().wino.persist && cin % BK == 0 && (T > S || tuning().wino.persist == 2) && h >= 2) {
@@ -1349,7 +1390,7 @@ int launch_conv_wino(const float* x, const float* u, const float* scale, const f
                                    (int)M, tw, w, cout, tn, sp, ord);
                 fixup_hop_end(s, fs);
             }
-            executed = executed_flop(false);
+            executed = executed_flop(false, false);
             timing_end(slot, 2.0 * (double)n * h * w * cout * 9.0 * cin, s, executed);
             RPG_CHECK_LAUNCH("conv3x3_wino43");
             return RPG_OK;
@@ -1366,9 +1407,12 @@ int launch_conv_wino(const float* x, const float* u, const float* scale, const f
             }
         }
         // one launch: the split workgroups first, then the whole tiles
-        const bool rm = rm_fits && rm_split();
+        const bool rm = rm_fits && rm_split(), tu = rm && tu_fits;
         const dim3 grid((unsigned)(sp.n_split + t_main));
-        if (rm)
+        if (tu)
+            hipLaunchKernelGGL((wino43_conv8_kernel<true, true>), grid, dim3(NT8), LDS8_BYTES, s, x, u, h, w, cin, cout, tw, (int)M, ep, tn,
+                               sp, ord.ntw);
+        else if (rm)
             hipLaunchKernelGGL(wino43_conv8_kernel<true>, grid, dim3(NT8), LDS8_BYTES, s, x, u, h, w, cin, cout, tw, (int)M, ep, tn, sp,
                                ord.ntw);
         else
@@ -1376,7 +1420,10 @@ int launch_conv_wino(const float* x, const float* u, const float* scale, const f
                                ord.ntw);
         if (sp.n_split && !sp.arrive) {
             hipStream_t fs = fixup_hop_begin(s);
-            if (rm)
+            if (tu)
+                hipLaunchKernelGGL((wino43_fixup_kernel<true, true>), dim3((unsigned)(T - t_main) * 32), dim3(256), 0, fs, sp.partial, ep,
+                                   (int)M, tw, w, cout, tn, sp, ord);
+            else if (rm)
                 hipLaunchKernelGGL(wino43_fixup_kernel<true>, dim3((unsigned)(T - t_main) * 32), dim3(256), 0, fs, sp.partial, ep, (int)M,
                                    tw, w, cout, tn, sp, ord);
             else
@@ -1384,7 +1431,7 @@ int launch_conv_wino(const float* x, const float* u, const float* scale, const f
                                    tw, w, cout, tn, sp, ord);
             fixup_hop_end(s, fs);
         }
-        executed = executed_flop(rm);
+        executed = executed_flop(rm, tu);
     } else {
         const int tm = (int)((M + BMT - 1) / BMT);
         executed = (double)tm * tn * (3 * ((cin + BK - 1) / BK)) * 48.0 * 4.0 * 4096.0;
