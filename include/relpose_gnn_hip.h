@@ -604,6 +604,30 @@ int rpg_conv_pair_bf16(const void* x, const void* wa_ohwi, const float* scale_a,
                        const float* scale_b, const float* shift_b, void* yb, int n, int h, int w, int cin, int cout, int k,
                        int stride, int pad, void* stream);
 
+/* The streaming kernels of rpg_resnet_forward_bf16 as entry points of their own (the composite runs the same launches):
+ * rpg_nchw3_to_nhwc8_bf16: images [n][3][h][w], fp32 (x_is_bf16 = 0) or bf16 (1), -> bf16 NHWC [n][h][w][8], channels 3..7 zero,
+ * rounded to nearest even (the first step of the three-kernel stem, RPG_TUNE_FUSED_STEM = 0).  rpg_maxpool3x3s2_nhwc_bf16:
+ * nn.MaxPool2d(3, 2, 1) on bf16 NHWC [n][h][w][c] -> [n][(h-1)/2+1][(w-1)/2+1][c], c % 8 == 0, NaN propagated.
+ * rpg_global_avgpool_nhwc_bf16: nn.AdaptiveAvgPool2d(1) on bf16 [n][hw][c] -> bf16 [n][c]: the pixels summed in fp32 in ascending
+ * order, one division by hw, one rounding.  Tensors 16-byte aligned; h w < 2^31 (RPG_ERR_BAD_ARG otherwise).                                                            */
+int rpg_nchw3_to_nhwc8_bf16(const void* x_nchw, int x_is_bf16, void* y_nhwc8, int n, int h, int w, void* stream);
+int rpg_maxpool3x3s2_nhwc_bf16(const void* x, void* y, int n, int h, int w, int c, void* stream);
+int rpg_global_avgpool_nhwc_bf16(const void* x, void* y, int n, int hw, int c, void* stream);
+
+/* HOST: what the launchers did with the last bf16 convolution, paired launch, fused BasicBlock or bf16 Linear of the calling thread
+ * (rpg_conv2d_bn_act_nhwc_bf16, rpg_conv_pair_bf16, rpg_basicblock64_bf16, rpg_linear_bf16 / _ex; after a composite forward: its
+ * last launch, the fc).  The dispatcher falls back from kernel to kernel silently; tests read here which one ran.
+ *    family    0 nothing launched (the shape was refused) | 1 general buffer-load kernel | 2 interleaved buffer-load kernel |
+ *              3 LDS-DMA kernel | 4 patch kernel | 5 patch kernel, persistent | 6 paired LDS-DMA launch | 7 fused BasicBlock |
+ *              8 fused BasicBlock, persistent | 9 fused BasicBlock, two-group schedule
+ *    bm, bn    the workgroup tile of the first kernel launched
+ *    detail    families 1, 2: the K step; 3, 6: the LDS-DMA configuration (RPG_TUNE_BF16_DMA - 10); 4, 5, 7-9: weight stages
+ *    launches  kernels launched: 2 where the tail re-tiling (RPG_TUNE_BF16_TAIL) split the rows; 3 if the main patch launch ran and
+ *              every tail tile then refused the shape -- the launcher runs a second kernel family over ALL rows, while family, bm,
+ *              bn and detail still name the first kernel
+ * A diagnostic for tests and tools: a few integer stores per launch, no effect on any launch.  RPG_ERR_BAD_ARG: a null pointer.  */
+int rpg_conv_bf16_last_route(int* family, int* bm, int* bn, int* detail, int* launches);
+
 /* ------------------------------------------------------------------------------------------- */
 /* Per-kernel timing with HIP events on the launch stream (used by bench.py for the roofline).  */
 /* ------------------------------------------------------------------------------------------- */

@@ -35,6 +35,7 @@ SYMBOLS = (
     "rpg_gnn_query_workspace_bytes", "rpg_gnn_forward_query_f32", "rpg_gnn_forward_query_bf16", "rpg_gemm_last_route", "rpg_get_tuning",
     "rpg_attention_aggregate_hidden_f32", "rpg_query_pose_consensus_f64", "rpg_pose_heads_mc_f32", "rpg_mc_advance",
     "rpg_query_pose_weighted_f64", "rpg_knn_graph_uniform_f32", "rpg_retrieve_cosine_gated_f32", "rpg_track_update_f64",
+    "rpg_nchw3_to_nhwc8_bf16", "rpg_maxpool3x3s2_nhwc_bf16", "rpg_global_avgpool_nhwc_bf16", "rpg_conv_bf16_last_route",
 )
 
 
@@ -97,6 +98,10 @@ def _declare(lib: C.CDLL) -> None:
     lib.rpg_get_tuning.argtypes = [_i, C.POINTER(_i), C.POINTER(_i)]
     lib.rpg_conv2d_bn_act_nhwc_bf16.argtypes = [_vp] * 6 + [_i] * 11 + [_vp]
     lib.rpg_basicblock64_bf16.argtypes = [_vp] * 8 + [_i] * 3 + [_vp]
+    lib.rpg_nchw3_to_nhwc8_bf16.argtypes = [_vp, _i, _vp, _i, _i, _i, _vp]
+    lib.rpg_maxpool3x3s2_nhwc_bf16.argtypes = [_vp, _vp, _i, _i, _i, _i, _vp]
+    lib.rpg_global_avgpool_nhwc_bf16.argtypes = [_vp, _vp, _i, _i, _i, _vp]
+    lib.rpg_conv_bf16_last_route.argtypes = [C.POINTER(_i)] * 5
     lib.rpg_resnet_bf16_workspace_bytes.argtypes = [_i, _i, _i, C.POINTER(_i)]
     lib.rpg_resnet_bf16_workspace_bytes.restype = _sz
     lib.rpg_resnet_forward_bf16.argtypes = [C.POINTER(_vp), _i, C.POINTER(_i), C.POINTER(_i), _i, _vp, _i, _i, _i, _vp,

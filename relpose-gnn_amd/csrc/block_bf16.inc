@@ -571,6 +571,7 @@ bool launch_block64_fused(const void* x, const void* w1, const float* scale1, co
                           const float* shift2, void* y, int n, int h, int w, hipStream_t s) {
     constexpr int BM2 = 512, BM1 = BM2 + 128, NS = 4, C = 64;
     constexpr int slab_bytes = 8 * 32 * (32 + 4) * 4;         // the epilogue's staging slabs (8 waves)
+    route_begin();
     if (!x || !w1 || !w2 || !scale1 || !shift1 || !scale2 || !shift2 || !y || n <= 0 || w < 4 || h < 1 ||
         !rpg::aligned16(scale1) || !rpg::aligned16(shift1) || !rpg::aligned16(scale2) || !rpg::aligned16(shift2))
         return false;
@@ -627,6 +628,7 @@ bool launch_block64_fused(const void* x, const void* w1, const float* scale1, co
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(block64_bf16_fused_kernel<BM2, 5, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
             once_pp[dev] = true;
         }
+        route_note(ROUTE_BLOCK_TWO_GROUP, BM2, C, 5);
         hipLaunchKernelGGL((block64_bf16_fused_kernel<BM2, 5, false, true>), dim3(a.n_tiles), dim3(512), lds + C * 64, s, a, reinterpret_cast<const __bf16*>(w1),
                            reinterpret_cast<const __bf16*>(w2), ep);
         return true;
@@ -635,11 +637,13 @@ bool launch_block64_fused(const void* x, const void* w1, const float* scale1, co
     // order needs blockIdx & 7 to be the XCD of every tile a workgroup walks); the epilogue slabs must fit buffer 1
     const int pgrid = rpg::num_cus() & ~7;
     if ((rpg::tuning().bf16.fuse_block & 2) && pgrid >= 8 && a.n_tiles > pgrid && a.patch_bytes >= slab_bytes) {
+        route_note(ROUTE_BLOCK_PERSIST, BM2, C, NS);
         hipLaunchKernelGGL((block64_bf16_fused_kernel<BM2, NS, true>), dim3(pgrid), dim3(512), lds, s, a, reinterpret_cast<const __bf16*>(w1),
                            reinterpret_cast<const __bf16*>(w2), ep);
         return true;
     }
     auto kern = block64_bf16_fused_kernel<BM2, NS, false>;
+    route_note(ROUTE_BLOCK, BM2, C, NS);
     hipLaunchKernelGGL(kern, dim3(a.n_tiles), dim3(512), lds, s, a, reinterpret_cast<const __bf16*>(w1), reinterpret_cast<const __bf16*>(w2), ep);
     return true;
 }

@@ -59,6 +59,24 @@ struct ConvArgsB {
     int img_elems = 0;         // elements between consecutive images; 0 = H * W * Cin (a Linear whose A rows have a pitch lda > k)
 };
 
+// What the launchers did with the last bf16 convolution / pair / fused block / Linear of this thread (rpg_conv_bf16_last_route; host
+// side only: a few integer stores per launch, nothing a kernel or a launch depends on).  The dispatcher falls back silently, so a
+// test that means a kernel reads here that it ran.  family / bm / bn / detail are those of the FIRST kernel launched (the main
+// launch where the tail re-tiling splits the rows); launches counts the kernels.
+enum RouteFamily {
+    ROUTE_NONE = 0, ROUTE_GENERAL = 1, ROUTE_INTERLEAVED = 2, ROUTE_DMA = 3, ROUTE_PATCH = 4, ROUTE_PATCH_PERSIST = 5, ROUTE_PAIR = 6,
+    ROUTE_BLOCK = 7, ROUTE_BLOCK_PERSIST = 8, ROUTE_BLOCK_TWO_GROUP = 9
+};
+struct RouteRecord {
+    int family, bm, bn, detail, launches;
+};
+thread_local RouteRecord t_route{};
+
+inline void route_begin() { t_route = RouteRecord{}; }
+inline void route_note(int family, int bm, int bn, int detail) {
+    if (t_route.launches++ == 0) { t_route.family = family; t_route.bm = bm; t_route.bn = bn; t_route.detail = detail; }
+}
+
 __device__ __forceinline__ uint4 ld16_or_zero(const __bf16* p, bool ok) {
     uint4 v = make_uint4(0u, 0u, 0u, 0u);
     if (ok) v = *reinterpret_cast<const uint4*>(p);
@@ -1168,6 +1186,7 @@ void launch_tile(const ConvArgsB& a, const __bf16* w, int M, int N, int K, const
         }
     }
     const int tn = (N + BN - 1) / BN, tm = (M + BM - 1) / BM;
+    route_note(ROUTE_GENERAL, BM, BN, BK);
     hipLaunchKernelGGL(kern, dim3(tm * tn), dim3(NT), lds, s, a, w, M, N, K, ep, tn);
 }
 
@@ -1183,6 +1202,7 @@ void launch_fast(const ConvArgsB& a, const __bf16* w, int M, int N, int K, const
         }
     }
     const int tn = (N + BN - 1) / BN, tm = (M + BM - 1) / BM;
+    route_note(ROUTE_INTERLEAVED, BM, BN, 64);
     hipLaunchKernelGGL(kern, dim3(tm * tn), dim3(NT), lds, s, a, w, M, N, K, ep, tn);
 }
 
@@ -1199,6 +1219,7 @@ void launch_dma(const ConvArgsB& a, const __bf16* w, int M, int N, int K, const 
         once[dev] = true;
     }
     const int tn = (N + BN - 1) / BN, tm = (M + BM - 1) / BM;
+    route_note(ROUTE_DMA, BM, BN, -1);                       // (launch_dma_config puts the configuration into detail)
     hipLaunchKernelGGL(kern, dim3(tm * tn), dim3(64 * WM * WN), lds, s, a, w, M, N, K, ep, tn);
 }
 
@@ -1216,6 +1237,7 @@ void launch_dma_pair(const DmaOne& c1in, const DmaOne& c2in, hipStream_t s) {
     DmaOne c1 = c1in, c2 = c2in;
     c1.tiles_n = (c1.N + BN - 1) / BN; c2.tiles_n = (c2.N + BN - 1) / BN;
     const int t1 = ((c1.M + BM - 1) / BM) * c1.tiles_n, t2 = ((c2.M + BM - 1) / BM) * c2.tiles_n;
+    route_note(ROUTE_PAIR, BM, BN, BK == 32 ? 7 : 0);        // detail: the LDS-DMA configuration whose tile this is
     hipLaunchKernelGGL(kern, dim3(t1 + t2), dim3(64 * WM * WN), lds, s, c1, c2, t1);
 }
 
@@ -1287,6 +1309,7 @@ bool launch_patch(const ConvArgsB& c, const __bf16* w, int nimg, int M, int N, c
         a.trace = tbuf;
     }
 #endif
+    route_note(PS ? ROUTE_PATCH_PERSIST : ROUTE_PATCH, BM, BN, NS);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, s, a, w, ep);
 #ifdef RPG_PATCH_TRACE
     if (tracing) {
@@ -1326,7 +1349,7 @@ bool launch_patch(const ConvArgsB& c, const __bf16* w, int nimg, int M, int N, c
 
 // configuration table of the LDS-DMA kernel (index = RPG_TUNE_BF16_DMA - 10); returns false if the index is unknown or the
 // shape is not eligible for it (Cin % BK)
-bool launch_dma_config(int cfg, const ConvArgsB& a, const __bf16* w, int M, int N, int K, const EpiB& ep, hipStream_t s) {
+bool launch_dma_config_tile(int cfg, const ConvArgsB& a, const __bf16* w, int M, int N, int K, const EpiB& ep, hipStream_t s) {
     const bool k64 = a.Cin % 64 == 0, k32 = a.Cin % 32 == 0;
     switch (cfg) {
         case 0: if (!k64) return false; launch_dma<256, 256, 2, 4, 64, 2>(a, w, M, N, K, ep, s); return true;   // 128 KB, wave 128 x 64
@@ -1344,6 +1367,12 @@ bool launch_dma_config(int cfg, const ConvArgsB& a, const __bf16* w, int M, int 
         // fatter workgroups lose more to the one-workgroup-per-CU prologue / epilogue than the wave tile wins in LDS reads)
         default: return false;
     }
+}
+
+bool launch_dma_config(int cfg, const ConvArgsB& a, const __bf16* w, int M, int N, int K, const EpiB& ep, hipStream_t s) {
+    if (!launch_dma_config_tile(cfg, a, w, M, N, K, ep, s)) return false;
+    t_route.detail = cfg;
+    return true;
 }
 
 // ---- streaming kernels on bf16 NHWC tensors (8 elements = 16 bytes per lane) ----
@@ -1419,6 +1448,32 @@ __global__ __launch_bounds__(NT) void global_avgpool_bf16_kernel(const uint4* __
     }
 }
 
+// The launches of the three streaming kernels: what the composite forward runs and what their entry points
+// (rpg_nchw3_to_nhwc8_bf16, rpg_maxpool3x3s2_nhwc_bf16, rpg_global_avgpool_nhwc_bf16) run.
+void launch_nchw3_to_nhwc8_bf16(const void* x_nchw, int x_is_bf16, void* y, int n, int h, int w, hipStream_t s) {
+    const long npix = (long)n * h * w;
+    if (x_is_bf16)
+        hipLaunchKernelGGL(nchw3_to_nhwc8_bf16_kernel<__bf16>, dim3(capped_grid(npix)), dim3(NT), 0, s,
+                           reinterpret_cast<const __bf16*>(x_nchw), reinterpret_cast<uint4*>(y), npix, h * w);
+    else
+        hipLaunchKernelGGL(nchw3_to_nhwc8_bf16_kernel<float>, dim3(capped_grid(npix)), dim3(NT), 0, s,
+                           reinterpret_cast<const float*>(x_nchw), reinterpret_cast<uint4*>(y), npix, h * w);
+}
+
+void launch_maxpool3x3s2_bf16(const void* x, void* y, int n, int h, int w, int c, hipStream_t s) {
+    const int c8 = c / 8, ho = rpg::conv_out(h, 3, 2, 1), wo = rpg::conv_out(w, 3, 2, 1);
+    const long total = (long)n * ho * wo * c8;
+    hipLaunchKernelGGL(maxpool3x3s2_bf16_kernel, dim3(capped_grid(total)), dim3(NT), 0, s, reinterpret_cast<const uint4*>(x),
+                       reinterpret_cast<uint4*>(y), h, w, c8, ho, wo, total);
+}
+
+void launch_global_avgpool_bf16(const void* x, void* y, int n, int hw, int c, hipStream_t s) {
+    const int c8 = c / 8;
+    const long total = (long)n * c8;
+    hipLaunchKernelGGL(global_avgpool_bf16_kernel, dim3(capped_grid(total)), dim3(NT), 0, s, reinterpret_cast<const uint4*>(x),
+                       reinterpret_cast<uint4*>(y), hw, c8, total);
+}
+
 }  // namespace
 
 namespace rpg {
@@ -1463,6 +1518,7 @@ int launch_linear_bf16(const void* a, const void* w, const float* bias, const fl
 int launch_linear_bf16_ex(const void* a, int lda, const void* w, const float* bias, const float* res, const int64_t* res_idx,
                           const float* res2, const int64_t* res2_idx, int ldr, const LinearBf16Out& o, int m, int k, int n_out,
                           int relu, hipStream_t s) {
+    route_begin();
     if (!a || !w || (!o.out && !o.out2) || m <= 0 || k <= 0 || n_out <= 0 || (k & 7) || (n_out & 3) || lda < k || (lda & 7) ||
         !aligned16(a) || !aligned16(w) || (o.out && !aligned16(o.out)) || (bias && !aligned16(bias)) ||
         (res && (!aligned16(res) || (ldr & 3) || ldr < n_out)) || (res2 && (!res || !res2_idx || !aligned16(res2))) ||
@@ -1497,6 +1553,7 @@ int launch_linear_bf16_ex(const void* a, int lda, const void* w, const float* bi
 // [n][ho][wo][cout], bf16, BN folded, ReLU on A only per `relu_a`); false: not eligible (the caller launches them one by one)
 bool launch_conv_pair_bf16(const void* x, const void* wa, const float* sa, const float* ha, void* ya, const void* wb_, const float* sb,
                            const float* hb, void* yb, int n, int h, int wd, int cin, int cout, int k, int stride, int pad, hipStream_t s) {
+    route_begin();
     if (!rpg::tuning().bf16.pair || rpg::tuning().bf16.dma != 1 || !x || !wa || !wb_ || !ya || !yb || n <= 0 || (cin & 31) || (cout & 3)) return false;
     const int ho = conv_out(h, k, stride, pad), wo = conv_out(wd, k, stride, pad);
     if (ho <= 0 || wo <= 0 || ho != conv_out(h, 1, stride, 0) || wo != conv_out(wd, 1, stride, 0)) return false;
@@ -1527,6 +1584,7 @@ bool launch_conv_pair_bf16(const void* x, const void* wa, const float* sa, const
 int launch_conv_bf16(const void* x, const void* w, const float* scale, const float* shift, const void* residual, void* y,
                      int n, int h, int wd, int cin, int cout, int kh, int kw, int stride, int pad, int relu, int out_f32,
                      hipStream_t s) {
+    route_begin();
     if (!x || !w || !y || n <= 0 || h <= 0 || wd <= 0 || cin <= 0 || cout <= 0 || kh <= 0 || kw <= 0 || stride <= 0 ||
         pad < 0 || (cin & 7) || (cout & 3) || !aligned16(x) || !aligned16(w) || !aligned16(y) ||
         (scale && !aligned16(scale)) || (shift && !aligned16(shift)) || (residual && (reinterpret_cast<uintptr_t>(residual) & 7)))
@@ -1703,20 +1761,11 @@ static int resnet_forward_bf16_impl(const void* const* tensors, int n_tensors, c
     } else {
         // three-kernel stem (RPG_TUNE_FUSED_STEM = 0, non-64-channel stems, no stem pack): re-layout (from fp32, or from images
         // the host already rounded to bf16 -- the same bits either way), generic convolution on the 8-channel image, max-pool
-        const long npix = (long)n * h * w;
-        if (x_is_bf16)
-            hipLaunchKernelGGL(nchw3_to_nhwc8_bf16_kernel<__bf16>, dim3(capped_grid(npix)), dim3(NT), 0, s,
-                               reinterpret_cast<const __bf16*>(x_nchw_any), reinterpret_cast<uint4*>(B.in), npix, h * w);
-        else
-            hipLaunchKernelGGL(nchw3_to_nhwc8_bf16_kernel<float>, dim3(capped_grid(npix)), dim3(NT), 0, s, x_nchw,
-                               reinterpret_cast<uint4*>(B.in), npix, h * w);
+        launch_nchw3_to_nhwc8_bf16(x_nchw_any, x_is_bf16, B.in, n, h, w, s);
         if ((rc = rpg::launch_conv_bf16(B.in, tensors[0], (const float*)tensors[1], (const float*)tensors[2], nullptr, B.stem, n, h,
                                         w, 8, planes[0], 7, 7, 2, 3, 1, 0, s)) != RPG_OK)
             return rc;
-        const int c8 = planes[0] / 8;
-        const long total = (long)n * B.h2 * B.w2 * c8;
-        hipLaunchKernelGGL(maxpool3x3s2_bf16_kernel, dim3(capped_grid(total)), dim3(NT), 0, s,
-                           reinterpret_cast<const uint4*>(B.stem), reinterpret_cast<uint4*>(buf[0]), B.h1, B.w1, c8, B.h2, B.w2, total);
+        launch_maxpool3x3s2_bf16(B.stem, buf[0], n, B.h1, B.w1, planes[0], s);
     }
     ti += 3;
     int cur = 0;
@@ -1796,12 +1845,7 @@ static int resnet_forward_bf16_impl(const void* const* tensors, int n_tensors, c
         cur = (cur + 2) & 3;
     }
     // the walk has ended: b.cin x b.h x b.w is the last activation tensor
-    {
-        const int c8 = b.cin / 8;
-        const long total = (long)n * c8;
-        hipLaunchKernelGGL(global_avgpool_bf16_kernel, dim3(capped_grid(total)), dim3(NT), 0, s,
-                           reinterpret_cast<const uint4*>(buf[cur]), reinterpret_cast<uint4*>(B.pool), b.h * b.w, c8, total);
-    }
+    launch_global_avgpool_bf16(buf[cur], B.pool, n, b.h * b.w, b.cin, s);
     // fc as a 1x1 convolution on a 1x1 image: [n][1][1][cin] x [feat][1][1][cin], bias in `shift`, fp32 output
     return rpg::launch_conv_bf16(B.pool, tensors[ti], nullptr, (const float*)tensors[ti + 1], nullptr, feat, n, 1, 1, b.cin,
                                  feat_dim, 1, 1, 1, 0, 0, 1, s);
@@ -1828,6 +1872,39 @@ extern "C" int rpg_basicblock64_bf16(const void* x, const void* w1_ohwi, const f
     if (!x || !y || x == y || !rpg::aligned16(x) || !rpg::aligned16(y) || !rpg::aligned16(w1_ohwi) || !rpg::aligned16(w2_ohwi)) return RPG_ERR_BAD_ARG;
     if (!launch_block64_fused(x, w1_ohwi, scale1, shift1, w2_ohwi, scale2, shift2, y, n, h, w, rpg::as_stream(stream))) return RPG_ERR_BAD_ARG;
     RPG_CHECK_LAUNCH("basicblock64_bf16");
+    return RPG_OK;
+}
+
+// The streaming kernels of the composite forward as entry points of their own (the composite calls the same launch helpers).
+extern "C" int rpg_nchw3_to_nhwc8_bf16(const void* x_nchw, int x_is_bf16, void* y_nhwc8, int n, int h, int w, void* stream) {
+    if (!x_nchw || !y_nhwc8 || n <= 0 || h <= 0 || w <= 0 || (long)h * w >= (1L << 31) || !rpg::aligned16(y_nhwc8) ||
+        (reinterpret_cast<uintptr_t>(x_nchw) & (x_is_bf16 ? 1 : 3)))
+        return RPG_ERR_BAD_ARG;
+    launch_nchw3_to_nhwc8_bf16(x_nchw, x_is_bf16, y_nhwc8, n, h, w, rpg::as_stream(stream));
+    RPG_CHECK_LAUNCH("nchw3_to_nhwc8_bf16");
+    return RPG_OK;
+}
+
+extern "C" int rpg_maxpool3x3s2_nhwc_bf16(const void* x, void* y, int n, int h, int w, int c, void* stream) {
+    if (!x || !y || n <= 0 || h <= 0 || w <= 0 || (long)h * w >= (1L << 31) || c <= 0 || (c & 7) || !rpg::aligned16(x) ||
+        !rpg::aligned16(y))
+        return RPG_ERR_BAD_ARG;
+    launch_maxpool3x3s2_bf16(x, y, n, h, w, c, rpg::as_stream(stream));
+    RPG_CHECK_LAUNCH("maxpool3x3s2_bf16");
+    return RPG_OK;
+}
+
+extern "C" int rpg_global_avgpool_nhwc_bf16(const void* x, void* y, int n, int hw, int c, void* stream) {
+    if (!x || !y || n <= 0 || hw <= 0 || c <= 0 || (c & 7) || !rpg::aligned16(x) || !rpg::aligned16(y))
+        return RPG_ERR_BAD_ARG;
+    launch_global_avgpool_bf16(x, y, n, hw, c, rpg::as_stream(stream));
+    RPG_CHECK_LAUNCH("global_avgpool_bf16");
+    return RPG_OK;
+}
+
+extern "C" int rpg_conv_bf16_last_route(int* family, int* bm, int* bn, int* detail, int* launches) {
+    if (!family || !bm || !bn || !detail || !launches) return RPG_ERR_BAD_ARG;
+    *family = t_route.family; *bm = t_route.bm; *bn = t_route.bn; *detail = t_route.detail; *launches = t_route.launches;
     return RPG_OK;
 }
 

@@ -1001,6 +1001,20 @@ def gemm_last_route() -> Dict[str, object]:
     return rec
 
 
+BF16_ROUTE_FAMILIES = ("none", "general", "interleaved", "dma", "patch", "patch_persistent", "pair", "block", "block_persistent",
+                       "block_two_group")
+
+
+def conv_bf16_last_route() -> Dict[str, object]:
+    """What the launchers did with this thread's last bf16 convolution / paired launch / fused block / bf16 Linear
+    (rpg_conv_bf16_last_route): family (one of BF16_ROUTE_FAMILIES; "none": the shape was refused), bm, bn (the tile of the first
+    kernel launched), detail (K step | LDS-DMA configuration | weight stages), launches (2: the tail re-tiling split the rows)."""
+    v = [C.c_int() for _ in range(5)]
+    L.check(L.lib().rpg_conv_bf16_last_route(*[C.byref(f) for f in v]), "conv_bf16_last_route")
+    fam, bm, bn, detail, launches = (int(f.value) for f in v)
+    return {"family": BF16_ROUTE_FAMILIES[fam], "bm": bm, "bn": bn, "detail": detail, "launches": launches}
+
+
 def attention_rows(gtp: torch.Tensor) -> torch.Tensor:
     gtp = _req(gtp, "gtp")
     r, c3 = gtp.shape

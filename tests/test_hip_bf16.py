@@ -29,6 +29,19 @@ def _rand(*shape, seed=0, scale=1.0):
     return torch.randn(*shape, generator=torch.Generator().manual_seed(seed)) * scale
 
 
+def _assert_route(dev, keys, shape, f32out, family):
+    """The launch just made ran the kernel family the case means: the observed route (rpg_conv_bf16_last_route) equals the
+    dispatcher's rule restated in bf16_sweep_ref.py for this device, and is of ``family``.  keys: tuning key names -> values;
+    shape: (n, h, w, cin, cout, k, stride, pad)."""
+    import bf16_sweep_ref as B
+    from relpose_gnn_amd import ops
+    r = ops.conv_bf16_last_route()
+    got = (r["family"], r["bm"], r["bn"], r["detail"], r["launches"])
+    want = B.bf16_route(keys, *shape, False, f32out, torch.cuda.get_device_properties(dev).multi_processor_count)
+    assert got == want and got[0] == family, (keys, shape, "observed", got, "restated", want, "meant", family)
+    return got
+
+
 @pytest.mark.parametrize("n,h,w,cin,cout,k,stride,pad,res,relu,f32out", [
     (2, 9, 11, 8, 16, 3, 1, 1, False, True, False),       # ragged M, K=72 (K tail), tiny channels
     (1, 16, 16, 8, 64, 7, 2, 3, False, True, False),      # stem shape with Cin padded to 8
@@ -243,10 +256,16 @@ def test_conv_bf16_dma_configs(dev, cfg, n, h, w, cin, cout, k, stride, pad, res
         ref = ref + r.float()
     if relu:
         ref = F.relu(ref)
-    with ops.tuned({ops.TUNE_BF16_DMA: 10 + cfg}):
+    # (the patch kernel off: by shape it takes the 40 layer-1 images -- 125,440 rows -- in FRONT of a forced LDS-DMA configuration,
+    # and did in this test until the route was observed)
+    with ops.tuned({ops.TUNE_BF16_DMA: 10 + cfg, ops.TUNE_BF16_PATCH: 0}):
         y = ops.conv2d_bn_act_nhwc_bf16(x.permute(0, 2, 3, 1).contiguous().to(dev), wt.permute(0, 2, 3, 1).contiguous().to(dev),
                                         scale.to(dev), shift.to(dev), None if r is None else r.permute(0, 2, 3, 1).contiguous().to(dev),
                                         stride=stride, pad=pad, relu=relu, out_f32=f32out)
+        # the configuration itself where Cin is a multiple of its K step (64: configurations 0-5 and 8), else the fall-back
+        eligible = cin % (32 if cfg in (6, 7, 9) else 64) == 0
+        _assert_route(dev, {"BF16_DMA": 10 + cfg, "BF16_PATCH": 0}, (n, h, w, cin, cout, k, stride, pad), f32out,
+                      "dma" if eligible else ("interleaved" if cin % 64 == 0 else "general"))
     assert rel_err(y.float().cpu().permute(0, 3, 1, 2), ref) < (1e-4 if f32out else 1e-2)
 
 
@@ -256,9 +275,9 @@ def test_conv_bf16_dma_configs(dev, cfg, n, h, w, cin, cout, k, stride, pad, res
     (24, 28, 28, 128, 128, True, True),     # layer-2 shape
     (9, 14, 14, 256, 256, False, True),     # layer-3 shape: tiles span 2 images, ragged M (1764)
     (70, 7, 7, 512, 512, True, True),       # layer-4 shape: tiles span 6-7 images (zero rows between them), 16 chunks
-    (3, 13, 17, 192, 72, True, False),      # odd sizes, ragged N, 6 chunks
+    (3, 13, 17, 192, 72, True, False),      # odd sizes, ragged N, 6 chunks (patch kernel under mode 3 only: see _patch_kernel_case)
     (5, 8, 11, 64, 320, False, True),       # 256x341's last stage; N = 320: two channel tiles, the second ragged
-    (2, 5, 3, 128, 128, True, True),        # tiny image: 3 of 16 slots per patch row used, the whole batch inside one tile
+    (2, 5, 3, 128, 128, True, True),        # tiny image, a FALL-BACK case: no patch tile takes it (244 / 125 pieces, 64 fit), the interleaved kernel runs
     (1, 64, 86, 64, 64, False, True),       # 256x341's first stage: 96 slots per row
     (256, 14, 14, 256, 256, True, True),    # 196 tiles of 256 x 256: the wide tile (and its four-stage form) is dispatched
     (300, 7, 7, 512, 512, False, True),     # 58 x 2 tiles of 256 x 256 is too few -> 256 x 128; 53-KB patches: three stages only
@@ -271,7 +290,7 @@ def test_conv3x3_bf16_patch_kernel(dev, mode, n, h, w, cin, cout, res, relu):
     (70, 56, 56, 64, 64, True, True),       # layer 1: 429 tiles of 512 rows on 256 CUs (1.7 rounds: workgroups with 1 and with 2 tiles), ragged last tile
     (171, 56, 56, 64, 64, False, True),     # 1048 tiles: 4.1 rounds, the stage rotation of the four-stage form wraps across tiles
     (100, 40, 40, 64, 64, True, True),      # 48 slots per row, 18 patch rows: 313 tiles, ragged
-    (300, 13, 17, 64, 64, True, False),     # small odd images: tiles span 3 images, 130 tiles only -> not eligible, one workgroup per tile
+    (300, 13, 17, 64, 64, True, False),     # small odd images: a FALL-BACK case -- the 512 x 64 tile's patch is 80 pieces here (64 fit), the LDS-DMA kernel runs both times
     (200, 28, 28, 128, 40, False, True),    # 307 tiles, 4 chunks per tile (the wrap happens in front of chunk 3), ragged N = 40 inside the one channel tile
 ])
 def test_conv3x3_bf16_patch_kernel_persistent(dev, n, h, w, cin, cout, res, relu):
@@ -301,11 +320,20 @@ def _patch_kernel_case(dev, mode, persist, n, h, w, cin, cout, res, relu):
         ref = F.relu(ref)
     args = (x.permute(0, 2, 3, 1).contiguous().to(dev), wt.permute(0, 2, 3, 1).contiguous().to(dev), scale.to(dev), shift.to(dev),
             None if r is None else r.permute(0, 2, 3, 1).contiguous().to(dev))
+    # The route is observed.  Shapes of these lists that NO by-width patch tile takes (found when the route was first read; they had
+    # run these kernels all along): 2 x 5 x 3 (244 pieces on the 512 x 128 tile, 125 on 256 x 128; 64 fit) under every mode; 13 x 17 with
+    # Cout = 72 (512 x 128: 80 pieces), 64 x 86 and 300 x 13 x 17 with Cout = 64 (512 x 64: 66 and 80 pieces) under modes 2 and 12 --
+    # the 256 x 128 tile of mode 3 takes 13 x 17 and 64 x 86.  tests/test_hip_bf16_sweep.py runs every patch tile on its smallest maps.
+    shape = (n, h, w, cin, cout, 3, 1, 1)
+    small = (n, h, w) == (2, 5, 3) or (mode != 3 and (n, h, w) in ((3, 13, 17), (1, 64, 86)))
+    family = "dma" if (n, h, w) == (300, 13, 17) else "interleaved" if small else "patch"
     with ops.tuned({ops.TUNE_BF16_PATCH: mode, ops.TUNE_BF16_PERSIST: 0}):
         y = ops.conv2d_bn_act_nhwc_bf16(*args, stride=1, pad=1, relu=relu)
+        _assert_route(dev, {"BF16_PATCH": mode, "BF16_PERSIST": 0}, shape, False, family)
     if persist:
         with ops.tuned({ops.TUNE_BF16_PATCH: mode, ops.TUNE_BF16_PERSIST: 1}):
             y1 = ops.conv2d_bn_act_nhwc_bf16(*args, stride=1, pad=1, relu=relu)
+            _assert_route(dev, {"BF16_PATCH": mode, "BF16_PERSIST": 1}, shape, False, "dma" if family == "dma" else "patch_persistent")
         assert torch.equal(y1, y)
         y = y1
     got = y.float().cpu().permute(0, 3, 1, 2)
@@ -640,6 +668,8 @@ def test_patch_kernel_tail_retiling_is_bit_identical(dev, n, h, w, c, res):
     for tail in (3, 0):                                   # both re-tilings on (layer-2 and layer-3 style) / one launch
         with ops.tuned({ops.TUNE_BF16_TAIL: tail}):
             outs[tail] = ops.conv2d_bn_act_nhwc_bf16(x, wt, sc, sh, r, stride=1, pad=1, relu=True)
+            route = _assert_route(dev, {"BF16_TAIL": tail}, (n, h, w, c, c, 3, 1, 1), False, "patch")
+            assert route[4] == (2 if tail else 1)         # the split happened / one launch
     assert torch.equal(outs[3], outs[0])
     for i in (0, n // 2, n - 1):                               # first image, one in the middle, the last (tail launch)
         ref = F.conv2d(x[i:i + 1].float().permute(0, 3, 1, 2).cpu(), wt.float().permute(0, 3, 1, 2).cpu(), padding=1)

@@ -57,7 +57,7 @@ SHAPES = {
     "stem7x7": (1, 16, 16, 8, 64, 7, 2, 3),             # the stem's convolution on the 8-channel image
     "ragged_s2": (3, 13, 17, 192, 72, 3, 2, 1),         # ragged M (189) and N (72), 3 K steps per tap (odd), padding taps, stride 2
     "ragged_s1": (5, 23, 19, 64, 72, 3, 1, 1),          # ragged M (2185) and N, odd number of K steps per workgroup, stride 1
-    "ragged_192": (3, 13, 17, 192, 72, 3, 1, 1),        # the patch kernel's odd case: 6 chunks, ragged N
+    "ragged_192": (3, 13, 17, 192, 72, 3, 1, 1),        # the patch kernel's odd case: 6 chunks, ragged N (on the 256 x 128 tile, mode 3, only)
     "cin96": (5, 9, 11, 96, 40, 3, 1, 1),               # only the 32-wide K step configurations apply
     "ds1x1": (2, 14, 14, 64, 128, 1, 2, 0),             # downsample 1x1 / stride 2: a single K step
     "layer1": (40, 56, 56, 64, 64, 3, 1, 1),            # model shapes (224 x 224 input)
@@ -65,7 +65,8 @@ SHAPES = {
     "layer2_64": (64, 28, 28, 128, 128, 3, 1, 1),       # 392 tiles of 128 x 128
     "layer3": (9, 14, 14, 256, 256, 3, 1, 1),           # ragged M (1764), 36 K steps of 64
     "layer4": (8, 7, 7, 512, 512, 3, 1, 1),
-    "tiny_img": (2, 5, 3, 128, 128, 3, 1, 1),           # 3 of 16 patch slots per row used, the whole batch inside one tile
+    "tiny_img": (2, 5, 3, 128, 128, 3, 1, 1),           # a FALL-BACK case: 244 patch pieces on the 512 x 128 tile, 125 on 256 x 128 (64 fit) -- no
+                                                        # patch tile takes it, 30 rows are too few for the LDS-DMA kernel: the interleaved kernel runs
     "fc": (37, 1, 1, 512, 2048, 1, 1, 0),               # the fc as a 1x1 convolution on a 1x1 image (fp32 output in the model)
     "persist_ragged": (100, 40, 40, 64, 64, 3, 1, 1),   # 313 tiles of 512 rows (more than one round: the persistent form), ragged
     "tail_l3_res": (400, 14, 14, 256, 256, 3, 1, 1),    # the shapes of test_patch_kernel_tail_retiling_is_bit_identical
@@ -97,14 +98,23 @@ def _nhwc(t, dev):
     return None if t is None else t.permute(0, 2, 3, 1).contiguous().to(dev)
 
 
-def _conv_check(dev, name, dist, res, relu, tuning, out_f32=False, what=""):
+def _conv_check(dev, name, dist, res, relu, tuning, out_f32=False, what="", family=None):
+    """family: the kernel family the case is meant to run ("patch", "dma", ...).  The observed route (rpg_conv_bf16_last_route) must
+    then be that family AND equal the dispatcher's rule restated in bf16_sweep_ref.py for this device."""
+    import bf16_sweep_ref as B
     from relpose_gnn_amd import ops
     x, wt, scale, shift, r, ref, memo = _conv_case(name, dist, res)
     stride, pad = SHAPES[name][6], SHAPES[name][7]
     with ops.tuned(tuning):
         y = ops.conv2d_bn_act_nhwc_bf16(_nhwc(x, dev), _nhwc(wt, dev), scale.to(dev), shift.to(dev), _nhwc(r, dev), stride=stride,
                                         pad=pad, relu=relu, out_f32=out_f32)
+        route = ops.conv_bf16_last_route()
         torch.cuda.synchronize()
+    if family is not None:
+        got = (route["family"], route["bm"], route["bn"], route["detail"], route["launches"])
+        cus = torch.cuda.get_device_properties(dev).multi_processor_count
+        want = B.bf16_route({ops.TUNING_KEYS[k]: v for k, v in tuning.items()}, *SHAPES[name], res, out_f32, cus)
+        assert got == want and got[0] == family, (name, what, "observed", got, "restated", want, "meant", family)
     tag = f"conv {name} {dist} res={int(bool(res))} relu={int(relu)} {what}"
     if out_f32:
         assert y.dtype == torch.float32
@@ -172,9 +182,14 @@ def test_conv_general_kernel_k_step(dev, name, dist, bk):
 def test_conv_dma_configs(dev, cfg, name, dist, res, relu, f32out):
     """RPG_TUNE_BF16_DMA = 10 + cfg: every configuration of the LDS-DMA kernel (tile, wave grid, K step, LDS images); where one is
     not eligible (Cin % K step) the launcher falls back and the check still holds.
-    Observed on an MI355X for the fp32 output (fc, wide): c_observed 1.62 against c_ref 1.24 on every configuration."""
+    Observed on an MI355X for the fp32 output (fc, wide): c_observed 1.62 against c_ref 1.24 on every configuration.
+    The route is observed: the configuration where Cin is a multiple of its K step, else the fall-back the rule names."""
+    import bf16_sweep_ref as B
     from relpose_gnn_amd import ops
-    _conv_check(dev, name, dist, res, relu, {ops.TUNE_BF16_DMA: 10 + cfg}, f32out, f"dma={cfg}")
+    bk = B.DMA_CONFIGS[cfg][2]
+    fallback = "interleaved" if SHAPES[name][3] % 64 == 0 else "general"          # (Cin = 96: configurations 6, 7 and 9 only)
+    _conv_check(dev, name, dist, res, relu, {ops.TUNE_BF16_DMA: 10 + cfg}, f32out, f"dma={cfg}",
+                family="dma" if SHAPES[name][3] % bk == 0 else fallback)
 
 
 @pytest.mark.parametrize("mode", [2, 3, 12], ids=["by_width", "tile256x128", "by_width_3stages"])
@@ -184,9 +199,14 @@ def test_conv_dma_configs(dev, cfg, name, dist, res, relu, f32out):
     ids=lambda v: str(v))
 def test_conv_patch_kernel(dev, mode, name, dist, res, relu):
     """RPG_TUNE_BF16_PATCH 2 / 3 / 12: the patch kernel wherever eligible, by output width, on the 256 x 128 tile, and without
-    the four-weight-stage form."""
+    the four-weight-stage form.  The route is observed: the patch kernel, but for two fall-backs to the interleaved kernel that ran
+    unnoticed before the route was read -- tiny_img under every mode, and ragged_192 under the by-width modes (Cout = 72 asks for
+    the 512 x 128 tile, whose patch on 13 x 17 maps is 40 rows of 32 slots = 80 pieces; the 256 x 128 tile of mode 3 takes it, 46
+    pieces).  tests/test_hip_bf16_sweep.py runs the patch tiles on their smallest maps."""
     from relpose_gnn_amd import ops
-    _conv_check(dev, name, dist, res, relu, {ops.TUNE_BF16_PATCH: mode}, what=f"patch={mode}")
+    fallback = name == "tiny_img" or (name == "ragged_192" and mode != 3)
+    _conv_check(dev, name, dist, res, relu, {ops.TUNE_BF16_PATCH: mode}, what=f"patch={mode}",
+                family="interleaved" if fallback else "patch")
 
 
 @pytest.mark.parametrize("name,dist,res,relu", [("persist_ragged", "wide", True, True), ("persist_ragged", "unit", False, True),
@@ -195,7 +215,8 @@ def test_conv_patch_kernel_persistent(dev, name, dist, res, relu):
     """RPG_TUNE_BF16_PERSIST = 1 with the patch kernel: 313 ragged tiles on 256 CUs (the persistent form walks them), and the
     layer-1 shape whose 245 tiles fit one round (not eligible: one workgroup per tile)."""
     from relpose_gnn_amd import ops
-    _conv_check(dev, name, dist, res, relu, {ops.TUNE_BF16_PATCH: 2, ops.TUNE_BF16_PERSIST: 1}, what="persistent")
+    _conv_check(dev, name, dist, res, relu, {ops.TUNE_BF16_PATCH: 2, ops.TUNE_BF16_PERSIST: 1}, what="persistent",
+                family="patch_persistent" if name == "persist_ragged" else "patch")
 
 
 @pytest.mark.parametrize("lean", [1, 0], ids=["lean", "general_epilogue"])
@@ -218,7 +239,8 @@ def test_conv_patch_kernel_tail_retiling(dev, name, res):
     """RPG_TUNE_BF16_TAIL = 3 (both re-tilings: the rows beyond the last full round of tiles go to a second launch with smaller
     tiles) at the shapes of test_patch_kernel_tail_retiling_is_bit_identical -- every image, main and tail launch."""
     from relpose_gnn_amd import ops
-    _conv_check(dev, name, "wide", res, True, {ops.TUNE_BF16_TAIL: 3}, what="tail=3")
+    _conv_check(dev, name, "wide", res, True, {ops.TUNE_BF16_TAIL: 3}, what="tail=3", family="patch")
+    assert ops.conv_bf16_last_route()["launches"] == 2
 
 
 @pytest.mark.parametrize("n,h,w,cin,cout", [(48, 56, 56, 64, 128), (48, 28, 28, 128, 256), (64, 34, 50, 64, 128)],
@@ -463,8 +485,8 @@ def test_bf16_encoder_vs_bf16_emulating_oracle(dev, h, w, nimg):
         rel_l2(HIP bf16 features, E64 features) <= 3 d_ref    (3: margin for the kernels' different summation order)
     Rounding flips amplify through 36 layers, so no per-element interval holds at this level; per LAYER it does: every convolution of
     the encoder (the stem through the fused stem kernel, the fc with its fp32 output) runs through its op-level entry point on
-    E64's bf16 input to that layer and passes the interval check.  (The global average pool has no op-level entry point: it is
-    covered by the feature distance only.)
+    E64's bf16 input to that layer and passes the interval check.  (The global average pool, the max-pool and the re-layout are
+    covered by the feature distance here; tests/test_hip_bf16_sweep.py holds each bit-exact through its own entry point.)
     Measured on an MI355X (profiles/bf16_rounding_observed.json), 8 images: 224 x 224: d_ref 2.32e-3, HIP 2.20e-3; 256 x 341:
     d_ref 2.01e-3, HIP 2.01e-3 -- the kernels are as far from E64 as the float32 evaluation of the same rounding points is, a
     third of the 3 d_ref allowed; all 36 convolutions pass per layer, the fc's observed c is 1.35 / 1.54 (c_ref 1.14 / 0.92)."""
