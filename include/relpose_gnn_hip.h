@@ -233,6 +233,25 @@ int rpg_retrieve_cosine_gated_f32(const float* q, const float* db, const float* 
                                   const double* db_gate, const double* prior, double r2, double cos_half, int rot_gate,
                                   int32_t* gate_info, int64_t* neighbours, float* sims, void* workspace, size_t workspace_bytes,
                                   int32_t* status, void* stream);
+/* rpg_retrieve_cosine_gated_f32 on a map that holds several scenes back to back (the reference evaluates scene by scene, each
+ * against its own database: dataset_7Scenes_multi.py:273-345).  scene_first int64 [n_scenes + 1] (device): scene s owns the map
+ * rows [scene_first[s], scene_first[s + 1]); q_scene int32 [g] (device): the scene of every query.  Query g gets, bit for bit
+ * (neighbours, sims, gate_info, its share of status), what rpg_retrieve_cosine_gated_f32 gives when every row outside its scene
+ * is excluded as a row of its group is: the group filter applies inside the scene, the gate counts the scene's allowed rows,
+ * a query with no allowed row keeps row 0 and NaN.  The rows outside cost nothing: the product launch skips the 16-row tiles
+ * no query of a 64-query chunk ranks and stores only the pairs inside a scope, the selection sweeps [lo, hi) only.  lo and hi
+ * are clamped into [0, m] with hi >= lo on the device (nothing is read out of bounds whatever the arrays hold; boundaries need
+ * not be multiples of 16); a q_scene[g] outside [0, n_scenes) adds 1 to status and ranks nothing for that query (row 0, NaN).
+ * scene_first and q_scene both NULL: this IS rpg_retrieve_cosine_gated_f32 (same launches, same bits); exactly one NULL, or
+ * n_scenes < 1 with both given: RPG_ERR_BAD_ARG.  Workspace rpg_retrieve_workspace_bytes(g, m, d) with m the whole map's row
+ * count (the column slices, and with them the summation order, stay a function of (m, d)); no further launch, allocation or
+ * synchronisation.                                                                                                       */
+int rpg_retrieve_cosine_scoped_f32(const float* q, const float* db, const float* db_inv_norm, const int64_t* q_group,
+                                   const int64_t* db_group, const int32_t* ranks, int g, int k, int64_t m, int d,
+                                   const double* db_gate, const double* prior, double r2, double cos_half, int rot_gate,
+                                   int32_t* gate_info, const int64_t* scene_first, const int32_t* q_scene, int n_scenes,
+                                   int64_t* neighbours, float* sims, void* workspace, size_t workspace_bytes, int32_t* status,
+                                   void* stream);
 /* The update launch of a tracking loop (no counterpart in the reference, which relocalises every frame on its own,
  * testing/test.py:192-267): for each of s cameras, from this frame's pose-rule row rows [s][16] (its first seven doubles the
  * predicted (t, q)) and the consensus integers inliers int32 [s][2] = (inliers, used) of rpg_query_pose_consensus_f64:
@@ -810,6 +829,20 @@ int rpg_frames_u8_to_bf16(const uint8_t* frames, int n, int in_h, int in_w, int 
                           const int32_t* h_weights, const int32_t* v_bounds, const int32_t* v_weights, float mean0, float mean1,
                           float mean2, float std0, float std1, float std2, void* out_bf16, void* workspace, size_t workspace_bytes,
                           void* stream);
+/* The two launches above with the statistics per frame, for a batch whose frames come from several scenes (the reference
+ * reads one stats.txt per sequence, dataset_7Scenes_multi.py:290-298): scene_stats fp32 [n_scenes][6] = mean[3], std[3]
+ * (device), frame_scene int32 [n] (device).  A frame of scene s equals the launch above with scene s's six floats, bit for bit.
+ * status (int32, device) is incremented by the number of frames whose scene is outside [0, n_scenes); such a frame is
+ * transformed with scene 0's statistics.  The statistics are on the device, so the launch cannot check them: their maker does
+ * (std finite and non-zero, mean finite).  Tile plan, tables and alignment rules as above.                                */
+int rpg_frames_u8_to_f32_scenes(const uint8_t* frames, int n, int in_h, int in_w, int out_h, int out_w, const int32_t* h_bounds,
+                                const int32_t* h_weights, const int32_t* v_bounds, const int32_t* v_weights,
+                                const float* scene_stats, const int32_t* frame_scene, int n_scenes, int32_t* status, float* out,
+                                void* workspace, size_t workspace_bytes, void* stream);
+int rpg_frames_u8_to_bf16_scenes(const uint8_t* frames, int n, int in_h, int in_w, int out_h, int out_w, const int32_t* h_bounds,
+                                 const int32_t* h_weights, const int32_t* v_bounds, const int32_t* v_weights,
+                                 const float* scene_stats, const int32_t* frame_scene, int n_scenes, int32_t* status,
+                                 void* out_bf16, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

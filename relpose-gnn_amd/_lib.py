@@ -36,6 +36,7 @@ SYMBOLS = (
     "rpg_attention_aggregate_hidden_f32", "rpg_query_pose_consensus_f64", "rpg_pose_heads_mc_f32", "rpg_mc_advance",
     "rpg_query_pose_weighted_f64", "rpg_knn_graph_uniform_f32", "rpg_retrieve_cosine_gated_f32", "rpg_track_update_f64",
     "rpg_nchw3_to_nhwc8_bf16", "rpg_maxpool3x3s2_nhwc_bf16", "rpg_global_avgpool_nhwc_bf16", "rpg_conv_bf16_last_route",
+    "rpg_retrieve_cosine_scoped_f32", "rpg_frames_u8_to_f32_scenes", "rpg_frames_u8_to_bf16_scenes",
 )
 
 
@@ -130,6 +131,8 @@ def _declare(lib: C.CDLL) -> None:
     lib.rpg_frames_workspace_bytes.restype = _sz
     lib.rpg_frames_u8_to_f32.argtypes = [_vp] + [_i] * 5 + [_vp] * 4 + [C.c_float] * 6 + [_vp, _vp, _sz, _vp]
     lib.rpg_frames_u8_to_bf16.argtypes = lib.rpg_frames_u8_to_f32.argtypes
+    lib.rpg_frames_u8_to_f32_scenes.argtypes = [_vp] + [_i] * 5 + [_vp] * 4 + [_vp, _vp, _i, _vp] + [_vp, _vp, _sz, _vp]
+    lib.rpg_frames_u8_to_bf16_scenes.argtypes = lib.rpg_frames_u8_to_f32_scenes.argtypes
     lib.rpg_frames_plan.argtypes = [_i] * 4 + [_vp]
     lib.rpg_gather_graph_nodes_f32.argtypes = [_vp, _vp, _vp, _i, _i, C.c_int64, _i, _vp, _vp, _vp]
     lib.rpg_retrieve_workspace_bytes.argtypes = [_i, C.c_int64, _i]
@@ -139,6 +142,8 @@ def _declare(lib: C.CDLL) -> None:
     lib.rpg_retrieve_cosine_f32.argtypes = [_vp] * 6 + [_i, _i, C.c_int64, _i, _vp, _vp, _vp, _sz, _vp, _vp]
     lib.rpg_retrieve_cosine_gated_f32.argtypes = ([_vp] * 6 + [_i, _i, C.c_int64, _i, _vp, _vp, C.c_double, C.c_double, _i, _vp,
                                                   _vp, _vp, _vp, _sz, _vp, _vp])
+    lib.rpg_retrieve_cosine_scoped_f32.argtypes = ([_vp] * 6 + [_i, _i, C.c_int64, _i, _vp, _vp, C.c_double, C.c_double, _i, _vp,
+                                                   _vp, _vp, _i, _vp, _vp, _vp, _sz, _vp, _vp])
     lib.rpg_track_update_f64.argtypes = [_vp, _vp, _i, _i, C.c_double, _i, _vp, _vp, _vp, _vp]
     # the pose rules' four entry points: rel_pose .. query_targets and the six pose_m / pose_s doubles, then each rule's own
     qp = [_vp, _vp, _vp, C.c_int64, _vp, _vp, _i, _vp, C.c_int64, _vp, C.c_int64, _vp, _i, _vp] + [C.c_double] * 6

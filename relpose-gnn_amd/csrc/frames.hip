@@ -18,6 +18,11 @@
 // of [n][3][out_h][out_w] (consecutive lanes, consecutive columns).  The intermediate never leaves LDS, so the launch needs
 // no workspace.  Tiles are sized on the host so that a workgroup's LDS stays within kLdsBudget (full-width tiles where the
 // rows fit, narrower ones for large frames); the workgroups walk the tiles grid-stride.
+//
+// rpg_frames_u8_to_*_scenes: the same launch with the statistics per frame -- a device table [n_scenes][6] and one scene index per
+// frame -- for batches whose frames come from several scenes.  A workgroup crosses frames as it walks its tiles, so it rebuilds
+// the normalisation table when the next tile's frame is of another scene than the one the table was built for (768 divisions
+// per change, a few per workgroup when a batch is sorted or mixed alike); the arithmetic of an entry is the one above.
 #include "rpg_common.h"
 
 #include <math.h>
@@ -149,7 +154,7 @@ struct Norm<uint16_t> {                          // bf16 bits, round to nearest 
     }
 };
 
-struct Args {
+struct Geometry {
     const uint8_t* frames;
     long n;
     int in_h, in_w, out_h, out_w;
@@ -157,16 +162,30 @@ struct Args {
     const int* hw;
     const int* vb;
     const int* vw;
+};
+// the launch's arguments: the geometry and where the statistics come from -- by value (one set for the launch; the layout the
+// kernel has always had), or per frame from a device table (the *_scenes entries)
+struct ArgsByValue : Geometry {
     float mean[3], stdv[3];
 };
+struct ArgsByScene : Geometry {
+    const float* scene_stats;                    // [n_scenes][6] = mean[3], std[3]
+    const int32_t* frame_scene;                  // [n]
+    int n_scenes;
+    int32_t* status;
+};
+template <bool SCENES>
+struct FrameArgs { typedef ArgsByValue type; };
+template <>
+struct FrameArgs<true> { typedef ArgsByScene type; };
 
 __device__ inline int clip8(int acc) {
     const int v = acc >> kPrec;
     return v < 0 ? 0 : (v > 255 ? 255 : v);
 }
 
-template <typename OutT>
-__global__ __launch_bounds__(NT) void frames_kernel(Args a, Plan p, OutT* __restrict__ out) {
+template <typename OutT, bool SCENES>
+__global__ __launch_bounds__(NT) void frames_kernel(const typename FrameArgs<SCENES>::type a, Plan p, OutT* __restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     OutT* lut = reinterpret_cast<OutT*>(lds);
     int* htab = reinterpret_cast<int*>(lds + p.off_htab);         // [tc][2] bounds (xmin relative to the staged columns), [tc][hk] weights
@@ -175,11 +194,14 @@ __global__ __launch_bounds__(NT) void frames_kernel(Args a, Plan p, OutT* __rest
     uint8_t* tmp = lds + p.off_tmp;
     const int tid = threadIdx.x;
 
-    for (int i = tid; i < 768; i += NT) {
-        const int c = i >> 8;
-        const float x = ((float)(i & 255) / 255.0f - a.mean[c]) / a.stdv[c];     // ToTensor, Normalize (CPU fp32 semantics)
-        lut[i] = Norm<OutT>::make(x);
+    if constexpr (!SCENES) {
+        for (int i = tid; i < 768; i += NT) {
+            const int c = i >> 8;
+            const float x = ((float)(i & 255) / 255.0f - a.mean[c]) / a.stdv[c];     // ToTensor, Normalize (CPU fp32 semantics)
+            lut[i] = Norm<OutT>::make(x);
+        }
     }
+    [[maybe_unused]] int lut_scene = -1;          // SCENES: the scene the table holds (uniform over the workgroup)
 
     const long row_bytes = 3L * a.in_w;
     const long frame_bytes = row_bytes * a.in_h;
@@ -192,6 +214,14 @@ __global__ __launch_bounds__(NT) void frames_kernel(Args a, Plan p, OutT* __rest
         const int oy0 = ty * p.tr, oy1 = min(oy0 + p.tr, a.out_h);
         const int ox0 = tx * p.tc, ox1 = min(ox0 + p.tc, a.out_w);
         const int th = oy1 - oy0, tw = ox1 - ox0;
+        int scene = 0;
+        if constexpr (SCENES) {
+            scene = a.frame_scene[f];
+            if (scene < 0 || scene >= a.n_scenes) {       // counted once per frame, by the workgroup of its first tile
+                if (t == 0 && tid == 0) atomicAdd(a.status, 1);
+                scene = 0;
+            }
+        }
         int r0 = oy0, r1 = oy1, c0 = ox0, c1 = ox1;
         if (p.need_v) {
             r0 = a.vb[2 * oy0];
@@ -210,6 +240,17 @@ __global__ __launch_bounds__(NT) void frames_kernel(Args a, Plan p, OutT* __rest
         const int seg = 3 * (c1 - c0);
 
         __syncthreads();                          // the previous tile's readers are done with the LDS image
+        if constexpr (SCENES) {
+            if (scene != lut_scene) {                 // visible to the readers after the barrier that follows the staging
+                const float* ms = a.scene_stats + 6 * (long)scene;
+                for (int i = tid; i < 768; i += NT) {
+                    const int c = i >> 8;
+                    const float x = ((float)(i & 255) / 255.0f - ms[c]) / ms[3 + c];
+                    lut[i] = Norm<OutT>::make(x);
+                }
+                lut_scene = scene;
+            }
+        }
         // ---- tables of this tile, relative to the staged rows / columns
         if (p.need_h) {
             for (int i = tid; i < tw; i += NT) {
@@ -298,18 +339,28 @@ __global__ __launch_bounds__(NT) void frames_kernel(Args a, Plan p, OutT* __rest
     }
 }
 
-template <typename OutT>
+bool stats_ok(const ArgsByValue& st) {
+    for (int c = 0; c < 3; ++c)
+        if (!(st.stdv[c] != 0.0f) || !isfinite(st.stdv[c]) || !isfinite(st.mean[c])) return false;
+    return true;
+}
+
+// the statistics are on the device, checked by their maker: here only the pointers
+bool stats_ok(const ArgsByScene& st) {
+    return st.scene_stats && st.frame_scene && st.status && st.n_scenes >= 1 && !(reinterpret_cast<uintptr_t>(st.scene_stats) & 3u) &&
+           !(reinterpret_cast<uintptr_t>(st.frame_scene) & 3u) && !(reinterpret_cast<uintptr_t>(st.status) & 3u);
+}
+
+template <typename OutT, bool SCENES>
 int launch_frames(const uint8_t* frames, int n, int in_h, int in_w, int out_h, int out_w, const int32_t* hb, const int32_t* hw,
-                  const int32_t* vb, const int32_t* vw, const float* mean, const float* stdv, OutT* out, hipStream_t s) {
+                  const int32_t* vb, const int32_t* vw, typename FrameArgs<SCENES>::type a, OutT* out, hipStream_t s) {
     if (!frames || !out || n <= 0 || !geometry_ok(in_h, in_w, out_h, out_w) ||
         (reinterpret_cast<uintptr_t>(out) % sizeof(OutT)) != 0)
         return RPG_ERR_BAD_ARG;
     if ((in_w != out_w && (!hb || !hw)) || (in_h != out_h && (!vb || !vw))) return RPG_ERR_BAD_ARG;
-    for (int c = 0; c < 3; ++c)
-        if (!(stdv[c] != 0.0f) || !isfinite(stdv[c]) || !isfinite(mean[c])) return RPG_ERR_BAD_ARG;
+    if (!stats_ok(a)) return RPG_ERR_BAD_ARG;
     Plan p;
     if (!make_plan(in_h, in_w, out_h, out_w, &p)) return RPG_ERR_BAD_ARG;
-    Args a;
     a.frames = frames;
     a.n = n;
     a.in_h = in_h;
@@ -320,15 +371,11 @@ int launch_frames(const uint8_t* frames, int n, int in_h, int in_w, int out_h, i
     a.hw = hw;
     a.vb = vb;
     a.vw = vw;
-    for (int c = 0; c < 3; ++c) {
-        a.mean[c] = mean[c];
-        a.stdv[c] = stdv[c];
-    }
     const long tiles = (long)n * p.tiles_y * p.tiles_x;
     const long per_cu = (long)(160 * 1024 / p.lds) < 8 ? (long)(160 * 1024 / p.lds) : 8;
     long grid = (long)rpg::num_cus() * (per_cu < 1 ? 1 : per_cu);
     if (grid > tiles) grid = tiles;
-    hipLaunchKernelGGL(frames_kernel<OutT>, dim3((unsigned)grid), dim3(NT), p.lds, s, a, p, out);
+    hipLaunchKernelGGL((frames_kernel<OutT, SCENES>), dim3((unsigned)grid), dim3(NT), p.lds, s, a, p, out);
     RPG_CHECK_LAUNCH("frames_u8");
     return RPG_OK;
 }
@@ -391,9 +438,11 @@ extern "C" int rpg_frames_u8_to_f32(const uint8_t* frames, int n, int in_h, int 
                                     size_t workspace_bytes, void* stream) {
     (void)workspace;
     if (workspace_bytes < rpg_frames_workspace_bytes(n, in_h, in_w, out_h, out_w)) return RPG_ERR_WORKSPACE;
-    const float mean[3] = {mean0, mean1, mean2}, stdv[3] = {std0, std1, std2};
-    return launch_frames<float>(frames, n, in_h, in_w, out_h, out_w, h_bounds, h_weights, v_bounds, v_weights, mean, stdv, out,
-                                rpg::as_stream(stream));
+    ArgsByValue st;                              // (the launcher fills in the geometry)
+    st.mean[0] = mean0, st.mean[1] = mean1, st.mean[2] = mean2;
+    st.stdv[0] = std0, st.stdv[1] = std1, st.stdv[2] = std2;
+    return launch_frames<float, false>(frames, n, in_h, in_w, out_h, out_w, h_bounds, h_weights, v_bounds, v_weights, st, out,
+                                       rpg::as_stream(stream));
 }
 
 extern "C" int rpg_frames_u8_to_bf16(const uint8_t* frames, int n, int in_h, int in_w, int out_h, int out_w, const int32_t* h_bounds,
@@ -402,7 +451,35 @@ extern "C" int rpg_frames_u8_to_bf16(const uint8_t* frames, int n, int in_h, int
                                      size_t workspace_bytes, void* stream) {
     (void)workspace;
     if (workspace_bytes < rpg_frames_workspace_bytes(n, in_h, in_w, out_h, out_w)) return RPG_ERR_WORKSPACE;
-    const float mean[3] = {mean0, mean1, mean2}, stdv[3] = {std0, std1, std2};
-    return launch_frames<uint16_t>(frames, n, in_h, in_w, out_h, out_w, h_bounds, h_weights, v_bounds, v_weights, mean, stdv,
-                                   static_cast<uint16_t*>(out), rpg::as_stream(stream));
+    ArgsByValue st;                              // (the launcher fills in the geometry)
+    st.mean[0] = mean0, st.mean[1] = mean1, st.mean[2] = mean2;
+    st.stdv[0] = std0, st.stdv[1] = std1, st.stdv[2] = std2;
+    return launch_frames<uint16_t, false>(frames, n, in_h, in_w, out_h, out_w, h_bounds, h_weights, v_bounds, v_weights, st,
+                                          static_cast<uint16_t*>(out), rpg::as_stream(stream));
+}
+
+extern "C" int rpg_frames_u8_to_f32_scenes(const uint8_t* frames, int n, int in_h, int in_w, int out_h, int out_w,
+                                           const int32_t* h_bounds, const int32_t* h_weights, const int32_t* v_bounds,
+                                           const int32_t* v_weights, const float* scene_stats, const int32_t* frame_scene,
+                                           int n_scenes, int32_t* status, float* out, void* workspace, size_t workspace_bytes,
+                                           void* stream) {
+    (void)workspace;
+    if (workspace_bytes < rpg_frames_workspace_bytes(n, in_h, in_w, out_h, out_w)) return RPG_ERR_WORKSPACE;
+    ArgsByScene st;                              // (the launcher fills in the geometry)
+    st.scene_stats = scene_stats, st.frame_scene = frame_scene, st.n_scenes = n_scenes, st.status = status;
+    return launch_frames<float, true>(frames, n, in_h, in_w, out_h, out_w, h_bounds, h_weights, v_bounds, v_weights, st, out,
+                                      rpg::as_stream(stream));
+}
+
+extern "C" int rpg_frames_u8_to_bf16_scenes(const uint8_t* frames, int n, int in_h, int in_w, int out_h, int out_w,
+                                            const int32_t* h_bounds, const int32_t* h_weights, const int32_t* v_bounds,
+                                            const int32_t* v_weights, const float* scene_stats, const int32_t* frame_scene,
+                                            int n_scenes, int32_t* status, void* out, void* workspace, size_t workspace_bytes,
+                                            void* stream) {
+    (void)workspace;
+    if (workspace_bytes < rpg_frames_workspace_bytes(n, in_h, in_w, out_h, out_w)) return RPG_ERR_WORKSPACE;
+    ArgsByScene st;                              // (the launcher fills in the geometry)
+    st.scene_stats = scene_stats, st.frame_scene = frame_scene, st.n_scenes = n_scenes, st.status = status;
+    return launch_frames<uint16_t, true>(frames, n, in_h, in_w, out_h, out_w, h_bounds, h_weights, v_bounds, v_weights, st,
+                                         static_cast<uint16_t*>(out), rpg::as_stream(stream));
 }

@@ -22,6 +22,14 @@
 // select workgroup first counts the allowed rows inside the gate -- one more sweep over m, ahead of the key-writing pass -- and,
 // when they cover its largest rank, gives the rows outside the key of an excluded row.  Null gate pointers launch the
 // instantiation without any of it.
+//
+// Scene scopes (rpg_retrieve_cosine_scoped_f32): a map that holds several scenes back to back gives every query a row range
+// [lo, hi) = its scene's rows.  The rows outside rank as rows of the query's own group do -- not at all -- so the plain entry with
+// an emulated group array is an exact oracle; what the scope adds is that they cost nothing: a dot workgroup whose 16 rows lie
+// outside the scope of every query of its chunk returns before it loads a database byte, a workgroup that computes stores only
+// the (query, row) pairs inside a scope, and every sweep of the select kernel runs over [lo, hi) alone (so it never reads a
+// product that was not written).  The column slices stay a function of (m, d) of the whole map: the bits of a similarity do not
+// depend on whether the call was scoped.  Null scope pointers launch the instantiations without any of it.
 #include "rpg_common.h"
 #include "pose_gate.h"
 
@@ -71,19 +79,62 @@ __device__ __forceinline__ float4 ld4_or_zero(const float* p, bool ok) {
     return ok ? *reinterpret_cast<const float4*>(p) : make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
+// ---- scene scopes ----------------------------------------------------------------------------------------------------------
+struct ScopeOn {
+    const int64_t* first;      // [n + 1]: scene s owns rows [first[s], first[s + 1])
+    const int32_t* q_scene;    // [g]
+    int n;
+};
+struct ScopeOff {};
+template <bool SCOPED>
+struct ScopeArgs { typedef ScopeOff type; };
+template <>
+struct ScopeArgs<true> { typedef ScopeOn type; };
+
+// Rows [lo, hi) of query gi, clamped into [0, m] with hi >= lo whatever the two arrays hold; -> false (and an empty range) for a
+// scene outside [0, n).
+__device__ __forceinline__ bool scope_of(const ScopeOn& sc, int gi, int64_t m, int64_t* lo, int64_t* hi) {
+    const int s = sc.q_scene[gi];
+    if (s < 0 || s >= sc.n) {
+        *lo = *hi = 0;
+        return false;
+    }
+    int64_t a = sc.first[s], b = sc.first[s + 1];
+    a = a < 0 ? 0 : (a > m ? m : a);
+    b = b < a ? a : (b > m ? m : b);
+    *lo = a;
+    *hi = b;
+    return true;
+}
+
 // A = queries (tile rows i), B = database rows (tile columns j).  Lane l holds A[i = l & 15][k = l >> 4] and B[k = l >> 4][j = l & 15];
 // a lane's float4 at column 16 u + 4 (l >> 4) feeds four MFMAs (.x .y .z .w), so one wave step of 64 columns is 16 MFMAs per
 // query tile, in a fixed column order.  D[i = 4 (l >> 4) + reg][j = l & 15].
-template <int NQ>
+// SCOPED: the chunk's scopes go to LDS first, and the workgroup returns when none of them meets its 16 rows.
+template <int NQ, bool SCOPED>
 __global__ __launch_bounds__(RT_NT) void retrieve_dot_kernel(const float* __restrict__ q, const float* __restrict__ db, int g,
                                                              int64_t m, int d, int blocks_per_split,
-                                                             float* __restrict__ part) {
+                                                             float* __restrict__ part,
+                                                             const typename ScopeArgs<SCOPED>::type sc) {
     __shared__ float red[RT_NT / 64][NQ][4][64];
+    __shared__ int64_t s_lo[SCOPED ? RT_QCHUNK : 1], s_hi[SCOPED ? RT_QCHUNK : 1];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int r16 = lane & 15, c4 = lane >> 4;
     const int64_t m0 = (int64_t)blockIdx.x * RT_ROWS;
     const int split = blockIdx.y;
     const int g0 = blockIdx.z * RT_QCHUNK;
+    if constexpr (SCOPED) {
+        int meets = 0;
+        if (threadIdx.x < RT_QCHUNK) {
+            int64_t lo = 0, hi = 0;
+            const int gi = g0 + (int)threadIdx.x;
+            if (gi < g) scope_of(sc, gi, m, &lo, &hi);
+            s_lo[threadIdx.x] = lo;
+            s_hi[threadIdx.x] = hi;
+            meets = lo < m0 + RT_ROWS && hi > m0;         // (an empty range meets nothing)
+        }
+        if (!__syncthreads_or(meets)) return;             // uniform: no query of this chunk ranks any of these 16 rows
+    }
 
     int64_t row = m0 + r16;
     if (row >= m) row = m - 1;                            // a tail tile reads a valid row again; its column is not stored
@@ -138,7 +189,9 @@ __global__ __launch_bounds__(RT_NT) void retrieve_dot_kernel(const float* __rest
         const float s = ((red[0][t][reg][lane] + red[1][t][reg][lane]) + red[2][t][reg][lane]) + red[3][t][reg][lane];
         const int gi = g0 + 16 * t + 4 * c4 + reg;
         const int64_t mm = m0 + r16;
-        if (gi < g && mm < m) part[((int64_t)split * g + gi) * m + mm] = s;
+        bool store = gi < g && mm < m;
+        if constexpr (SCOPED) store = store && mm >= s_lo[gi - g0] && mm < s_hi[gi - g0];
+        if (store) part[((int64_t)split * g + gi) * m + mm] = s;
     }
 }
 
@@ -176,15 +229,16 @@ constexpr int GATE_ROW = 7;                               // doubles per gate ro
 constexpr int GATE_UNROLL = 4;                            // rows a thread has in flight in a sweep over the gate rows
 
 // GATED = false is the kernel as it was before the gate existed (an empty struct more in its arguments): rpg_retrieve_cosine_f32
-// and the new entry point with null gate pointers launch that one.
-template <bool GATED>
+// and the new entry point with null gate pointers launch that one.  SCOPED = false likewise: [lo, hi) is [0, m) at compile time.
+template <bool GATED, bool SCOPED>
 __global__ __launch_bounds__(RS_NT) void retrieve_select_kernel(float* __restrict__ part, int nsplit,
                                                                 const float* __restrict__ q_inv, const float* __restrict__ db_inv,
                                                                 const int64_t* __restrict__ q_group,
                                                                 const int64_t* __restrict__ db_group,
                                                                 const int32_t* __restrict__ ranks, int g, int k, int64_t m,
                                                                 int64_t* __restrict__ nbrs, float* __restrict__ sims,
-                                                                int32_t* __restrict__ status, const typename GateArgs<GATED>::type ga) {
+                                                                int32_t* __restrict__ status, const typename GateArgs<GATED>::type ga,
+                                                                const typename ScopeArgs<SCOPED>::type sc) {
     __shared__ unsigned hist[256];
     __shared__ unsigned long long list[R_MAX];
     __shared__ int s_rank[K_MAX];
@@ -202,6 +256,10 @@ __global__ __launch_bounds__(RS_NT) void retrieve_select_kernel(float* __restric
     __syncthreads();
     const int64_t qg = q_group ? q_group[gi] : -1;
     const float qi = q_inv[gi];
+    // the rows this query ranks: every sweep below runs over [lo, hi) (uniform over the workgroup)
+    int64_t lo = 0, hi = m;
+    bool scene_ok = true;
+    if constexpr (SCOPED) scene_ok = scope_of(sc, gi, m, &lo, &hi);
     // similarity -> key of row mm, or KEY_EXCLUDED for a row the query does not rank; -> whether it is ranked
     auto write_key = [&](int64_t mm, bool allowed) {
         float dot = part[(int64_t)gi * m + mm];
@@ -220,19 +278,19 @@ __global__ __launch_bounds__(RS_NT) void retrieve_select_kernel(float* __restric
         // owns).  The map's 56 bytes per row come from beyond the L2 and one workgroup has little else to hide that latency with,
         // so a thread loads GATE_UNROLL rows before it judges the first (a row past the end reads row `base` again, unused).
         auto sweep = [&](auto&& body) {
-            for (int64_t base = tid; base < m; base += (int64_t)GATE_UNROLL * RS_NT) {
+            for (int64_t base = lo + tid; base < hi; base += (int64_t)GATE_UNROLL * RS_NT) {
                 double r[GATE_UNROLL][GATE_ROW];
 #pragma unroll
                 for (int u = 0; u < GATE_UNROLL; ++u) {
                     const int64_t mm = base + (int64_t)u * RS_NT;
-                    const double* src = ga.db_gate + (mm < m ? mm : base) * GATE_ROW;
+                    const double* src = ga.db_gate + (mm < hi ? mm : base) * GATE_ROW;
 #pragma unroll
                     for (int c = 0; c < GATE_ROW; ++c) r[u][c] = src[c];
                 }
 #pragma unroll
                 for (int u = 0; u < GATE_UNROLL; ++u) {
                     const int64_t mm = base + (int64_t)u * RS_NT;
-                    if (mm < m) body(mm, rpg::pose_gate_inside(r[u], p, ga.r2, ga.cos_half, ga.rot != 0));
+                    if (mm < hi) body(mm, rpg::pose_gate_inside(r[u], p, ga.r2, ga.cos_half, ga.rot != 0));
                 }
             }
         };
@@ -270,7 +328,7 @@ __global__ __launch_bounds__(RS_NT) void retrieve_select_kernel(float* __restric
     }
     if (!gated) {
         unsigned local = 0;
-        for (int64_t mm = tid; mm < m; mm += RS_NT) {
+        for (int64_t mm = lo + tid; mm < hi; mm += RS_NT) {
             const bool allowed = !(qg != -1 && db_group[mm] == qg);
             write_key(mm, allowed);
             local += allowed;
@@ -298,6 +356,7 @@ __global__ __launch_bounds__(RS_NT) void retrieve_select_kernel(float* __restric
             if (r > top) top = r;
         }
         if (!ascending) ++bad;
+        if (!scene_ok) bad = 1;                           // a scene that does not exist: counted once, nothing ranked
         if (bad) atomicAdd(status, bad);
         s_r = lim > 0 ? top + 1 : 0;
     }
@@ -315,13 +374,13 @@ __global__ __launch_bounds__(RS_NT) void retrieve_select_kernel(float* __restric
     unsigned long long prefix = 0, mask = 0;
     unsigned need = (unsigned)R;
     for (int shift = 56; shift >= 0; shift -= 8) {
-        if (shift < 32 && ((unsigned long long)(m - 1) >> shift) == 0) {      // every row index has digit 0 here
+        if (shift < 32 && ((unsigned long long)(hi - 1) >> shift) == 0) {     // every row index has digit 0 here (R > 0: hi >= 1)
             mask |= 0xFFull << shift;
             continue;
         }
         if (tid < 256) hist[tid] = 0;
         __syncthreads();
-        for (int64_t mm = tid; mm < m; mm += RS_NT) {
+        for (int64_t mm = lo + tid; mm < hi; mm += RS_NT) {
             const unsigned long long comp = ((unsigned long long)keys[mm] << 32) | (unsigned long long)mm;
             if ((comp & mask) == prefix) atomicAdd(&hist[(unsigned)(comp >> shift) & 255u], 1u);
         }
@@ -345,7 +404,7 @@ __global__ __launch_bounds__(RS_NT) void retrieve_select_kernel(float* __restric
     // collect the R pairs <= the threshold (slot order is arbitrary: the sort below fixes it), pad, sort ascending
     if (tid < R_MAX) list[tid] = ~0ull;
     __syncthreads();
-    for (int64_t mm = tid; mm < m; mm += RS_NT) {
+    for (int64_t mm = lo + tid; mm < hi; mm += RS_NT) {
         const unsigned long long comp = ((unsigned long long)keys[mm] << 32) | (unsigned long long)mm;
         if (comp <= prefix) {
             const unsigned slot = atomicAdd(&s_cnt, 1u);
@@ -417,6 +476,34 @@ int launch_inv_norms(const float* x, int64_t rows, int d, float* inv, hipStream_
     return RPG_OK;
 }
 
+template <bool SCOPED>
+int launch_dot_select(const float* q, const float* db, const float* q_inv, const float* db_inv_norm, const int64_t* q_group,
+                      const int64_t* db_group, const int32_t* ranks, int g, int k, int64_t m, int d, const double* db_gate,
+                      const double* prior, double r2, double cos_half, int rot_gate, int32_t* gate_info, int64_t* neighbours,
+                      float* sims, float* part, int32_t* status, const typename ScopeArgs<SCOPED>::type sc, hipStream_t s) {
+    int ns, bps;
+    split_plan(m, d, &ns, &bps);
+    const dim3 grid((unsigned)((m + RT_ROWS - 1) / RT_ROWS), (unsigned)ns, (unsigned)((g + RT_QCHUNK - 1) / RT_QCHUNK));
+    const int tiles = ((g < RT_QCHUNK ? g : RT_QCHUNK) + 15) / 16;
+    if (tiles <= 1)
+        hipLaunchKernelGGL((retrieve_dot_kernel<1, SCOPED>), grid, dim3(RT_NT), 0, s, q, db, g, m, d, bps, part, sc);
+    else if (tiles == 2)
+        hipLaunchKernelGGL((retrieve_dot_kernel<2, SCOPED>), grid, dim3(RT_NT), 0, s, q, db, g, m, d, bps, part, sc);
+    else
+        hipLaunchKernelGGL((retrieve_dot_kernel<4, SCOPED>), grid, dim3(RT_NT), 0, s, q, db, g, m, d, bps, part, sc);
+    RPG_CHECK_LAUNCH("retrieve_dot");
+    if (db_gate) {
+        const GateOn ga = {db_gate, prior, r2, cos_half, rot_gate, gate_info};
+        hipLaunchKernelGGL((retrieve_select_kernel<true, SCOPED>), dim3(g), dim3(RS_NT), 0, s, part, ns, q_inv, db_inv_norm, q_group,
+                           db_group, ranks, g, k, m, neighbours, sims, status, ga, sc);
+    } else {
+        hipLaunchKernelGGL((retrieve_select_kernel<false, SCOPED>), dim3(g), dim3(RS_NT), 0, s, part, ns, q_inv, db_inv_norm, q_group,
+                           db_group, ranks, g, k, m, neighbours, sims, status, GateOff{}, sc);
+    }
+    RPG_CHECK_LAUNCH("retrieve_select");
+    return RPG_OK;
+}
+
 }  // namespace
 
 extern "C" int rpg_retrieve_max_rank(void) { return R_MAX; }
@@ -432,11 +519,12 @@ extern "C" int rpg_row_inv_norms_f32(const float* x, int64_t m, int d, float* in
     return launch_inv_norms(x, m, d, inv_norm, rpg::as_stream(stream));
 }
 
-extern "C" int rpg_retrieve_cosine_gated_f32(const float* q, const float* db, const float* db_inv_norm, const int64_t* q_group,
+extern "C" int rpg_retrieve_cosine_scoped_f32(const float* q, const float* db, const float* db_inv_norm, const int64_t* q_group,
                                              const int64_t* db_group, const int32_t* ranks, int g, int k, int64_t m, int d,
                                              const double* db_gate, const double* prior, double r2, double cos_half, int rot_gate,
-                                             int32_t* gate_info, int64_t* neighbours, float* sims, void* workspace,
-                                             size_t workspace_bytes, int32_t* status, void* stream) {
+                                             int32_t* gate_info, const int64_t* scene_first, const int32_t* q_scene, int n_scenes,
+                                             int64_t* neighbours, float* sims, void* workspace, size_t workspace_bytes,
+                                             int32_t* status, void* stream) {
     if (!q || !db || !ranks || !neighbours || !workspace || !status || g < 1 || k < 1 || k > K_MAX || m < k ||
         m >= ((int64_t)1 << 31) || d <= 0 || (d & 3) || !rpg::aligned16(q) || !rpg::aligned16(db) || !rpg::aligned16(workspace) ||
         ((q_group == nullptr) != (db_group == nullptr)) || (reinterpret_cast<uintptr_t>(neighbours) & 7u) ||
@@ -449,6 +537,10 @@ extern "C" int rpg_retrieve_cosine_gated_f32(const float* q, const float* db, co
     if ((db_gate == nullptr) != (prior == nullptr) || (db_gate == nullptr) != (gate_info == nullptr) ||
         (reinterpret_cast<uintptr_t>(db_gate) & 7u) || (reinterpret_cast<uintptr_t>(prior) & 7u) ||
         (reinterpret_cast<uintptr_t>(gate_info) & 3u) || (db_gate && (!(r2 >= 0.0) || cos_half != cos_half)))
+        return RPG_ERR_BAD_ARG;
+    // the scopes: both pointers or neither, at least one scene
+    if ((scene_first == nullptr) != (q_scene == nullptr) || (reinterpret_cast<uintptr_t>(scene_first) & 7u) ||
+        (reinterpret_cast<uintptr_t>(q_scene) & 3u) || (scene_first && n_scenes < 1))
         return RPG_ERR_BAD_ARG;
     const WsLayout w = ws_layout(g, m, d);
     if (workspace_bytes < w.total) return RPG_ERR_WORKSPACE;
@@ -464,27 +556,21 @@ extern "C" int rpg_retrieve_cosine_gated_f32(const float* q, const float* db, co
         if (rc != RPG_OK) return rc;
         db_inv_norm = db_inv;
     }
-    int ns, bps;
-    split_plan(m, d, &ns, &bps);
-    const dim3 grid((unsigned)((m + RT_ROWS - 1) / RT_ROWS), (unsigned)ns, (unsigned)((g + RT_QCHUNK - 1) / RT_QCHUNK));
-    const int tiles = ((g < RT_QCHUNK ? g : RT_QCHUNK) + 15) / 16;
-    if (tiles <= 1)
-        hipLaunchKernelGGL(retrieve_dot_kernel<1>, grid, dim3(RT_NT), 0, s, q, db, g, m, d, bps, part);
-    else if (tiles == 2)
-        hipLaunchKernelGGL(retrieve_dot_kernel<2>, grid, dim3(RT_NT), 0, s, q, db, g, m, d, bps, part);
-    else
-        hipLaunchKernelGGL(retrieve_dot_kernel<4>, grid, dim3(RT_NT), 0, s, q, db, g, m, d, bps, part);
-    RPG_CHECK_LAUNCH("retrieve_dot");
-    if (db_gate) {
-        const GateOn ga = {db_gate, prior, r2, cos_half, rot_gate, gate_info};
-        hipLaunchKernelGGL(retrieve_select_kernel<true>, dim3(g), dim3(RS_NT), 0, s, part, ns, q_inv, db_inv_norm, q_group, db_group,
-                           ranks, g, k, m, neighbours, sims, status, ga);
-    } else {
-        hipLaunchKernelGGL(retrieve_select_kernel<false>, dim3(g), dim3(RS_NT), 0, s, part, ns, q_inv, db_inv_norm, q_group, db_group,
-                           ranks, g, k, m, neighbours, sims, status, GateOff{});
-    }
-    RPG_CHECK_LAUNCH("retrieve_select");
-    return RPG_OK;
+    if (scene_first)
+        return launch_dot_select<true>(q, db, q_inv, db_inv_norm, q_group, db_group, ranks, g, k, m, d, db_gate, prior, r2, cos_half,
+                                       rot_gate, gate_info, neighbours, sims, part, status, ScopeOn{scene_first, q_scene, n_scenes}, s);
+    return launch_dot_select<false>(q, db, q_inv, db_inv_norm, q_group, db_group, ranks, g, k, m, d, db_gate, prior, r2, cos_half,
+                                    rot_gate, gate_info, neighbours, sims, part, status, ScopeOff{}, s);
+}
+
+extern "C" int rpg_retrieve_cosine_gated_f32(const float* q, const float* db, const float* db_inv_norm, const int64_t* q_group,
+                                             const int64_t* db_group, const int32_t* ranks, int g, int k, int64_t m, int d,
+                                             const double* db_gate, const double* prior, double r2, double cos_half, int rot_gate,
+                                             int32_t* gate_info, int64_t* neighbours, float* sims, void* workspace,
+                                             size_t workspace_bytes, int32_t* status, void* stream) {
+    return rpg_retrieve_cosine_scoped_f32(q, db, db_inv_norm, q_group, db_group, ranks, g, k, m, d, db_gate, prior, r2, cos_half,
+                                          rot_gate, gate_info, nullptr, nullptr, 0, neighbours, sims, workspace, workspace_bytes,
+                                          status, stream);
 }
 
 extern "C" int rpg_retrieve_cosine_f32(const float* q, const float* db, const float* db_inv_norm, const int64_t* q_group,

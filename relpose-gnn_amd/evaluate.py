@@ -651,7 +651,7 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
                bf16_input: Optional[bool] = None, *, rule=None, query_descriptors=None, query_groups=None,
                postprocess: str = "host", fuse: Optional[str] = None, max_edges: int = 64, capture: bool = False,
                outputs: str = "all", inlier_t: float = INLIER_T, inlier_deg: float = INLIER_DEG,
-               weights: Optional[str] = None, var_floor: float = VAR_FLOOR, priors=None, gate=None):
+               weights: Optional[str] = None, var_floor: float = VAR_FLOOR, priors=None, gate=None, scenes=None):
     """The evaluation stream of the map path (``PoseNetX_R2.forward_map``): query g's graph is the query followed by the map
     rows ``neighbours[g]`` (its retrieved database images, dataset_7Scenes_multi.py:340-345).  Single process.
 
@@ -677,6 +677,13 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
     descriptors; what the gate did comes back with each micro-batch's results: ``stats["gate_state"]`` (0 = gated, 1 = no prior,
     2 = too few rows inside, ranked against the whole map) and ``stats["gate_rows"]`` (allowed rows inside), int [G], and
     ``.gate_state`` on an ``EvalResult``.  A captured step is keyed by the gate's parameters too.
+
+    ``scenes`` [G] (host integers): each query's scene, for a ``featmap.SceneAtlas`` -- the maps of several scenes in one --
+    and for a model whose ``frame_transform`` holds per-scene statistics (``forward_map(scenes=)``, which see).  One call then
+    serves the queries of all scenes, where the reference loops over its sequences (dataset_7Scenes_multi.py:273-345), each
+    query ranked inside its own scene; the scenes are sliced per micro-batch and staged like the priors, a captured step holds
+    them in a static tensor, and the re-run of an irregular kNN micro-batch carries them along.  With a ``rule`` on an atlas
+    they are required (ValueError without).
 
     ``postprocess="device"`` (default ``"host"``): the pose rule runs on the GPU behind every ``forward_map``
     (``query_pose.QueryPose.from_map`` on the map's poses and the device neighbours -- with a rule the rows ``forward_map`` has
@@ -760,6 +767,21 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
         fmap.gate_rows(gate)                      # (a map without poses raises here, before any work is queued)
         gate_h = np.zeros((int(queries.shape[0]), 2), dtype=np.int32)
     gkw = {} if gate is None else {"gate": gate}
+    sc_all = None
+    if scenes is not None:
+        sc_all = torch.as_tensor(scenes).cpu()
+        if sc_all.dim() != 1 or sc_all.shape[0] != int(queries.shape[0]) or sc_all.dtype.is_floating_point or sc_all.dtype == torch.bool:
+            raise ValueError(f"relocalize: scenes must be integers [{int(queries.shape[0])}] (one scene index per query), got "
+                             f"{tuple(sc_all.shape)} {sc_all.dtype}")
+        sc_all = sc_all.to(torch.int32).contiguous()
+        if torch.device(device).type == "cuda":
+            sc_all = sc_all.pin_memory()
+    from .featmap import FeatureMap, SceneAtlas
+    if rule is not None and isinstance(fmap, FeatureMap):          # refusals before any work is queued (an atlas without scenes, ...)
+        from .frames import SceneFrameTransform
+        for_frames = queries.dtype == torch.uint8 and isinstance(getattr(model, "frame_transform", None), SceneFrameTransform)
+        if isinstance(fmap, SceneAtlas) or not for_frames:         # (one scene's map: scenes that only the frame transform reads)
+            fmap._scope(None if sc_all is None else (sc_all.numpy().astype(np.int64), None), int(queries.shape[0]), rule, "relocalize")
     _check_postprocess("relocalize", postprocess, device)
     _check_fuse("relocalize", fuse, max_edges, ref_node, inlier_t, inlier_deg)
     inlier_t, inlier_deg = float(inlier_t), float(inlier_deg)
@@ -854,7 +876,7 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
         nonlocal n_captured
         key = ("step", tuple(x.shape), x.dtype, kk, None if rule is None else (rule.sampling_period, rule.random), postprocess,
                fuse, max_edges, qd is not None, targ is not None, outputs, inlier_t, inlier_deg, weights, var_floor, kp,
-               None if gate is None else gate.key,
+               None if gate is None else gate.key, sc_all is not None,
                None if mc is None else (id(mc), mc.samples, mc.seed))       # the sampler's count and seed are baked into the step
         step = captured.get(key)
         if step is None or step.fmap is not fmap or step.pose is not qp or step.stale():
@@ -863,7 +885,8 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
                 if qp is not None:
                     captured[qp_key] = qp
             step = captured[key] = GraphedForwardMap(model, fmap, x, kk, rule=rule, query_descriptors=qd, pose=qp,
-                                                     pose_kwargs=None if targ is None else {"query_targets": targ}, **okw, **gkw)
+                                                     pose_kwargs=None if targ is None else {"query_targets": targ}, **okw, **gkw,
+                                                     **({} if sc_all is None or rule is None else {"scenes": sc_all[:x.shape[0]]}))
             n_captured += 1
         return step
 
@@ -876,8 +899,9 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
             mc.place(mc_draw, b0 * n_per)
         if irr_dev is not None:
             irr_dev.zero_()
+        skw = {} if sc_all is None else {"scenes": sc_all[b0:b1]}
         if rule is None and not capture:
-            ab, rel, ei = model.forward_map(x, nb_dev[b0:b1], fmap, **okw, **ikw)
+            ab, rel, ei = model.forward_map(x, nb_dev[b0:b1], fmap, **okw, **ikw, **skw)
             return _Forward(ab, rel, ei, nb_dev[b0:b1]), irregular_back(irr_dev, b0)
         qd = None
         if qd_all is not None:
@@ -892,11 +916,12 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
             ranks = None
             if rule is not None and (rule.random or qg is not None):
                 # this call's rule draws, in query order, exactly what forward_map would have drawn from it
-                ranks = rule.ranks(fmap.n_allowed(fmap._query_groups(qg, b1 - b0)[0], b1 - b0))
+                ranks = rule.ranks(fmap.n_allowed(fmap._query_groups(qg, b1 - b0)[0], b1 - b0,
+                                                  *(() if sc_all is None else (sc_all[b0:b1].numpy().astype(np.int64),))))
             # x is one of the pipeline's two staging buffers (the copy of micro-batch i + 1 into the other one runs under this
             # replay), so the step copies it into its one static input: a device copy of the queries, ~1 % of the step
             out = step(x, None if rule is not None else nb_dev[b0:b1], ranks=ranks, query_descriptors=qd, query_groups=qg,
-                       query_targets=targ, **pkw)
+                       query_targets=targ, **pkw, **({} if rule is None else skw))
             n_replays += 1
             # The outputs are the step's STATIC tensors, which the replay of the next micro-batch overwrites.  Their copies to
             # pinned memory (read_back here and in _MicroBatchRunner.launch, right after this returns) are enqueued on the stream
@@ -904,7 +929,8 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
             return (_Forward(out.abs_pose, out.rel_pose, out.edge_index, out.neighbours,
                              None if rule is None else runner.read_back(out.neighbours), step.packed, step.gate_info),
                     irregular_back(getattr(step, "irregular", None), b0))
-        ab, rel, ei, nb_mb = model.forward_map(x, None, fmap, rule=rule, query_descriptors=qd, query_groups=qg, **okw, **ikw, **pkw, **gkw)
+        ab, rel, ei, nb_mb = model.forward_map(x, None, fmap, rule=rule, query_descriptors=qd, query_groups=qg, **okw, **ikw, **pkw, **gkw,
+                                               **skw)
         return (_Forward(ab, rel, ei, nb_mb, runner.read_back(nb_mb), gate_info=model.gate_info if gate is not None else None),
                 irregular_back(irr_dev, b0))
 
@@ -936,7 +962,7 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
         try:
             if mc is not None:
                 mc.place(mc_draw, b0 * n_per)
-            ab, rel, ei = model.forward_map(x, nb_mb, fmap)
+            ab, rel, ei = model.forward_map(x, nb_mb, fmap, **({} if sc_all is None else {"scenes": sc_all[b0:b0 + n]}))
             var = None if mc is None else mc.last.rel_var
             if qp is None:
                 return {"nb": None, "abs": ab.cpu(), "rel": rel.cpu(), "ei": ei.cpu(),

@@ -197,10 +197,13 @@ class FeatureMap:
             dev = (host if host.is_pinned() else host.pin_memory()).to(self.device, non_blocking=True)
         return host, dev
 
-    def n_allowed(self, query_groups_host, g: int):
+    def n_allowed(self, query_groups_host, g: int, scenes_host=None):
         """Per query the number of map rows its group leaves (numpy int64 [g]): M - count(groups == query_group), all M rows
-        for group -1 or without groups.  On the host: the rule's random draws are sized by it (retrieval.py)."""
+        for group -1 or without groups.  On the host: the rule's random draws are sized by it (retrieval.py).  ``scenes_host``:
+        a ``SceneAtlas`` counts inside each query's scene; a plain map takes none."""
         import numpy as np
+        if scenes_host is not None:
+            raise ValueError("n_allowed: scenes belong to a SceneAtlas (SceneAtlas.concat), this is one scene's FeatureMap")
         m = len(self)
         if query_groups_host is None or self.groups_host is None:
             return np.full(g, m, dtype=np.int64)
@@ -254,14 +257,25 @@ class FeatureMap:
             raise ValueError(f"{who}: a rule with random draws sizes them by each query's allowed-row count on the host, which a "
                              "pose gate changes on the device: use a rule without drop / random_start with a gate")
 
+    def _scope(self, scenes, g: int, rule, who: str, ranks_given: bool = False):
+        """The scene scope of a retrieval: None for one scene's map (which takes no ``scenes``); a ``SceneAtlas`` returns (host
+        scenes or None, q_scene int32 [g] on the device).  ``ranks_given``: the caller has the ranks already (a captured step
+        reads them from its static buffer), so nothing is drawn here and a random rule does not need the host form."""
+        if scenes is not None:
+            raise ValueError(f"{who}: scenes belong to a SceneAtlas (SceneAtlas.concat), this is one scene's FeatureMap")
+        return None
+
     def retrieve(self, query_descriptors: torch.Tensor, rule, query_groups=None, status=None, workspace=None, prior=None,
-                 gate=None, gate_info=None) -> torch.Tensor:
+                 gate=None, gate_info=None, scenes=None) -> torch.Tensor:
         """int64 [G, K] on the map's device: per query the map rows ``rule`` picks from the ranking of ``descriptor_matrix`` by
         cosine similarity to ``query_descriptors`` fp32 [G, Dd] (on the map's device), rows of the query's group left out
         (``query_groups`` [G], host integers; -1 or None: nothing left out).  ``status`` / ``workspace``: as ``ops.retrieve``.
         ``gate`` (retrieval.PoseGate) with ``prior`` float64 [G, 7] (a device tensor, or a host array, staged): the ranking is
         restricted to the rows near each query's prior pose (``ops.retrieve_gated``); ``gate_info`` int32 [G, 2] receives (state,
-        rows inside) -- pass a tensor to read them.  A rule with random draws raises ValueError with a gate."""
+        rows inside) -- pass a tensor to read them.  A rule with random draws raises ValueError with a gate.
+        ``scenes`` [G] (a ``SceneAtlas`` only, and required there): each query's scene, host integers or an int32 tensor on the
+        map's device; a query ranks its scene's rows alone (``ops.retrieve_scoped``).  A rule with random draws needs the host
+        form, as it needs host ``query_groups``."""
         from . import ops
         self.check_gate("retrieve", rule, prior, gate)
         if gate is None and gate_info is not None:
@@ -277,6 +291,15 @@ class FeatureMap:
         if gate is not None:
             gate_rows, prior = self.gate_rows(gate), self.prior_tensor(prior, g)
         qg_host, qg_dev = self._query_groups(query_groups, g)
+        scope = self._scope(scenes, g, rule, "retrieve")
+        if scope is not None:
+            ranks = rule.device_ranks(self.n_allowed(qg_host, g, scope[0]), self.device)
+            res = ops.retrieve_scoped(query_descriptors, db, ranks, self.scene_first, scope[1],
+                                      None if gate is None else gate_rows, prior, 0.0 if gate is None else gate.r2,
+                                      0.0 if gate is None else gate.cos_half, gate is not None and gate.rot,
+                                      db_inv_norm=self.inv_norms(), q_group=qg_dev, db_group=None if qg_dev is None else self.groups,
+                                      status=status, workspace=workspace, gate_info=gate_info)
+            return res if gate is None else res[0]
         ranks = rule.device_ranks(self.n_allowed(qg_host, g), self.device)
         if gate is not None:
             return ops.retrieve_gated(query_descriptors, db, ranks, gate_rows, prior, gate.r2,
@@ -309,6 +332,9 @@ class FeatureMap:
     # ---- persistence ------------------------------------------------------------------------------------------------
     def save(self, path) -> None:
         """Plain tensors plus metadata (str / int): ``torch.load(weights_only=True)`` reads it back."""
+        torch.save(self._saved(), path)
+
+    def _saved(self) -> dict:
         obj = {"format": FORMAT, "meta": dict(self.meta), "features": self.features.detach().cpu()}
         if self.poses is not None:
             obj["poses"] = self.poses.detach().cpu()
@@ -316,7 +342,7 @@ class FeatureMap:
             obj["descriptors"] = self.descriptors.detach().cpu()
         if self.groups_host is not None:
             obj["groups"] = self.groups_host
-        torch.save(obj, path)
+        return obj
 
     @classmethod
     def load(cls, path, device) -> "FeatureMap":
@@ -326,3 +352,151 @@ class FeatureMap:
         poses = obj.get("poses")                  # optional keys: a file written before they existed loads as before
         return cls(obj["features"].to(device), obj["meta"], None if poses is None else poses.to(device),
                    obj.get("descriptors"), obj.get("groups"))
+
+
+class SceneAtlas(FeatureMap):
+    """The maps of several scenes in one: their rows back to back, scene ``s`` owning rows ``[scene_first_host[s],
+    scene_first_host[s + 1])``.  The reference evaluates its scenes one after the other, each against its own database
+    (dataset_7Scenes_multi.py:273-345); an atlas serves queries of different scenes in one batch: ``retrieve`` /
+    ``forward_map(rule=, scenes=)`` rank every query against its own scene's rows only (``ops.retrieve_scoped``, at the cost of
+    that scene's rows), and everything behind retrieval -- the gather, the GNN, the pose rule over ``poses[neighbours]`` -- never
+    knew about scenes.  Build one with ``SceneAtlas.concat``; ``scene(i)`` gives scene ``i`` back as a ``FeatureMap`` over the
+    same storage."""
+
+    def __init__(self, features, meta, poses=None, descriptors=None, groups=None, scene_first=None, names=None):
+        import numpy as np
+        super().__init__(features, meta, poses, descriptors, groups)
+        if scene_first is None:
+            raise ValueError("SceneAtlas: scene_first [S + 1] is required (build an atlas with SceneAtlas.concat)")
+        first = np.asarray(torch.as_tensor(scene_first).cpu().numpy() if torch.is_tensor(scene_first) else scene_first)
+        if first.ndim != 1 or first.shape[0] < 2 or first.dtype.kind not in "iu":
+            raise ValueError(f"SceneAtlas: scene_first must be integers [S + 1 >= 2], got {first.shape} {first.dtype}")
+        first = first.astype(np.int64)
+        if first[0] != 0 or first[-1] != len(self) or (np.diff(first) < 1).any():
+            raise ValueError(f"SceneAtlas: scene_first must ascend strictly from 0 to the row count {len(self)} (no empty scene), "
+                             f"got {first.tolist()}")
+        self.scene_first_host = first
+        self.scene_first = torch.from_numpy(first).to(self.device)
+        n = first.shape[0] - 1
+        self.names = [str(i) for i in range(n)] if names is None else [str(v) for v in names]
+        if len(self.names) != n or len(set(self.names)) != n:
+            raise ValueError(f"SceneAtlas: names must be {n} distinct names, got {self.names}")
+        self._scene_group_counts = None
+
+    @property
+    def n_scenes(self) -> int:
+        return int(self.scene_first_host.shape[0] - 1)
+
+    def __repr__(self) -> str:
+        return f"SceneAtlas(scenes={self.n_scenes}, {super().__repr__()})"
+
+    @classmethod
+    def concat(cls, maps, names=None) -> "SceneAtlas":
+        """One atlas from per-scene ``FeatureMap``s: a sequence (``names`` optional) or a dict name -> map (in its order).  The
+        maps must be on one device and share ``meta`` (one encoder made them); poses, descriptors and groups must be held by
+        all of them or by none, descriptor widths must agree (ValueError otherwise).  Group ids keep their values: they are
+        compared inside a query's scene only."""
+        import numpy as np
+        if isinstance(maps, dict):
+            if names is not None:
+                raise ValueError("SceneAtlas.concat: a dict of maps carries its names")
+            names, maps = list(maps.keys()), list(maps.values())
+        maps = list(maps)
+        if not maps or not all(isinstance(m, FeatureMap) for m in maps):
+            raise ValueError("SceneAtlas.concat: needs at least one FeatureMap (a sequence or a dict of them)")
+        head = maps[0]
+        for i, m in enumerate(maps[1:], 1):
+            if m.meta != head.meta:
+                raise ValueError(f"SceneAtlas.concat: map {i} was made by another encoder than map 0 ({m.meta} != {head.meta})")
+            if m.device != head.device:
+                raise ValueError(f"SceneAtlas.concat: map {i} is on {m.device}, map 0 on {head.device}")
+            for what in ("poses", "descriptors", "groups"):
+                if (getattr(m, what) is None) != (getattr(head, what) is None):
+                    raise ValueError(f"SceneAtlas.concat: {what} must be held by every map or by none (map {i} differs from map 0)")
+            if head.descriptors is not None and m.descriptors.shape[1] != head.descriptors.shape[1]:
+                raise ValueError(f"SceneAtlas.concat: map {i}'s descriptors have {m.descriptors.shape[1]} columns, map 0's "
+                                 f"{head.descriptors.shape[1]}")
+        first = np.concatenate([[0], np.cumsum([len(m) for m in maps])]).astype(np.int64)
+        return cls(torch.cat([m.features for m in maps]), head.meta,
+                   None if head.poses is None else torch.cat([m.poses for m in maps]),
+                   None if head.descriptors is None else torch.cat([m.descriptors for m in maps]),
+                   None if head.groups_host is None else torch.cat([m.groups_host for m in maps]), first, names)
+
+    def extend(self, *a, **k):
+        raise NotImplementedError("SceneAtlas.extend: rows appended to an atlas would belong to no scene; extend the scene's own "
+                                  "FeatureMap and build the atlas again with SceneAtlas.concat")
+
+    def scene_of_rows(self):
+        """numpy int64 [M]: the scene of every row."""
+        import numpy as np
+        return np.repeat(np.arange(self.n_scenes, dtype=np.int64), np.diff(self.scene_first_host))
+
+    def scene_index(self, name) -> int:
+        return self.names.index(str(name))
+
+    def scene(self, i: int) -> FeatureMap:
+        """Scene ``i`` as a ``FeatureMap`` over the atlas's storage (rows ``scene_first_host[i] : scene_first_host[i + 1]``)."""
+        i = int(i)
+        if not 0 <= i < self.n_scenes:
+            raise IndexError(f"scene {i} outside [0, {self.n_scenes})")
+        a, b = int(self.scene_first_host[i]), int(self.scene_first_host[i + 1])
+        fm = FeatureMap(self.features[a:b], self.meta, None if self.poses is None else self.poses[a:b],
+                        None if self.descriptors is None else self.descriptors[a:b],
+                        None if self.groups_host is None else self.groups_host[a:b])
+        if self.groups is not None:
+            fm.groups = self.groups[a:b]
+        return fm
+
+    def n_allowed(self, query_groups_host, g: int, scenes_host=None):
+        """Per query the rows of its scene minus those of its group inside that scene (numpy int64 [g]).  ``scenes_host=None``
+        (the scenes are on the device only): the smallest scene's size for every query -- what a rule without random draws is
+        checked against; the kernel counts the ranks a query's own scene cannot serve."""
+        import numpy as np
+        sizes = np.diff(self.scene_first_host)
+        if scenes_host is None:
+            return np.full(g, int(sizes.min()), dtype=np.int64)
+        sc = np.asarray(scenes_host, dtype=np.int64).reshape(-1)
+        if sc.shape[0] != g or (sc.size and (sc.min() < 0 or sc.max() >= self.n_scenes)):
+            raise IndexError(f"scenes must be [{g}] indices inside [0, {self.n_scenes})")
+        out = sizes[sc].astype(np.int64)
+        if query_groups_host is None or self.groups_host is None:
+            return out
+        if self._scene_group_counts is None:
+            pairs, counts = np.unique(np.stack([self.scene_of_rows(), self.groups_host.numpy()], axis=1), axis=0, return_counts=True)
+            self._scene_group_counts = {(int(p[0]), int(p[1])): int(c) for p, c in zip(pairs, counts)}
+        for i, (s, q) in enumerate(zip(sc.tolist(), torch.as_tensor(query_groups_host).tolist())):
+            if q != -1:
+                out[i] -= self._scene_group_counts.get((s, q), 0)
+        return out
+
+    def _scope(self, scenes, g: int, rule, who: str, ranks_given: bool = False):
+        from .frames import scenes_to_device
+        if scenes is None:
+            raise ValueError(f"{who}: a SceneAtlas ranks every query inside its own scene: scenes [G] is required (ranking across "
+                             "scenes is never what was meant; scene(i) gives one scene's map)")
+        host, dev = scenes if isinstance(scenes, tuple) else scenes_to_device(scenes, g, self.device, who)
+        if host is None and rule is not None and rule.random and not ranks_given:
+            raise ValueError(f"{who}: a rule with random draws sizes them by each query's allowed rows on the host: pass scenes "
+                             "as host integers, not as a device tensor")
+        if host is not None and host.size and (host.min() < 0 or host.max() >= self.n_scenes):
+            raise IndexError(f"{who}: scenes has entries outside [0, {self.n_scenes})")
+        smallest = int((self.scene_first_host[1:] - self.scene_first_host[:-1]).min())
+        if rule is not None and rule.k > smallest:
+            raise ValueError(f"{who}: the rule picks {rule.k} rows, the smallest scene has {smallest}")
+        return host, dev
+
+    def save(self, path) -> None:
+        """``FeatureMap.save``'s file with two more keys (``scene_first``, ``scene_names``): ``FeatureMap.load`` reads it as
+        one plain map, ``SceneAtlas.load`` as the atlas."""
+        torch.save(dict(self._saved(), scene_first=torch.from_numpy(self.scene_first_host.copy()), scene_names=list(self.names)), path)
+
+    @classmethod
+    def load(cls, path, device) -> "SceneAtlas":
+        obj = torch.load(path, map_location="cpu", weights_only=True)
+        if not isinstance(obj, dict) or obj.get("format") != FORMAT:
+            raise ValueError(f"{path}: not a saved FeatureMap (format {FORMAT!r})")
+        if "scene_first" not in obj:
+            raise ValueError(f"{path}: a saved FeatureMap without scenes (load it with FeatureMap.load)")
+        poses = obj.get("poses")
+        return cls(obj["features"].to(device), obj["meta"], None if poses is None else poses.to(device), obj.get("descriptors"),
+                   obj.get("groups"), obj["scene_first"], obj.get("scene_names"))

@@ -108,6 +108,12 @@ class GraphedForwardMap:
     ``tracking.Tracker``, captured with this step -- gates the next replay.  ``self.gate_info`` int32 [G, 2] = (state, rows
     inside), static, valid after a replay like the outputs.
 
+    ``scenes`` [G] (with a rule on a ``featmap.SceneAtlas``, where it is required): each query's scene at the capture.
+    ``self.scenes`` -- int32 [G], static -- is what the retrieval inside the graph scopes every query by (``forward_map(scenes=)``):
+    ``scenes=`` of a call is copied into it and a call without leaves it as it is, so replays follow its current contents with no
+    new capture (a tracking loop writes a camera's scene there when it moves to another room).  uint8 frames stay outside the
+    graph, so a per-scene frame transform runs ahead of the call.
+
     A model with ``droprate > 0`` is captured only with ``model.mc_dropout`` set (mc_dropout.McDropout): the step then returns the
     means over its dropout samples, the one-thread kernel that advances the draw counter is part of the graph, so every replay
     draws the next masks, and ``node_base`` is read from the device state a caller sets ahead of the replay.  ``self.spread``
@@ -126,7 +132,8 @@ class GraphedForwardMap:
     ``RuntimeError`` instead of replaying over storage that is no longer the model's or the map's."""
 
     def __init__(self, model, fmap, example_queries: torch.Tensor, k: Optional[int] = None, *, rule=None, query_descriptors=None,
-                 pose=None, pose_kwargs: Optional[dict] = None, warmup: int = 2, outputs: str = "all", gate=None, _after=None):
+                 pose=None, pose_kwargs: Optional[dict] = None, warmup: int = 2, outputs: str = "all", gate=None, _after=None,
+                 scenes=None):
         self.refuse(model, example_queries)
         model._check_outputs(outputs, None)
         q = example_queries
@@ -164,6 +171,14 @@ class GraphedForwardMap:
         # _after (tracking.Tracker): called with this object and every step's MapStep behind its launches -- in the warm-up and in the capture, so
         # what it launches is part of the graph
         self.gate, self._after = gate, _after
+        self.scenes = None
+        if rule is not None:
+            # None for one scene's map (which takes no scenes); the warm-up and the capture draw nothing (see the ranks below)
+            scope = fmap._scope(scenes, g, rule, "GraphedForwardMap", ranks_given=True)
+            if scope is not None:
+                self.scenes = scope[1].clone()
+        elif scenes is not None:
+            raise ValueError("GraphedForwardMap: scenes scope retrieval: pass a rule (frames are transformed outside the graph)")
         self.prior = self.gate_info = None
         if gate is not None:
             fmap.gate_rows(gate)                  # cached on the map: made here, outside the capture, and held below
@@ -276,6 +291,8 @@ class GraphedForwardMap:
                 kw.update(gate=self.gate, _static=(self.ranks, self.query_groups, self.prior, self.gate_info))
             else:
                 kw["_static"] = (self.ranks, self.query_groups)
+            if self.scenes is not None:
+                kw["scenes"] = self.scenes
             ab, rel, ei, nb = m.forward_map(self.queries, None, self.fmap, rule=self.rule, query_descriptors=self.query_descriptors,
                                             outputs=self.outputs, **kw)
         if self.gate is not None:
@@ -306,6 +323,7 @@ class GraphedForwardMap:
                 "counters": m._counters.counters, "pose_counters": None if self.pose is None else self.pose._bad.counters,
                 "features": f.features, "poses": f.poses, "descriptors": f.descriptors, "groups": f.groups,
                 "inv_norms": f._inv_norms if self.rule is not None else None,
+                "scene_first": getattr(f, "scene_first", None) if self.scenes is not None else None,
                 "gate_rows": None if self.gate is None else f._gate_rows.get((tuple(self.gate.pose_m), tuple(self.gate.pose_s)))}
 
     @staticmethod
@@ -313,7 +331,8 @@ class GraphedForwardMap:
         """Objects by identity, the map's storage by (address, rows): what must be unchanged for the graph to be replayed."""
         return (id(r["library"]), id(r["encoder"]), id(r["gnn"]), id(r["gnn_bf16"]), r["dtypes"], id(r["counters"]),
                 id(r["pose_counters"]), _storage(r["features"]), _storage(r["poses"]), _storage(r["descriptors"]),
-                _storage(r["groups"]), _storage(r["inv_norms"]), id(r["mc_state"]), _storage(r["gate_rows"]))
+                _storage(r["groups"]), _storage(r["inv_norms"]), id(r["mc_state"]), _storage(r["scene_first"]),
+                _storage(r["gate_rows"]))
 
     def stale(self) -> bool:
         """True once the model or the map no longer hold what the graph was captured over."""
@@ -334,12 +353,15 @@ class GraphedForwardMap:
 
     @torch.no_grad()
     def __call__(self, queries: torch.Tensor, neighbours: Optional[torch.Tensor] = None, ranks=None, query_descriptors=None,
-                 query_groups=None, query_targets=None, prior=None) -> MapStep:
+                 query_groups=None, query_targets=None, prior=None, scenes=None) -> MapStep:
         """Copy the given inputs into the static buffers (non-blocking, on the current stream; a tensor that IS the static buffer
         -- ``self.queries`` filled by the caller -- is not copied), replay, publish the deferred counters.  ``ranks``: int32 [G, K]
         (tensor or array) in place of the rule's own, which are otherwise drawn here, on the host, as ``forward_map`` draws them;
         ``query_groups`` [G]: host integers, as ``forward_map`` takes them.  ``prior`` [G, 7] (a gated step only): copied into the
-        static prior; None leaves that buffer as it is."""
+        static prior; None leaves that buffer as it is.  ``scenes`` [G] (a step captured on a SceneAtlas only; host integers or an
+        int32 device tensor): copied into the static scenes; None leaves them as they are.  A rule with random draws, and
+        ``query_groups``, size the ranks by each query's allowed rows inside its scene: such a call needs ``scenes`` as host
+        integers every time (or the caller's own ``ranks``), ValueError otherwise."""
         if self.stale():
             raise RuntimeError("GraphedForwardMap is stale: the model's packed weights / precision or the feature map's storage "
                                "have changed since the capture (refresh_packed, load_state_dict, .to(), FeatureMap.extend): "
@@ -364,13 +386,23 @@ class GraphedForwardMap:
             if self.gate is None:
                 raise ValueError("GraphedForwardMap: prior given, but the graph was captured without a gate")
             prior_dev = self.fmap.prior_tensor(prior, self.g, "GraphedForwardMap")
+        sc_host = sc_dev = None
+        if scenes is not None:
+            if self.scenes is None:
+                raise ValueError("GraphedForwardMap: scenes given, but the graph was captured without (no rule on a SceneAtlas)")
+            sc_host, sc_dev = self.fmap._scope(scenes, self.g, self.rule, "GraphedForwardMap", ranks_given=ranks is not None)
         self.model._counters.poll()               # as the eager call starts: the report of the previous call, if it has landed
         host_ranks, qg_dev, fixed = None, None, False
         if self.rule is not None:
             qg_host, qg_dev = self.fmap._query_groups(query_groups, self.g)
             if ranks is None:
                 if self.rule.random or qg_host is not None:
-                    ranks = self.rule.ranks(self.fmap.n_allowed(qg_host, self.g))
+                    if self.scenes is not None and sc_host is None:
+                        # the draws are sized by each query's allowed rows inside ITS scene, and the static scenes are on the
+                        # device (where a tracker may have rewritten them): the host cannot size them
+                        raise ValueError("GraphedForwardMap: a rule with random draws, or query_groups, on a SceneAtlas needs this "
+                                         "call's scenes as host integers (scenes=), or ranks= of the caller's own")
+                    ranks = self.rule.ranks(self.fmap.n_allowed(qg_host, self.g, *(() if self.scenes is None else (sc_host,))))
                 elif not self._ranks_fixed:       # an earlier call left its own ranks in the static buffer
                     ranks = self._fixed_ranks
             fixed = ranks is self._fixed_ranks and ranks is not None
@@ -387,6 +419,8 @@ class GraphedForwardMap:
                 self._copy_in(static, given)
         if prior_dev is not None:
             self._copy_in(self.prior, prior_dev)
+        if sc_dev is not None:
+            self._copy_in(self.scenes, sc_dev)
         if host_ranks is not None:
             self.ranks.copy_(host_ranks, non_blocking=True)
             self._ranks_fixed = fixed

@@ -264,6 +264,48 @@ def frames_u8_to_bf16(frames: torch.Tensor, out_hw: Tuple[int, int], tables, mea
     return _frames(frames, out_hw, tables, mean, std, torch.bfloat16, out)
 
 
+def _frames_scenes(frames, out_hw, tables, scene_stats, frame_scene, dtype, status, out) -> torch.Tensor:
+    frames = _req(frames, "frames", torch.uint8)
+    if frames.dim() != 4 or frames.shape[3] != 3:
+        raise ValueError(f"frames: expected uint8 [n, H, W, 3] (RGB, HWC), got {tuple(frames.shape)}")
+    n, h, w, _ = frames.shape
+    oh, ow = int(out_hw[0]), int(out_hw[1])
+    hb, hw, vb, vw = tables
+    _frames_axis_tables("horizontal", w, ow, hb, hw, frames.device)
+    _frames_axis_tables("vertical", h, oh, vb, vw, frames.device)
+    stats, scene = _req(scene_stats, "scene_stats"), _req(frame_scene, "frame_scene", torch.int32)
+    if stats.dim() != 2 or stats.shape[0] < 1 or stats.shape[1] != 6 or stats.device != frames.device:
+        raise ValueError(f"frames: scene_stats must be fp32 [S >= 1, 6] (mean[3], std[3]) on the frames' GPU, got {tuple(stats.shape)}")
+    if tuple(scene.shape) != (n,) or scene.device != frames.device:
+        raise ValueError(f"frames: frame_scene must be int32 [{n}] on the frames' GPU, got {tuple(scene.shape)}")
+    out = _out(out, (n, 3, oh, ow), dtype, frames.device, "frames")
+    status, own = _status_arg(status, frames.device, "frames")
+    fn = L.lib().rpg_frames_u8_to_bf16_scenes if dtype == torch.bfloat16 else L.lib().rpg_frames_u8_to_f32_scenes
+    L.check(fn(_p(frames), n, h, w, oh, ow, _p(hb), _p(hw), _p(vb), _p(vw), _p(stats), _p(scene), stats.shape[0], status.data_ptr(),
+               _p(out), None, 0, _stream()), "frames_u8_scenes")
+    bad = _own_count(status, own)
+    if bad:
+        raise IndexError(f"frame_scene has {bad} entry(ies) outside the statistics' scenes [0, {stats.shape[0]})")
+    return out
+
+
+def frames_u8_to_f32_scenes(frames: torch.Tensor, out_hw: Tuple[int, int], tables, scene_stats: torch.Tensor,
+                            frame_scene: torch.Tensor, status: Optional[torch.Tensor] = None,
+                            out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``frames_u8_to_f32`` with the statistics per frame (rpg_frames_u8_to_f32_scenes): ``scene_stats`` fp32 [S, 6] = mean[3],
+    std[3] per scene and ``frame_scene`` int32 [n], both on the frames' GPU.  A scene outside [0, S) is counted into ``status``
+    (int32 device tensor, accumulates; the frame takes scene 0's statistics) -- with ``status=None`` the count is read back
+    here (one synchronisation) and a non-zero count raises IndexError."""
+    return _frames_scenes(frames, out_hw, tables, scene_stats, frame_scene, torch.float32, status, out)
+
+
+def frames_u8_to_bf16_scenes(frames: torch.Tensor, out_hw: Tuple[int, int], tables, scene_stats: torch.Tensor,
+                             frame_scene: torch.Tensor, status: Optional[torch.Tensor] = None,
+                             out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """As ``frames_u8_to_f32_scenes``, rounded to bf16 (nearest even)."""
+    return _frames_scenes(frames, out_hw, tables, scene_stats, frame_scene, torch.bfloat16, status, out)
+
+
 def resize_table(n_in: int, n_out: int):
     """HOST: Pillow's 8-bit bilinear table of one axis -> (bounds int32 [n_out, 2], weights int32 [n_out, ksize])."""
     lib = L.lib()
@@ -602,8 +644,53 @@ def retrieve_gated(q: torch.Tensor, db: torch.Tensor, ranks, db_gate: torch.Tens
     return (*res, info) if return_sims else (res, info)
 
 
-def _retrieve(q, db, ranks, db_inv_norm, q_group, db_group, return_sims, status, workspace, out, gate):
-    """``retrieve`` / ``retrieve_gated``: ``gate`` = None, or (db_gate, prior, r2, cos_half, rot_gate, gate_info) checked."""
+def retrieve_scoped(q: torch.Tensor, db: torch.Tensor, ranks, scene_first: Optional[torch.Tensor],
+                    q_scene: Optional[torch.Tensor], db_gate: Optional[torch.Tensor] = None,
+                    prior: Optional[torch.Tensor] = None, r2: float = 0.0, cos_half: float = 0.0, rot_gate: bool = False,
+                    db_inv_norm: Optional[torch.Tensor] = None, q_group: Optional[torch.Tensor] = None,
+                    db_group: Optional[torch.Tensor] = None, return_sims: bool = False, status: Optional[torch.Tensor] = None,
+                    workspace: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                    gate_info: Optional[torch.Tensor] = None):
+    """``retrieve`` / ``retrieve_gated`` on a map of several scenes (rpg_retrieve_cosine_scoped_f32): ``scene_first`` int64
+    [S + 1] (scene s owns rows [scene_first[s], scene_first[s + 1])) and ``q_scene`` int32 [G], on the inputs' GPU; query g ranks
+    its scene's rows only, exactly as if the rows outside were of its group.  A ``q_scene`` outside [0, S) counts 1 into
+    ``status`` and ranks nothing (row 0).  Both None: the gated entry itself.  ``db_gate`` and ``prior`` (both or neither)
+    gate as ``retrieve_gated`` does; then -> (neighbours [, sims], gate_info), otherwise neighbours [, sims]."""
+    if (scene_first is None) != (q_scene is None):
+        raise ValueError("retrieve_scoped: scene_first and q_scene go together (both or neither)")
+    if (db_gate is None) != (prior is None):
+        raise ValueError("retrieve_scoped: db_gate and prior go together (both or neither)")
+    if not torch.is_tensor(q) or not torch.is_tensor(db) or q.dim() != 2 or db.dim() != 2:
+        raise ValueError("retrieve_scoped: q [G, d] and db [M, d] must be 2-D tensors")
+    g, m = q.shape[0], db.shape[0]
+    scope = None
+    if scene_first is not None:
+        first, qs = _req(scene_first, "scene_first", torch.int64), _req(q_scene, "q_scene", torch.int32)
+        if first.dim() != 1 or first.shape[0] < 2 or tuple(qs.shape) != (g,) or first.device != q.device or qs.device != q.device:
+            raise ValueError(f"retrieve_scoped: scene_first must be int64 [S + 1 >= 2] and q_scene int32 [{g}] on the inputs' GPU, "
+                             f"got {tuple(first.shape)} and {tuple(qs.shape)}")
+        scope = (first, qs, first.shape[0] - 1)
+    gate = None
+    if db_gate is not None:
+        dbg, pr = _req(db_gate, "db_gate", torch.float64), _req(prior, "prior", torch.float64)
+        if tuple(dbg.shape) != (m, 7) or tuple(pr.shape) != (g, 7) or dbg.device != q.device or pr.device != q.device:
+            raise ValueError(f"retrieve_scoped: db_gate must be float64 [{m}, 7] and prior float64 [{g}, 7] on the inputs' GPU, got "
+                             f"{tuple(dbg.shape)} and {tuple(pr.shape)}")
+        r2, cos_half = float(r2), float(cos_half)
+        if not r2 >= 0.0 or cos_half != cos_half:
+            raise ValueError(f"retrieve_scoped: r2 must be >= 0 and cos_half a number, got {r2} and {cos_half}")
+        gate = (dbg, pr, r2, cos_half, int(bool(rot_gate)), _out(gate_info, (g, 2), torch.int32, q.device, "retrieve_scoped"))
+    elif gate_info is not None:
+        raise ValueError("retrieve_scoped: gate_info is an output of gated retrieval: pass db_gate and prior")
+    res = _retrieve(q, db, ranks, db_inv_norm, q_group, db_group, return_sims, status, workspace, out, gate, scope, True)
+    if gate is None:
+        return res
+    return (*res, gate[5]) if return_sims else (res, gate[5])
+
+
+def _retrieve(q, db, ranks, db_inv_norm, q_group, db_group, return_sims, status, workspace, out, gate, scope=None, scoped=False):
+    """``retrieve`` / ``retrieve_gated`` / ``retrieve_scoped``: ``gate`` = None, or (db_gate, prior, r2, cos_half, rot_gate,
+    gate_info) checked; ``scope`` = None, or (scene_first, q_scene, n_scenes) checked; ``scoped``: through the scoped entry."""
     q, db = _req(q, "q"), _req(db, "db")
     if q.dim() != 2 or db.dim() != 2:
         raise ValueError("retrieve: q [G, d] and db [M, d] must be 2-D")
@@ -639,7 +726,14 @@ def _retrieve(q, db, ranks, db_inv_norm, q_group, db_group, return_sims, status,
     nbrs = _out(out, (g, k), torch.int64, q.device, "retrieve")
     sims = torch.empty((g, k), dtype=torch.float32, device=q.device) if return_sims else None
     status, own = _status_arg(status, q.device, "retrieve")
-    if gate is None:
+    if scoped:
+        dbg, pr, r2, cos_half, rot, info = gate if gate is not None else (None, None, 0.0, 0.0, 0, None)
+        first, qs, ns = scope if scope is not None else (None, None, 0)
+        L.check(lib.rpg_retrieve_cosine_scoped_f32(_p(q), _p(db), _p(db_inv_norm), _p(q_group), _p(db_group), _p(ranks), g, k, m, d,
+                                                   _p(dbg), _p(pr), r2, cos_half, rot, _p(info), _p(first), _p(qs), ns, _p(nbrs),
+                                                   _p(sims), workspace.data_ptr(), workspace.numel(), status.data_ptr(), _stream()),
+                "retrieve_scoped")
+    elif gate is None:
         L.check(lib.rpg_retrieve_cosine_f32(_p(q), _p(db), _p(db_inv_norm), _p(q_group), _p(db_group), _p(ranks), g, k, m, d,
                                             _p(nbrs), _p(sims), workspace.data_ptr(), workspace.numel(), status.data_ptr(),
                                             _stream()), "retrieve")
@@ -652,7 +746,7 @@ def _retrieve(q, db, ranks, db_inv_norm, q_group, db_group, return_sims, status,
     bad = _own_count(status, own)
     if bad:
         raise IndexError(f"ranks has {bad} entry(ies) outside a query's allowed rows / the kernel's R_MAX, or rows that do "
-                         "not ascend")
+                         "not ascend" + (", or q_scene has entries outside the scenes" if scope is not None else ""))
     return (nbrs, sims) if return_sims else nbrs
 
 

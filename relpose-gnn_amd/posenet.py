@@ -296,10 +296,10 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
         report that is not in yet is seen by the next look."""
         self._counters.check(wait)
 
-    def _prepare(self, x: torch.Tensor, what: str):
+    def _prepare(self, x: torch.Tensor, what: str, scenes=None):
         """The start of every forward: images as the encoder takes them, the bad-edge report of the previous call if it has
-        landed, packed weights.  -> (x [n, 3, H, W], the library, the device counters int32 [16])."""
-        x = self._encoder_input(x, what)                                          # posenet.py:1035
+        landed, packed weights.  -> (x [n, 3, H, W], the library, the device counters int32 [16]).  ``scenes``: as ``encode``'s."""
+        x = self._encoder_input(x, what, scenes)                                  # posenet.py:1035
         lib = _L.lib()
         self._counters.poll()                     # bad-edge report of the previous call, if it has landed
         # all weight packing happens here, on the caller's stream, BEFORE any side stream is forked off it
@@ -572,15 +572,17 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
         return self._enc_digest
 
     @torch.no_grad()
-    def encode(self, x: torch.Tensor) -> torch.Tensor:
+    def encode(self, x: torch.Tensor, scenes=None) -> torch.Tensor:
         """Encoder features [n, feat_dim] fp32 of images ``x`` (what ``forward`` runs at posenet.py:1037, before the optional
         model-level attention): fp32 processed images [n, 3*H*W] / [n, 3, H, W], bf16 ones for the bf16 encoder, or uint8 frames
-        [n, H, W, 3] through ``frame_transform``; on the GPU."""
+        [n, H, W, 3] through ``frame_transform``; on the GPU.  ``scenes`` [n] (host integers or an int32 tensor on the GPU): the
+        scene of every frame, required for uint8 frames when ``frame_transform`` is a ``frames.SceneFrameTransform`` (ValueError
+        without) and not read otherwise."""
         if not torch.is_tensor(x) or not x.is_cuda:
             raise RuntimeError("encode: the images must be a tensor on the GPU (there is no CPU fallback)")
         if x.size(0) == 0:
             raise ValueError("encode: no images")
-        x = self._encoder_input(x, "images")
+        x = self._encoder_input(x, "images", scenes)
         self._enc.ensure_packed(self.feature_extractor.state_dict, "", x.device)
         return self._encode_small(x)
 
@@ -658,7 +660,7 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
     @torch.no_grad()
     def forward_map(self, queries: torch.Tensor, neighbours: Optional[torch.Tensor], fmap, k=None, *, rule=None,
                     query_descriptors: Optional[torch.Tensor] = None, query_groups=None, outputs: str = "all", _static=None,
-                    _irregular: Optional[torch.Tensor] = None, prior=None, gate=None):
+                    _irregular: Optional[torch.Tensor] = None, prior=None, gate=None, scenes=None):
         """The forward of G graphs, each query g followed by the K database images ``neighbours[g]`` of the feature map ``fmap``
         (dataset_7Scenes_multi.py:340-345) -- with only the G queries through the encoder.  Returns what
         ``forward(fc_batch(assembled, K + 1), k)`` returns for the assembled images: (abs_pose [G*(K+1), 6], rel_pose [E, 6],
@@ -708,6 +710,14 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
         = (state, rows inside) on the device, valid behind this call's launches like ``mc_dropout.last`` -- and None by every
         call without a gate.
 
+        ``scenes`` [G] (host integers, or an int32 tensor on the GPU): each query's scene.  With a ``rule`` on a
+        ``featmap.SceneAtlas`` it is required (ValueError without: ranking across scenes is never what was meant) and every query
+        is ranked against its own scene's rows only (``ops.retrieve_scoped``: both ``outputs`` modes, ``static_knn``,
+        ``mc_dropout`` and the gate, whose "rows inside" are then the scene's); a rule with random draws needs the host form, and a
+        rule whose ``k`` exceeds the smallest scene is refused.  With given ``neighbours``, or on one scene's map, it is read by the frame transform only:
+        uint8 queries of a model whose ``frame_transform`` is a ``frames.SceneFrameTransform`` need it.  A scene index outside
+        the atlas / the statistics is reported like a bad neighbour.
+
         ``_static`` (graphed.GraphedForwardMap only): ``(ranks int32 [G, K], query groups int64 [G] or None)`` already on the
         device, read in place of the two per-call host products above, so that nothing of the call depends on host data; with a
         gate two more elements, ``(..., prior float64 [G, 7], gate_info int32 [G, 2])``: the step's static prior (which a
@@ -727,9 +737,12 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
         if prior is not None or gate is not None:
             fmap.check_gate("forward_map", rule, prior, gate)
         self.gate_info = None
+        if scenes is not None and torch.is_tensor(queries):
+            from .frames import scenes_to_device
+            scenes = scenes_to_device(scenes, queries.size(0), queries.device, "forward_map")      # (host or None, device)
         if rule is not None:
             return self._forward_map_retrieve(queries, fmap, k, rule, query_descriptors, query_groups, _static, outputs, _irregular,
-                                              prior, gate)
+                                              prior, gate, scenes)
         if not torch.is_tensor(queries) or not torch.is_tensor(neighbours):
             raise TypeError("forward_map: queries and neighbours must be tensors")
         if neighbours.dtype != torch.int64 or neighbours.dim() != 2:
@@ -742,7 +755,7 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
             raise ValueError(f"forward_map: {queries.size(0)} queries but neighbours has {g} rows")
         self._map_devices(queries, fmap, "neighbours", neighbours)
         nb = neighbours.contiguous()
-        return self._forward_map_run(queries, fmap, k, g, kk, lambda qf, g0, g1, st, wkey: nb[g0:g1], outputs, _irregular)
+        return self._forward_map_run(queries, fmap, k, g, kk, lambda qf, g0, g1, st, wkey: nb[g0:g1], outputs, _irregular, scenes)
 
     @staticmethod
     def _map_devices(queries, fmap, name: str, t: Optional[torch.Tensor]) -> None:
@@ -755,7 +768,7 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
                                f"must be on the same GPU")
 
     def _forward_map_retrieve(self, queries, fmap, k, rule, query_descriptors, query_groups, static=None, outputs="all",
-                              irregular=None, prior=None, gate=None):
+                              irregular=None, prior=None, gate=None, scenes=None):
         """``forward_map`` with the neighbours retrieved per stream slot from that slot's query features (or descriptors).
         ``static``: see ``forward_map``'s ``_static``."""
         if not torch.is_tensor(queries):
@@ -779,9 +792,16 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
         dev = queries.device
         # everything the slots share is made here, on the caller's stream, before any side stream is forked off it
         qd = None if qd is None else qd.contiguous()
+        # a SceneAtlas: (host scenes or None, q_scene int32 [G] on the device); None for one scene's map -- which takes no scenes,
+        # except those that only the per-scene frame transform of uint8 queries reads
+        from .featmap import SceneAtlas
+        from .frames import SceneFrameTransform
+        for_frames = queries.dtype == torch.uint8 and isinstance(self.frame_transform, SceneFrameTransform)
+        scope = fmap._scope(scenes if isinstance(fmap, SceneAtlas) or not for_frames else None, g, rule, "forward_map",
+                            ranks_given=static is not None)
         if static is None:
             qg_host, qg_dev = fmap._query_groups(query_groups, g)
-            ranks = rule.device_ranks(fmap.n_allowed(qg_host, g), dev)
+            ranks = rule.device_ranks(fmap.n_allowed(qg_host, g) if scope is None else fmap.n_allowed(qg_host, g, scope[0]), dev)
         else:                                     # the host's per-call products, already in the caller's device buffers
             ranks, qg_dev = static[:2]
         gate_rows = prior_dev = info = None
@@ -800,6 +820,13 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
 
         def neighbours_of(qf, g0, g1, st, wkey):
             ws = self._ws_pool.get((400 + wkey[0], wkey[1]), int(ws_bytes(g1 - g0, db.shape[0], db.shape[1])), dev)
+            if scope is not None:
+                res = ops.retrieve_scoped(qf if qd is None else qd[g0:g1], db, ranks[g0:g1], fmap.scene_first, scope[1][g0:g1],
+                                          gate_rows, None if gate is None else prior_dev[g0:g1], 0.0 if gate is None else gate.r2,
+                                          0.0 if gate is None else gate.cos_half, gate is not None and gate.rot, db_inv_norm=inv,
+                                          q_group=None if qg_dev is None else qg_dev[g0:g1], db_group=db_groups, status=st,
+                                          workspace=ws, out=nb_out[g0:g1], gate_info=None if gate is None else info[g0:g1])
+                return res if gate is None else res[0]
             if gate is not None:
                 return ops.retrieve_gated(qf if qd is None else qd[g0:g1], db, ranks[g0:g1], gate_rows, prior_dev[g0:g1], gate.r2,
                                           gate.cos_half, gate.rot, db_inv_norm=inv, q_group=None if qg_dev is None else qg_dev[g0:g1],
@@ -807,14 +834,14 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
             return ops.retrieve(qf if qd is None else qd[g0:g1], db, ranks[g0:g1], db_inv_norm=inv,
                                 q_group=None if qg_dev is None else qg_dev[g0:g1], db_group=db_groups, status=st, workspace=ws,
                                 out=nb_out[g0:g1])
-        return (*self._forward_map_run(queries, fmap, k, g, kk, neighbours_of, outputs, irregular), nb_out)
+        return (*self._forward_map_run(queries, fmap, k, g, kk, neighbours_of, outputs, irregular, scenes), nb_out)
 
-    def _forward_map_run(self, queries, fmap, k, g, kk, neighbours_of, outputs="all", irregular=None):
+    def _forward_map_run(self, queries, fmap, k, g, kk, neighbours_of, outputs="all", irregular=None, scenes=None):
         """``neighbours_of(qf, g0, g1, status, wkey)``: the map rows int64 [g1 - g0, K] of queries g0..g1, whose encoder features
         are ``qf``, made on the current (slot) stream.  ``irregular``: ``forward_map``'s ``_irregular``."""
         fmap.check(self)
         self._mc()
-        x, lib, status = self._prepare(queries, "queries")
+        x, lib, status = self._prepare(queries, "queries", scenes)
         dev = x.device
         n_per = kk + 1
         kp = self._static_columns(k, kk)          # > 0: the kNN graph at fixed positions (static_knn)
@@ -854,16 +881,16 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
         feat = ops.gather_graph_nodes(qf, fmap.features, neighbours_of(qf, 0, g, status[8:9], (-1, 0)), status=status[8:9])
         return self._forward_tail(lib, feat, edge_index, batch, k, query, uniform)
 
-    def _encoder_input(self, x: torch.Tensor, what: str) -> torch.Tensor:
+    def _encoder_input(self, x: torch.Tensor, what: str, scenes=None) -> torch.Tensor:
         """Images as the encoder takes them: uint8 frames through ``frame_transform``, dtype checked, viewed as [n, 3, H, W]."""
         if x.dtype == torch.uint8 and self.frame_transform is not None:
-            x = self._transform_frames(x)
+            x = self._transform_frames(x, scenes)
         if x.dtype != torch.float32 and not (x.dtype == torch.bfloat16 and self.accepts_bf16_input):
             raise TypeError(f"{what} must be float32 (the reference's input dtype; bf16 images are taken by the bf16 encoder "
                             f"only), got {x.dtype}")
         return x.view(x.size(0), 3, self.input_img_height, -1)                    # posenet.py:1035
 
-    def _transform_frames(self, frames: torch.Tensor) -> torch.Tensor:
+    def _transform_frames(self, frames: torch.Tensor, scenes=None) -> torch.Tensor:
         """uint8 frames [n, H, W, 3] -> the encoder's input [n, 3, input_img_height, W'] through ``frame_transform``, in bf16 for
         the bf16 encoder (it rounds fp32 input to bf16 first thing: same poses) and fp32 otherwise.  Written into a pooled buffer
         on the caller's stream, before any side stream is forked off it; the buffer is reused by the next call, which the
@@ -879,6 +906,17 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
         n = frames.shape[0]
         nbytes = n * 3 * oh * ow * (2 if dtype == torch.bfloat16 else 4)
         buf = self._ws_pool.get((200, 0), max(nbytes, 16), frames.device)[:nbytes].view(dtype).view(n, 3, oh, ow)
+        from .frames import SceneFrameTransform
+        if isinstance(ft, SceneFrameTransform):   # the statistics follow every frame's scene
+            if scenes is None:
+                raise ValueError("frame_transform holds per-scene statistics (SceneFrameTransform): uint8 frames need scenes [n], "
+                                 "one scene index per frame")
+            if isinstance(scenes, tuple):         # (host, device), already staged by forward_map: checked here as apply checks
+                if scenes[0] is not None and scenes[0].size and (scenes[0].min() < 0 or scenes[0].max() >= len(ft)):
+                    raise IndexError(f"scenes has entries outside the frame transform's scenes [0, {len(ft)})")
+                scenes = scenes[1]
+            # a device tensor's entries cannot be checked here: a scene outside the statistics is counted like a bad neighbour
+            return ft.apply(frames, scenes, dtype, out=buf, status=self._counters.tensor(frames.device)[8:9])
         return ft.apply(frames, dtype, out=buf)
 
     def _encode_small(self, x: torch.Tensor) -> torch.Tensor:

@@ -37,13 +37,14 @@ TrackStep = namedtuple("TrackStep", "rows inliers accepted gate_info neighbours"
 class Tracker:
     def __init__(self, model, fmap, rule, gate, pose, streams: int = 1, min_inliers: int = 2, min_ratio: float = 0.5,
                  max_lost: int = 3, capture: bool = True, outputs: str = "query", example: Optional[torch.Tensor] = None,
-                 query_descriptors: Optional[torch.Tensor] = None):
+                 query_descriptors: Optional[torch.Tensor] = None, scenes=None):
         """``pose``: a ``QueryPose(fuse="consensus", ...)`` -- the accept rule reads its integers (anything else: ValueError).
         ``gate``: a ``retrieval.PoseGate``; ``rule``: a ``RetrievalRule`` without random draws.  ``example``: frames [streams,
         ...] as ``forward_map`` takes them (fp32, or bf16 for the bf16 encoder), on the map's GPU: the shape every step has
         (required with ``capture=True``, where it is the capture's example).  ``query_descriptors``: an example [streams, Dd] for a
         map that holds its own retrieval descriptors.  ``mc_dropout`` / ``static_knn`` models: as ``GraphedForwardMap`` takes
-        them."""
+        them.  ``scenes`` [streams] (a ``featmap.SceneAtlas`` only, where it is required): the scene every camera stands in;
+        ``self.scenes`` -- int32 [streams] on the device, static -- scopes every step's retrieval, and ``move`` rewrites it."""
         if getattr(pose, "fuse", None) != "consensus":
             raise ValueError("Tracker: pose must be a QueryPose(fuse='consensus', ...): the accept rule reads its (inliers, used)")
         if gate is None or rule is None:
@@ -71,12 +72,16 @@ class Tracker:
         self.lost = torch.zeros(streams, dtype=torch.int32, device=dev)
         self.accepted = torch.zeros(streams, dtype=torch.int32, device=dev)
         self._step = None
+        scope = fmap._scope(scenes, streams, rule, "Tracker")             # None for one scene's map (which takes no scenes)
+        self.scenes = None if scope is None else scope[1].clone()
         if capture:
             from .graphed import GraphedForwardMap
             # the update launch goes behind the pose rule of every step the class issues: warm-up, capture -- and so every replay
             self._step = GraphedForwardMap(model, fmap, example, rule=rule, query_descriptors=query_descriptors, pose=pose,
-                                           outputs=outputs, gate=gate, _after=self._update)
+                                           outputs=outputs, gate=gate, _after=self._update,
+                                           **({} if self.scenes is None else {"scenes": self.scenes}))
             self.prior = self._step.prior
+            self.scenes = self._step.scenes       # the captured step's static tensor: what every replay reads
         else:
             model._check_outputs(outputs, None)
             self.prior = torch.full((streams, 7), float("nan"), dtype=torch.float64, device=dev)
@@ -106,7 +111,8 @@ class Tracker:
             return TrackStep(out.rows, self._step.inliers, self.accepted, self._step.gate_info, out.neighbours)
         m = self.model
         ab, rel, ei, nb = m.forward_map(frames, None, self.fmap, rule=self.rule, query_descriptors=query_descriptors,
-                                        outputs=self.outputs, prior=self.prior, gate=self.gate)
+                                        outputs=self.outputs, prior=self.prior, gate=self.gate,
+                                        **({} if self.scenes is None else {"scenes": self.scenes}))
         info = m.gate_info
         var = None if self._sigma is None else m.mc_dropout.last.rel_var
         rows = self.pose.from_map(rel, ei, self.fmap, nb, edge_first=self._edge_first, out=self._rows, inliers=self._ints,
@@ -130,6 +136,20 @@ class Tracker:
         self.prior[idx] = float("nan")
         self.lost[idx] = 0
         self.accepted[idx] = 0
+
+    def move(self, stream: int, scene: int) -> None:
+        """Camera ``stream`` now stands in ``scene`` (an index of the atlas): written into the static scenes, so the next step
+        ranks its frame there with no new capture -- and its prior and ``lost`` count are forgotten, because a prior from
+        another room must not gate."""
+        if self.scenes is None:
+            raise ValueError("Tracker.move: the tracker's map is one scene's FeatureMap (scenes belong to a SceneAtlas)")
+        stream, scene = int(stream), int(scene)
+        if not 0 <= stream < self.streams:
+            raise IndexError(f"Tracker.move: stream index outside [0, {self.streams})")
+        if not 0 <= scene < self.fmap.n_scenes:
+            raise IndexError(f"Tracker.move: scene outside [0, {self.fmap.n_scenes})")
+        self.scenes[stream] = scene
+        self.reset([stream])
 
     def state(self) -> dict:
         """Host copies of ``prior`` [S, 7], ``lost`` [S] and ``accepted`` [S] (numpy; this waits for the device)."""
