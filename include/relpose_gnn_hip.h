@@ -252,6 +252,42 @@ int rpg_retrieve_cosine_scoped_f32(const float* q, const float* db, const float*
                                    int32_t* gate_info, const int64_t* scene_first, const int32_t* q_scene, int n_scenes,
                                    int64_t* neighbours, float* sims, void* workspace, size_t workspace_bytes, int32_t* status,
                                    void* stream);
+/* rpg_retrieve_cosine_scoped_f32 for queries that are not told their scene: they elect it (no counterpart in the reference,
+ * which is handed one scene at a time).  For a query g that elects, with V = vote_top:
+ *   voters     the rows at positions 0 .. V-1 of the order rpg_retrieve_cosine_f32 defines over all m rows (similarity
+ *              descending, row ascending, non-finite similarities last) -- no group filter (group ids mean something inside a
+ *              scene only) and no gate: the rows that call returns for ranks 0 .. V-1 without groups
+ *   scene      voter row r belongs to the scene s with scene_first[s] <= r < scene_first[s + 1], the boundaries clamped into
+ *              [0, m] as the scoped entry clamps them; s is found by binary search, so scene_first is expected not to descend
+ *              (if it does, some voters find no owner; nothing is read out of bounds).  A row no scene owns does not vote
+ *   election   the scene with the most voters; among tied scenes the one that owns the best-placed voter (NOT the lowest
+ *              index); -1 with no voter
+ *   output     scene_info[g] = (elected scene, its votes), q_scene[g] = elected scene
+ *   retrieval  bit for bit (neighbours, sims, gate_info, share of status) what rpg_retrieve_cosine_scoped_f32 gives with
+ *              q_scene[g] = the elected scene: groups and gate apply inside it; an elected -1 is an out-of-range scene there
+ * A NaN query needs no special case: all its similarities are non-finite, its voters are rows 0 .. V-1.
+ * elect_mode RPG_ELECT_ALL: every query elects; q_scene is an output only.  RPG_ELECT_LOST: query g elects when q_scene[g] ==
+ * -1 on entry or, with a gate, when prior[g] has a non-finite component; any other query is held: scoped by q_scene[g] exactly
+ * as the scoped entry does it (out-of-range values counted likewise), scene_info[g] = (q_scene[g], 0).  Elected entries of
+ * q_scene are overwritten, so the next call (or replay of a captured one) holds them.
+ * RPG_ERR_BAD_ARG before any launch: scene_first, q_scene or scene_info NULL or misaligned, n_scenes < 1, vote_top outside
+ * [1, 64] or above m, an unknown mode, and everything the scoped entry refuses.  Workspace
+ * rpg_retrieve_elect_workspace_bytes(g, m, d) >= rpg_retrieve_workspace_bytes(g, m, d): the vote keeps its keys uint32 [g][m]
+ * beside the products, which it reads and never writes.  Launches: the scoped entry's, plus the vote launch (one workgroup per
+ * query) between the product launch and the selection, plus with RPG_ELECT_LOST and a gate a mark launch ahead of the
+ * product launch that writes -1 into q_scene where the prior is not finite.  With RPG_ELECT_ALL the product launch is the
+ * unscoped one; with RPG_ELECT_LOST a scoped one in which an electing query's range is [0, m): a 16-row tile no query of the
+ * 64-query chunk ranks or votes over is still skipped before its first load.  The column slices stay a function of (m, d).
+ * No allocation, no synchronisation (graph-capturable).                                                                  */
+#define RPG_ELECT_ALL 1
+#define RPG_ELECT_LOST 2
+size_t rpg_retrieve_elect_workspace_bytes(int g, int64_t m, int d);
+int rpg_retrieve_cosine_elect_f32(const float* q, const float* db, const float* db_inv_norm, const int64_t* q_group,
+                                  const int64_t* db_group, const int32_t* ranks, int g, int k, int64_t m, int d,
+                                  const double* db_gate, const double* prior, double r2, double cos_half, int rot_gate,
+                                  int32_t* gate_info, const int64_t* scene_first, int32_t* q_scene, int n_scenes, int vote_top,
+                                  int elect_mode, int32_t* scene_info, int64_t* neighbours, float* sims, void* workspace,
+                                  size_t workspace_bytes, int32_t* status, void* stream);
 /* The update launch of a tracking loop (no counterpart in the reference, which relocalises every frame on its own,
  * testing/test.py:192-267): for each of s cameras, from this frame's pose-rule row rows [s][16] (its first seven doubles the
  * predicted (t, q)) and the consensus integers inliers int32 [s][2] = (inliers, used) of rpg_query_pose_consensus_f64:

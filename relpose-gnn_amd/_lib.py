@@ -37,6 +37,7 @@ SYMBOLS = (
     "rpg_query_pose_weighted_f64", "rpg_knn_graph_uniform_f32", "rpg_retrieve_cosine_gated_f32", "rpg_track_update_f64",
     "rpg_nchw3_to_nhwc8_bf16", "rpg_maxpool3x3s2_nhwc_bf16", "rpg_global_avgpool_nhwc_bf16", "rpg_conv_bf16_last_route",
     "rpg_retrieve_cosine_scoped_f32", "rpg_frames_u8_to_f32_scenes", "rpg_frames_u8_to_bf16_scenes",
+    "rpg_retrieve_elect_workspace_bytes", "rpg_retrieve_cosine_elect_f32",
 )
 
 
@@ -144,7 +145,11 @@ def _declare(lib: C.CDLL) -> None:
                                                   _vp, _vp, _vp, _sz, _vp, _vp])
     lib.rpg_retrieve_cosine_scoped_f32.argtypes = ([_vp] * 6 + [_i, _i, C.c_int64, _i, _vp, _vp, C.c_double, C.c_double, _i, _vp,
                                                    _vp, _vp, _i, _vp, _vp, _vp, _sz, _vp, _vp])
-    lib.rpg_track_update_f64.argtypes = [_vp, _vp, _i, _i, C.c_double, _i, _vp, _vp, _vp, _vp]
+    lib.rpg_retrieve_elect_workspace_bytes.argtypes = [_i, C.c_int64, _i]
+    lib.rpg_retrieve_elect_workspace_bytes.restype = _sz
+    lib.rpg_retrieve_cosine_elect_f32.argtypes = ([_vp] * 6 + [_i, _i, C.c_int64, _i, _vp, _vp, C.c_double, C.c_double, _i, _vp,
+                                                  _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp, _vp])
+    lib.rpg_track_update_f64.argtypes =[_vp, _vp, _i, _i, C.c_double, _i, _vp, _vp, _vp, _vp]
     # the pose rules' four entry points: rel_pose .. query_targets and the six pose_m / pose_s doubles, then each rule's own
     qp = [_vp, _vp, _vp, C.c_int64, _vp, _vp, _i, _vp, C.c_int64, _vp, C.c_int64, _vp, _i, _vp] + [C.c_double] * 6
     lib.rpg_query_pose_f64.argtypes = qp + [_i, _vp, _vp, _vp]

@@ -30,6 +30,15 @@
 // the (query, row) pairs inside a scope, and every sweep of the select kernel runs over [lo, hi) alone (so it never reads a
 // product that was not written).  The column slices stay a function of (m, d) of the whole map: the bits of a similarity do not
 // depend on whether the call was scoped.  Null scope pointers launch the instantiations without any of it.
+//
+// Finding the scene (rpg_retrieve_cosine_elect_f32): a query that is not told its scene elects it.  Its products are computed
+// against every row (the unscoped dot instantiation when every query elects; otherwise a scoped one in which an electing query's
+// range is [0, m)), and retrieve_vote_kernel, a launch of its own between (2) and (3), one workgroup per query, reads them
+// without writing them: unfiltered keys of all m rows go to a workspace region of their own, the same radix select takes the
+// vote_top best (key, row) pairs, each finds its scene by binary search in scene_first, and the scene with the most voters -- the
+// best-placed voter's among tied ones -- goes into q_scene.  Then (3) is the scoped selection as it stands, on that q_scene.
+// With RPG_ELECT_LOST a one-thread-per-query mark launch ahead of (2) writes -1 into q_scene where the prior is not finite, so
+// that every kernel of the call decides "elects" by the same test, q_scene[g] == -1.
 #include "rpg_common.h"
 #include "pose_gate.h"
 
@@ -110,8 +119,9 @@ __device__ __forceinline__ bool scope_of(const ScopeOn& sc, int gi, int64_t m, i
 // A = queries (tile rows i), B = database rows (tile columns j).  Lane l holds A[i = l & 15][k = l >> 4] and B[k = l >> 4][j = l & 15];
 // a lane's float4 at column 16 u + 4 (l >> 4) feeds four MFMAs (.x .y .z .w), so one wave step of 64 columns is 16 MFMAs per
 // query tile, in a fixed column order.  D[i = 4 (l >> 4) + reg][j = l & 15].
-// SCOPED: the chunk's scopes go to LDS first, and the workgroup returns when none of them meets its 16 rows.
-template <int NQ, bool SCOPED>
+// SCOPED: the chunk's scopes go to LDS first, and the workgroup returns when none of them meets its 16 rows.  ELECT (with
+// SCOPED): a query with q_scene -1 votes over every row, so its range is [0, m).
+template <int NQ, bool SCOPED, bool ELECT = false>
 __global__ __launch_bounds__(RT_NT) void retrieve_dot_kernel(const float* __restrict__ q, const float* __restrict__ db, int g,
                                                              int64_t m, int d, int blocks_per_split,
                                                              float* __restrict__ part,
@@ -128,7 +138,12 @@ __global__ __launch_bounds__(RT_NT) void retrieve_dot_kernel(const float* __rest
         if (threadIdx.x < RT_QCHUNK) {
             int64_t lo = 0, hi = 0;
             const int gi = g0 + (int)threadIdx.x;
-            if (gi < g) scope_of(sc, gi, m, &lo, &hi);
+            if (gi < g) {
+                if (ELECT && sc.q_scene[gi] == -1)
+                    hi = m;
+                else
+                    scope_of(sc, gi, m, &lo, &hi);
+            }
             s_lo[threadIdx.x] = lo;
             s_hi[threadIdx.x] = hi;
             meets = lo < m0 + RT_ROWS && hi > m0;         // (an empty range meets nothing)
@@ -436,6 +451,166 @@ __global__ __launch_bounds__(RS_NT) void retrieve_select_kernel(float* __restric
     }
 }
 
+// ---- the vote ---------------------------------------------------------------------------------------------------------------------
+constexpr int ELECT_ALL = 1, ELECT_LOST = 2;              // RPG_ELECT_ALL, RPG_ELECT_LOST
+
+// RPG_ELECT_LOST, ahead of the dot launch: a query without a finite prior elects, which every later kernel reads as q_scene -1.
+__global__ __launch_bounds__(NORM_NT) void retrieve_mark_lost_kernel(const double* __restrict__ prior, int g,
+                                                                     int32_t* __restrict__ q_scene) {
+    const int gi = blockIdx.x * NORM_NT + threadIdx.x;
+    if (gi >= g) return;
+    double p[GATE_ROW];
+    for (int i = 0; i < GATE_ROW; ++i) p[i] = prior[(int64_t)gi * GATE_ROW + i];
+    if (!rpg::pose_gate_finite7(p)) q_scene[gi] = -1;
+}
+
+// The scene that owns `row`, or -1: the last s with clamp(first[s]) <= row by binary search (boundaries that do not descend
+// are what a map has; whatever they hold, s stays inside [0, n) and the owner is confirmed with the clamping of scope_of).
+__device__ __forceinline__ int scene_of_row(const int64_t* __restrict__ first, int n, int64_t m, int64_t row) {
+    auto clamped = [&](int s) {
+        const int64_t a = first[s];
+        return a < 0 ? 0 : (a > m ? m : a);
+    };
+    int lo = 0, hi = n;                                   // the answer is in [lo, hi); first[n] only bounds the last scene
+    while (hi - lo > 1) {
+        const int mid = lo + (hi - lo) / 2;
+        if (clamped(mid) <= row)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    const int64_t a = clamped(lo);
+    int64_t b = first[lo + 1];
+    b = b < a ? a : (b > m ? m : b);
+    return row >= a && row < b ? lo : -1;
+}
+
+// One workgroup per query, between the dot launch and the selection.  It reads `part` and never writes it (the selection turns
+// slice 0 into keys in place afterwards): the keys of all m rows -- the sums of write_key, unfiltered -- go to `vkeys`, the
+// radix select of the selection takes the V-th smallest (key << 32 | row), the V pairs are sorted in LDS, and the voters are
+// counted per scene by comparing the V scenes with one another (no table of n counters, so n is unbounded).  The one LDS
+// atomic that decides is an integer max.  all == 0: a query whose q_scene is not -1 is held, scene_info = (its scene, 0).
+__global__ __launch_bounds__(RS_NT) void retrieve_vote_kernel(const float* __restrict__ part, int nsplit,
+                                                              const float* __restrict__ q_inv, const float* __restrict__ db_inv,
+                                                              int g, int64_t m, int vote_top, int all,
+                                                              const int64_t* __restrict__ first, int n, uint32_t* __restrict__ vkeys,
+                                                              int32_t* __restrict__ q_scene, int32_t* __restrict__ scene_info) {
+    __shared__ unsigned hist[256];
+    __shared__ unsigned long long list[K_MAX];
+    __shared__ int s_scene[K_MAX];
+    __shared__ unsigned s_cnt, s_bucket, s_need, s_best;
+    const int tid = threadIdx.x;
+    const int gi = blockIdx.x;
+    if (!all) {                                           // uniform over the workgroup
+        const int32_t held = q_scene[gi];
+        if (held != -1) {
+            if (tid == 0) {
+                scene_info[2 * (int64_t)gi] = held;
+                scene_info[2 * (int64_t)gi + 1] = 0;
+            }
+            return;
+        }
+    }
+    uint32_t* keys = vkeys + (int64_t)gi * m;             // element mm is written and read by the same thread in every pass
+    const float qi = q_inv[gi];
+    for (int64_t mm = tid; mm < m; mm += RS_NT) {
+        float dot = part[(int64_t)gi * m + mm];
+        for (int s = 1; s < nsplit; ++s) dot += part[((int64_t)s * g + gi) * m + mm];          // slice order, as write_key
+        const float sim = dot * qi * db_inv[mm];
+        keys[mm] = sim_key(sim);
+    }
+    if (tid == 0) {
+        s_cnt = 0;
+        s_best = 0;
+    }
+    if (tid < K_MAX) {
+        list[tid] = ~0ull;
+        s_scene[tid] = -1;
+    }
+    // radix select of the V-th smallest pair (1 <= V <= m: it exists), as in retrieve_select_kernel
+    unsigned long long prefix = 0, mask = 0;
+    unsigned need = (unsigned)vote_top;
+    for (int shift = 56; shift >= 0; shift -= 8) {
+        if (shift < 32 && ((unsigned long long)(m - 1) >> shift) == 0) {
+            mask |= 0xFFull << shift;
+            continue;
+        }
+        if (tid < 256) hist[tid] = 0;
+        __syncthreads();
+        for (int64_t mm = tid; mm < m; mm += RS_NT) {
+            const unsigned long long comp = ((unsigned long long)keys[mm] << 32) | (unsigned long long)mm;
+            if ((comp & mask) == prefix) atomicAdd(&hist[(unsigned)(comp >> shift) & 255u], 1u);
+        }
+        __syncthreads();
+        if (tid == 0) {
+            unsigned cum = 0;
+            int b = 0;
+            for (; b < 255; ++b) {
+                const unsigned h = hist[b];
+                if (cum + h >= need) break;
+                cum += h;
+            }
+            s_bucket = (unsigned)b;
+            s_need = need - cum;
+        }
+        __syncthreads();
+        prefix |= (unsigned long long)s_bucket << shift;
+        mask |= 0xFFull << shift;
+        need = s_need;
+    }
+    __syncthreads();                                      // (every digit skipped, m == 1: the initialisation above still lands)
+    for (int64_t mm = tid; mm < m; mm += RS_NT) {
+        const unsigned long long comp = ((unsigned long long)keys[mm] << 32) | (unsigned long long)mm;
+        if (comp <= prefix) {
+            const unsigned slot = atomicAdd(&s_cnt, 1u);
+            if (slot < (unsigned)K_MAX) list[slot] = comp;
+        }
+    }
+    for (int size = 2; size <= K_MAX; size <<= 1) {
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            __syncthreads();
+            if (tid < K_MAX / 2) {
+                const int i = 2 * tid - (tid & (stride - 1));
+                const int j = i + stride;
+                const bool up = (i & size) == 0;
+                const unsigned long long a = list[i], b = list[j];
+                if ((a > b) == up) {
+                    list[i] = b;
+                    list[j] = a;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    // voter tid (position tid of the order) finds its scene; then counts the voters of that scene and the best-placed of them
+    if (tid < vote_top && list[tid] != ~0ull) {
+        int64_t row = (int64_t)(list[tid] & 0xFFFFFFFFull);
+        if (row >= m) row = m - 1;
+        s_scene[tid] = scene_of_row(first, n, m, row);
+    }
+    __syncthreads();
+    if (tid < vote_top && s_scene[tid] >= 0) {
+        const int mine = s_scene[tid];
+        unsigned votes = 0;
+        int best = K_MAX - 1;
+        for (int i = K_MAX - 1; i >= 0; --i)
+            if (s_scene[i] == mine) {
+                ++votes;
+                best = i;
+            }
+        atomicMax(&s_best, votes * (unsigned)K_MAX + (unsigned)(K_MAX - 1 - best));       // most votes, then the earliest position
+    }
+    __syncthreads();
+    if (tid == 0) {
+        const unsigned best = s_best;
+        const int32_t votes = (int32_t)(best / (unsigned)K_MAX);
+        const int32_t scene = votes ? s_scene[K_MAX - 1 - (int)(best % (unsigned)K_MAX)] : -1;
+        q_scene[gi] = scene;
+        scene_info[2 * (int64_t)gi] = scene;
+        scene_info[2 * (int64_t)gi + 1] = votes;
+    }
+}
+
 // ---- host side -----------------------------------------------------------------------------------------------------------------
 size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
@@ -476,22 +651,30 @@ int launch_inv_norms(const float* x, int64_t rows, int d, float* inv, hipStream_
     return RPG_OK;
 }
 
-template <bool SCOPED>
-int launch_dot_select(const float* q, const float* db, const float* q_inv, const float* db_inv_norm, const int64_t* q_group,
-                      const int64_t* db_group, const int32_t* ranks, int g, int k, int64_t m, int d, const double* db_gate,
-                      const double* prior, double r2, double cos_half, int rot_gate, int32_t* gate_info, int64_t* neighbours,
-                      float* sims, float* part, int32_t* status, const typename ScopeArgs<SCOPED>::type sc, hipStream_t s) {
+template <bool SCOPED, bool ELECT>
+int launch_dot(const float* q, const float* db, int g, int64_t m, int d, float* part, const typename ScopeArgs<SCOPED>::type sc,
+               hipStream_t s) {
     int ns, bps;
     split_plan(m, d, &ns, &bps);
     const dim3 grid((unsigned)((m + RT_ROWS - 1) / RT_ROWS), (unsigned)ns, (unsigned)((g + RT_QCHUNK - 1) / RT_QCHUNK));
     const int tiles = ((g < RT_QCHUNK ? g : RT_QCHUNK) + 15) / 16;
     if (tiles <= 1)
-        hipLaunchKernelGGL((retrieve_dot_kernel<1, SCOPED>), grid, dim3(RT_NT), 0, s, q, db, g, m, d, bps, part, sc);
+        hipLaunchKernelGGL((retrieve_dot_kernel<1, SCOPED, ELECT>), grid, dim3(RT_NT), 0, s, q, db, g, m, d, bps, part, sc);
     else if (tiles == 2)
-        hipLaunchKernelGGL((retrieve_dot_kernel<2, SCOPED>), grid, dim3(RT_NT), 0, s, q, db, g, m, d, bps, part, sc);
+        hipLaunchKernelGGL((retrieve_dot_kernel<2, SCOPED, ELECT>), grid, dim3(RT_NT), 0, s, q, db, g, m, d, bps, part, sc);
     else
-        hipLaunchKernelGGL((retrieve_dot_kernel<4, SCOPED>), grid, dim3(RT_NT), 0, s, q, db, g, m, d, bps, part, sc);
+        hipLaunchKernelGGL((retrieve_dot_kernel<4, SCOPED, ELECT>), grid, dim3(RT_NT), 0, s, q, db, g, m, d, bps, part, sc);
     RPG_CHECK_LAUNCH("retrieve_dot");
+    return RPG_OK;
+}
+
+template <bool SCOPED>
+int launch_select(const float* q_inv, const float* db_inv_norm, const int64_t* q_group, const int64_t* db_group,
+                  const int32_t* ranks, int g, int k, int64_t m, int d, const double* db_gate, const double* prior, double r2,
+                  double cos_half, int rot_gate, int32_t* gate_info, int64_t* neighbours, float* sims, float* part, int32_t* status,
+                  const typename ScopeArgs<SCOPED>::type sc, hipStream_t s) {
+    int ns, bps;
+    split_plan(m, d, &ns, &bps);
     if (db_gate) {
         const GateOn ga = {db_gate, prior, r2, cos_half, rot_gate, gate_info};
         hipLaunchKernelGGL((retrieve_select_kernel<true, SCOPED>), dim3(g), dim3(RS_NT), 0, s, part, ns, q_inv, db_inv_norm, q_group,
@@ -502,6 +685,55 @@ int launch_dot_select(const float* q, const float* db, const float* q_inv, const
     }
     RPG_CHECK_LAUNCH("retrieve_select");
     return RPG_OK;
+}
+
+template <bool SCOPED>
+int launch_dot_select(const float* q, const float* db, const float* q_inv, const float* db_inv_norm, const int64_t* q_group,
+                      const int64_t* db_group, const int32_t* ranks, int g, int k, int64_t m, int d, const double* db_gate,
+                      const double* prior, double r2, double cos_half, int rot_gate, int32_t* gate_info, int64_t* neighbours,
+                      float* sims, float* part, int32_t* status, const typename ScopeArgs<SCOPED>::type sc, hipStream_t s) {
+    const int rc = launch_dot<SCOPED, false>(q, db, g, m, d, part, sc, s);
+    if (rc != RPG_OK) return rc;
+    return launch_select<SCOPED>(q_inv, db_inv_norm, q_group, db_group, ranks, g, k, m, d, db_gate, prior, r2, cos_half, rot_gate,
+                                 gate_info, neighbours, sims, part, status, sc, s);
+}
+
+// What every retrieval entry refuses before a launch: the shapes and alignments, the gate's three pointers together or not at
+// all with a radius that is a number, the scopes' two pointers together or not at all with at least one scene.
+bool retrieve_args_ok(const float* q, const float* db, const float* db_inv_norm, const int64_t* q_group, const int64_t* db_group,
+                      const int32_t* ranks, int g, int k, int64_t m, int d, const double* db_gate, const double* prior, double r2,
+                      double cos_half, const int32_t* gate_info, const int64_t* scene_first, const int32_t* q_scene, int n_scenes,
+                      const int64_t* neighbours, const float* sims, const void* workspace, const int32_t* status) {
+    if (!q || !db || !ranks || !neighbours || !workspace || !status || g < 1 || k < 1 || k > K_MAX || m < k ||
+        m >= ((int64_t)1 << 31) || d <= 0 || (d & 3) || !rpg::aligned16(q) || !rpg::aligned16(db) || !rpg::aligned16(workspace) ||
+        ((q_group == nullptr) != (db_group == nullptr)) || (reinterpret_cast<uintptr_t>(neighbours) & 7u) ||
+        (reinterpret_cast<uintptr_t>(q_group) & 7u) || (reinterpret_cast<uintptr_t>(db_group) & 7u) ||
+        (reinterpret_cast<uintptr_t>(ranks) & 3u) || (reinterpret_cast<uintptr_t>(status) & 3u) ||
+        (reinterpret_cast<uintptr_t>(sims) & 3u) || (reinterpret_cast<uintptr_t>(db_inv_norm) & 3u) ||
+        (g + RT_QCHUNK - 1) / RT_QCHUNK > 65535)
+        return false;
+    if ((db_gate == nullptr) != (prior == nullptr) || (db_gate == nullptr) != (gate_info == nullptr) ||
+        (reinterpret_cast<uintptr_t>(db_gate) & 7u) || (reinterpret_cast<uintptr_t>(prior) & 7u) ||
+        (reinterpret_cast<uintptr_t>(gate_info) & 3u) || (db_gate && (!(r2 >= 0.0) || cos_half != cos_half)))
+        return false;
+    if ((scene_first == nullptr) != (q_scene == nullptr) || (reinterpret_cast<uintptr_t>(scene_first) & 7u) ||
+        (reinterpret_cast<uintptr_t>(q_scene) & 3u) || (scene_first && n_scenes < 1))
+        return false;
+    return true;
+}
+
+// The electing call's workspace: the scoped call's, then the vote's keys uint32 [g][m].
+struct ElectLayout {
+    WsLayout w;
+    size_t vkeys, total;
+};
+
+ElectLayout elect_layout(int g, int64_t m, int d) {
+    ElectLayout e;
+    e.w = ws_layout(g, m, d);
+    e.vkeys = e.w.total;
+    e.total = e.vkeys + round_up((size_t)g * (size_t)m * sizeof(uint32_t), 256);
+    return e;
 }
 
 }  // namespace
@@ -525,22 +757,8 @@ extern "C" int rpg_retrieve_cosine_scoped_f32(const float* q, const float* db, c
                                              int32_t* gate_info, const int64_t* scene_first, const int32_t* q_scene, int n_scenes,
                                              int64_t* neighbours, float* sims, void* workspace, size_t workspace_bytes,
                                              int32_t* status, void* stream) {
-    if (!q || !db || !ranks || !neighbours || !workspace || !status || g < 1 || k < 1 || k > K_MAX || m < k ||
-        m >= ((int64_t)1 << 31) || d <= 0 || (d & 3) || !rpg::aligned16(q) || !rpg::aligned16(db) || !rpg::aligned16(workspace) ||
-        ((q_group == nullptr) != (db_group == nullptr)) || (reinterpret_cast<uintptr_t>(neighbours) & 7u) ||
-        (reinterpret_cast<uintptr_t>(q_group) & 7u) || (reinterpret_cast<uintptr_t>(db_group) & 7u) ||
-        (reinterpret_cast<uintptr_t>(ranks) & 3u) || (reinterpret_cast<uintptr_t>(status) & 3u) ||
-        (reinterpret_cast<uintptr_t>(sims) & 3u) || (reinterpret_cast<uintptr_t>(db_inv_norm) & 3u) ||
-        (g + RT_QCHUNK - 1) / RT_QCHUNK > 65535)
-        return RPG_ERR_BAD_ARG;
-    // the gate: its three pointers together or not at all, a radius that is a number
-    if ((db_gate == nullptr) != (prior == nullptr) || (db_gate == nullptr) != (gate_info == nullptr) ||
-        (reinterpret_cast<uintptr_t>(db_gate) & 7u) || (reinterpret_cast<uintptr_t>(prior) & 7u) ||
-        (reinterpret_cast<uintptr_t>(gate_info) & 3u) || (db_gate && (!(r2 >= 0.0) || cos_half != cos_half)))
-        return RPG_ERR_BAD_ARG;
-    // the scopes: both pointers or neither, at least one scene
-    if ((scene_first == nullptr) != (q_scene == nullptr) || (reinterpret_cast<uintptr_t>(scene_first) & 7u) ||
-        (reinterpret_cast<uintptr_t>(q_scene) & 3u) || (scene_first && n_scenes < 1))
+    if (!retrieve_args_ok(q, db, db_inv_norm, q_group, db_group, ranks, g, k, m, d, db_gate, prior, r2, cos_half, gate_info,
+                          scene_first, q_scene, n_scenes, neighbours, sims, workspace, status))
         return RPG_ERR_BAD_ARG;
     const WsLayout w = ws_layout(g, m, d);
     if (workspace_bytes < w.total) return RPG_ERR_WORKSPACE;
@@ -561,6 +779,58 @@ extern "C" int rpg_retrieve_cosine_scoped_f32(const float* q, const float* db, c
                                        rot_gate, gate_info, neighbours, sims, part, status, ScopeOn{scene_first, q_scene, n_scenes}, s);
     return launch_dot_select<false>(q, db, q_inv, db_inv_norm, q_group, db_group, ranks, g, k, m, d, db_gate, prior, r2, cos_half,
                                     rot_gate, gate_info, neighbours, sims, part, status, ScopeOff{}, s);
+}
+
+extern "C" size_t rpg_retrieve_elect_workspace_bytes(int g, int64_t m, int d) {
+    if (g <= 0 || m <= 0 || d <= 0) return 0;
+    return elect_layout(g, m, d).total;
+}
+
+extern "C" int rpg_retrieve_cosine_elect_f32(const float* q, const float* db, const float* db_inv_norm, const int64_t* q_group,
+                                            const int64_t* db_group, const int32_t* ranks, int g, int k, int64_t m, int d,
+                                            const double* db_gate, const double* prior, double r2, double cos_half, int rot_gate,
+                                            int32_t* gate_info, const int64_t* scene_first, int32_t* q_scene, int n_scenes,
+                                            int vote_top, int elect_mode, int32_t* scene_info, int64_t* neighbours, float* sims,
+                                            void* workspace, size_t workspace_bytes, int32_t* status, void* stream) {
+    if (!scene_first || !q_scene || !scene_info || (reinterpret_cast<uintptr_t>(scene_info) & 3u) || vote_top < 1 ||
+        vote_top > K_MAX || vote_top > m || (elect_mode != ELECT_ALL && elect_mode != ELECT_LOST) ||
+        !retrieve_args_ok(q, db, db_inv_norm, q_group, db_group, ranks, g, k, m, d, db_gate, prior, r2, cos_half, gate_info,
+                          scene_first, q_scene, n_scenes, neighbours, sims, workspace, status))
+        return RPG_ERR_BAD_ARG;
+    const ElectLayout e = elect_layout(g, m, d);
+    if (workspace_bytes < e.total) return RPG_ERR_WORKSPACE;
+    hipStream_t s = rpg::as_stream(stream);
+    char* base = static_cast<char*>(workspace);
+    float* q_inv = reinterpret_cast<float*>(base + e.w.q_inv);
+    float* part = reinterpret_cast<float*>(base + e.w.part);
+    uint32_t* vkeys = reinterpret_cast<uint32_t*>(base + e.vkeys);
+    int rc = launch_inv_norms(q, g, d, q_inv, s);
+    if (rc != RPG_OK) return rc;
+    if (!db_inv_norm) {
+        float* db_inv = reinterpret_cast<float*>(base + e.w.db_inv);
+        rc = launch_inv_norms(db, m, d, db_inv, s);
+        if (rc != RPG_OK) return rc;
+        db_inv_norm = db_inv;
+    }
+    const ScopeOn sc = {scene_first, q_scene, n_scenes};
+    if (elect_mode == ELECT_ALL) {
+        rc = launch_dot<false, false>(q, db, g, m, d, part, ScopeOff{}, s);
+    } else {
+        if (prior) {
+            hipLaunchKernelGGL(retrieve_mark_lost_kernel, dim3((unsigned)((g + NORM_NT - 1) / NORM_NT)), dim3(NORM_NT), 0, s, prior, g,
+                               q_scene);
+            RPG_CHECK_LAUNCH("retrieve_mark_lost");
+        }
+        rc = launch_dot<true, true>(q, db, g, m, d, part, sc, s);
+    }
+    if (rc != RPG_OK) return rc;
+    int ns, bps;
+    split_plan(m, d, &ns, &bps);
+    hipLaunchKernelGGL(retrieve_vote_kernel, dim3(g), dim3(RS_NT), 0, s, part, ns, q_inv, db_inv_norm, g, m, vote_top,
+                       elect_mode == ELECT_ALL ? 1 : 0, scene_first, n_scenes, vkeys, q_scene, scene_info);
+    RPG_CHECK_LAUNCH("retrieve_vote");
+    return launch_select<true>(q_inv, db_inv_norm, q_group, db_group, ranks, g, k, m, d, db_gate, prior, r2, cos_half, rot_gate,
+                               gate_info, neighbours, sims, part, status, sc, s);
 }
 
 extern "C" int rpg_retrieve_cosine_gated_f32(const float* q, const float* db, const float* db_inv_norm, const int64_t* q_group,

@@ -337,6 +337,8 @@ class EvalResult:
     sigma_t: Optional[np.ndarray] = None     # [G] float, weights="variance" only: predicted deviation of the fused translation
     sigma_q: Optional[np.ndarray] = None     # [G] float, weights="variance" only: that of the rotation, in log-quaternion units
     gate_state: Optional[np.ndarray] = None  # [G] int, relocalize(priors=, gate=) only: 0 gated, 1 no prior, 2 fell back to the whole map
+    scene: Optional[np.ndarray] = None       # [G] int, relocalize(scenes=SceneVote) only: the scene every query elected (-1: none)
+    scene_votes: Optional[np.ndarray] = None # [G] int, ... and the votes it was elected with
 
     @property
     def median_t(self) -> float:
@@ -559,7 +561,8 @@ def _check_weights(who: str, model, weights, fuse, var_floor):
 
 # what relocalize's forward hands to its read-back: forward_map's outputs, the neighbours on the device, the retrieved ones on
 # their way to the host (None: they were given), and the pose rule's output block where a captured step has already filled it
-_Forward = namedtuple("_Forward", "abs_pose rel_pose edge_index neighbours host_neighbours back gate_info", defaults=(None, None, None))
+_Forward = namedtuple("_Forward", "abs_pose rel_pose edge_index neighbours host_neighbours back gate_info scene_info",
+                      defaults=(None, None, None, None))
 
 
 def _result_from_rows(rows: np.ndarray) -> EvalResult:
@@ -684,6 +687,13 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
     query ranked inside its own scene; the scenes are sliced per micro-batch and staged like the priors, a captured step holds
     them in a static tensor, and the re-run of an irregular kNN micro-batch carries them along.  With a ``rule`` on an atlas
     they are required (ValueError without).
+    A ``retrieval.SceneVote`` in their place (a ``rule`` without random draws on an atlas): the queries are not told their
+    scene; every query elects it on the GPU from its most similar rows of the whole atlas and is ranked there
+    (``forward_map(scenes=SceneVote)``, which see for what is refused -- here before any work is queued).  The elected scenes
+    and their votes come back with each micro-batch's results, the way the gate states do: ``stats["scene"]`` and
+    ``stats["scene_votes"]``, int [G], and ``.scene`` / ``.scene_votes`` on an ``EvalResult``.  ``capture=True`` is served (the
+    vote is part of the captured step, which is keyed by ``SceneVote.key`` too), and the re-run of an irregular kNN
+    micro-batch carries the elected scenes along as explicit scenes.
 
     ``postprocess="device"`` (default ``"host"``): the pose rule runs on the GPU behind every ``forward_map``
     (``query_pose.QueryPose.from_map`` on the map's poses and the device neighbours -- with a rule the rows ``forward_map`` has
@@ -767,8 +777,15 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
         fmap.gate_rows(gate)                      # (a map without poses raises here, before any work is queued)
         gate_h = np.zeros((int(queries.shape[0]), 2), dtype=np.int32)
     gkw = {} if gate is None else {"gate": gate}
-    sc_all = None
-    if scenes is not None:
+    from .retrieval import SceneVote
+    sc_all = vote = scene_h = None
+    if isinstance(scenes, SceneVote):
+        vote = scenes
+        if rule is None:
+            raise ValueError("relocalize: a SceneVote finds the scene retrieval ranks in: pass a rule and no neighbours (given "
+                             "neighbours are used as they are)")
+        scene_h = np.zeros((int(queries.shape[0]), 2), dtype=np.int32)
+    elif scenes is not None:
         sc_all = torch.as_tensor(scenes).cpu()
         if sc_all.dim() != 1 or sc_all.shape[0] != int(queries.shape[0]) or sc_all.dtype.is_floating_point or sc_all.dtype == torch.bool:
             raise ValueError(f"relocalize: scenes must be integers [{int(queries.shape[0])}] (one scene index per query), got "
@@ -780,7 +797,13 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
     if rule is not None and isinstance(fmap, FeatureMap):          # refusals before any work is queued (an atlas without scenes, ...)
         from .frames import SceneFrameTransform
         for_frames = queries.dtype == torch.uint8 and isinstance(getattr(model, "frame_transform", None), SceneFrameTransform)
-        if isinstance(fmap, SceneAtlas) or not for_frames:         # (one scene's map: scenes that only the frame transform reads)
+        if vote is not None:
+            if for_frames:
+                raise ValueError("relocalize: uint8 queries of a SceneFrameTransform need their scene's statistics before the "
+                                 "encoder, and a SceneVote knows the scene only behind it: pass processed queries (or use a plain "
+                                 "FrameTransform)")
+            fmap._scope(vote, int(queries.shape[0]), rule, "relocalize")
+        elif isinstance(fmap, SceneAtlas) or not for_frames:       # (one scene's map: scenes that only the frame transform reads)
             fmap._scope(None if sc_all is None else (sc_all.numpy().astype(np.int64), None), int(queries.shape[0]), rule, "relocalize")
     _check_postprocess("relocalize", postprocess, device)
     _check_fuse("relocalize", fuse, max_edges, ref_node, inlier_t, inlier_deg)
@@ -876,7 +899,7 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
         nonlocal n_captured
         key = ("step", tuple(x.shape), x.dtype, kk, None if rule is None else (rule.sampling_period, rule.random), postprocess,
                fuse, max_edges, qd is not None, targ is not None, outputs, inlier_t, inlier_deg, weights, var_floor, kp,
-               None if gate is None else gate.key, sc_all is not None,
+               None if gate is None else gate.key, sc_all is not None, None if vote is None else vote.key,
                None if mc is None else (id(mc), mc.samples, mc.seed))       # the sampler's count and seed are baked into the step
         step = captured.get(key)
         if step is None or step.fmap is not fmap or step.pose is not qp or step.stale():
@@ -886,7 +909,8 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
                     captured[qp_key] = qp
             step = captured[key] = GraphedForwardMap(model, fmap, x, kk, rule=rule, query_descriptors=qd, pose=qp,
                                                      pose_kwargs=None if targ is None else {"query_targets": targ}, **okw, **gkw,
-                                                     **({} if sc_all is None or rule is None else {"scenes": sc_all[:x.shape[0]]}))
+                                                     **({"scenes": vote} if vote is not None else {} if sc_all is None or rule is None
+                                                        else {"scenes": sc_all[:x.shape[0]]}))
             n_captured += 1
         return step
 
@@ -899,7 +923,7 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
             mc.place(mc_draw, b0 * n_per)
         if irr_dev is not None:
             irr_dev.zero_()
-        skw = {} if sc_all is None else {"scenes": sc_all[b0:b1]}
+        skw = {} if sc_all is None else {"scenes": sc_all[b0:b1]}       # (a vote: the captured step's own; eager, below)
         if rule is None and not capture:
             ab, rel, ei = model.forward_map(x, nb_dev[b0:b1], fmap, **okw, **ikw, **skw)
             return _Forward(ab, rel, ei, nb_dev[b0:b1]), irregular_back(irr_dev, b0)
@@ -927,11 +951,13 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
             # pinned memory (read_back here and in _MicroBatchRunner.launch, right after this returns) are enqueued on the stream
             # the replay ran on BEFORE the next launch() enqueues its replay there: stream order keeps micro-batch i's results.
             return (_Forward(out.abs_pose, out.rel_pose, out.edge_index, out.neighbours,
-                             None if rule is None else runner.read_back(out.neighbours), step.packed, step.gate_info),
+                             None if rule is None else runner.read_back(out.neighbours), step.packed, step.gate_info,
+                             step.scene_info),
                     irregular_back(getattr(step, "irregular", None), b0))
         ab, rel, ei, nb_mb = model.forward_map(x, None, fmap, rule=rule, query_descriptors=qd, query_groups=qg, **okw, **ikw, **pkw, **gkw,
-                                               **skw)
-        return (_Forward(ab, rel, ei, nb_mb, runner.read_back(nb_mb), gate_info=model.gate_info if gate is not None else None),
+                                               **(skw if vote is None else {"scenes": vote}))
+        return (_Forward(ab, rel, ei, nb_mb, runner.read_back(nb_mb), gate_info=model.gate_info if gate is not None else None,
+                         scene_info=model.scene_info if vote is not None else None),
                 irregular_back(irr_dev, b0))
 
     def read_back_of(chunk, x, fwd):
@@ -941,7 +967,7 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
             return {"nb": fwd.host_neighbours, "abs": fwd.abs_pose, "rel": fwd.rel_pose,
                     "ei": fwd.edge_index if model.knn > 0 else None,
                     "var": mc.last.rel_var if weights is not None and poses_h is not None else None, "irr": irr,
-                    "gate": fwd.gate_info}
+                    "gate": fwd.gate_info, "scene": fwd.scene_info}
         back = fwd.back
         if back is None:                   # everything the rule writes travels back in one tensor, one copy
             b0, n = chunk[0].first, x.shape[0]
@@ -950,7 +976,7 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
                         rel_var=None if spread is None else mc.last.rel_var,
                         query_targets=None if targ_dev is None else targ_dev[b0:b0 + n],
                         edge_first=None if fc_first is None else fc_first[:n + 1])
-        return {"nb": fwd.host_neighbours, "rel": back, "irr": irr, "gate": fwd.gate_info}
+        return {"nb": fwd.host_neighbours, "rel": back, "irr": irr, "gate": fwd.gate_info, "scene": fwd.scene_info}
 
     def general_again(b0, n):
         """A micro-batch that reported an irregular graph, once more through the general kNN build (static_knn off, the whole
@@ -962,7 +988,10 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
         try:
             if mc is not None:
                 mc.place(mc_draw, b0 * n_per)
-            ab, rel, ei = model.forward_map(x, nb_mb, fmap, **({} if sc_all is None else {"scenes": sc_all[b0:b0 + n]}))
+            # (a vote: the scenes this micro-batch elected -- they have landed with its neighbours -- as explicit scenes)
+            again = {"scenes": sc_all[b0:b0 + n]} if sc_all is not None else (
+                {"scenes": torch.from_numpy(scene_h[b0:b0 + n, 0].copy())} if vote is not None else {})
+            ab, rel, ei = model.forward_map(x, nb_mb, fmap, **again)
             var = None if mc is None else mc.last.rel_var
             if qp is None:
                 return {"nb": None, "abs": ab.cpu(), "rel": rel.cpu(), "ei": ei.cpu(),
@@ -988,6 +1017,8 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
             nb_h[b0:b0 + host["nb"].shape[0]] = host["nb"].numpy()
         if host.get("gate") is not None:
             gate_h[b0:b0 + host["gate"].shape[0]] = host["gate"].numpy()
+        if host.get("scene") is not None:
+            scene_h[b0:b0 + host["scene"].shape[0]] = host["scene"].numpy()
         rows_of = rows_per
         if host.get("irr") is not None and int(host["irr"][0]):
             host, rows_of = general_again(b0, sum(int(c.x.shape[0]) for c in item.chunk)), n_per
@@ -1017,6 +1048,8 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
         stats["neighbours"] = nb_h
         if gate_h is not None:
             stats["gate_state"], stats["gate_rows"] = gate_h[:, 0].copy(), gate_h[:, 1].copy()
+        if scene_h is not None:
+            stats["scene"], stats["scene_votes"] = scene_h[:, 0].copy(), scene_h[:, 1].copy()
         if capture:
             stats.update(graphs_captured=n_captured, graph_replays=n_replays)
         if kp:
@@ -1028,6 +1061,8 @@ def relocalize(model, fmap, queries: torch.Tensor, neighbours=None, micro_batch:
         res.neighbours = nb_h
         if gate_h is not None:
             res.gate_state = gate_h[:, 0].copy()
+        if scene_h is not None:
+            res.scene, res.scene_votes = scene_h[:, 0].copy(), scene_h[:, 1].copy()
     elif stats is not None and acc.ints is not None:          # no EvalResult to carry them: the two arrays go to stats
         ints = acc.integers()
         stats["inliers"], stats["used"] = ints[:, 0].copy(), ints[:, 1].copy()

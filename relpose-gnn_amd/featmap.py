@@ -257,16 +257,18 @@ class FeatureMap:
             raise ValueError(f"{who}: a rule with random draws sizes them by each query's allowed-row count on the host, which a "
                              "pose gate changes on the device: use a rule without drop / random_start with a gate")
 
-    def _scope(self, scenes, g: int, rule, who: str, ranks_given: bool = False):
+    def _scope(self, scenes, g: int, rule, who: str, ranks_given: bool = False, lost_ok: bool = False):
         """The scene scope of a retrieval: None for one scene's map (which takes no ``scenes``); a ``SceneAtlas`` returns (host
-        scenes or None, q_scene int32 [g] on the device).  ``ranks_given``: the caller has the ranks already (a captured step
-        reads them from its static buffer), so nothing is drawn here and a random rule does not need the host form."""
+        scenes or None, q_scene int32 [g] on the device) -- or, for a ``retrieval.SceneVote``, (None, None, the vote): the caller
+        provides the q_scene the election writes.  ``ranks_given``: the caller has the ranks already (a captured step reads them
+        from its static buffer), so nothing is drawn here and a random rule does not need the host form.  ``lost_ok``: the caller
+        keeps its scenes on the device between calls, so a vote with ``lost_only`` means something."""
         if scenes is not None:
             raise ValueError(f"{who}: scenes belong to a SceneAtlas (SceneAtlas.concat), this is one scene's FeatureMap")
         return None
 
     def retrieve(self, query_descriptors: torch.Tensor, rule, query_groups=None, status=None, workspace=None, prior=None,
-                 gate=None, gate_info=None, scenes=None) -> torch.Tensor:
+                 gate=None, gate_info=None, scenes=None, scene_info=None) -> torch.Tensor:
         """int64 [G, K] on the map's device: per query the map rows ``rule`` picks from the ranking of ``descriptor_matrix`` by
         cosine similarity to ``query_descriptors`` fp32 [G, Dd] (on the map's device), rows of the query's group left out
         (``query_groups`` [G], host integers; -1 or None: nothing left out).  ``status`` / ``workspace``: as ``ops.retrieve``.
@@ -275,9 +277,14 @@ class FeatureMap:
         rows inside) -- pass a tensor to read them.  A rule with random draws raises ValueError with a gate.
         ``scenes`` [G] (a ``SceneAtlas`` only, and required there): each query's scene, host integers or an int32 tensor on the
         map's device; a query ranks its scene's rows alone (``ops.retrieve_scoped``).  A rule with random draws needs the host
-        form, as it needs host ``query_groups``."""
+        form, as it needs host ``query_groups``.  A ``retrieval.SceneVote`` in its place: every query elects its scene from the
+        most similar rows of the whole atlas (``ops.retrieve_elect``) and is ranked there; ``scene_info`` int32 [G, 2] receives
+        (elected scene, votes) -- pass a tensor to read them.  The ranks are checked against the smallest scene."""
         from . import ops
         self.check_gate("retrieve", rule, prior, gate)
+        from .retrieval import SceneVote
+        if scene_info is not None and not isinstance(scenes, SceneVote):
+            raise ValueError("retrieve: scene_info is an output of a scene vote: pass scenes=retrieval.SceneVote(...)")
         if gate is None and gate_info is not None:
             raise ValueError("retrieve: gate_info is an output of gated retrieval: pass prior and gate")
         if not torch.is_tensor(query_descriptors) or query_descriptors.dim() != 2:
@@ -292,6 +299,13 @@ class FeatureMap:
             gate_rows, prior = self.gate_rows(gate), self.prior_tensor(prior, g)
         qg_host, qg_dev = self._query_groups(query_groups, g)
         scope = self._scope(scenes, g, rule, "retrieve")
+        if scope is not None and len(scope) == 3:
+            ranks = rule.device_ranks(self.n_allowed(qg_host, g, None), self.device)
+            return ops.retrieve_elect(query_descriptors, db, ranks, self.scene_first, scope[2].top,
+                                      db_gate=None if gate is None else gate_rows, prior=prior, r2=0.0 if gate is None else gate.r2,
+                                      cos_half=0.0 if gate is None else gate.cos_half, rot_gate=gate is not None and gate.rot,
+                                      db_inv_norm=self.inv_norms(), q_group=qg_dev, db_group=None if qg_dev is None else self.groups,
+                                      status=status, workspace=workspace, gate_info=gate_info, scene_info=scene_info)[0]
         if scope is not None:
             ranks = rule.device_ranks(self.n_allowed(qg_host, g, scope[0]), self.device)
             res = ops.retrieve_scoped(query_descriptors, db, ranks, self.scene_first, scope[1],
@@ -469,8 +483,22 @@ class SceneAtlas(FeatureMap):
                 out[i] -= self._scene_group_counts.get((s, q), 0)
         return out
 
-    def _scope(self, scenes, g: int, rule, who: str, ranks_given: bool = False):
+    def _scope(self, scenes, g: int, rule, who: str, ranks_given: bool = False, lost_ok: bool = False):
         from .frames import scenes_to_device
+        from .retrieval import SceneVote
+        smallest = int((self.scene_first_host[1:] - self.scene_first_host[:-1]).min())
+        if isinstance(scenes, SceneVote):
+            if scenes.lost_only and not lost_ok:
+                raise ValueError(f"{who}: SceneVote(lost_only=True) holds the scenes earlier calls elected, which only a step with "
+                                 "static scenes keeps: a GraphedForwardMap with a gate, or a tracking.Tracker")
+            if rule is not None and rule.random:
+                raise ValueError(f"{who}: a rule with random draws sizes them on the host by each query's scene, which a SceneVote "
+                                 "finds on the device: use a rule without drop / random_start with a vote")
+            if scenes.top > len(self):
+                raise ValueError(f"{who}: the vote takes the {scenes.top} most similar rows, the atlas has {len(self)}")
+            if rule is not None and rule.k > smallest:
+                raise ValueError(f"{who}: the rule picks {rule.k} rows, the smallest scene has {smallest}")
+            return None, None, scenes
         if scenes is None:
             raise ValueError(f"{who}: a SceneAtlas ranks every query inside its own scene: scenes [G] is required (ranking across "
                              "scenes is never what was meant; scene(i) gives one scene's map)")
@@ -480,7 +508,6 @@ class SceneAtlas(FeatureMap):
                              "as host integers, not as a device tensor")
         if host is not None and host.size and (host.min() < 0 or host.max() >= self.n_scenes):
             raise IndexError(f"{who}: scenes has entries outside [0, {self.n_scenes})")
-        smallest = int((self.scene_first_host[1:] - self.scene_first_host[:-1]).min())
         if rule is not None and rule.k > smallest:
             raise ValueError(f"{who}: the rule picks {rule.k} rows, the smallest scene has {smallest}")
         return host, dev

@@ -22,11 +22,32 @@ camera that sends one frame at a time.
 """
 from __future__ import annotations
 
+import contextlib
+import gc
 from collections import namedtuple
 from typing import Optional
 
 import numpy as np
 import torch
+
+
+@contextlib.contextmanager
+def _capturing(graph, stream):
+    """``torch.cuda.graph(graph, stream=stream)`` with Python's cycle collector held off.  A dead reference cycle may hold
+    captured graphs -- a model and the steps in its ``_map_captures``, which hold the model, are one -- and the collector runs
+    whenever enough objects have been allocated: in the middle of a capture, too.  On ROCm the destructor of a
+    ``torch.cuda.CUDAGraph`` synchronises the device, which is not permitted while a stream is capturing and, raised from a
+    destructor, ends the process.  So such cycles are collected here, ahead of the capture (``torch.cuda.graph`` no longer does
+    that itself), and the collector stays off until the capture has ended."""
+    gc.collect()
+    was_enabled = gc.isenabled()
+    gc.disable()
+    try:
+        with torch.cuda.graph(graph, stream=stream):
+            yield
+    finally:
+        if was_enabled:
+            gc.enable()
 
 
 class GraphedForward:
@@ -48,7 +69,7 @@ class GraphedForward:
                 model(self.static)
             if hasattr(model, "check_edge_index"):
                 model.check_edge_index()          # validates the example's edge_index (one sync, before the capture)
-            with torch.cuda.graph(self.graph, stream=side):
+            with _capturing(self.graph, side):
                 self.out = model(self.static)
         torch.cuda.current_stream().wait_stream(side)
 
@@ -113,6 +134,12 @@ class GraphedForwardMap:
     ``scenes=`` of a call is copied into it and a call without leaves it as it is, so replays follow its current contents with no
     new capture (a tracking loop writes a camera's scene there when it moves to another room).  uint8 frames stay outside the
     graph, so a per-scene frame transform runs ahead of the call.
+    A ``retrieval.SceneVote`` in its place: the election is part of the graph (``forward_map(scenes=SceneVote)``).  ``self.scenes``
+    is then what the election writes and ``self.scene_info`` -- int32 [G, 2] = (elected scene, its votes), static -- is valid after
+    a replay like the outputs.  ``lost_only=False``: every replay elects every query (``scenes=`` of a call is refused).
+    ``lost_only=True`` (a gate is required): ``self.scenes`` starts at -1 = "elect"; a query elects when its entry is -1 or its
+    static prior is not finite, and otherwise stays in the scene an earlier replay elected; ``scenes=`` of a call still copies
+    explicit indices in, -1 among them.
 
     A model with ``droprate > 0`` is captured only with ``model.mc_dropout`` set (mc_dropout.McDropout): the step then returns the
     means over its dropout samples, the one-thread kernel that advances the draw counter is part of the graph, so every replay
@@ -171,11 +198,15 @@ class GraphedForwardMap:
         # _after (tracking.Tracker): called with this object and every step's MapStep behind its launches -- in the warm-up and in the capture, so
         # what it launches is part of the graph
         self.gate, self._after = gate, _after
-        self.scenes = None
+        self.scenes = self.vote = self.scene_info = None
         if rule is not None:
             # None for one scene's map (which takes no scenes); the warm-up and the capture draw nothing (see the ranks below)
-            scope = fmap._scope(scenes, g, rule, "GraphedForwardMap", ranks_given=True)
-            if scope is not None:
+            scope = fmap._scope(scenes, g, rule, "GraphedForwardMap", ranks_given=True, lost_ok=gate is not None)
+            if scope is not None and len(scope) == 3:         # a SceneVote: the election writes the static scenes
+                self.vote = scope[2]
+                self.scenes = torch.full((g,), -1, dtype=torch.int32, device=dev)
+                self.scene_info = torch.zeros((g, 2), dtype=torch.int32, device=dev)
+            elif scope is not None:
                 self.scenes = scope[1].clone()
         elif scenes is not None:
             raise ValueError("GraphedForwardMap: scenes scope retrieval: pass a rule (frames are transformed outside the graph)")
@@ -242,12 +273,14 @@ class GraphedForwardMap:
                 self._step()
                 if self.prior is not None:        # (an _after that accepted the warm-up's pose: the capture starts without a prior)
                     self.prior.fill_(float("nan"))
+                if self.vote is not None:         # (... and without the scenes the warm-up elected)
+                    self.scenes.fill_(-1)
             if mc_saved is not None:
                 mc.state(dev).copy_(mc_saved)
             model.check_edge_index()              # one sync, before the capture: the warm-up's inputs were valid
             if pose is not None:
                 pose.check()
-            with torch.cuda.graph(self.graph, stream=side):
+            with _capturing(self.graph, side):
                 self.out = self._step()
             if mc is not None:
                 mc._init[0] = mc._word(mc_draw)   # the host's count of the draws, which the warm-up forwards moved on as well
@@ -291,12 +324,16 @@ class GraphedForwardMap:
                 kw.update(gate=self.gate, _static=(self.ranks, self.query_groups, self.prior, self.gate_info))
             else:
                 kw["_static"] = (self.ranks, self.query_groups)
-            if self.scenes is not None:
+            if self.vote is not None:
+                kw.update(scenes=self.vote, _vote=(self.scenes, self.scene_info))
+            elif self.scenes is not None:
                 kw["scenes"] = self.scenes
             ab, rel, ei, nb = m.forward_map(self.queries, None, self.fmap, rule=self.rule, query_descriptors=self.query_descriptors,
                                             outputs=self.outputs, **kw)
         if self.gate is not None:
             m.gate_info = self.gate_info
+        if self.vote is not None:
+            m.scene_info = self.scene_info
         rows = None
         if self.pose is not None:
             # (a weighted rule: the variances this forward has just left -- in the capture, the step's static spread.rel_var)
@@ -361,7 +398,8 @@ class GraphedForwardMap:
         static prior; None leaves that buffer as it is.  ``scenes`` [G] (a step captured on a SceneAtlas only; host integers or an
         int32 device tensor): copied into the static scenes; None leaves them as they are.  A rule with random draws, and
         ``query_groups``, size the ranks by each query's allowed rows inside its scene: such a call needs ``scenes`` as host
-        integers every time (or the caller's own ``ranks``), ValueError otherwise."""
+        integers every time (or the caller's own ``ranks``), ValueError otherwise.  A step captured with a ``SceneVote``: with
+        ``lost_only`` the indices may hold -1 (elect); without, every replay elects and ``scenes`` is refused."""
         if self.stale():
             raise RuntimeError("GraphedForwardMap is stale: the model's packed weights / precision or the feature map's storage "
                                "have changed since the capture (refresh_packed, load_state_dict, .to(), FeatureMap.extend): "
@@ -390,13 +428,22 @@ class GraphedForwardMap:
         if scenes is not None:
             if self.scenes is None:
                 raise ValueError("GraphedForwardMap: scenes given, but the graph was captured without (no rule on a SceneAtlas)")
-            sc_host, sc_dev = self.fmap._scope(scenes, self.g, self.rule, "GraphedForwardMap", ranks_given=ranks is not None)
+            if self.vote is None:
+                sc_host, sc_dev = self.fmap._scope(scenes, self.g, self.rule, "GraphedForwardMap", ranks_given=ranks is not None)
+            elif not self.vote.lost_only:
+                raise ValueError("GraphedForwardMap: the step was captured with a SceneVote that every query elects by: scenes "
+                                 "of a call would be overwritten (capture with lost_only=True to hold given scenes)")
+            else:
+                from .frames import scenes_to_device
+                sc_host, sc_dev = scenes_to_device(scenes, self.g, self.fmap.device, "GraphedForwardMap")
+                if sc_host is not None and sc_host.size and (sc_host.min() < -1 or sc_host.max() >= self.fmap.n_scenes):
+                    raise IndexError(f"GraphedForwardMap: scenes has entries outside [-1, {self.fmap.n_scenes}) (-1: elect)")
         self.model._counters.poll()               # as the eager call starts: the report of the previous call, if it has landed
         host_ranks, qg_dev, fixed = None, None, False
         if self.rule is not None:
             qg_host, qg_dev = self.fmap._query_groups(query_groups, self.g)
             if ranks is None:
-                if self.rule.random or qg_host is not None:
+                if self.rule.random or (qg_host is not None and self.vote is None):    # (a vote: the smallest scene, fixed)
                     if self.scenes is not None and sc_host is None:
                         # the draws are sized by each query's allowed rows inside ITS scene, and the static scenes are on the
                         # device (where a tracker may have rewritten them): the host cannot size them
@@ -432,6 +479,7 @@ class GraphedForwardMap:
         self.graph.replay()
         if self.gate is not None:
             self.model.gate_info = self.gate_info
+        self.model.scene_info = self.scene_info
         if self.spread is not None:               # the replayed step advanced the draw counter on the device
             self.model.mc_dropout.last = self.spread
             self.model.mc_dropout.advanced()

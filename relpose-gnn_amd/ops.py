@@ -688,9 +688,64 @@ def retrieve_scoped(q: torch.Tensor, db: torch.Tensor, ranks, scene_first: Optio
     return (*res, gate[5]) if return_sims else (res, gate[5])
 
 
-def _retrieve(q, db, ranks, db_inv_norm, q_group, db_group, return_sims, status, workspace, out, gate, scope=None, scoped=False):
-    """``retrieve`` / ``retrieve_gated`` / ``retrieve_scoped``: ``gate`` = None, or (db_gate, prior, r2, cos_half, rot_gate,
-    gate_info) checked; ``scope`` = None, or (scene_first, q_scene, n_scenes) checked; ``scoped``: through the scoped entry."""
+def retrieve_elect(q: torch.Tensor, db: torch.Tensor, ranks, scene_first: torch.Tensor, top: int = 16,
+                   q_scene: Optional[torch.Tensor] = None, lost_only: bool = False, db_gate: Optional[torch.Tensor] = None,
+                   prior: Optional[torch.Tensor] = None, r2: float = 0.0, cos_half: float = 0.0, rot_gate: bool = False,
+                   db_inv_norm: Optional[torch.Tensor] = None, q_group: Optional[torch.Tensor] = None,
+                   db_group: Optional[torch.Tensor] = None, return_sims: bool = False, status: Optional[torch.Tensor] = None,
+                   workspace: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                   gate_info: Optional[torch.Tensor] = None, scene_info: Optional[torch.Tensor] = None):
+    """``retrieve_scoped`` for queries that are not told their scene (rpg_retrieve_cosine_elect_f32): the ``top`` (1 .. 64, at
+    most M) most similar rows of the whole map -- ``retrieve(q, db, ranks=arange(top))`` without groups -- vote for the scene
+    that owns them, the scene with the most votes (among tied ones the best-placed voter's) is elected, and the query is ranked
+    inside it bit for bit as ``retrieve_scoped`` ranks it there.  ``lost_only=False``: every query elects; ``q_scene`` int32 [G]
+    (made here when None) is an output.  ``lost_only=True``: ``q_scene`` is required, in and out: query g elects when
+    ``q_scene[g] == -1`` or, with a gate, when ``prior[g]`` is not finite, and is otherwise held in ``q_scene[g]``; elected entries
+    are overwritten.  -> (neighbours [, sims] [, gate_info], q_scene, scene_info), ``scene_info`` int32 [G, 2] = (elected scene,
+    its votes), (held scene, 0) for a held query, -1 when no row voted.  ``workspace``: at least
+    rpg_retrieve_elect_workspace_bytes(G, M, d) bytes.  Everything else as ``retrieve_scoped``."""
+    if (db_gate is None) != (prior is None):
+        raise ValueError("retrieve_elect: db_gate and prior go together (both or neither)")
+    if not torch.is_tensor(q) or not torch.is_tensor(db) or q.dim() != 2 or db.dim() != 2:
+        raise ValueError("retrieve_elect: q [G, d] and db [M, d] must be 2-D tensors")
+    g, m = q.shape[0], db.shape[0]
+    top = int(top)
+    if not 1 <= top <= 64 or top > m:
+        raise ValueError(f"retrieve_elect: top must be in [1, 64] and at most the map's {m} rows, got {top}")
+    first = _req(scene_first, "scene_first", torch.int64)
+    if first.dim() != 1 or first.shape[0] < 2 or first.device != q.device:
+        raise ValueError(f"retrieve_elect: scene_first must be int64 [S + 1 >= 2] on the inputs' GPU, got {tuple(first.shape)}")
+    if q_scene is None:
+        if lost_only:
+            raise ValueError("retrieve_elect: lost_only reads q_scene (-1: elect): pass it")
+        q_scene = torch.empty(g, dtype=torch.int32, device=q.device)
+    qs = _req(q_scene, "q_scene", torch.int32)
+    if tuple(qs.shape) != (g,) or qs.device != q.device or qs is not q_scene:       # (written in place: no contiguous copy)
+        raise ValueError(f"retrieve_elect: q_scene must be a contiguous int32 [{g}] on the inputs' GPU, got {tuple(qs.shape)}")
+    gate = None
+    if db_gate is not None:
+        dbg, pr = _req(db_gate, "db_gate", torch.float64), _req(prior, "prior", torch.float64)
+        if tuple(dbg.shape) != (m, 7) or tuple(pr.shape) != (g, 7) or dbg.device != q.device or pr.device != q.device:
+            raise ValueError(f"retrieve_elect: db_gate must be float64 [{m}, 7] and prior float64 [{g}, 7] on the inputs' GPU, got "
+                             f"{tuple(dbg.shape)} and {tuple(pr.shape)}")
+        r2, cos_half = float(r2), float(cos_half)
+        if not r2 >= 0.0 or cos_half != cos_half:
+            raise ValueError(f"retrieve_elect: r2 must be >= 0 and cos_half a number, got {r2} and {cos_half}")
+        gate = (dbg, pr, r2, cos_half, int(bool(rot_gate)), _out(gate_info, (g, 2), torch.int32, q.device, "retrieve_elect"))
+    elif gate_info is not None:
+        raise ValueError("retrieve_elect: gate_info is an output of gated retrieval: pass db_gate and prior")
+    info = _out(scene_info, (g, 2), torch.int32, q.device, "retrieve_elect")
+    res = _retrieve(q, db, ranks, db_inv_norm, q_group, db_group, return_sims, status, workspace, out, gate,
+                    (first, qs, first.shape[0] - 1), True, (top, 2 if lost_only else 1, info))
+    res = res if return_sims else (res,)
+    return (*res, qs, info) if gate is None else (*res, gate[5], qs, info)
+
+
+def _retrieve(q, db, ranks, db_inv_norm, q_group, db_group, return_sims, status, workspace, out, gate, scope=None, scoped=False,
+              elect=None):
+    """``retrieve`` / ``retrieve_gated`` / ``retrieve_scoped`` / ``retrieve_elect``: ``gate`` = None, or (db_gate, prior, r2,
+    cos_half, rot_gate, gate_info) checked; ``scope`` = None, or (scene_first, q_scene, n_scenes) checked; ``scoped``: through the
+    scoped entry; ``elect`` = None, or (top, mode, scene_info) checked: through the electing entry (with a scope)."""
     q, db = _req(q, "q"), _req(db, "db")
     if q.dim() != 2 or db.dim() != 2:
         raise ValueError("retrieve: q [G, d] and db [M, d] must be 2-D")
@@ -718,7 +773,7 @@ def _retrieve(q, db, ranks, db_inv_norm, q_group, db_group, return_sims, status,
         if db_inv_norm.shape != (m,) or db_inv_norm.device != q.device:
             raise ValueError(f"retrieve: db_inv_norm must be fp32 [{m}] on the inputs' GPU")
     lib = L.lib()
-    need = int(lib.rpg_retrieve_workspace_bytes(g, m, d))
+    need = int((lib.rpg_retrieve_workspace_bytes if elect is None else lib.rpg_retrieve_elect_workspace_bytes)(g, m, d))
     if workspace is None:
         workspace = torch.empty(need, dtype=torch.uint8, device=q.device)
     elif workspace.dtype != torch.uint8 or workspace.device != q.device or not workspace.is_contiguous():
@@ -726,7 +781,14 @@ def _retrieve(q, db, ranks, db_inv_norm, q_group, db_group, return_sims, status,
     nbrs = _out(out, (g, k), torch.int64, q.device, "retrieve")
     sims = torch.empty((g, k), dtype=torch.float32, device=q.device) if return_sims else None
     status, own = _status_arg(status, q.device, "retrieve")
-    if scoped:
+    if elect is not None:
+        dbg, pr, r2, cos_half, rot, info = gate if gate is not None else (None, None, 0.0, 0.0, 0, None)
+        first, qs, ns = scope
+        L.check(lib.rpg_retrieve_cosine_elect_f32(_p(q), _p(db), _p(db_inv_norm), _p(q_group), _p(db_group), _p(ranks), g, k, m, d,
+                                                  _p(dbg), _p(pr), r2, cos_half, rot, _p(info), _p(first), _p(qs), ns, elect[0],
+                                                  elect[1], _p(elect[2]), _p(nbrs), _p(sims), workspace.data_ptr(),
+                                                  workspace.numel(), status.data_ptr(), _stream()), "retrieve_elect")
+    elif scoped:
         dbg, pr, r2, cos_half, rot, info = gate if gate is not None else (None, None, 0.0, 0.0, 0, None)
         first, qs, ns = scope if scope is not None else (None, None, 0)
         L.check(lib.rpg_retrieve_cosine_scoped_f32(_p(q), _p(db), _p(db_inv_norm), _p(q_group), _p(db_group), _p(ranks), g, k, m, d,

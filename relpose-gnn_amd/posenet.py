@@ -187,6 +187,7 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
         self.mc_dropout = None
         # what the last forward_map's pose gate did, int32 [G, 2] = (state, rows inside) on the device; None without a gate
         self.gate_info = None
+        self.scene_info = None
         # with knn > 0: forward_map builds the kNN graph of its equal-sized graphs at fixed positions (rpg_knn_graph_uniform_f32):
         # no edge count for the host to wait for, so the two-stream schedule, outputs="query" and the captured step serve the
         # model; a graph whose reference list is irregular raises IrregularKnnGraph by the index_check contract (a plain
@@ -660,7 +661,7 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
     @torch.no_grad()
     def forward_map(self, queries: torch.Tensor, neighbours: Optional[torch.Tensor], fmap, k=None, *, rule=None,
                     query_descriptors: Optional[torch.Tensor] = None, query_groups=None, outputs: str = "all", _static=None,
-                    _irregular: Optional[torch.Tensor] = None, prior=None, gate=None, scenes=None):
+                    _irregular: Optional[torch.Tensor] = None, prior=None, gate=None, scenes=None, _vote=None):
         """The forward of G graphs, each query g followed by the K database images ``neighbours[g]`` of the feature map ``fmap``
         (dataset_7Scenes_multi.py:340-345) -- with only the G queries through the encoder.  Returns what
         ``forward(fc_batch(assembled, K + 1), k)`` returns for the assembled images: (abs_pose [G*(K+1), 6], rel_pose [E, 6],
@@ -717,11 +718,21 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
         rule whose ``k`` exceeds the smallest scene is refused.  With given ``neighbours``, or on one scene's map, it is read by the frame transform only:
         uint8 queries of a model whose ``frame_transform`` is a ``frames.SceneFrameTransform`` need it.  A scene index outside
         the atlas / the statistics is reported like a bad neighbour.
+        A ``retrieval.SceneVote`` in its place (a ``rule`` on a ``SceneAtlas`` only): the queries are not told their scene, each
+        elects it from its most similar rows of the whole atlas and is ranked there (``ops.retrieve_elect``) -- the same poses
+        and neighbours, bit for bit, as with the elected scenes given.  Both ``outputs`` modes, ``static_knn``, ``mc_dropout`` and
+        the gate are served; the result is left on the model as ``self.scene_info`` -- int32 [G, 2] = (elected scene, its votes)
+        on the device, like ``gate_info`` -- and None by every call without a vote.  Refused (ValueError): a rule with random draws
+        (their sizes follow the scene, on the host), given ``neighbours``, uint8 queries of a ``frames.SceneFrameTransform`` (the
+        statistics are needed before the encoder, the scene is known behind it; a plain ``FrameTransform`` is served), ``top``
+        above the atlas's rows, and ``lost_only`` (a step with static scenes only).
 
         ``_static`` (graphed.GraphedForwardMap only): ``(ranks int32 [G, K], query groups int64 [G] or None)`` already on the
         device, read in place of the two per-call host products above, so that nothing of the call depends on host data; with a
         gate two more elements, ``(..., prior float64 [G, 7], gate_info int32 [G, 2])``: the step's static prior (which a
         tracking loop updates on the device) and where the states go.
+        ``_vote`` (GraphedForwardMap, tracking.Tracker; with ``scenes=SceneVote``): ``(q_scene int32 [G], scene_info int32 [G, 2])``,
+        the caller's static tensors that the election reads (``lost_only``: -1 elects) and writes.
         ``_irregular`` (relocalize, GraphedForwardMap): an int32 [1] device counter of the caller's that the irregular nodes are
         added to INSTEAD of the model's own counters -- the caller looks at it and nothing raises."""
         self._check_outputs(outputs, k)
@@ -737,12 +748,26 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
         if prior is not None or gate is not None:
             fmap.check_gate("forward_map", rule, prior, gate)
         self.gate_info = None
-        if scenes is not None and torch.is_tensor(queries):
+        self.scene_info = None
+        from .retrieval import SceneVote
+        if isinstance(scenes, SceneVote):
+            from .frames import SceneFrameTransform
+            if rule is None:
+                raise ValueError("forward_map: a SceneVote finds the scene retrieval ranks in: pass a rule and neighbours=None "
+                                 "(given neighbours are used as they are)")
+            if (torch.is_tensor(queries) and queries.dtype == torch.uint8
+                    and isinstance(self.frame_transform, SceneFrameTransform)):
+                raise ValueError("forward_map: uint8 queries of a SceneFrameTransform need their scene's statistics before the "
+                                 "encoder, and a SceneVote knows the scene only behind it: pass processed queries (or use a plain "
+                                 "FrameTransform)")
+        elif _vote is not None:
+            raise ValueError("forward_map: _vote goes with scenes=SceneVote(...)")
+        elif scenes is not None and torch.is_tensor(queries):
             from .frames import scenes_to_device
             scenes = scenes_to_device(scenes, queries.size(0), queries.device, "forward_map")      # (host or None, device)
         if rule is not None:
             return self._forward_map_retrieve(queries, fmap, k, rule, query_descriptors, query_groups, _static, outputs, _irregular,
-                                              prior, gate, scenes)
+                                              prior, gate, scenes, _vote)
         if not torch.is_tensor(queries) or not torch.is_tensor(neighbours):
             raise TypeError("forward_map: queries and neighbours must be tensors")
         if neighbours.dtype != torch.int64 or neighbours.dim() != 2:
@@ -768,9 +793,9 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
                                f"must be on the same GPU")
 
     def _forward_map_retrieve(self, queries, fmap, k, rule, query_descriptors, query_groups, static=None, outputs="all",
-                              irregular=None, prior=None, gate=None, scenes=None):
+                              irregular=None, prior=None, gate=None, scenes=None, vote_out=None):
         """``forward_map`` with the neighbours retrieved per stream slot from that slot's query features (or descriptors).
-        ``static``: see ``forward_map``'s ``_static``."""
+        ``static``: see ``forward_map``'s ``_static``; ``vote_out``: its ``_vote``."""
         if not torch.is_tensor(queries):
             raise TypeError("forward_map: queries must be a tensor")
         if fmap.descriptors is not None and query_descriptors is None:
@@ -798,7 +823,15 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
         from .frames import SceneFrameTransform
         for_frames = queries.dtype == torch.uint8 and isinstance(self.frame_transform, SceneFrameTransform)
         scope = fmap._scope(scenes if isinstance(fmap, SceneAtlas) or not for_frames else None, g, rule, "forward_map",
-                            ranks_given=static is not None)
+                            ranks_given=static is not None, lost_ok=vote_out is not None)
+        # a SceneVote: (None, None, the vote) -- the election writes q_scene, which the slots slice like the ranks
+        vote = scope[2] if scope is not None and len(scope) == 3 else None
+        q_scene = None
+        if vote is not None:
+            q_scene, scene_info = vote_out if vote_out is not None else (
+                torch.empty(g, dtype=torch.int32, device=dev), torch.empty((g, 2), dtype=torch.int32, device=dev))
+            self.scene_info = scene_info
+            scenes = None                         # (nothing for the frame transform to read)
         if static is None:
             qg_host, qg_dev = fmap._query_groups(query_groups, g)
             ranks = rule.device_ranks(fmap.n_allowed(qg_host, g) if scope is None else fmap.n_allowed(qg_host, g, scope[0]), dev)
@@ -816,10 +849,18 @@ class PoseNetX_R2(nn.Module):  # noqa: N801 - reference spelling
         inv, db = fmap.inv_norms(), fmap.descriptor_matrix
         db_groups = None if qg_dev is None else fmap.groups
         nb_out = torch.empty((g, kk), dtype=torch.int64, device=dev)
-        ws_bytes = _L.lib().rpg_retrieve_workspace_bytes
+        ws_bytes = _L.lib().rpg_retrieve_workspace_bytes if vote is None else _L.lib().rpg_retrieve_elect_workspace_bytes
 
         def neighbours_of(qf, g0, g1, st, wkey):
             ws = self._ws_pool.get((400 + wkey[0], wkey[1]), int(ws_bytes(g1 - g0, db.shape[0], db.shape[1])), dev)
+            if vote is not None:
+                return ops.retrieve_elect(qf if qd is None else qd[g0:g1], db, ranks[g0:g1], fmap.scene_first, vote.top,
+                                          q_scene=q_scene[g0:g1], lost_only=vote.lost_only, db_gate=gate_rows,
+                                          prior=None if gate is None else prior_dev[g0:g1], r2=0.0 if gate is None else gate.r2,
+                                          cos_half=0.0 if gate is None else gate.cos_half, rot_gate=gate is not None and gate.rot,
+                                          db_inv_norm=inv, q_group=None if qg_dev is None else qg_dev[g0:g1], db_group=db_groups,
+                                          status=st, workspace=ws, out=nb_out[g0:g1],
+                                          gate_info=None if gate is None else info[g0:g1], scene_info=scene_info[g0:g1])[0]
             if scope is not None:
                 res = ops.retrieve_scoped(qf if qd is None else qd[g0:g1], db, ranks[g0:g1], fmap.scene_first, scope[1][g0:g1],
                                           gate_rows, None if gate is None else prior_dev[g0:g1], 0.0 if gate is None else gate.r2,

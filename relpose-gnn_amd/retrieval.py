@@ -141,3 +141,36 @@ class PoseGate:
 
     def __repr__(self) -> str:
         return f"PoseGate(radius={self.radius}, max_deg={self.max_deg}, pose_m={self.pose_m}, pose_s={self.pose_s})"
+
+
+ELECT_ALL, ELECT_LOST = 1, 2                                  # RPG_ELECT_ALL, RPG_ELECT_LOST
+
+
+class SceneVote:
+    """Goes where ``scenes=`` goes on a ``featmap.SceneAtlas``, in place of the indices: the queries are not told their scene,
+    they elect it on the GPU (``ops.retrieve_elect`` / rpg_retrieve_cosine_elect_f32).  The ``top`` most similar rows of the
+    WHOLE atlas (no group filter, no gate) vote for the scene that owns them; the scene with the most votes -- among tied ones
+    the scene of the best-placed voter -- is the one the query is then ranked in, exactly as if it had been given.  ``top`` in
+    [1, 64] (ValueError otherwise; above the atlas's row count is refused where the atlas is known).
+    ``lost_only``: only the queries whose static scene is -1, or whose prior is not finite, elect; the others stay in the scene
+    they hold -- for a step whose scenes live on the device between calls (``GraphedForwardMap`` with a gate,
+    ``tracking.Tracker``, which always works this way); anywhere else it is a ValueError."""
+
+    def __init__(self, top: int = 16, lost_only: bool = False):
+        if isinstance(top, bool) or int(top) != top or not 1 <= int(top) <= K_MAX:
+            raise ValueError(f"SceneVote: top must be an integer in [1, {K_MAX}], got {top!r}")
+        if not isinstance(lost_only, bool):
+            raise ValueError(f"SceneVote: lost_only must be a bool, got {type(lost_only).__name__}")
+        self.top, self.lost_only = int(top), lost_only
+
+    @property
+    def mode(self) -> int:
+        return ELECT_LOST if self.lost_only else ELECT_ALL
+
+    @property
+    def key(self) -> tuple:
+        """What a captured step is keyed by: two votes with the same key are the same vote."""
+        return ("vote", self.top, self.lost_only)
+
+    def __repr__(self) -> str:
+        return f"SceneVote(top={self.top}, lost_only={self.lost_only})"

@@ -30,8 +30,9 @@ from . import ops
 
 # what a step returns, all on the device (with capture=True: the step's static tensors, overwritten by the next step): the pose
 # rule's rows float64 [S, 16], its (inliers, used) int32 [S, 2], accepted int32 [S], the gate's (state, rows inside) int32 [S, 2]
-# and the retrieved map rows int64 [S, K]
-TrackStep = namedtuple("TrackStep", "rows inliers accepted gate_info neighbours")
+# and the retrieved map rows int64 [S, K]; with scenes=SceneVote the vote's (elected scene, its votes) int32 [S, 2] -- (held
+# scene, 0) for a camera that stayed in its room --, None otherwise
+TrackStep = namedtuple("TrackStep", "rows inliers accepted gate_info neighbours scene_info", defaults=(None,))
 
 
 class Tracker:
@@ -44,7 +45,13 @@ class Tracker:
         (required with ``capture=True``, where it is the capture's example).  ``query_descriptors``: an example [streams, Dd] for a
         map that holds its own retrieval descriptors.  ``mc_dropout`` / ``static_knn`` models: as ``GraphedForwardMap`` takes
         them.  ``scenes`` [streams] (a ``featmap.SceneAtlas`` only, where it is required): the scene every camera stands in;
-        ``self.scenes`` -- int32 [streams] on the device, static -- scopes every step's retrieval, and ``move`` rewrites it."""
+        ``self.scenes`` -- int32 [streams] on the device, static -- scopes every step's retrieval, and ``move`` rewrites it.
+        A ``retrieval.SceneVote`` in its place: the tracker finds the rooms itself.  It is treated as ``lost_only``: a camera
+        elects its scene from the whole atlas on its first frame, again once the update launch has forgotten its prior (past
+        ``max_lost`` lost frames), and again after ``reset(streams)`` -- which in this mode also writes -1 ("elect") into those
+        cameras' scenes; while it is tracked it stays in its room, at the cost of that room's rows.  ``TrackStep.scene_info`` holds
+        (elected scene, votes) per camera, (held scene, 0) for one that did not elect; ``move`` raises ValueError.  With
+        ``capture=True`` the vote is part of the captured graph: a frame stays one H2D copy and one replay."""
         if getattr(pose, "fuse", None) != "consensus":
             raise ValueError("Tracker: pose must be a QueryPose(fuse='consensus', ...): the accept rule reads its (inliers, used)")
         if gate is None or rule is None:
@@ -72,16 +79,25 @@ class Tracker:
         self.lost = torch.zeros(streams, dtype=torch.int32, device=dev)
         self.accepted = torch.zeros(streams, dtype=torch.int32, device=dev)
         self._step = None
-        scope = fmap._scope(scenes, streams, rule, "Tracker")             # None for one scene's map (which takes no scenes)
-        self.scenes = None if scope is None else scope[1].clone()
+        scope = fmap._scope(scenes, streams, rule, "Tracker", lost_ok=True)  # None for one scene's map (which takes no scenes)
+        self.vote = self.scene_info = None
+        if scope is not None and len(scope) == 3:
+            from .retrieval import SceneVote
+            self.vote = SceneVote(scope[2].top, lost_only=True)
+            self.scenes = torch.full((streams,), -1, dtype=torch.int32, device=dev)
+            self.scene_info = torch.zeros((streams, 2), dtype=torch.int32, device=dev)
+        else:
+            self.scenes = None if scope is None else scope[1].clone()
         if capture:
             from .graphed import GraphedForwardMap
             # the update launch goes behind the pose rule of every step the class issues: warm-up, capture -- and so every replay
             self._step = GraphedForwardMap(model, fmap, example, rule=rule, query_descriptors=query_descriptors, pose=pose,
                                            outputs=outputs, gate=gate, _after=self._update,
-                                           **({} if self.scenes is None else {"scenes": self.scenes}))
+                                           **({} if self.scenes is None else
+                                              {"scenes": self.scenes if self.vote is None else self.vote}))
             self.prior = self._step.prior
             self.scenes = self._step.scenes       # the captured step's static tensor: what every replay reads
+            self.scene_info = self._step.scene_info
         else:
             model._check_outputs(outputs, None)
             self.prior = torch.full((streams, 7), float("nan"), dtype=torch.float64, device=dev)
@@ -108,24 +124,28 @@ class Tracker:
             raise ValueError(f"Tracker.step: frames must be a tensor of {self.streams} frame(s), one per stream")
         if self._step is not None:
             out = self._step(frames, query_descriptors=query_descriptors)        # prior=None: the device's own
-            return TrackStep(out.rows, self._step.inliers, self.accepted, self._step.gate_info, out.neighbours)
+            return TrackStep(out.rows, self._step.inliers, self.accepted, self._step.gate_info, out.neighbours, self.scene_info)
         m = self.model
         ab, rel, ei, nb = m.forward_map(frames, None, self.fmap, rule=self.rule, query_descriptors=query_descriptors,
                                         outputs=self.outputs, prior=self.prior, gate=self.gate,
-                                        **({} if self.scenes is None else {"scenes": self.scenes}))
+                                        **({} if self.scenes is None else {"scenes": self.scenes} if self.vote is None else
+                                           {"scenes": self.vote, "_vote": (self.scenes, self.scene_info)}))
         info = m.gate_info
         var = None if self._sigma is None else m.mc_dropout.last.rel_var
         rows = self.pose.from_map(rel, ei, self.fmap, nb, edge_first=self._edge_first, out=self._rows, inliers=self._ints,
                                   rel_var=var, spread=self._sigma)
-        out = TrackStep(rows, self._ints, self.accepted, info, nb)
+        out = TrackStep(rows, self._ints, self.accepted, info, nb, self.scene_info)
         self._update(None, out)
         return out
 
     def reset(self, streams=None) -> None:
         """Forget the prior of every camera (or of the cameras ``streams``, indices): their next frame is relocalised against
-        the whole map, and their ``lost`` count starts at 0."""
+        the whole map, and their ``lost`` count starts at 0.  With a ``SceneVote`` their scenes are forgotten too (-1): the
+        next frame elects them."""
         if streams is None:
             self.prior.fill_(float("nan"))
+            if self.vote is not None:
+                self.scenes.fill_(-1)
             self.lost.zero_()
             self.accepted.zero_()
             return
@@ -134,6 +154,8 @@ class Tracker:
             raise IndexError(f"Tracker.reset: stream index outside [0, {self.streams})")
         idx = idx.to(self.prior.device)
         self.prior[idx] = float("nan")
+        if self.vote is not None:
+            self.scenes[idx] = -1
         self.lost[idx] = 0
         self.accepted[idx] = 0
 
@@ -143,6 +165,9 @@ class Tracker:
         another room must not gate."""
         if self.scenes is None:
             raise ValueError("Tracker.move: the tracker's map is one scene's FeatureMap (scenes belong to a SceneAtlas)")
+        if self.vote is not None:
+            raise ValueError("Tracker.move: this tracker finds the rooms itself (scenes=SceneVote): reset(streams) makes a camera "
+                             "elect its scene again")
         stream, scene = int(stream), int(scene)
         if not 0 <= stream < self.streams:
             raise IndexError(f"Tracker.move: stream index outside [0, {self.streams})")
