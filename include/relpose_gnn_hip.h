@@ -208,6 +208,11 @@ int rpg_gather_graph_nodes_f32(const float* query_feat, const float* map_feat, c
  * entry.  Three or four launches, no allocation, no synchronisation (graph-capturable).                               */
 size_t rpg_retrieve_workspace_bytes(int g, int64_t m, int d);
 int rpg_retrieve_max_rank(void);
+/* HOST, no launch: what the product launch of every retrieval entry does with (g, m, d), from the launchers' own planner --
+ * plan4 = (column slices, 64-column blocks per slice, 16-query tiles per workgroup NQ in {1, 2, 4}, 64-query chunks).  The
+ * first two depend on (m, d) only and are part of the summation order.  RPG_ERR_BAD_ARG outside 1 <= g, 1 <= m < 2^31,
+ * d > 0, d % 4 == 0.                                                                                                   */
+int rpg_retrieve_plan(int g, int64_t m, int d, int32_t* plan4);
 /* inv_norm[r] = 1 / |x_r| (0 for a zero row), x [m][d], d % 4 == 0, 16-byte aligned rows. */
 int rpg_row_inv_norms_f32(const float* x, int64_t m, int d, float* inv_norm, void* stream);
 int rpg_retrieve_cosine_f32(const float* q, const float* db, const float* db_inv_norm, const int64_t* q_group,

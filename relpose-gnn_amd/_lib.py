@@ -37,7 +37,7 @@ SYMBOLS = (
     "rpg_query_pose_weighted_f64", "rpg_knn_graph_uniform_f32", "rpg_retrieve_cosine_gated_f32", "rpg_track_update_f64",
     "rpg_nchw3_to_nhwc8_bf16", "rpg_maxpool3x3s2_nhwc_bf16", "rpg_global_avgpool_nhwc_bf16", "rpg_conv_bf16_last_route",
     "rpg_retrieve_cosine_scoped_f32", "rpg_frames_u8_to_f32_scenes", "rpg_frames_u8_to_bf16_scenes",
-    "rpg_retrieve_elect_workspace_bytes", "rpg_retrieve_cosine_elect_f32",
+    "rpg_retrieve_elect_workspace_bytes", "rpg_retrieve_cosine_elect_f32", "rpg_retrieve_plan",
 )
 
 
@@ -139,6 +139,7 @@ def _declare(lib: C.CDLL) -> None:
     lib.rpg_retrieve_workspace_bytes.argtypes = [_i, C.c_int64, _i]
     lib.rpg_retrieve_workspace_bytes.restype = _sz
     lib.rpg_retrieve_max_rank.argtypes = []
+    lib.rpg_retrieve_plan.argtypes = [_i, C.c_int64, _i, _vp]
     lib.rpg_row_inv_norms_f32.argtypes = [_vp, C.c_int64, _i, _vp, _vp]
     lib.rpg_retrieve_cosine_f32.argtypes = [_vp] * 6 + [_i, _i, C.c_int64, _i, _vp, _vp, _vp, _sz, _vp, _vp]
     lib.rpg_retrieve_cosine_gated_f32.argtypes = ([_vp] * 6 + [_i, _i, C.c_int64, _i, _vp, _vp, C.c_double, C.c_double, _i, _vp,

@@ -214,8 +214,10 @@ __global__ __launch_bounds__(RT_NT) void retrieve_dot_kernel(const float* __rest
 // Larger similarity -> smaller key; -0 and +0 share a key; NaN / inf order after every finite value.
 __device__ __forceinline__ uint32_t sim_key(float s) {
     if (!(fabsf(s) <= FLT_MAX)) return KEY_NONFINITE;
-    s += 0.0f;
-    const uint32_t u = __float_as_uint(s);
+    // -0 takes +0's key, by its bits.  (Not `s += 0.0f`: that add was contracted with the product that made s into one fma, and
+    // the fma's single rounding of a negative product that underflows is -0 -- a key of its own, one below +0's.)
+    uint32_t u = __float_as_uint(s);
+    if (u == 0x80000000u) u = 0u;
     const uint32_t asc = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
     return ~asc;
 }
@@ -651,13 +653,18 @@ int launch_inv_norms(const float* x, int64_t rows, int d, float* inv, hipStream_
     return RPG_OK;
 }
 
+// Query tiling of the dot kernel: chunks of RT_QCHUNK queries (grid.z), and the 16-query tiles of the fullest chunk, which pick
+// the NQ instantiation (1, 2, or 4 for three and four tiles).
+int query_chunks(int g) { return (g + RT_QCHUNK - 1) / RT_QCHUNK; }
+int query_tiles(int g) { return ((g < RT_QCHUNK ? g : RT_QCHUNK) + 15) / 16; }
+
 template <bool SCOPED, bool ELECT>
 int launch_dot(const float* q, const float* db, int g, int64_t m, int d, float* part, const typename ScopeArgs<SCOPED>::type sc,
                hipStream_t s) {
     int ns, bps;
     split_plan(m, d, &ns, &bps);
-    const dim3 grid((unsigned)((m + RT_ROWS - 1) / RT_ROWS), (unsigned)ns, (unsigned)((g + RT_QCHUNK - 1) / RT_QCHUNK));
-    const int tiles = ((g < RT_QCHUNK ? g : RT_QCHUNK) + 15) / 16;
+    const dim3 grid((unsigned)((m + RT_ROWS - 1) / RT_ROWS), (unsigned)ns, (unsigned)query_chunks(g));
+    const int tiles = query_tiles(g);
     if (tiles <= 1)
         hipLaunchKernelGGL((retrieve_dot_kernel<1, SCOPED, ELECT>), grid, dim3(RT_NT), 0, s, q, db, g, m, d, bps, part, sc);
     else if (tiles == 2)
@@ -743,6 +750,19 @@ extern "C" int rpg_retrieve_max_rank(void) { return R_MAX; }
 extern "C" size_t rpg_retrieve_workspace_bytes(int g, int64_t m, int d) {
     if (g <= 0 || m <= 0 || d <= 0) return 0;
     return ws_layout(g, m, d).total;
+}
+
+// HOST: what launch_dot would launch for (g, m, d), from split_plan and the tile rule it uses itself.  No launch.
+extern "C" int rpg_retrieve_plan(int g, int64_t m, int d, int32_t out[4]) {
+    if (!out || g < 1 || m < 1 || m >= ((int64_t)1 << 31) || d <= 0 || (d & 3)) return RPG_ERR_BAD_ARG;
+    int ns, bps;
+    split_plan(m, d, &ns, &bps);
+    const int tiles = query_tiles(g);
+    out[0] = ns;
+    out[1] = bps;
+    out[2] = tiles <= 1 ? 1 : (tiles == 2 ? 2 : 4);
+    out[3] = query_chunks(g);
+    return RPG_OK;
 }
 
 extern "C" int rpg_row_inv_norms_f32(const float* x, int64_t m, int d, float* inv_norm, void* stream) {
